@@ -7,12 +7,17 @@ launch) -> pose decoder -> pose epilogue (-> all-gather of the result rows when 
 Workload per GPU: 256 synthetic 1024-point clouds x 20 grasps (BASELINE.json configs[2];
 configs[3] = the same 256 clouds per GPU on 8 GPUs => weak scaling).
 
-Prints ONE JSON line (rank 0) with the driver's keys plus
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line (rank 0): metric, value
+(grasps/s), unit, higher_is_better, dtype, ms_per_step (wall time of one timed step), config.
+--dump-outputs DIR also writes what the last timed step returned (poses, confidences) as .npy files.
+
+With --full the line also carries what takes launches or processes of its own:
   roofline      dominant kernel (the fused denoise loop, f32 MFMA bound), timed with HIP
                 events on the launch stream inside this run
   cpu_baseline  the CPU oracle (a torch-CPU port of the reference graph) timed on this
                 box's host cores on a bounded sample (rank 0, N = 1 only)
   kernels       extra per-kernel roofline records (set-abstraction gather: HBM bound, ...)
+(a plain run reports them as null / [])
 """
 import argparse
 import json
@@ -109,9 +114,16 @@ def parse():
     ap.add_argument("--noise", choices=["tensor", "kernel", "device"], default="tensor",
                     help="DDPM step noise: a [steps, B G, 1, D] torch.randn tensor per batch (the reference's draws, default) or "
                          "drawn inside the fused launch (gldm_denoise_rng: Philox4x32-10 keyed on the global latent index)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the roofline of the dominant kernel, the per-kernel and "
+                         "per-stage records, the exact-f32 and set-abstraction-encoder whole steps and the CPU baseline "
+                         "(off by default: a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float32; at most 64 MB in all, a "
+                         "fixed seeded sample of rows beyond that)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--minimal", action="store_true",
-                    help="only the timed steps + the roofline launches of the dominant kernel (no stage split, no "
+                    help="with --full: only the timed steps + the roofline launches of the dominant kernel (no stage split, no "
                          "set-abstraction / one-object records): what the rocprofv3 --stats run uses, so that the "
                          "kernel's average duration in the trace is over bench-workload launches only")
     ap.add_argument("--dry-run", action="store_true",
@@ -119,6 +131,8 @@ def parse():
     ap.add_argument("--streams", type=int, default=3,
                     help="HIP streams the steps alternate over (2: batch k+1's encoder overlaps batch k's denoise tail)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.scheduler is None:
         a.scheduler = "ddpm" if a.experiment == "ppc" else "ddim"
     if a.ddim_steps is None:
@@ -138,6 +152,26 @@ def event_time(fn, iters, lead=1):
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) * 1e-3 / iters
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write `arrays` ({name: tensor with one row per grasp, or None}) to out_dir/<name>.npy as float32.  Beyond
+    DUMP_LIMIT_BYTES in all, every array keeps the same fraction of its rows: a sorted sample drawn with a fixed seed
+    (arrays with equal row counts keep the same rows), whose indices go to out_dir/<name>_rows.npy (float64)."""
+    import numpy as np
+    arrays = {k: v.detach().float().cpu() for k, v in arrays.items() if v is not None}
+    total = sum(v.numel() * 4 + v.shape[0] * 8 for v in arrays.values())   # values + a float64 index per row
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            n = v.shape[0]
+            keep = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:n * DUMP_LIMIT_BYTES // total].sort().values
+            v = v[keep]
+            np.save(os.path.join(out_dir, name + "_rows.npy"), keep.double().numpy())
+        np.save(os.path.join(out_dir, name + ".npy"), v.numpy())
 
 
 def count_gpus_without_hip():
@@ -298,6 +332,9 @@ def main():
     from graspldm_amd.synthetic import synthetic_batch
 
     B, G, N, S = args.clouds_per_gpu, args.grasps, args.points, args.ddim_steps
+    # the DDPM per-step noise is drawn from torch's default generator: seeded, so that the same arguments give the same
+    # inputs in every run (--dump-outputs)
+    torch.manual_seed(1234 + rank)
     ppc = args.experiment == "ppc"
     D = 16 if ppc else 4   # grasp latent size = positions of the denoiser
     ldm = build_fpc_ldm(n_points=N, scheduler=args.scheduler, device=dev, **(dict(latent=16, pc_latent=256) if ppc else {}))
@@ -340,9 +377,8 @@ def main():
         # the epilogue runs on the rank's OWN rows; what crosses xGMI is one all-gather of the result rows [B G, 7]
         # (the latent-level outputs the north star names: 28 bytes per grasp), nothing is repeated per rank
         H, un, conf = pose_epilogue(tm, lg, gmean, gstd, G)
-        if world > 1:
-            gather_results(torch.cat([tm, lg], dim=1), B * G, world * B * G)
-        return H
+        rows = gather_results(torch.cat([tm, lg], dim=1), B * G, world * B * G) if world > 1 else None
+        return H, un, conf, rows
 
     if streams is not None:
         # setup, not a step: each stream's first batch allocates its memory pool and its engine scratch
@@ -359,17 +395,17 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    H_last = None
     for _ in range(args.steps):
-        H_last = step()
+        last = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    H_last, un_last, conf_last, rows_last = last
     # the timed batches must be real results: no lost step-segment hand-off (the engine's error word), finite poses
     eng.check()
-    if H_last is not None and not bool(torch.isfinite(H_last).all()):
+    if not bool(torch.isfinite(H_last).all()):
         raise SystemExit("bench.py: non-finite poses in the timed region")
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -377,9 +413,15 @@ def main():
         dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
     grasps_per_s = world * B * G * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        # what the last timed step returned: poses [B G, 4, 4], unnormalised (translation, MRP) rows [B G, 6], grasp
+        # confidences [B G, 1]; on N > 1 ranks also the all-gathered (normalised tmrp, logit) rows of the node
+        dump_outputs(args.dump_outputs, dict(poses_H=H_last, poses_tmrp=un_last, confidence=conf_last,
+                                             gathered_tmrp_logit=rows_last))
 
     out = None
-    if rank == 0:
+    roof, kernels, cpu = None, [], None
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel: the fused denoise loop
         z = ldm.vae_model.encode_pc(pcs)
         cemb = eng.cond_embed(z)
@@ -671,6 +713,7 @@ def main():
                                           + (f"{r['value']:.1f} grasps/s ({r['clouds']} clouds in {r['seconds']:.1f} s)" if r.get("value") else "no result within 120 s")
                                           for r in runs),
                        runs=runs)
+    if rank == 0:
         out = dict(metric="grasps/sec whole-node (%d-pt cloud, %d %s steps)" % (N, S, args.scheduler.upper()), value=grasps_per_s,
                    unit="grasps/s", n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=ms_per_step,
                    higher_is_better=True, scaling="weak", vs_baseline=None,

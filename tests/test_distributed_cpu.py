@@ -219,3 +219,31 @@ def test_bench_workload_label_follows_arguments():
     assert 0.9 < b.denoiser_executed_mfma_flop_l16() / b.DENOISER_FLOP_PER_LATENT_STEP_PPC < 1.3
     # the CPU leg sizes itself by the CPUs the job may use (affinity mask, cgroup quota), never more than the host reports
     assert 1 <= b.usable_cores() <= (os.cpu_count() or 1)
+
+
+def test_bench_dump_outputs_float32_and_bounded(tmp_path):
+    """bench.py --dump-outputs: float32 .npy per array; beyond the cap, the same seeded rows of arrays with equal row
+    counts, their indices alongside, and the same files on a second call."""
+    import importlib.util
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    H = torch.arange(40 * 16, dtype=torch.float64).view(40, 4, 4)
+    conf = torch.arange(40, dtype=torch.float32).view(40, 1)
+    b.dump_outputs(str(tmp_path / "small"), dict(poses_H=H, confidence=conf, gathered_tmrp_logit=None))
+    assert sorted(os.listdir(tmp_path / "small")) == ["confidence.npy", "poses_H.npy"]
+    got = np.load(tmp_path / "small" / "poses_H.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, H.float().numpy())
+    b.DUMP_LIMIT_BYTES = 1000
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), dict(poses_H=H, confidence=conf))
+    total = sum(os.path.getsize(tmp_path / "a" / f) - 128 for f in os.listdir(tmp_path / "a"))   # less the .npy headers
+    assert total <= 1000
+    rows = np.load(tmp_path / "a" / "poses_H_rows.npy")
+    assert rows.dtype == np.float64 and 0 < rows.size < 40 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(rows, np.load(tmp_path / "a" / "confidence_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "poses_H.npy"), H[rows.astype(np.int64)].float().numpy())
+    for f in os.listdir(tmp_path / "a"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))

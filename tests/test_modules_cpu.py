@@ -84,12 +84,12 @@ def test_pointnet_schemas_match_reference():
 
 
 def test_shipped_config_file_builds_when_reference_is_present():
-    path = "/root/reference/configs/generation/fpc/fpc_1a_latentc3_z4_pc64_180k.py"
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present (GPU box)")
+    """The model section of the reference's shipped fpc config (configs/generation/fpc/fpc_1a_latentc3_z4_pc64_180k.py),
+    as Config.fromfile parses it, stored as data in tests/golden/config_fpc_1a_model.json."""
     from graspldm_amd.builder import build_model_from_cfg
     from graspldm_amd.config import Config
-    cfg = Config.fromfile(path)
+    with open(os.path.join(GOLDEN, "config_fpc_1a_model.json")) as f:
+        cfg = Config.fromdict(json.load(f))
     ldm = build_model_from_cfg(cfg.model.ddm)
     ldm.set_vae_model(build_model_from_cfg(cfg.model.vae))
     ldm2 = build_model_from_cfg(cfg.model.ddm)  # configs are reusable here (single-use in the reference)

@@ -6,11 +6,11 @@ root=$GRAFT_REPO_ROOT
 out=$root/gpurun_out/profiles_$tag
 mkdir -p $out
 cd $root
-python bench.py --steps 20 --warmup 5 > $out/${tag}_bench.json 2> $out/bench.err
-python bench.py --scheduler ddpm --ddim-steps 1000 --points 4096 --grasps 200 --clouds-per-gpu 64 --steps 3 --warmup 1 > $out/${tag}_bench_c5.json 2>> $out/bench.err
-python bench.py --scheduler ddpm --ddim-steps 1000 --points 4096 --grasps 200 --clouds-per-gpu 64 --steps 3 --warmup 1 --minimal --noise kernel > $out/${tag}_bench_c5_noise_in_kernel.json 2>> $out/bench.err
+python bench.py --full --steps 20 --warmup 5 > $out/${tag}_bench.json 2> $out/bench.err
+python bench.py --scheduler ddpm --ddim-steps 1000 --points 4096 --grasps 200 --clouds-per-gpu 64 --steps 3 --warmup 1 --full > $out/${tag}_bench_c5.json 2>> $out/bench.err
+python bench.py --scheduler ddpm --ddim-steps 1000 --points 4096 --grasps 200 --clouds-per-gpu 64 --steps 3 --warmup 1 --full --minimal --noise kernel > $out/${tag}_bench_c5_noise_in_kernel.json 2>> $out/bench.err
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_s1 -o run -- /usr/bin/python3 $root/bench.py --steps 6 --warmup 2 --no-cpu-baseline --streams 1 --minimal > $out/${tag}_bench_streams1_under_rocprof.json 2> $out/prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_s1 -o run -- python3 $root/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --streams 1 --minimal > $out/${tag}_bench_streams1_under_rocprof.json 2> $out/prof.err
 cd $root
 python3 - $out $tag <<'PY'
 import csv, glob, sys
@@ -30,7 +30,7 @@ rm -rf $out/prof_s1
 head -c 600 $out/${tag}_bench.json; echo; head -c 300 $out/${tag}_bench_c5.json; echo; head -5 $out/${tag}_bench_streams1_kernel_stats.csv | cut -c1-160
 # round 4 additions: the ppc experiment, the decoder alone, the set-abstraction kernels and the encoder kernels under counters
 cd $root
-python bench.py --experiment ppc --steps 2 --warmup 1 --no-cpu-baseline > $out/${tag}_bench_ppc.json 2>> $out/bench.err
+python bench.py --experiment ppc --steps 2 --warmup 1 --full --no-cpu-baseline > $out/${tag}_bench_ppc.json 2>> $out/bench.err
 bash tools/pmc_kernels.sh ${tag}_sa tools/run_sa_once.py 256 > $out/pmck_sa.log 2>&1
 cp gpurun_out/pmck_${tag}_sa.json $out/${tag}_point_ops_pmc_raw.json
 bash tools/prof_kernels.sh ${tag}_enc tools/bench_encoders.py --shipped --only "PVCNNEncoder(fpc)" --batch-sizes 256 --iterations 5 > $out/${tag}_encoder_kernels.txt 2>&1
