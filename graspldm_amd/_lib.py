@@ -10,7 +10,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # GLDM_LIB: another build of the same library (diagnostic builds: make -C graspldm_amd/csrc EXTRA=... OUT=...)
 LIB_PATH = os.environ.get("GLDM_LIB") or os.path.join(_PKG, "libgldm_hip.so")
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class GldmError(RuntimeError):
@@ -43,6 +43,8 @@ _SIGNATURES = {
     "gldm_step_noise_rng": [_ull, _ll, _i, _i, _i, _vp, _vp],
     "gldm_decode": [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp],
     "gldm_pose_epilogue": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "gldm_encode": [_vp, _vp, _vp, _i, _vp, _i, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _vp],
+    "gldm_pose_prologue": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
     "gldm_conv3d_k3": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
     "gldm_conv3d_k3_cl": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
     "gldm_conv3d_k3_generic": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],

@@ -6,7 +6,9 @@
 //                    tmrp / class_logits heads);
 //   * gldm_sa_mlp_forward : the fused set-abstraction core (gather + grouped MLP + max)
 //                    on the same GEMM core;
-//   * gldm_r1d_cond_embed, gldm_pose_epilogue : the small ops either side.
+//   * gldm_encode  : GraspCVAE.encode (in_layer, ResNet1D, out_layer folded into the
+//                    bottleneck's mu / logvar, reparameterisation), the same engine.
+//   * gldm_r1d_cond_embed, gldm_pose_prologue, gldm_pose_epilogue : the small ops either side.
 //
 // Mapping to CDNA4
 //   A workgroup owns a tile of NC activation columns = NC/L samples x L positions and walks
@@ -2506,7 +2508,12 @@ struct RunArgs {
   long long noise_base;
   int noise_on;
   float *out0;            // denoise: x_out [n][L]; decode: tmrp [n][6]
-  float *out1;            // decode: logit [n]
+  float *out1;            // decode: logit [n]; encode: logvar [n][Lz]
+  // encode (GLDM_HEAD_ENCODER; out0 = mu [n][Lz]): z = mix_mu mu + mix_eps eps (exp(logvar / 2) if eps_times_std), or null
+  float *out2;
+  const float *eps;       // [n][Lz] or null
+  float mix_mu, mix_eps;
+  int eps_times_std;
   float *ws;              // workspace: chain header + hand-off granules (+ the decoder's scale/shift table)
   float *park;            // position-major engine with a 256-channel last level: 64 KiB of scratch per workgroup (Ctx::park)
   const float *ss_tab;    // [n_cond][ss_stride] scale/shift rows of every ResnetBlock per conditioning cloud, or null
@@ -3352,6 +3359,32 @@ __global__ __launch_bounds__(Geo<NC>::kThreads, 2) void r1d_kernel(const RunArgs
       const int gi = samp0 + s;
       if (s < nsamp && gi < a.n_samples) a.out0[(size_t)gi * L + l] = a.sched_kind == GLDM_SCHED_NONE ? epsr[tid_e] : lat[tid_e];
     }
+  } else if (L == 16 && d.head_kind == GLDM_HEAD_ENCODER) {   // (16-position nets only: gldm_encode checks)
+    // out_layer folded into the bottleneck (r1d_pack): thread (sample, j) takes rows j (mu) and Lz + j (logvar) of the
+    // [2 Lz][L] head and, when asked, mixes the latent from them (grasp_vae.py:552-561; add_noise of mu)
+    int nl = d.n_head >> 1;
+    asm volatile("" : "+s"(nl));   // opaque, like nh below
+    if (tid_e < S * nl) {
+      const int s = tid_e / nl, j = tid_e - s * nl;
+      const int gi = samp0 + s;
+      if (s < nsamp && gi < a.n_samples) {
+        const float *wm = a.weights + d.head_w + j * L, *wv = wm + nl * L;
+        float mu = a.weights[d.head_b + j], lv = a.weights[d.head_b + nl + j];
+        for (int l = 0; l < L; ++l) {
+          const float e = epsr[col_of(s, l)];
+          mu += wm[l] * e;
+          lv += wv[l] * e;
+        }
+        const size_t o = (size_t)gi * nl + j;
+        a.out0[o] = mu;
+        a.out1[o] = lv;
+        if (a.out2) {
+          float z = a.mix_mu * mu;
+          if (a.eps) z += a.mix_eps * a.eps[o] * (a.eps_times_std ? expf(0.5f * lv) : 1.0f);
+          a.out2[o] = z;
+        }
+      }
+    }
   } else {
     // heads: rows 0..5 tmrp, row 6 class logit; input = the L-vector of each sample
     int nh = d.n_head;
@@ -3416,6 +3449,48 @@ __global__ void pose_epilogue_kernel(const float *__restrict__ tmrp, const float
   h[8] = 2.0f * (xz - yw);   h[9] = 2.0f * (yz + xw);     h[10] = -x2 - y2 + z2 + w2;   h[11] = v[2];
   h[12] = 0.f; h[13] = 0.f; h[14] = 0.f; h[15] = 1.0f;
   if (conf) conf[i] = 1.0f / (1.0f + expf(-logit[i]));
+}
+
+// The way back (rotations.py:305-309,115-163): arg-max over (R00, R11, R22, trace) with the first maximum winning (torch
+// argmax), the SciPy branch formulas, normalise, q.xyz / (1 + q.w), then the dataset's (x - mean) / std.  Same operation
+// order as the reference on the same f32 values (no contraction), so the branch is the reference's.
+__global__ void pose_prologue_kernel(const float *__restrict__ H, const float *__restrict__ label,
+                                     const float *__restrict__ mean, const float *__restrict__ stdv, int n, int gpc,
+                                     float *__restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int cl = i / gpc;
+  const float *h = H + (size_t)i * 16;
+  float m[3][3];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) m[r][c] = h[4 * r + c];
+  const float dg[4] = {m[0][0], m[1][1], m[2][2], (m[0][0] + m[1][1]) + m[2][2]};
+  int ch = 0;
+  for (int q = 1; q < 4; ++q) ch = dg[q] > dg[ch] ? q : ch;
+  float q4[4];
+  if (ch == 3) {
+    q4[0] = m[2][1] - m[1][2];
+    q4[1] = m[0][2] - m[2][0];
+    q4[2] = m[1][0] - m[0][1];
+    q4[3] = 1.0f + dg[3];
+  } else {
+    // constant indices only (a runtime-indexed register array would go to scratch)
+    const float mii = ch == 0 ? m[0][0] : (ch == 1 ? m[1][1] : m[2][2]);
+    const float mji = ch == 0 ? m[1][0] : (ch == 1 ? m[2][1] : m[0][2]), mij = ch == 0 ? m[0][1] : (ch == 1 ? m[1][2] : m[2][0]);
+    const float mki = ch == 0 ? m[2][0] : (ch == 1 ? m[0][1] : m[1][2]), mik = ch == 0 ? m[0][2] : (ch == 1 ? m[1][0] : m[2][1]);
+    const float mkj = ch == 0 ? m[2][1] : (ch == 1 ? m[0][2] : m[1][0]), mjk = ch == 0 ? m[1][2] : (ch == 1 ? m[2][0] : m[0][1]);
+    const float qi = (1.0f - dg[3]) + 2.0f * mii, qj = mji + mij, qk = mki + mik;
+    q4[0] = ch == 0 ? qi : (ch == 1 ? qk : qj);
+    q4[1] = ch == 0 ? qj : (ch == 1 ? qi : qk);
+    q4[2] = ch == 0 ? qk : (ch == 1 ? qj : qi);
+    q4[3] = mkj - mjk;
+  }
+  const float nrm = sqrtf(((q4[0] * q4[0] + q4[1] * q4[1]) + q4[2] * q4[2]) + q4[3] * q4[3]);
+  const float den = 1.0f + q4[3] / nrm;
+  const float v[6] = {h[3], h[7], h[11], (q4[0] / nrm) / den, (q4[1] / nrm) / den, (q4[2] / nrm) / den};
+  const int w = label ? 7 : 6;
+  for (int q = 0; q < 6; ++q) out[(size_t)i * w + q] = (v[q] - mean[cl * 6 + q]) / stdv[cl * 6 + q];
+  if (label) out[(size_t)i * 7 + 6] = label[i];
 }
 #pragma clang fp contract(fast)
 
@@ -5067,7 +5142,7 @@ GLDM_API int gldm_decode(const gldm_r1d_desc *desc, const float *weights, const 
   if (st != GLDM_OK) return st;
   if (!weights || !cemb || !z_h || !tmrp || !logit || !workspace || n_samples <= 0 || samples_per_cond <= 0)
     return GLDM_ERR_INVALID_ARG;
-  if (desc->latent_dim <= 0 || desc->n_head != 7) return GLDM_ERR_INVALID_ARG;
+  if (desc->latent_dim <= 0 || desc->n_head != 7 || desc->head_kind != GLDM_HEAD_DECODER) return GLDM_ERR_INVALID_ARG;
   RunArgs a{};
   a.d = *desc;
   a.weights = weights; a.temb = nullptr; a.cemb = cemb; a.samples_per_cond = samples_per_cond;
@@ -5085,6 +5160,46 @@ GLDM_API int gldm_decode(const gldm_r1d_desc *desc, const float *weights, const 
     a.ss_stride = rows;
   }
   return launch_r1d(a, reinterpret_cast<hipStream_t>(stream));
+}
+
+GLDM_API int gldm_encode(const gldm_r1d_desc *desc, const float *weights, const float *cemb, int samples_per_cond,
+                         const float *h, int n_samples, const float *eps, float mix_mu, float mix_eps, int eps_times_std,
+                         float *mu, float *logvar, float *z, void *workspace, gldm_stream_t stream) {
+  int st = validate(desc);
+  if (st != GLDM_OK) return st;
+  if (!weights || !cemb || !h || !mu || !logvar || !workspace || n_samples <= 0 || samples_per_cond <= 0)
+    return GLDM_ERR_INVALID_ARG;
+  if (desc->latent_dim <= 0 || desc->head_kind != GLDM_HEAD_ENCODER || desc->n_head < 2 || (desc->n_head & 1) ||
+      desc->n_head > 2 * GLDM_R1D_MAX_LATENT)
+    return GLDM_ERR_INVALID_ARG;
+  if (desc->seq_len != 16) return GLDM_ERR_UNSUPPORTED;   // the encoder head is compiled into the 16-position engines only
+  RunArgs a{};
+  a.d = *desc;
+  a.weights = weights; a.temb = nullptr; a.cemb = cemb; a.samples_per_cond = samples_per_cond;
+  a.x_in = h; a.n_samples = n_samples; a.n_steps = 1; a.sched_kind = GLDM_SCHED_NONE;
+  a.out0 = mu; a.out1 = logvar; a.out2 = z; a.eps = eps; a.mix_mu = mix_mu; a.mix_eps = mix_eps;
+  a.eps_times_std = eps_times_std; a.ws = reinterpret_cast<float *>(workspace);
+  const int rows = ss_table_rows(desc);
+  if (rows > 0) {  // as gldm_decode: the per-cloud scale/shift table behind the hand-off granules
+    const long long off = ws_layout(desc, n_samples).ss_off;
+    float *tab = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + off);
+    const int n_cond = (n_samples + samples_per_cond - 1) / samples_per_cond;
+    hipLaunchKernelGGL(ss_table_kernel, dim3(n_cond), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *desc, weights,
+                       cemb, rows, tab);
+    if (hipGetLastError() != hipSuccess) return GLDM_ERR_LAUNCH;
+    a.ss_tab = tab;
+    a.ss_stride = rows;
+  }
+  return launch_r1d(a, reinterpret_cast<hipStream_t>(stream));
+}
+
+GLDM_API int gldm_pose_prologue(const float *H, const float *label, const float *grasp_mean, const float *grasp_std, int n,
+                                int grasps_per_cloud, int n_clouds, float *h, gldm_stream_t stream) {
+  if (!H || !grasp_mean || !grasp_std || !h || n <= 0 || grasps_per_cloud <= 0 || n_clouds <= 0) return GLDM_ERR_INVALID_ARG;
+  if ((long long)n_clouds * grasps_per_cloud < (long long)n) return GLDM_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(pose_prologue_kernel, dim3((n + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), H,
+                     label, grasp_mean, grasp_std, n, grasps_per_cloud, h);
+  return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
 }
 
 GLDM_API int gldm_pose_epilogue(const float *tmrp, const float *logit, const float *grasp_mean,

@@ -100,6 +100,7 @@ class GaussianDiffusion1D(nn.Module):
         self._noise_scheduler_type = noise_scheduler_type
         self._num_inference_steps = None
         self._tables = {}
+        self._host_coef = {}
         if hasattr(model, "max_timesteps"):
             model.max_timesteps = max(model.max_timesteps, num_steps)
 
@@ -118,9 +119,20 @@ class GaussianDiffusion1D(nn.Module):
             self._tables[key] = (ts.to(device), coef.to(device))
         return self._tables[key]
 
+    def add_noise_scalars(self, step):
+        """(sqrt(abar_t), sqrt(1 - abar_t)) of inference step `step` as host floats: the scheduler's add_noise
+        (x_t = a x_0 + s noise) in the f32 values the step table holds."""
+        key = (self._noise_scheduler_type, self._num_inference_steps)
+        if key not in self._host_coef:
+            self._host_coef[key] = make_schedule_tables(self._noise_scheduler_type, self.num_steps, self.beta_start,
+                                                        self.beta_end, self.beta_schedule, self.variance_type,
+                                                        self._num_inference_steps)[1][:, :2].tolist()
+        s, a = self._host_coef[key][step]
+        return a, s
+
     @torch.no_grad()
     def sample(self, z_cond=None, batch_size=1, return_all=False, device=None, samples_per_cond=1, x_T=None,
-               step_noise=None, noise_source="tensor", noise_seed=None, noise_base=0, **kwargs):
+               step_noise=None, noise_source="tensor", noise_seed=None, noise_base=0, start_step=0, **kwargs):
         """Reverse diffusion (gaussian_diffusion.py:232-277).  x_T is drawn on the CPU
         generator then moved, exactly like the reference (:253); DDPM per-step noise is
         drawn on the device ([steps, B, 1, D]) unless `step_noise` is given.  One HIP launch
@@ -131,7 +143,11 @@ class GaussianDiffusion1D(nn.Module):
         generator (gldm_denoise_rng) instead of from a [steps, B, 1, D] tensor -- the same distribution, not torch's
         stream; `noise_seed` defaults to one draw of torch's CPU generator (so torch.manual_seed still fixes a run) and
         `noise_base` is the global index of this batch's first latent: ranks of a sharded job that share a seed MUST pass
-        their own (distributed.shard_noise_base), or they add identical step noise to different latents."""
+        their own (distributed.shard_noise_base), or they add identical step noise to different latents.
+
+        start_step=k (additive; GraspLatentDDM.refine_grasps): x_T is the latent at inference step k and only steps k.. of
+        the schedule run.  `step_noise` then has one row per LAUNCHED step, and the in-kernel stream is keyed on the index
+        within the launched slice (its first step draws with step number 0), not on k + i."""
         device = torch.device(device if device is not None else z_cond.device)
         if device.type != "cuda":
             raise RuntimeError("sampling runs on the GPU only (graspldm_amd has no CPU path)")
@@ -139,6 +155,10 @@ class GaussianDiffusion1D(nn.Module):
             x_T = torch.randn((batch_size, self.channels, self.n_dims))
         x_T = x_T.to(device)
         ts, coef = self._schedule(device)
+        if start_step:
+            if not 0 < start_step < ts.numel():
+                raise ValueError(f"start_step must lie in [0, {ts.numel()}), not {start_step}")
+            ts, coef = ts[start_step:], coef[start_step:]   # whole rows: the table's 16-byte alignment holds
         kind = SCHED_DDIM if self._noise_scheduler_type == "ddim" else SCHED_DDPM
         if noise_source not in ("tensor", "kernel"):
             raise ValueError(f"noise_source must be 'tensor' or 'kernel', not {noise_source!r}")

@@ -69,6 +69,51 @@ class GraspLatentDDM(nn.Module):
             steps.append([t.detach().cpu() for t in o])
         return final, steps
 
+    @torch.no_grad()
+    def encode_grasps(self, xyz, grasps):
+        """Latent distribution of given grasps (GraspCVAE.encode as GraspLatentDDM.forward calls it, grasp_ldm.py:159-163):
+        xyz [B,N,3], grasps [B*G, 6|7] normalised rows -> (mu, logvar) [B*G, L]."""
+        mu, logvar, _, _, _ = self.vae_model._encode(xyz, grasps, want_z=False)
+        return mu, logvar
+
+    @torch.no_grad()
+    def _refine(self, xyz, grasps, strength, noise=None, **kwargs):
+        if self.is_elucidated_diffusion:
+            raise NotImplementedError("refine_grasps runs the DDIM / DDPM samplers only (Elucidated samplers start from "
+                                      "their own sigma schedule)")
+        if not 0.0 <= float(strength) <= 1.0:
+            raise ValueError(f"strength must lie in [0, 1], not {strength}")
+        dm, vae = self.diffusion_model, self.vae_model
+        S = len(dm._schedule(xyz.device)[0])
+        k = S - int(round(S * float(strength)))
+        if k >= S:   # nothing to diffuse: decode the mean
+            mu, logvar, x, z_pc, g = vae._encode(xyz, grasps, eps=None)
+        else:
+            n = grasps.shape[0]
+            if noise is None:
+                noise = torch.randn(n, vae.grasp_latent_size)
+            a, s = dm.add_noise_scalars(k)
+            # x_k = add_noise(mu, noise, ts[k]) comes out of the encode launch itself
+            mu, logvar, x_k, z_pc, g = vae._encode(xyz, grasps, eps=noise.reshape(n, -1).to(xyz.device), mix=(a, s),
+                                                   eps_times_std=False)
+            if not hasattr(dm.model, "class_embedding"):
+                kwargs.pop("metas", None)
+            kwargs.setdefault("device", xyz.device)
+            x, _ = dm.sample(z_cond=z_pc, batch_size=n, samples_per_cond=g, x_T=x_k.unsqueeze(1), start_step=k, **kwargs)
+            x = x.squeeze(-2)
+        tmrp, logit = vae.decoder(x, z_pc, samples_per_cond=g)
+        return (tmrp, logit), dict(mu=mu, logvar=logvar, x0=x, start_step=k)
+
+    def refine_grasps(self, xyz, grasps, strength, noise=None, **sampler_kwargs):
+        """Start the reverse diffusion from given grasps instead of from noise: encode them (mu), diffuse mu forward to
+        inference step k = S - round(S * strength) with `noise` [B*G, L] (default: CPU generator, moved), run steps k..S-1
+        in the fused launch, decode.  strength 0 decodes mu; strength 1 runs the whole schedule from add_noise(mu) at its
+        first timestep.  sampler_kwargs as generate_grasps (step_noise: one row per launched step; noise_source="kernel":
+        the in-kernel stream counts steps from the launch's first, see GaussianDiffusion1D.sample).
+        Returns ((tmrp [B*G,6], cls_logit [B*G,1]), [])."""
+        out, _ = self._refine(xyz, grasps, strength, noise=noise, **sampler_kwargs)
+        return out, []
+
     def check_engines(self):
         """Raise GldmError if any fused denoise launch so far lost a step-segment hand-off between workgroups (its latents
         are NaN then): the synchronising form of the check every launch makes without a host sync.  The inference harness

@@ -1,7 +1,7 @@
 """GraspCVAE (generation half): mirror of `grasp_ldm/models/grasp_vae.py` with the same
 constructor arguments, sub-module names and state_dict keys (encoder.pc_encoder.*,
-encoder.grasp_encoder.*, bottleneck.*, decoder.*).  The training-only parts
-(grasp encoder, bottleneck, losses) are parameter containers so checkpoints load strictly."""
+encoder.grasp_encoder.*, bottleneck.*, decoder.*).  Both directions run: cloud + latent -> pose (decoder) and
+cloud + grasp -> latent (grasp encoder + bottleneck, one HIP launch: gldm_encode).  Losses are training-only."""
 from typing import Union
 
 import torch
@@ -60,7 +60,8 @@ class ConditionalGraspPoseDecoder(nn.Module):
 
 
 class ConditionalGraspPoseEncoder(nn.Module):
-    """grasp_vae.py:439-536 (training-time: parameter container only)."""
+    """grasp_vae.py:439-536: Linear(D->R) -> ResNet1D -> Linear(R->L).  On the fused path (GraspCVAE.encode) the
+    bottleneck's mu / logvar Linears ride on the same launch as the folded head (r1d_pack: encoder=)."""
 
     def __init__(self, config, latent_size, feature_resolution=16):
         super().__init__()
@@ -71,16 +72,64 @@ class ConditionalGraspPoseEncoder(nn.Module):
         self.in_layer = nn.Linear(self.in_features, feature_resolution)
         self.net = ResNet1D(dim=feature_resolution, **args)
         self.out_layer = nn.Linear(self.net.out_features, self.out_features)
+        self._engine, self._key = None, None          # fused with a bottleneck
+        self._engine_plain, self._key_plain = None, None  # out_layer only (forward() on its own)
 
-    def forward(self, x, cond):
-        raise NotImplementedError("grasp encoding is a training-time path (out of scope)")
+    def _pack(self, device, rows, bottleneck):
+        from .r1d import R1dEngine, pack_resnet1d
+        sd = {k: v.detach().float().cpu() for k, v in self.state_dict().items()}
+        lz = self.out_features
+        if bottleneck is not None:
+            bn = {k: v.detach().float().cpu() for k, v in bottleneck.state_dict().items()}
+            head = dict(mu_w=bn["mu.weight"], mu_b=bn["mu.bias"], logvar_w=bn["logvar.weight"], logvar_b=bn["logvar.bias"])
+        else:   # identity bottleneck: mu = out_layer's output
+            head = dict(mu_w=torch.eye(lz), mu_b=torch.zeros(lz), logvar_w=torch.eye(lz), logvar_b=torch.zeros(lz))
+        packed = pack_resnet1d(sd, "net.", groups=self.net.groups, seq_len=self.feature_resolution, cond_rows=rows,
+                               encoder=dict(in_w=sd["in_layer.weight"], in_b=sd["in_layer.bias"],
+                                            out_w=sd["out_layer.weight"], out_b=sd["out_layer.bias"], **head))
+        return R1dEngine(packed, device)
+
+    def _get_engine(self, device, rows, bottleneck=None):
+        from ._cache import params_key, publish
+        params = list(self.parameters()) + (list(bottleneck.parameters()) if bottleneck is not None else [])
+        key = params_key(params, device, rows)
+        if bottleneck is not None:
+            if self._engine is None or self._key != key:
+                self._engine, self._key = self._pack(device, rows, bottleneck), key
+                publish(device)
+            return self._engine
+        if self._engine_plain is None or self._key_plain != key:
+            self._engine_plain, self._key_plain = self._pack(device, rows, None), key
+            publish(device)
+        return self._engine_plain
+
+    @torch.no_grad()
+    def forward(self, x, cond, samples_per_cond=1):
+        """x [n,1,D], cond [n / samples_per_cond, R, Dc] -> [n,1,L] (grasp_vae.py:518-536)."""
+        if not x.is_cuda:
+            raise RuntimeError("x must be a CUDA tensor (graspldm_amd has no CPU path)")
+        eng = self._get_engine(x.device, 1 if cond.ndim == 2 else cond.shape[1])
+        out, _, _ = eng.encode(x.reshape(x.shape[0], -1), eng.cond_embed(cond), samples_per_cond, want_z=False)
+        return out.unsqueeze(-2)
 
 
 class VAEBottleneck(nn.Module):
+    """grasp_vae.py:539-574.  On their own these are two tiny Linears (plain torch on the tensor's device); the fused
+    path (GraspCVAE.encode) never calls them."""
+
     def __init__(self, in_features, latent_size):
         super().__init__()
         self.mu = nn.Linear(in_features, latent_size)
         self.logvar = nn.Linear(in_features, latent_size)
+
+    def reparameterize(self, mu, logvar):
+        std = torch.exp(0.5 * logvar)
+        eps = torch.randn(std.shape).to(std.device)   # CPU generator, then moved (the rule generate_grasps follows)
+        return mu + eps * std
+
+    @torch.no_grad()
+    def forward(self, z):
+        return self.mu(z), self.logvar(z)
 
 
 class PcConditionedGraspEncoder(nn.Module):
@@ -102,6 +151,18 @@ class PcConditionedGraspEncoder(nn.Module):
 
     def get_conditioning_latent(self, xyz):
         return self.encode_pc(xyz)
+
+    @torch.no_grad()
+    def forward(self, xyz, h, z_pc=None):
+        """grasp_vae.py:305-344: (z_grasp [n,1,L], z_pc [n,R,Dc] repeated per grasp).  A given z_pc is taken as the
+        reference takes it: already one row block per grasp."""
+        if not h.is_cuda:
+            raise RuntimeError("h must be a CUDA tensor (graspldm_amd has no CPU path)")
+        if z_pc is not None:
+            return self.grasp_encoder(h.unsqueeze(1), cond=z_pc), z_pc
+        reps = h.shape[0] // xyz.shape[0]
+        z = self.pc_encoder(xyz)
+        return self.grasp_encoder(h.unsqueeze(1), cond=z, samples_per_cond=reps), z.repeat_interleave(reps, dim=0)
 
 
 class GraspCVAE(nn.Module):
@@ -145,5 +206,45 @@ class GraspCVAE(nn.Module):
             z_h = torch.randn(xyz.shape[0] * num_grasps, self.grasp_latent_size)
         return self.decoder(z_h.to(xyz.device), z_pc, samples_per_cond=num_grasps)
 
-    def forward(self, *a, **k):
-        raise NotImplementedError("VAE training forward is out of scope: graspldm_amd is the generation path")
+    @torch.no_grad()
+    def _encode(self, xyz, grasp, eps=None, mix=(1.0, 1.0), eps_times_std=True, want_z=True):
+        """One cloud-encoder pass, one cond_embed, one gldm_encode -> (mu, logvar, z, z_pc [B,R,Dc], grasps per cloud).
+        The cloud latent is shared by index (grasp i -> cloud i // G), like the decoder does."""
+        if not (xyz.is_cuda and grasp.is_cuda):
+            raise RuntimeError("xyz and grasp must be CUDA tensors (graspldm_amd has no CPU path)")
+        assert xyz.ndim == 3, (f"Input pointcloud should be  3-dim tensor of shape [B, N, 3]. "
+                               f"Found a {xyz.ndim} dimensional tensor.")
+        n, b = grasp.shape[0], xyz.shape[0]
+        if n % b:
+            raise RuntimeError(f"{n} grasps do not split over {b} clouds")
+        z_pc = self.encode_pc(xyz)
+        ge = self.encoder.grasp_encoder
+        eng = ge._get_engine(xyz.device, 1 if z_pc.ndim == 2 else z_pc.shape[1], self.bottleneck)
+        mu, logvar, z = eng.encode(grasp, eng.cond_embed(z_pc), n // b, eps=eps, mix=mix, eps_times_std=eps_times_std,
+                                   want_z=want_z)
+        return mu, logvar, z, z_pc, n // b
+
+    @torch.no_grad()
+    def encode(self, xyz, grasp, eps=None):
+        """grasp_vae.py:104-117 -> ((mu, logvar, z), (None, None, z_pc)).  eps [B*G, L] (additive): the normals of the
+        reparameterisation; None draws them on the CPU generator and moves them, so torch.manual_seed reproduces the
+        reference's randn_like stream.  z_pc comes back repeated per grasp [B*G, R, Dc] as in the reference."""
+        if not (xyz.is_cuda and grasp.is_cuda):
+            raise RuntimeError("xyz and grasp must be CUDA tensors (graspldm_amd has no CPU path)")
+        if eps is None:
+            eps = torch.randn(grasp.shape[0], self.grasp_latent_size)
+        mu, logvar, z, z_pc, g = self._encode(xyz, grasp, eps=eps.to(xyz.device))
+        return (mu, logvar, z), (None, None, z_pc.repeat_interleave(g, dim=0))
+
+    def forward(self, xyz, grasp, compute_loss=True, eps=None, **kwargs):
+        """grasp_vae.py:119-147.  compute_loss=False: encode -> reparameterise -> decode, (tmrp, logit).  The losses are
+        training (compute_loss=True, the reference's default, raises)."""
+        if compute_loss:
+            raise NotImplementedError("VAE losses are training-only (out of scope): call forward(xyz, grasp, "
+                                      "compute_loss=False) for the reconstruction")
+        if not (xyz.is_cuda and grasp.is_cuda):
+            raise RuntimeError("xyz and grasp must be CUDA tensors (graspldm_amd has no CPU path)")
+        if eps is None:
+            eps = torch.randn(grasp.shape[0], self.grasp_latent_size)
+        _, _, z, z_pc, g = self._encode(xyz, grasp, eps=eps.to(xyz.device))
+        return self.decoder(z, z_pc, samples_per_cond=g)

@@ -18,7 +18,7 @@ import torch
 
 from .builder import build_model_from_cfg
 from .checkpoint import Experiment, fix_state_dict_prefix, load_weights as _load_weights, model_section  # noqa: F401
-from .r1d import pose_epilogue
+from .r1d import pose_epilogue, pose_prologue
 
 PC_STD, MRP_STD = 0.05, 0.5
 
@@ -99,11 +99,29 @@ class _InferenceBase:
         kw = getattr(self, "_norm", None) or dict(pc_shift=0.0, pc_scale=PC_STD, mrp_scale=MRP_STD, grasp_shift=None)
         return normalize_input(pc.to(self.device), **kw)
 
-    def infer_on_pointcloud(self, pc, num_grasps=10, return_intermediate=False, num_points=None,
-                            use_farthest_point=True):
-        """tools/inference.py:658-666 (= generate_on_pointcloud, grasp_ldm/inference/inference_base.py:161-179).
-        `num_points` (additive): first bring every cloud to the encoder's point count
-        (PointCloudHelpers.regularize_pc_point_count; farthest-point selection by default)."""
+    def _grasp_encoder(self):
+        vae = getattr(self.model, "vae_model", None) or self.model
+        return vae.encoder.grasp_encoder
+
+    def normalize_grasps(self, H, metas, label=None):
+        """Poses in the cloud's (un-normalised) frame -> the encoder's input rows: H [B,G,4,4] (or [G,4,4] for one cloud)
+        -> [B*G, 6|7] = ((t, mrp) - grasp_mean) / grasp_std, with the label column appended when the encoder's in_layer
+        takes 7 features.  label defaults to ones: the success flag the dataset appends to good grasps
+        (dataset/acronym/acronym.py:224).  One HIP launch (gldm_pose_prologue)."""
+        H = H.to(self.device)
+        if H.ndim == 3:
+            H = H.unsqueeze(0)
+        if H.ndim != 4 or H.shape[-2:] != (4, 4):
+            raise RuntimeError(f"grasps must be [B,G,4,4] or [G,4,4], not {tuple(H.shape)}")
+        b, g = H.shape[:2]
+        lab = None
+        if self._grasp_encoder().in_features == 7:
+            lab = torch.ones(b * g, device=self.device) if label is None else label.to(self.device).reshape(-1).float()
+        return pose_prologue(H.reshape(b * g, 4, 4), lab, metas["grasp_mean"].to(self.device),
+                             metas["grasp_std"].to(self.device), g)
+
+    def prepare_pointcloud(self, pc, num_points=None, use_farthest_point=True):
+        """The front half of infer_on_pointcloud: bring a raw cloud to the encoder's point count, normalise -> (pc, metas)."""
         pc = pc.to(self.device)
         if num_points is not None and pc.shape[-2] != num_points:
             from .pointcloud import PointCloudHelpers
@@ -111,7 +129,14 @@ class _InferenceBase:
             reg = torch.stack([PointCloudHelpers.regularize_pc_point_count(c, num_points, use_farthest_point)
                                for c in clouds])
             pc = reg[0] if pc.ndim == 2 else reg
-        pcn, metas = self.normalize_input(pc)
+        return self.normalize_input(pc)
+
+    def infer_on_pointcloud(self, pc, num_grasps=10, return_intermediate=False, num_points=None,
+                            use_farthest_point=True):
+        """tools/inference.py:658-666 (= generate_on_pointcloud, grasp_ldm/inference/inference_base.py:161-179).
+        `num_points` (additive): first bring every cloud to the encoder's point count
+        (PointCloudHelpers.regularize_pc_point_count; farthest-point selection by default)."""
+        pcn, metas = self.prepare_pointcloud(pc, num_points, use_farthest_point)
         return self.generate_grasps(pcn, metas, num_grasps=num_grasps, return_intermediate=return_intermediate)
 
     generate_on_pointcloud = infer_on_pointcloud
@@ -196,6 +221,25 @@ class InferenceLDM(_InferenceBase):
                                                           return_intermediate=return_intermediate, x_T=x_T, **extra)
         return self._results(batch, metas, tmrp, logit, batch.shape[0], num_grasps, all_steps=steps)
 
+    @torch.no_grad()
+    def refine_grasps(self, pc, metas, H, strength=0.3, noise=None, **kwargs):
+        """Reverse diffusion started from given grasps H [B,G,4,4] (cloud frame, un-normalised) instead of from noise
+        (GraspLatentDDM.refine_grasps).  Same result dict as generate_grasps, plus latent_mu / latent_logvar [B,G,L]."""
+        batch = (pc.unsqueeze(0) if pc.ndim == 2 else pc).to(self.device)
+        if self.fast_sampler in ("DPMPP", "HEUN"):
+            raise NotImplementedError("refine_grasps runs the DDIM / DDPM samplers only")
+        if self.num_inference_steps is not None:
+            self.model.set_inference_timesteps(self.num_inference_steps)
+        h = self.normalize_grasps(H, metas, label=kwargs.pop("label", None))
+        g = h.shape[0] // batch.shape[0]
+        extra = {k: kwargs[k] for k in ("step_noise", "cls_cond", "noise_source", "noise_seed", "noise_base") if k in kwargs}
+        if hasattr(self.model.diffusion_model.model, "class_embedding"):
+            extra["metas"] = {k: (v.to(self.device) if isinstance(v, torch.Tensor) else v) for k, v in metas.items()}
+        (tmrp, logit), lat = self.model._refine(batch, h, strength, noise=noise, **extra)
+        out = self._results(batch, metas, tmrp, logit, batch.shape[0], g)
+        out["latent_mu"], out["latent_logvar"] = lat["mu"].view(batch.shape[0], g, -1), lat["logvar"].view(batch.shape[0], g, -1)
+        return out
+
 
 class InferenceVAE(_InferenceBase):
     def __init__(self, exp_name=None, exp_out_root=None, use_ema_model=True, data_root=None, data_split="test",
@@ -217,4 +261,19 @@ class InferenceVAE(_InferenceBase):
         tmrp, logit = self.model.generate_grasps(batch, num_grasps, z_h=z_h)
         out = self._results(batch, metas, tmrp, logit, batch.shape[0], num_grasps)
         out.pop("all_steps_grasps")
+        return out
+
+    @torch.no_grad()
+    def reconstruct_grasps(self, pc, metas, H, eps=None, **kwargs):
+        """Given grasps H [B,G,4,4] (cloud frame, un-normalised) through the VAE: normalise -> encode -> decode
+        (GraspCVAE.forward(compute_loss=False)).  eps [B*G, L]: the normals of the reparameterisation; None decodes the
+        mean (z = mu).  Same result dict as generate_grasps, plus latent_mu / latent_logvar [B,G,L]."""
+        batch = (pc.unsqueeze(0) if pc.ndim == 2 else pc).to(self.device)
+        h = self.normalize_grasps(H, metas, label=kwargs.pop("label", None))
+        vae = getattr(self.model, "vae_model", None) or self.model
+        mu, logvar, z, z_pc, g = vae._encode(batch, h, eps=None if eps is None else eps.to(self.device))
+        tmrp, logit = vae.decoder(z, z_pc, samples_per_cond=g)
+        out = self._results(batch, metas, tmrp, logit, batch.shape[0], g)
+        out.pop("all_steps_grasps")
+        out["latent_mu"], out["latent_logvar"] = mu.view(batch.shape[0], g, -1), logvar.view(batch.shape[0], g, -1)
         return out

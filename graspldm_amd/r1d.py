@@ -1,6 +1,6 @@
 """Device-side handle of one packed 1-D ResNet (denoiser or pose decoder):
 owns the packed weight buffer on the GPU and calls the fused HIP engine through
-the C ABI (gldm_r1d_cond_embed / gldm_denoise / gldm_decode)."""
+the C ABI (gldm_r1d_cond_embed / gldm_denoise / gldm_decode / gldm_encode)."""
 import ctypes
 
 import torch
@@ -147,6 +147,28 @@ class R1dEngine:
                    n, L.ptr(tmrp), L.ptr(logit), L.ptr(ws), L.current_stream(self.device))
         return tmrp, logit
 
+    def encode(self, h, cemb, samples_per_cond, eps=None, mix=(1.0, 1.0), eps_times_std=True, want_z=True):
+        """Grasp encoder + bottleneck in one launch: h [n, 6|7] -> (mu, logvar, z) [n, Lz] each, with
+        z = mix[0] mu + mix[1] eps (exp(logvar / 2) if eps_times_std); eps None: z = mix[0] mu; want_z False: z is None."""
+        n = h.shape[0]
+        h = h.reshape(n, -1).contiguous().float()
+        if h.shape[1] != int(self.desc.latent_dim):
+            raise RuntimeError(f"h has {h.shape[1]} columns; this encoder's in_layer takes {int(self.desc.latent_dim)}")
+        lz = int(self.desc.n_head) // 2
+        if eps is not None:
+            eps = eps.reshape(n, -1).contiguous().float()
+            if eps.shape[1] != lz or eps.device != self.device:
+                raise RuntimeError(f"eps must be [n, {lz}] on {self.device}")
+        mu = torch.empty((n, lz), dtype=torch.float32, device=self.device)
+        logvar = torch.empty_like(mu)
+        z = torch.empty_like(mu) if want_z else None
+        ws = self._workspace(n)
+        with torch.cuda.device(self.device):
+            L.call("gldm_encode", self._desc_ptr(), L.ptr(self.weights), L.ptr(cemb), int(samples_per_cond), L.ptr(h), n,
+                   L.ptr(eps), float(mix[0]), float(mix[1]), 1 if eps_times_std else 0, L.ptr(mu), L.ptr(logvar), L.ptr(z),
+                   L.ptr(ws), L.current_stream(self.device))
+        return mu, logvar, z
+
 
 def step_noise_rng(noise_seed, noise_base, step, n, seq_len, device):
     """[n, seq_len] unit normals: exactly what denoise_rng adds at `step` to latents noise_base .. noise_base + n - 1."""
@@ -189,3 +211,25 @@ def pose_epilogue(tmrp, logit, grasp_mean, grasp_std, grasps_per_cloud):
         L.call("gldm_pose_epilogue", L.ptr(tm), L.ptr(lg), L.ptr(gm), L.ptr(gs), n, gpc, n_clouds,
                L.ptr(H), L.ptr(un), L.ptr(conf), L.current_stream(dev))
     return H, un, conf
+
+
+def pose_prologue(H, label, grasp_mean, grasp_std, grasps_per_cloud):
+    """H_to_tmrp + normalise (+ label column) in one launch, the inverse of pose_epilogue
+    (utils/rotations.py:305-309; the dataset's (x - mean) / std).  H [n,4,4]; label [n] or None -> [n, 7 | 6]."""
+    H = H.reshape(-1, 4, 4).contiguous().float()
+    n = H.shape[0]
+    dev = H.device
+    gpc = int(grasps_per_cloud)
+    if gpc <= 0 or n % gpc:
+        raise RuntimeError(f"{n} grasps do not split into clouds of {gpc}")
+    n_clouds = n // gpc
+    lb = label.to(dev).reshape(-1).contiguous().float() if label is not None else None
+    if lb is not None and lb.numel() != n:
+        raise RuntimeError(f"label has {lb.numel()} entries for {n} grasps")
+    gm = _per_cloud_rows(grasp_mean.to(dev), n_clouds, "grasp_mean")
+    gs = _per_cloud_rows(grasp_std.to(dev), n_clouds, "grasp_std")
+    out = torch.empty((n, 7 if lb is not None else 6), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        L.call("gldm_pose_prologue", L.ptr(H), L.ptr(lb), L.ptr(gm), L.ptr(gs), n, gpc, n_clouds, L.ptr(out),
+               L.current_stream(dev))
+    return out

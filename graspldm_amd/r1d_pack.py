@@ -18,6 +18,8 @@ MAX_LEVELS = 6
 MAX_RESBLOCKS = 2 * MAX_LEVELS + 1
 SCHED_NONE, SCHED_DDIM, SCHED_DDPM = 0, 1, 2
 SCHED_COEF_STRIDE = 8
+HEAD_DECODER, HEAD_ENCODER = 0, 1
+MAX_LATENT = 32
 
 
 class R1dResblock(ctypes.Structure):
@@ -44,7 +46,8 @@ class R1dDesc(ctypes.Structure):
                 ("rb", R1dResblock * MAX_RESBLOCKS), ("lv", R1dLevel * MAX_LEVELS),
                 ("final_w", ctypes.c_int32), ("final_b", ctypes.c_int32),
                 ("latent_dim", ctypes.c_int32), ("in_w", ctypes.c_int32), ("in_b", ctypes.c_int32),
-                ("head_w", ctypes.c_int32), ("head_b", ctypes.c_int32), ("n_head", ctypes.c_int32)]
+                ("head_w", ctypes.c_int32), ("head_b", ctypes.c_int32), ("n_head", ctypes.c_int32),
+                ("head_kind", ctypes.c_int32)]
 
 
 def mfma_a_fragments(w2d):
@@ -154,11 +157,15 @@ def time_embedding_table(sd, p, num_steps):
     return F.linear(F.gelu(h), sd[p + "time_mlp.3.weight"], sd[p + "time_mlp.3.bias"]).contiguous()
 
 
-def pack_resnet1d(sd, p, groups, seq_len, cond_rows=3, num_steps=None, decoder=None):
+def pack_resnet1d(sd, p, groups, seq_len, cond_rows=3, num_steps=None, decoder=None, encoder=None):
     """sd: flat state dict (CPU f32), p: prefix of the ResNet1D / TimeConditionedResNet1D.
     decoder: None or dict(in_w, in_b, tmrp_w, tmrp_b, cls_w, cls_b) for the pose decoder.
+    encoder: None or dict(in_w, in_b, out_w, out_b, mu_w, mu_b, logvar_w, logvar_b) for the grasp encoder (exclusive with
+    decoder): out_layer is folded into the bottleneck, head rows [W_mu W_out; W_logvar W_out] (f64, rounded once).
     Returns dict(desc=R1dDesc, weights=f32 tensor, temb=[T,E] or None,
                  cond_w=[E,Dc], cond_b=[E])."""
+    if decoder is not None and encoder is not None:
+        raise ValueError("decoder= and encoder= are exclusive: one network has one head")
     sd = {k: v.detach().float().cpu() for k, v in sd.items() if k.startswith(p)}
     d = R1dDesc()
     buf = _Buf()
@@ -274,6 +281,23 @@ def pack_resnet1d(sd, p, groups, seq_len, cond_rows=3, num_steps=None, decoder=N
         d.head_w = buf.add(torch.cat([decoder["tmrp_w"], decoder["cls_w"]]))
         d.head_b = buf.add(torch.cat([decoder["tmrp_b"], decoder["cls_b"]]))
         d.n_head = 7
+        d.head_kind = HEAD_DECODER
+    elif encoder is not None:
+        enc = {k: v.detach().cpu().double() for k, v in encoder.items()}
+        if enc["in_w"].shape[0] != seq_len or enc["out_w"].shape[1] != seq_len:
+            raise ValueError("in_layer must map the grasp row to seq_len features and out_layer read seq_len features")
+        lz = enc["mu_w"].shape[0]
+        if enc["logvar_w"].shape[0] != lz or lz > MAX_LATENT:
+            raise ValueError(f"mu / logvar must have the same number of rows, at most {MAX_LATENT}")
+        d.latent_dim = enc["in_w"].shape[1]
+        d.in_w = buf.add(enc["in_w"].float())
+        d.in_b = buf.add(enc["in_b"].float())
+        # nothing sits between out_layer and the bottleneck (grasp_vae.py:113-115): W (W_out x + b_out) + b, exact algebra
+        d.head_w = buf.add(torch.cat([enc["mu_w"] @ enc["out_w"], enc["logvar_w"] @ enc["out_w"]]).float())
+        d.head_b = buf.add(torch.cat([enc["mu_w"] @ enc["out_b"] + enc["mu_b"],
+                                      enc["logvar_w"] @ enc["out_b"] + enc["logvar_b"]]).float())
+        d.n_head = 2 * lz
+        d.head_kind = HEAD_ENCODER
     else:
         d.latent_dim = 0
     d.seq_len = seq_len

@@ -210,8 +210,14 @@ typedef struct gldm_r1d_desc {
   int32_t latent_dim;   /* D of z_h; 0 for the denoiser                           */
   int32_t in_w, in_b;   /* in_layer [L][D], [L]                                   */
   int32_t head_w, head_b; /* rows tmrp(6) then class_logits(1): [7][L], [7]       */
-  int32_t n_head;       /* 7                                                      */
+  int32_t n_head;       /* 7 (decoder) or 2 * latent size (encoder)               */
+  int32_t head_kind;    /* ABI 11: GLDM_HEAD_DECODER (0: rows 0..5 tmrp, row 6 logit) or GLDM_HEAD_ENCODER: n_head = 2 Lz
+                           rows [2 Lz][L], rows 0..Lz-1 = W_mu W_out, rows Lz..2 Lz-1 = W_logvar W_out, biases folded
+                           likewise (grasp_vae.py:113-115,532-536: nothing sits between out_layer and the bottleneck);
+                           Lz <= GLDM_R1D_MAX_LATENT */
 } gldm_r1d_desc;
+enum gldm_head_kind { GLDM_HEAD_DECODER = 0, GLDM_HEAD_ENCODER = 1 };
+#define GLDM_R1D_MAX_LATENT 32
 
 enum gldm_sched_kind { GLDM_SCHED_NONE = 0, GLDM_SCHED_DDIM = 1, GLDM_SCHED_DDPM = 2, GLDM_SCHED_DPMPP = 3 };
 #define GLDM_SCHED_COEF_STRIDE 8
@@ -298,6 +304,28 @@ int gldm_step_noise_rng(unsigned long long noise_seed, long long noise_base, int
 int gldm_decode(const gldm_r1d_desc *desc, const float *weights, const float *cemb, int samples_per_cond,
                 const float *z_h /*[n,D]*/, int n_samples, float *tmrp /*[n,6]*/, float *logit /*[n,1]*/,
                 void *workspace, gldm_stream_t stream);
+
+/* ref: grasp_ldm/models/grasp_vae.py:104-117 (GraspCVAE.encode) = :518-536 (ConditionalGraspPoseEncoder.forward:
+ * in_layer -> ResNet1D -> out_layer) + :552-574 (VAEBottleneck.forward and .reparameterize), one engine launch on the
+ * engine gldm_decode takes for the same descriptor.  `desc` carries the encoder head (GLDM_HEAD_ENCODER, Lz = n_head / 2);
+ * h [n, latent_dim] is the normalised grasp row [t, mrp(, label)].  mu / logvar [n, Lz]; when z is given,
+ *   z = mix_mu * mu + mix_eps * eps * (eps_times_std ? exp(0.5 * logvar) : 1)      (eps NULL: z = mix_mu * mu)
+ * (1, 1, 1) is reparameterize; (sqrt(abar_t), sqrt(1 - abar_t), 0) is the scheduler's add_noise of mu to timestep t,
+ * the start of a partial reverse diffusion.  Workspace as gldm_decode.  A decoder descriptor is GLDM_ERR_INVALID_ARG
+ * (and gldm_decode rejects an encoder one). */
+int gldm_encode(const gldm_r1d_desc *desc, const float *weights, const float *cemb, int samples_per_cond,
+                const float *h /*[n,latent_dim]*/, int n_samples, const float *eps /*[n,Lz] or NULL*/, float mix_mu,
+                float mix_eps, int eps_times_std, float *mu /*[n,Lz]*/, float *logvar /*[n,Lz]*/,
+                float *z /*[n,Lz] or NULL*/, void *workspace, gldm_stream_t stream);
+
+/* ref: grasp_ldm/utils/rotations.py:305-309 (H_to_tmrp) with :115-163 (rotmat_to_mrp: arg-max over R00, R11, R22, trace
+ * with the first maximum winning a tie, the SciPy branch formulas, normalise, q.xyz / (1 + q.w); NOT canonicalised: the
+ * shadow set |m| > 1 comes back when the chosen branch gives w < 0) + the dataset's normalisation, the inverse of
+ * gldm_pose_epilogue:  h[i, 0..5] = ((t, mrp) - mean) / std,  h[i, 6] = label[i] when label is given (width 7, else 6).
+ * mean / std per cloud as in gldm_pose_epilogue. */
+int gldm_pose_prologue(const float *H /*[n,4,4]*/, const float *label /*[n] or NULL*/, const float *grasp_mean,
+                       const float *grasp_std, int n, int grasps_per_cloud, int n_clouds, float *h /*[n,6|7]*/,
+                       gldm_stream_t stream);
 
 /* ref: tools/inference.py:64-94,628-647 + grasp_ldm/utils/rotations.py:171-302:
  * un = tmrp*std+mean; H = tmrp_to_H(un); conf = sigmoid(logit).  mean AND std are

@@ -7,7 +7,10 @@ Additive flags: --pc_file FILE [--num_points N] (generate on a sensor cloud read
 the reference's `generate_on_pointcloud`, grasp_ldm/inference/inference_base.py:161-212, which its own CLI does not
 reach -- it only iterates ACRONYM items, tools/generate_grasps.py:109-131), --device, --seed, --synthetic N (run on N-point synthetic object clouds with
 the synthetic weight recipe when no experiment directory / ACRONYM data is available; there is
-no network here for either), --out FILE.npz.  `--inference_steps` is honoured (the reference
+no network here for either), --out FILE.npz, --refine_from FILE [--refine_strength S] (start from given grasps instead of
+from noise: with --mode VAE the file's grasps are reconstructed through the VAE, with --mode LDM they are encoded, diffused
+forward to `S` of the schedule and denoised again; FILE is .npy / .npz key `grasps`, [G,4,4] or [B,G,4,4] -- one set per
+sample / cloud file in order --, un-normalised, in the cloud's frame; --num_grasps is taken from the file then).  `--inference_steps` is honoured (the reference
 silently ignores it: it passes use_fast_sampler=False, tools/generate_grasps.py:69-79).
 """
 import argparse
@@ -46,6 +49,12 @@ def parse_args(argv=None):
                    help="encoder point count for --pc_file (default: the model's pc encoder n_points)")
     p.add_argument("--random_resample", action="store_true",
                    help="with --pc_file: random subsampling instead of farthest-point selection")
+    p.add_argument("--refine_from", type=str, default=None, metavar="FILE",
+                   help="grasps to start from ([G,4,4] or [B,G,4,4], .npy or .npz key `grasps`; cloud frame, un-normalised): "
+                        "reconstructed (--mode VAE) or refined by partial reverse diffusion (--mode LDM)")
+    p.add_argument("--refine_strength", type=float, default=0.3,
+                   help="with --refine_from and --mode LDM: the share of the schedule to diffuse forward and denoise again "
+                        "(0 = decode the encoder's mean, 1 = the whole schedule)")
     p.add_argument("--out", type=str, default=None, help="write results of all samples to this .npz")
     return p.parse_args(argv)
 
@@ -71,8 +80,44 @@ def setup_model(args):
                         use_ema_model=args.use_ema_model, device=args.device)
 
 
+def read_grasp_file(path):
+    """[G,4,4] or [B,G,4,4] float32 from .npy / .npz (key `grasps`) -> tensor [B,G,4,4] (B = 1 for a single set)."""
+    z = np.load(path)
+    if hasattr(z, "files"):
+        if "grasps" not in z.files:
+            raise SystemExit(f"{path}: no array named `grasps` (found {list(z.files)})")
+        z = z["grasps"]
+    H = np.asarray(z, dtype=np.float32)
+    if H.ndim == 3:
+        H = H[None]
+    if H.ndim != 4 or H.shape[-2:] != (4, 4) or H.shape[1] == 0:
+        raise SystemExit(f"{path}: grasps must be [G,4,4] or [B,G,4,4], found {H.shape}")
+    if not np.isfinite(H).all():
+        raise SystemExit(f"{path}: grasps hold non-finite entries")
+    return torch.from_numpy(H)
+
+
+def run_one(args, model, pcn, metas, start, i):
+    """One cloud: generation, or reconstruction / refinement of the i-th grasp set of --refine_from."""
+    if start is None:
+        return model.generate_grasps(pcn, metas, num_grasps=args.num_grasps)
+    H = start[i if start.shape[0] > 1 else 0].unsqueeze(0)
+    if args.mode == "LDM":
+        return model.refine_grasps(pcn, metas, H, strength=args.refine_strength)
+    return model.reconstruct_grasps(pcn, metas, H)
+
+
 def main(argv=None):
     args = parse_args(argv)
+    start = None
+    if args.refine_from:
+        if not 0.0 <= args.refine_strength <= 1.0:
+            raise SystemExit("--refine_strength must lie in [0, 1]")
+        start = read_grasp_file(args.refine_from)
+        args.num_grasps = int(start.shape[1])
+        want = len(args.pc_file) if args.pc_file else args.num_samples
+        if start.shape[0] not in (1, want):
+            raise SystemExit(f"--refine_from holds {start.shape[0]} grasp sets for {want} clouds (one set, or one per cloud)")
     if args.conditioning != "unconditional":
         raise SystemExit("class / region conditioned models are not shipped with the reference (out of scope)")
     if args.visualize:
@@ -88,8 +133,12 @@ def main(argv=None):
         n_pts = args.num_points or encoder_points(model.model)
         for path in args.pc_file:
             pc = torch.from_numpy(read_cloud_file(path))
-            res = model.infer_on_pointcloud(pc, num_grasps=args.num_grasps, num_points=n_pts,
-                                            use_farthest_point=not args.random_resample)
+            if start is None:
+                res = model.infer_on_pointcloud(pc, num_grasps=args.num_grasps, num_points=n_pts,
+                                                use_farthest_point=not args.random_resample)
+            else:
+                pcn, metas = model.prepare_pointcloud(pc, num_points=n_pts, use_farthest_point=not args.random_resample)
+                res = run_one(args, model, pcn, metas, start, len(results))
             conf = res["confidence"].flatten()
             print(f"{path}: {pc.shape[0]} points -> {n_pts}; grasps {tuple(res['grasps'].shape)}  "
                   f"confidence mean {conf.mean().item():.3f}  best {conf.max().item():.3f}")
@@ -103,7 +152,7 @@ def main(argv=None):
         else:
             raise SystemExit("ACRONYM dataset loading is out of scope: pass the object's cloud with --pc_file FILE "
                              "(.npy / .ply / ...), or run on synthetic clouds with --synthetic N")
-        res = model.generate_grasps(pc, metas, num_grasps=args.num_grasps)
+        res = run_one(args, model, pc, metas, start, i)
         conf = res["confidence"].flatten()
         print(f"sample {i}: cloud #{idx}  grasps {tuple(res['grasps'].shape)}  "
               f"confidence mean {conf.mean().item():.3f}  best {conf.max().item():.3f}")
@@ -123,9 +172,11 @@ def encoder_points(model):
 
 def finish(args, results):
     if args.out:
+        extra = {k: torch.cat([r[k] for r in results]).cpu().numpy() for k in ("latent_mu", "latent_logvar")
+                 if all(k in r for r in results)}
         np.savez_compressed(args.out, grasps=torch.cat([r["grasps"] for r in results]).cpu().numpy(),
                             grasp_tmrp=torch.cat([r["grasp_tmrp"] for r in results]).cpu().numpy(),
-                            confidence=torch.cat([r["confidence"] for r in results]).cpu().numpy())
+                            confidence=torch.cat([r["confidence"] for r in results]).cpu().numpy(), **extra)
         print("wrote", args.out)
     return results
 
