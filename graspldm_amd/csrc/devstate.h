@@ -34,12 +34,10 @@ inline int cu_count() {
   return n;
 }
 
-// Raise a kernel's dynamic-LDS limit to at least `bytes` on the current device.  `Tag` makes one array per call site
-// (= per kernel); the array holds the largest size already set, so a later call that asks for more re-applies the
-// attribute, and two threads racing on the first launch both set it (the launch of either then finds it set).
-template <class Tag>
-inline void allow_dynamic_lds(const void *kernel, int bytes) {
-  static std::atomic<int> set_bytes[kMaxDevices];
+// Raise a kernel's dynamic-LDS limit to at least `bytes` on the current device.  `set_bytes` is that kernel's array: it
+// holds the largest size already set, so a later call that asks for more re-applies the attribute, and two threads racing
+// on the first launch both set it (the launch of either then finds it set).
+inline void raise_dynamic_lds(std::atomic<int> (&set_bytes)[kMaxDevices], const void *kernel, int bytes) {
   const int dev = current_device();
   if (dev >= 0 && set_bytes[dev].load(std::memory_order_acquire) >= bytes) return;
   (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
@@ -48,6 +46,22 @@ inline void allow_dynamic_lds(const void *kernel, int bytes) {
     while (cur < bytes && !set_bytes[dev].compare_exchange_weak(cur, bytes, std::memory_order_release)) {
     }
   }
+}
+
+// `Tag` makes one array per call site (= per kernel).
+template <class Tag>
+inline void allow_dynamic_lds(const void *kernel, int bytes) {
+  static std::atomic<int> set_bytes[kMaxDevices];
+  raise_dynamic_lds(set_bytes, kernel, bytes);
+}
+
+// Keyed on the kernel itself (one array per kernel), with the launch behind it: `lds_bytes` of dynamic LDS under a limit
+// raised to at least `limit_bytes`.  The caller reads hipGetLastError().
+template <auto Kernel, class... Args>
+inline void launch_dynamic_lds(dim3 grid, dim3 block, int limit_bytes, size_t lds_bytes, hipStream_t stream, Args... args) {
+  static std::atomic<int> set_bytes[kMaxDevices];
+  raise_dynamic_lds(set_bytes, reinterpret_cast<const void *>(Kernel), limit_bytes);
+  hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, stream, args...);
 }
 
 }  // namespace gldm_dev

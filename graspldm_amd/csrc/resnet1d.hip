@@ -1,125 +1,31 @@
-// resnet1d.hip -- the fused 1-D ResNet engine of GraspLDM on gfx950:
-//   * gldm_denoise : the whole reverse-diffusion loop (T steps of
-//                    TimeConditionedResNet1D.forward + DDIM/DDPM update) in ONE
-//                    launch; the latent never leaves the chip between steps;
-//   * gldm_decode  : ConditionalGraspPoseDecoder.forward (in_layer, ResNet1D,
-//                    tmrp / class_logits heads);
-//   * gldm_sa_mlp_forward : the fused set-abstraction core (gather + grouped MLP + max)
-//                    on the same GEMM core;
-//   * gldm_encode  : GraspCVAE.encode (in_layer, ResNet1D, out_layer folded into the
-//                    bottleneck's mu / logvar, reparameterisation), the same engine.
-//   * gldm_r1d_cond_embed, gldm_pose_prologue, gldm_pose_epilogue : the small ops either side.
-//
-// Mapping to CDNA4
-//   A workgroup owns a tile of NC activation columns = NC/L samples x L positions and walks
-//   every layer with activations resident in LDS as [channel][column] (XOR-swizzled so MFMA
-//   B-fragment reads are conflict free).  Two geometries are built from one template:
-//     NC = 32: 4 waves, 80 KiB LDS  -> TWO workgroups per CU.  The network is ~50 short
-//              barrier-separated phases per step; a second, independent workgroup fills the
-//              MFMA pipe while the first sits in a norm pass, a barrier or an L2 round trip.
-//              This is the production geometry of the denoiser / decoder.
-//     NC = 64: 8 waves, 150 KiB LDS -> one workgroup per CU (fused set abstraction: one centre
-//              with U = 64 neighbours per tile).
-//   Every conv / 1x1 is a GEMM  W[Cout x taps*Cin] * X[taps*Cin x NC]  on
-//   v_mfma_f32_16x16x4_f32 (exact f32: the parity budget is 1e-4 on poses after 100 steps and
-//   the reference's eps is dtype dependent, so no bf16 here).  Weights (standardised and laid
-//   out in fragment order on the host) stream L2 -> VGPR as 16-byte coalesced global loads, a
-//   few 16-channel blocks ahead; B operands are unconditional, batched LDS reads.  k = 3 convs
-//   keep one accumulator set per tap on UNSHIFTED columns and apply the halo shift once to the
-//   result tiles (lane shifts inside the 16-lane rows of the C/D layout), so the k-loop is
-//   loads + MFMA only (tap-major: a tap's fragment registers are refilled right after its sweep).
-//   GroupNorm, the time/condition scale-shift, SiLU and the residual add live in the conv epilogue
-//   (statistics over the wave's own accumulators); LayerNorm / softmax run with lane = (row slot,
-//   column) and reduce with DPP / permlane swaps.  The step is a tape of ~48 ops in LDS, interpreted
-//   by a switch with every phase inlined (see run_tape).
-//   LinearAttention at n = L is reassociated:  out = V (K^T Q)  (an L x L matrix per sample
-//   and head) instead of (V K^T) Q: 8x fewer FLOPs, same math.
-#include <hip/hip_runtime.h>
-#include <type_traits>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-
-#include "gldm.h"
-#include "wstream.h"
-#include "devstate.h"
-
-#define GLDM_API extern "C" __attribute__((visibility("default")))
-
-// Diagnostic knobs (phase skipping, per-op cycle stamps, workgroup stagger) exist only in builds made
-// with -DGLDM_DEBUG_KNOBS (make EXTRA=-DGLDM_DEBUG_KNOBS); the shipped kernels contain none of them.
-#ifdef GLDM_DEBUG_KNOBS
-#define GLDM_SKIP(c, bit) ((c).skip & (bit))
-#define GLDM_STAMPS(p) (p)
-#else
-#define GLDM_SKIP(c, bit) false
-#define GLDM_STAMPS(p) ((long long *)nullptr)
-#endif
+// resnet1d.hip -- the fused 1-D ResNet engine of GraspLDM on gfx950 and the small ops either side:
+//   * gldm_denoise[_rng] : the whole reverse-diffusion loop (T steps of TimeConditionedResNet1D.forward + the scheduler
+//                          update) in ONE launch; the latent never leaves the chip between steps;
+//   * gldm_decode        : ConditionalGraspPoseDecoder.forward (in_layer, ResNet1D, tmrp / class_logits heads);
+//   * gldm_encode        : GraspCVAE.encode (in_layer, ResNet1D, out_layer folded into mu / logvar, reparameterisation);
+//   * gldm_r1d_cond_embed, gldm_pose_prologue, gldm_pose_epilogue, gldm_step_noise_rng; ss_table_kernel (the per-cloud
+//     scale / shift table of nets without a time embedding) runs in front of decode / encode.
+// One kernel template, r1d_kernel<NC, L>: a workgroup owns NC activation columns = NC / L samples x L positions and walks
+// every layer with the activations resident in LDS; weights (standardised, folded and laid out in fragment order by
+// r1d_pack.py) stream L2 -> VGPR.  GroupNorm, the time / condition scale-shift, SiLU and the residual add live in the conv
+// epilogues; LinearAttention at n = L is reassociated, out = V (K^T Q); persistent workgroups splice the left-over tiles'
+// steps between them over {value, tag} granules in global memory (the chain).  Four instantiations:
+//   <64, 4>   the shipped latent denoiser: 8 waves, one workgroup per CU, position-major columns (16 position + sample: a
+//             k = 3 tap is the neighbouring n-tile), GEMMs on the f16 matrix pipe through the hi + lo split with the B
+//             operands in LDS as pre-split planes (conv_pm3_wave, gemm_pm3_pl); a ResnetBlock is one op; the 4 / 32 /
+//             64-channel levels are one wave-local op in registers (quad_narrow.h).
+//   <64, 16>  the shipped pose decoder, grasp encoder and 16-position denoiser: column = 4 position + sample, zero-padded
+//             plane rows so that taps are shifted reads (gemm_sm3_pl); narrow levels in quad16_narrow.h, qkv_att16_pm.
+//   <32, *>   the f32 engine (numerics.f32_only(), and every descriptor outside pm_supported() / pm16_supported()): 4 waves,
+//             two workgroups per CU, sample-major columns, v_mfma_f32_16x16x4_f32 through mfma_core.h's conv_gemm.
+// The step is a tape of ops built on the host (build_tape) and interpreted by run_tape with every phase inlined: in the
+// kernel arguments (RunArgs::pm_tape) for the 64-column engines, built in LDS by the 32-column one.
+// Device code first (engine pieces, the network, r1d_kernel, the small kernels), then the host side, then the entry points.
+#include "mfma_core.h"
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-typedef __attribute__((address_space(3))) float lds_f;   // explicit LDS pointers: 32-bit ds_* addressing
-typedef __attribute__((address_space(3))) f32x4 lds_f4;
-
-constexpr int kHeads = 4, kDimHead = 32, kHidden = kHeads * kDimHead;  // LinearAttention defaults
-constexpr int kMaxC = 256;
 constexpr int kMaxSegs = 64;  // tiles (+ one spliced step segment) a persistent workgroup can be given
-
-// Geometry and LDS map (floats) of one workgroup.  X: block input / residual stream, H: scratch.
-template <int NC>
-struct Geo {
-  static constexpr int kWaves = NC / 8;           // 8 waves at 64 columns, 4 at 32
-  static constexpr int kThreads = kWaves * 64;
-  static constexpr int kNT = NC / 16;             // 16-column n-tiles
-  static constexpr int kRP = 64 / NC;             // rows a wave touches per pass: lane = (sub, column)
-  static constexpr int kSlots = kWaves * kRP;     // row slots of the norm passes
-  static constexpr int kBufX = 0;
-  static constexpr int kBufH = kMaxC * NC;
-  static constexpr int kBufY = 128 * NC;          // attention: LayerNorm output, later to_out output
-  static constexpr int kBufO = kBufH;             // attention output, 128 rows
-  static constexpr int kBufQKV = kBufO + kHidden * NC;  // two heads of q,k,v: 192 rows
-  static constexpr int kArena = kBufQKV + 192 * NC;
-  static constexpr int kMiscLat = kArena;         // [NC] current latent row
-  static constexpr int kMiscEps = kMiscLat + NC;
-  static constexpr int kMiscG = kMiscEps + NC;    // [S][E] <= 320
-  static constexpr int kMiscRed1 = kMiscG + 320;  // [kWaves][NC] cross-wave exchange slots (per wave and column)
-  static constexpr int kMiscRed2 = kMiscRed1 + kWaves * NC;
-  static constexpr int kMiscTape = kMiscRed2 + kWaves * NC;  // [kMaxOps][12] ints: the step program (+ its length)
-  static constexpr int kMiscSegs = kMiscTape + 1024;         // [kMaxSegs][4] ints: this workgroup's (tile, s0, s1) list
-  static constexpr int kMiscOld = kMiscSegs + 256;           // [NC] previous step's denoised row (DPM++ 2M)
-  // 64-column engines: per-sample range of a ResnetBlock's H (conv_pm3_wave): [8 waves][16] published bounds, [16] scales
-  static constexpr int kMiscHb = kMiscOld + NC;
-  static constexpr int kMiscHs = kMiscHb + (NC == 64 ? 8 * 16 : 0);
-  static constexpr int kMiscQ = kMiscHs + (NC == 64 ? 16 : 0);    // quad engine hand-shake words (quad_narrow.h): 8 + 4 x 64 ints
-  static constexpr int kMiscQTab = kMiscQ + (NC == 64 ? 16 + 4 * 64 : 0);   // [2 x 380] byte offsets of the quad engines' weight streams (292 / 336 / 380 fragments)
-  static constexpr int kLdsFloats = kMiscQTab + (NC == 64 ? 2 * 380 : 0);
-};
-static_assert(Geo<64>::kLdsFloats * 4 <= 160 * 1024, "LDS budget (1 WG/CU)");
-static_assert(Geo<32>::kLdsFloats * 4 * 2 <= 160 * 1024, "LDS budget (2 WG/CU)");
-
-// (Tried: XOR with row bit 0 ^ row bit 2, which also frees the accumulator stores (rows 4 kq + r) of their 2-way bank
-// conflict.  The B-fragment reads of a k-block then need two base registers instead of one with immediate offsets,
-// and every GEMM phase got 5-7 % slower.)
-template <int NC>
-__device__ __forceinline__ int swz(int row, int col) { return row * NC + (col ^ ((row & 1) << 4)); }
-
-// Position-major engine (64 columns, split-f16 GEMMs): a B fragment of v_mfma_f32_16x16x32_f16 is rows 8 g + j
-// (g = lane >> 4, j = 0..7) of one column per lane, so the four lane groups of a read sit 8 rows apart in the same
-// columns.  XOR-ing the column's position tile with bits 3-4 of the row sends them to four different 16-bank groups:
-// every B read is conflict free, with ONE lane base per tile (the XOR does not depend on j or on the 32-row block).
-__device__ __forceinline__ int pswz(int row, int col) { return row * 64 + (col ^ (((row >> 3) & 3) << 4)); }
-
-// Split operands (see "split-f16 GEMM core" below): every f32 value travels as kSplit = 2 f16 numbers, hi + lo.
-constexpr int kSplit = 2;
-constexpr int kFragBytes = kSplit * 1024;        // one weight fragment: [plane][lane 64][8 f16]
-
-// Pre-split activation planes of the 64-column engines.  A tensor that is only ever read as a GEMM B operand is kept
-// in LDS already split into its two f16 planes, in B-fragment order:
-//   [32-channel block kb][plane hi|lo][g = 0..3][column 0..63][8 f16 = channels 32 kb + 8 g + 0..7]
-// (8 KiB per 32 channels).  The producer's epilogue splits each element ONCE (its accumulators hold 4 consecutive
-// channels of a column: one ds_write_b64 per plane); the eight consumer waves read a whole fragment plane with one
-// ds_read_b128 per lane and their k-loops are loads + MFMA only.
 constexpr int kPlaneH = 128 * 64;                 // H planes: floats [8192, 16384): 4 blocks of 32 channels
 constexpr int kPlaneX = kPlaneH + 4 * kSplit * 1024;   // X planes: floats [16384, 24576)
 constexpr int kPlaneMaxC = 128;
@@ -128,138 +34,7 @@ constexpr int kPlaneMaxC = 128;
 // floats [0, 16384)): the down conv writes the planes of the new residual stream X there (and X itself as f32 rows);
 // conv1 reads the planes and, behind its GroupNorm exchange barrier (every wave is past its k-loop), overwrites them with
 // the planes of H; conv2 reads those and adds act(GN(conv)) to the f32 rows for the final 1x1.
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
-typedef __attribute__((address_space(3))) u32x4 lds_u4;
-typedef __attribute__((address_space(3))) u32x2_t lds_u2;
-// Geometry of the plane rows.  LL = 4 (position-major tiles of the 4-position denoiser): 64 columns per (block, plane, g)
-// row.  LL = 16 (the 16-position nets: pose decoder, ppc denoiser; column = 4 * position + sample, 4 samples per tile):
-// 72 entries per row, the 64 columns at entries 4 .. 67 between four ZERO entries on each side, so that the taps of a
-// k = 3 conv are the same reads shifted by one position = 4 entries (entry 4 t + column for tap t), with no masks.
-template <int LL>
-struct PG {
-  static constexpr int kCols = LL == 16 ? 72 : 64;   // 16-byte entries per row
-  static constexpr int kOff = LL == 16 ? 4 : 0;      // entry of column 0
-  static constexpr int kPlaneU4 = 4 * kCols;         // entries per plane of a 32-channel block
-  static constexpr int kBlockU4 = kSplit * kPlaneU4; // per block
-  static constexpr int kBlockFloats = 4 * kBlockU4;
-  static constexpr int kH = 128 * 64;                // H planes (floats), 4 blocks
-  static constexpr int kX = kH + 4 * kBlockFloats;   // X planes
-  // the 256-channel level's one set, 8 blocks.  LL = 4: behind the 256 f32 rows of X; LL = 16: over both regions (its f32
-  // rows 128 .. 255 lie over the first blocks: the residual stream is parked in global scratch, Ctx::park)
-  static constexpr int kW = LL == 16 ? kH : 256 * 64;
-  static constexpr int kEnd = kW + 8 * kBlockFloats;
-};
 static_assert(PG<4>::kH == kPlaneH && PG<4>::kX == kPlaneX, "plane regions");
-static_assert(PG<4>::kEnd <= 512 * 64, "position-major planes end in front of the attention exchange slots");
-static_assert(PG<16>::kEnd <= Geo<64>::kArena, "padded planes fit the arena");
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-// (a, b) -> packed f16 hi parts and packed f16 lo parts: x = hi + lo up to 2^-22 |x| (f16 subnormals are kept by the
-// matrix pipe -- tools/micro/mfma_f16_split -- so small lo parts lose nothing but bits below 2^-25).
-// v_cvt_pk_f16_f32 (round to nearest even), the remainders from the packed halves by v_fma_mix_f32, v_cvt_pk_f16_f32.
-__device__ __forceinline__ void split_f16x2(float a, float b, unsigned &hi, unsigned &lo) {
-  const f16x2 h = __builtin_convertvector(f32x2{a, b}, f16x2);
-  const float ra = __builtin_fmaf((float)h[0], -1.0f, a), rb = __builtin_fmaf((float)h[1], -1.0f, b);
-  hi = __builtin_bit_cast(unsigned, h);
-  lo = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{ra, rb}, f16x2));
-}
-// rows c0 .. c0 + 3 (c0 % 4 == 0) of column n -> the two planes
-template <int LL = 4>
-__device__ __forceinline__ void store_planes4(float *planes, int c0, int n, float v0, float v1, float v2, float v3) {
-  unsigned h0, h1, l0, l1;
-  split_f16x2(v0, v1, h0, l0);
-  split_f16x2(v2, v3, h1, l1);
-  // dword address: (((kb * kSplit + plane) * 4 + g) * kCols + kOff + n) * 4 + 2 * (half of the 8-group)
-  using G = PG<LL>;
-  const int a = ((((c0 >> 5) * kSplit) * 4 + ((c0 >> 3) & 3)) * G::kCols + G::kOff + n) * 4 + ((c0 >> 2) & 1) * 2;
-  lds_u2 *d = (lds_u2 *)(planes + a);
-  d[0] = u32x2_t{h0, h1};
-  d[2 * G::kPlaneU4] = u32x2_t{l0, l1};    // next plane: kPlaneU4 entries of 16 bytes = 2 kPlaneU4 u2
-}
-
-// ---- range scale of split operands ------------------------------------------------------------------------------------
-// f16 carries 5 exponent bits: a value of 65520 or more has hi = inf (and lo = x - inf = NaN), one below 2^-14 a subnormal
-// hi.  Where the DATA sets an operand's magnitude (a gathered neighbourhood, a cloud's features, the ReLU outputs behind
-// them: BatchNorm is folded, so everything scales with the input) the tile is split as x / s with s a power of two chosen
-// from the tile's largest magnitude (measured where the staged values sit in registers, a bound  R m + B  -- R the layer's
-// largest row sum of |W|, B its largest |bias| -- for the hidden layers behind them) and s is folded back where the
-// accumulators leave the matrix pipe: exact, wave uniform, three or four VALU instructions per tile and layer.  s = 1 for
-// anything ordinary (2^-8 <= m < 2^14): every bit is then what it was without the scale.
-__device__ __forceinline__ float range_pow2(float m) {   // m >= 0 (a maximum of magnitudes or a bound on one), wave uniform
-  int e = (int)((__float_as_uint(m) >> 23) & 0xffu) - 127;   // floor(log2 m) of a normal m
-  if ((e >= -8 && e < 14) || e < -100 || e > 100) return 1.0f;   // ordinary; nothing there; beyond rescue (inf / nan included)
-  e = e < -40 ? -40 : e;                                     // biases divided by s stay finite
-  return __uint_as_float((unsigned)(e - 13 + 127) << 23);    // m / s in [2^13, 2^14)
-}
-__device__ __forceinline__ float pow2_inv(float s) { return __uint_as_float((254u << 23) - __float_as_uint(s)); }   // s = 2^k, |k| <= 126
-
-__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
-__device__ __forceinline__ float silu(float x) { return x * __builtin_amdgcn_rcpf(1.0f + fast_exp(-x)); }
-
-
-// Cross-lane reductions on the VALU: DPP operands for the lanes of a sample (quad / row mirrors: each
-// step adds the partial sum of the complementary lane group, so every lane ends with the total) and
-// v_permlane32_swap for the two halves of a wave.  A ds_bpermute shuffle costs an LDS round trip each.
-// (mov_dpp leaves the destination's previous value undefined for lanes without a source -- every control used with it
-// covers all lanes; update_dpp(0, ...) made the compiler clear the destination with a v_mov_b32 in front of every one.)
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float x) {
-  static_assert(CTRL <= 0xFF || (CTRL >= 0x121 && CTRL <= 0x12F) || CTRL == 0x140 || CTRL == 0x141, "a control that covers all lanes");
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), CTRL, 0xf, 0xf, false));
-}
-// max(a, b) as ONE instruction: fmaxf on values that come out of a bit cast (DPP / permlane results) gets a canonicalising
-// v_max_f32 x, x per operand in front of it
-__device__ __forceinline__ float vmax(float a, float b) {
-  float r;
-  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-// max(x, x seen through the DPP control): one v_max_f32_dpp (the s_nop covers the VALU-write -> DPP-read hazard, which
-// nobody checks inside an asm statement)
-template <int CTRL>
-__device__ __forceinline__ float dpp_max(float x) {
-  float r;
-  if constexpr (CTRL == 0x124) asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 row_ror:4 row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(x));
-  else if constexpr (CTRL == 0x128) asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(x));
-  else if constexpr (CTRL == 0xB1) asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(x));
-  else if constexpr (CTRL == 0x4E) asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(x));
-  else static_assert(CTRL == 0x124, "add the control's assembler spelling");
-  return r;
-}
-template <int L>
-__device__ __forceinline__ float group_sum(float x) {  // sum over the L lanes (columns) of a sample
-  x += dpp_mov<0xB1>(x);                   // quad_perm [1,0,3,2]
-  x += dpp_mov<0x4E>(x);                   // quad_perm [2,3,0,1]
-  if constexpr (L >= 8) x += dpp_mov<0x141>(x);   // row_half_mirror
-  if constexpr (L >= 16) x += dpp_mov<0x140>(x);  // row_mirror
-  return x;
-}
-__device__ __forceinline__ float half_sum(float x) {  // lanes i and i ^ 32
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float row_pair_sum(float x) {  // lanes i and i ^ 16
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float row_pair_max(float x) {
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return vmax(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float half_max(float x) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return vmax(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-
-__device__ __forceinline__ float row16_max(float x) {  // max over the 16 lanes of a DPP row
-  x = dpp_max<0xB1>(x);   // quad_perm [1,0,3,2]
-  x = dpp_max<0x4E>(x);   // quad_perm [2,3,0,1]
-  x = fmaxf(x, dpp_mov<0x141>(x));  // row_half_mirror
-  x = fmaxf(x, dpp_mov<0x140>(x));  // row_mirror
-  return x;
-}
-
 #if defined(GLDM_DEBUG_KNOBS) && defined(GLDM_WAVE_STAMPS)   // per-wave conv stamps cost ~1.5 k cycles per op: their own switch
 __device__ long long g_wv_stamp[8][32][8];   // per wave, ring of the last 32 position-major convs: in, k-loop done, out, shape,
                                              // statistics published (in front of the exchange barrier), partners merged
@@ -271,292 +46,8 @@ __device__ int g_wv_cnt[8];
 #define GLDM_WV_STAMP(c, k, v) do {} while (0)
 #define GLDM_WV_NEXT(c) do {} while (0)
 #endif
-struct Ctx {
-  const float *w;   // packed weights
-  float *lds;
-  int tid, wave, lane;
-  int skip;         // diagnostic phase-skip mask (GLDM_R1D_SKIP), 0 in production
-  int nta;          // live 16-column n-tiles of this workgroup (kNT = full tile, 1 = tail tile)
-  // scale / shift rows precomputed per conditioning cloud (pose decoder: ss_table_kernel), for the tile's samples 0 and
-  // 1 (16-position engine: a 16-column n-tile is one sample), or null: computed in the epilogue
-  const float *ss_row[2] = {nullptr, nullptr};
-  const float *ss_lane = nullptr;   // 16-position 64-column engine: the same rows for THIS LANE's sample (lane & 3), or null
-  // position-major engine, 256-channel level: this workgroup's 64 KiB of global scratch where the residual stream is
-  // parked (f32) between the level's down conv and the end of its ResnetBlock, while LDS holds the split planes
-  float *park = nullptr;
-};
 
-// ---------------------------------------------------------------- GEMM ----
-// Every conv / 1x1 is  acc[mi][ni] += W[16(mt0+mi).., :] * im2col(src)[:, 16(nt0+ni)..]
-// on v_mfma_f32_16x16x4_f32.  Packed weights: k = tap * Cin + ci, 16-deep k-blocks.
-template <int L>
-__device__ __forceinline__ float tap_left(float v, bool keep) {  // value of column n-1
-  const float f = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111 /*row_shr:1*/, 0xf, 0xf, true));
-  return (L >= 16 || keep) ? f : 0.f;
-}
-template <int L>
-__device__ __forceinline__ float tap_right(float v, bool keep) {  // value of column n+1
-  const float f = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x101 /*row_shl:1*/, 0xf, 0xf, true));
-  return (L >= 16 || keep) ? f : 0.f;
-}
-
-// Fast path (Cin % 16 == 0).  A 16-column tile never straddles a sample (L divides 16), so the
-// row-boundary lanes of the halo shift are exactly the lanes whose tap falls outside the sample:
-// zero fill (bound_ctrl) for L = 16, an extra (col % L) mask for L = 4.
-struct NoPre { __device__ __forceinline__ void operator()() const {} };
-// pre(): work that does not depend on the GEMM, run right after the first weight fragments have been requested (it
-// then costs nothing while their round trip is outstanding).
-template <int NC, int L, int TAPS, int MT, int NT, int PF, class PRE = NoPre>
-__device__ __forceinline__ void gemm_fast_pf(const Ctx &c, const float *__restrict__ wp, int cblocks, int mt0, int nt0,
-                                             const float *src, f32x4 (&acc)[MT][NT], const PRE &pre = PRE()) {
-  // PF = weight blocks in flight; cblocks % PF == 0.  The unrolled body is UNCONDITIONAL: a load
-  // whose only consumer sits behind a branch is sunk into that branch by the compiler (and then
-  // waited for at once), and a branch around a load forces s_waitcnt 0 at the join.  Block indices
-  // are clamped instead; the redundant re-loads at the tail are harmless.
-  const int col = c.lane & 15, kq = c.lane >> 4;
-  const int kblocks = TAPS * cblocks;
-  const WStream wv(wp, c.lane);
-  // B-fragment addresses.  Row 4 j + kq has the parity of kq for every j, so the swizzle is the same for all four
-  // k-steps, and with nt0 even it only swaps the n-tiles of a pair: at 8 n-tiles (nt0 = 0) two lane-dependent bases
-  // (even / odd n-tile) plus compile-time offsets, which the reads carry as immediates -- not 32 registers.  (At 2 and
-  // 4 n-tiles the engine's phases measured 1 % slower this way, spill-free as they became.)
-  int boff[4][NT];
-  if constexpr (NT >= 8) {
-    int bb[2];
-#pragma unroll
-    for (int e = 0; e < 2; ++e) bb[e] = swz<NC>(kq, 16 * (nt0 + e) + col);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int ni = 0; ni < NT; ++ni) boff[j][ni] = bb[ni & 1] + 4 * j * NC + 16 * (ni & ~1);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int ni = 0; ni < NT; ++ni) boff[j][ni] = swz<NC>(4 * j + kq, 16 * (nt0 + ni) + col);
-  }
-  f32x4 a[PF][TAPS][MT];
-  // B values: double buffered over k-blocks, except at 8 n-tiles, where a k-step's 8+ MFMAs are cover enough: the row
-  // of step j is refilled from the next block the moment step j's MFMAs have issued (three steps to arrive), in ONE
-  // set of registers (32 fewer at NT = 8).
-  constexpr bool kBS = NT >= 8 && PF > 1;
-  float b[kBS ? 1 : 2][4][NT];
-  f32x4 side[TAPS > 1 ? 2 : 1][MT][NT];  // tap 0 and tap 2 partial results (tap 1 goes to acc)
-  if (TAPS == 3) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni) side[t][mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-  // part = -1: the whole block; part 0..2: the third of the block's fragments issued beside
-  // k-step `part` (a burst of every wave's loads at the block boundary stalls all of them in the
-  // vector-memory issue queue while the MFMA pipe idles: spread, the two pipes overlap)
-  auto load_a = [&](int buf, int cb, int part) {
-#pragma unroll
-    for (int t = 0; t < TAPS; ++t)
-#pragma unroll
-      for (int mi = 0; mi < MT; ++mi)
-        if (part < 0 || (t * MT + mi) % 3 == part)
-          a[buf][t][mi] = wv[((size_t)(mt0 + mi) * kblocks + t * cblocks + cb) * 64];
-  };
-  const lds_f *src3 = (const lds_f *)src;
-  auto load_b = [&](int buf, int cb) {
-    const lds_f *s = src3 + cb * 16 * NC;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int ni = 0; ni < NT; ++ni) b[buf][j][ni] = s[boff[j][ni]];
-  };
-  auto mfma_step = [&](int abuf, int bbuf, int j) {
-    if (TAPS == 3) {
-#pragma unroll
-      for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni)
-          side[0][mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[abuf][0][mi][j], b[bbuf][j][ni], side[0][mi][ni], 0, 0, 0);
-#pragma unroll
-      for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[abuf][TAPS > 1 ? 1 : 0][mi][j], b[bbuf][j][ni], acc[mi][ni], 0, 0, 0);
-#pragma unroll
-      for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni)
-          side[TAPS > 1 ? 1 : 0][mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[abuf][TAPS > 2 ? 2 : 0][mi][j], b[bbuf][j][ni], side[TAPS > 1 ? 1 : 0][mi][ni], 0, 0, 0);
-    } else {
-#pragma unroll
-      for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[abuf][0][mi][j], b[bbuf][j][ni], acc[mi][ni], 0, 0, 0);
-    }
-  };
-  const int last = cblocks - 1;
-  if constexpr (PF == 1) {
-    for (int cb = 0; cb < cblocks; ++cb) {
-      load_a(0, cb, -1);
-      load_b(0, cb);
-      if (cb == 0) pre();
-#pragma unroll
-      for (int j = 0; j < 4; ++j) mfma_step(0, 0, j);
-    }
-  } else {
-#pragma unroll
-    for (int u = 0; u < PF - 1; ++u) load_a(u, u < last ? u : last, -1);
-    load_b(0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    pre();
-    __builtin_amdgcn_sched_barrier(0);
-    for (int cb0 = 0; cb0 < cblocks; cb0 += PF) {
-#pragma unroll
-      for (int u = 0; u < PF; ++u) {
-        const int cb = cb0 + u;
-        const int acb = cb + PF - 1 < last ? cb + PF - 1 : last, bcb = cb + 1 < last ? cb + 1 : last;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (j < 3) load_a((u + PF - 1) % PF, acb, j);
-          if (!kBS && j == 0) load_b((u + 1) & 1, bcb);
-          __builtin_amdgcn_sched_barrier(0);
-          mfma_step(u, kBS ? 0 : (u & 1), j);
-          __builtin_amdgcn_sched_barrier(0);
-          if constexpr (kBS) {
-            const lds_f *sn = src3 + bcb * 16 * NC;
-#pragma unroll
-            for (int ni = 0; ni < NT; ++ni) b[0][j][ni] = sn[boff[j][ni]];
-          }
-        }
-      }
-    }
-  }
-  if (TAPS == 3) {
-    const bool keepL = (col & (L - 1)) != 0, keepR = (col & (L - 1)) != (L - 1);
-#pragma unroll
-    for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < NT; ++ni)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          acc[mi][ni][r] += tap_left<L>(side[0][mi][ni][r], keepL) + tap_right<L>(side[TAPS > 1 ? 1 : 0][mi][ni][r], keepR);
-  }
-}
-
-// k = 3 convs, tap-major: inside a 16-channel block the three taps are swept one after the other
-// (4 k-steps each), and the moment a tap's sweep has issued its MFMAs its fragment registers are
-// refilled with the NEXT block's fragments of that tap.  Every weight load then has exactly one
-// block of MFMAs (48 at 2 x 2 tiles) to arrive, with ONE set of fragment registers and never more
-// than a block's worth of loads in flight per wave: the double-buffered form kept up to two, and
-// a long weight stream queued in the CU's vector-memory path is what delays the co-resident
-// workgroup's short phases.
-template <int NC, int L, int MT, int NT>
-__device__ __forceinline__ void gemm_fast_tap3(const Ctx &c, const float *__restrict__ wp, int cblocks, int mt0, int nt0,
-                                               const float *src, f32x4 (&acc)[MT][NT]) {
-  const int col = c.lane & 15, kq = c.lane >> 4;
-  const int kblocks = 3 * cblocks;
-  const WStream wv(wp, c.lane);
-  int boff[4][NT];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int ni = 0; ni < NT; ++ni) boff[j][ni] = swz<NC>(4 * j + kq, 16 * (nt0 + ni) + col);
-  f32x4 a[3][MT];
-  float b[2][4][NT];
-  f32x4 side[2][MT][NT];  // tap 0 and tap 2 partial results (tap 1 goes to acc)
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < NT; ++ni) side[t][mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const lds_f *src3 = (const lds_f *)src;
-  auto load_b = [&](int buf, int cb) {
-    const lds_f *s = src3 + cb * 16 * NC;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int ni = 0; ni < NT; ++ni) b[buf][j][ni] = s[boff[j][ni]];
-  };
-  const int last = cblocks - 1;
-#pragma unroll
-  for (int t = 0; t < 3; ++t)
-#pragma unroll
-    for (int mi = 0; mi < MT; ++mi) a[t][mi] = wv[((size_t)(mt0 + mi) * kblocks + t * cblocks) * 64];
-  load_b(0, 0);
-  for (int cb0 = 0; cb0 < cblocks; cb0 += 2) {  // two blocks per trip: the B double buffer alternates statically
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int cb = cb0 + u;
-      const int nb = cb + 1 < last ? cb + 1 : last;  // clamped: the loads stay unconditional
-      load_b(1 - u, nb);
-#pragma unroll
-      for (int t = 0; t < 3; ++t) {
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < NT; ++ni) {
-              f32x4 &d = t == 1 ? acc[mi][ni] : side[t >> 1][mi][ni];
-              d = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t][mi][j], b[u][j][ni], d, 0, 0, 0);
-            }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int mi = 0; mi < MT; ++mi) a[t][mi] = wv[((size_t)(mt0 + mi) * kblocks + t * cblocks + nb) * 64];
-      }
-    }
-  }
-  const bool keepL = (col & (L - 1)) != 0, keepR = (col & (L - 1)) != (L - 1);
-#pragma unroll
-  for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NT; ++ni)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        acc[mi][ni][r] += tap_left<L>(side[0][mi][ni][r], keepL) + tap_right<L>(side[1][mi][ni][r], keepR);
-}
-
-
-// ---- split-f16 GEMM core of the 64-column engines ------------------------------------------------------------
-// f32 matrix products on the f16 matrix pipe.  v_mfma_f32_16x16x32_f16 delivers 16x the FLOP/cycle of
-// v_mfma_f32_16x16x4_f32, so an f32 product computed EXACTLY ENOUGH from f16 pieces still wins: every f32 operand is
-// written as hi + lo, two f16 numbers (11 + 11 significant bits; the matrix pipe keeps f16 subnormals, so a small lo
-// part loses only bits below 2^-25), and a product a b is the sum of three partial products,
-//   a b ~ a_hi b_lo + a_lo b_hi + a_hi b_hi      (three MFMAs, f32 accumulation),
-// the dropped one (lo lo) being <= 2^-22 |a b|.  3/16 of the f32-MFMA time -- and half of what the three-piece bf16
-// split of rounds 3-4 took (six products) at the same measured accuracy: on a 16 x 16 x 768 product the error relative
-// to sum |a b| is 1.3e-7 (f32 fma chain: 1.3e-7; bf16 x 3: 1.5e-7), on operands spread over 15 binades 3.5e-7 (5.6e-7;
-// 3.4e-7) -- tools/micro/mfma_f16_split, profiles/r05_mfma_f16_split.txt.  Weights are split once on the host
-// (r1d_pack.py: mfma_a_fragments_f16x2, layout in gldm.h); activations are split by the producing epilogue
-// (store_planes4) or as they are read from LDS (split_planes8).  Range: |x| < 65504 (f16); the packers refuse weights
-// beyond it, activations of these nets are O(10) behind their norms.
-// Measured against the reference's vectors: single forwards 1.7e-6 from the f32 graph, 100 DDIM steps 1.8e-6
-// (tools/study/f16x2_error.py), well inside the 2e-5 / 1e-4 parity bars.
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-
-// x[0..7] (consecutive k of one column) -> the planes of a B fragment
-__device__ __forceinline__ void split_planes8(const float (&x)[8], u32x4 (&pl)[kSplit]) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    unsigned h, l;
-    split_f16x2(x[2 * q], x[2 * q + 1], h, l);
-    pl[0][q] = h;
-    pl[1][q] = l;
-  }
-}
-__device__ __forceinline__ f32x4 mfma_h(const u32x4 &a, const u32x4 &b, const f32x4 &c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-// acc += A B with both operands split: small terms first
-__device__ __forceinline__ f32x4 mfma_split(const u32x4 (&a)[kSplit], const u32x4 (&b)[kSplit], f32x4 acc) {
-  acc = mfma_h(a[0], b[1], acc);
-  acc = mfma_h(a[1], b[0], acc);
-  return mfma_h(a[0], b[0], acc);
-}
-
-// Position-major k = 3 conv (see gemm_pm3 below for the tile algebra) on split-f16 operands.  wp3: split fragments
+// Position-major k = 3 conv on split-f16 operands.  wp3: split fragments
 // of [Cout x 3 Cin], k = tap * Cin + ci, 32-deep k-blocks (Cin % 32 == 0).  One set of A registers per tap: the
 // moment a tap's MFMAs have issued, its registers are refilled with the next channel block's fragments of that tap,
 // which then have the two other taps' MFMAs (and the partner wave's) to arrive.  The raw f32 B values of the next
@@ -574,7 +65,6 @@ constexpr bool kExpNoB = false;
 // First weight fragments of a position-major k = 3 conv, requested by the CALLER ahead of the conv (the fused
 // ResnetBlock op asks for its second conv's while the first conv's epilogue runs): block 0's three tap sets of a
 // one-m-tile wave, tap 0's set of a two-m-tile wave -- what the k-loop would otherwise request cold and wait ~1 k cycles for.
-struct NoPreA { static constexpr bool on = false; };
 template <int MT>
 struct PreA {
   static constexpr bool on = true;
@@ -802,414 +292,12 @@ __device__ __forceinline__ void gemm_sm3_pl(const Ctx &c, const float *__restric
     }
   }
 }
-
-// 1x1 conv with the B operand from pre-split planes (the folded-LayerNorm qkv conv reads the X planes).
-// MS: stride between the wave's m-tiles (the fused qkv + attention phase takes a head's q, k and v rows: 8 m-tiles apart).
-// FIRST: NoFirst, or Frag3 = block 0's fragments of the first m-tile, requested by the caller ahead of the call (by value in
-// registers: a pointer to them would put the array on the stack).
-struct NoFirst { static constexpr bool on = false; };
-struct Frag3 { static constexpr bool on = true; u32x4 p[kSplit]; };
-template <int KB32, int MT, int NT, class PRE = NoPre, int MS = 1, int LL = 4, class FIRST = NoFirst>
-__device__ __forceinline__ void gemm1_pl(const Ctx &c, const float *__restrict__ wp3, int mt0, int nt0, const float *planes,
-                                         f32x4 (&acc)[MT][NT], const PRE &pre = PRE(), const FIRST &first = FIRST()) {
-  const int col = c.lane & 15, g = c.lane >> 4;
-  const WStream wv(wp3, c.lane);
-  using PGx = PG<LL>;
-  const lds_u4 *pl3 = (const lds_u4 *)planes + g * PGx::kCols + PGx::kOff + 16 * nt0 + col;
-  u32x4 a[2][MT][kSplit];
-  u32x4 bs[2][kSplit];
-  auto load_a = [&](int buf, int kb) {
-#pragma unroll
-    for (int mi = 0; mi < MT; ++mi) {
-      const int sb = ((mt0 + mi * MS) * KB32 + kb) * kFragBytes;   // one scalar offset per (m-tile, block), the planes by immediates
-#pragma unroll
-      for (int pl = 0; pl < kSplit; ++pl) a[buf][mi][pl] = wv.raw_at(sb, pl * 1024);
-    }
-  };
-  auto load_b = [&](int buf, int kb, int ni) {
-#pragma unroll
-    for (int pl = 0; pl < kSplit; ++pl) bs[buf][pl] = pl3[(kb * kSplit + pl) * PGx::kPlaneU4 + 16 * ni];
-  };
-  if constexpr (FIRST::on) {
-#pragma unroll
-    for (int pl = 0; pl < kSplit; ++pl) a[0][0][pl] = first.p[pl];
-    if constexpr (MT > 1) {
-#pragma unroll
-      for (int mi = 1; mi < MT; ++mi) {
-        const int sb = ((mt0 + mi * MS) * KB32) * kFragBytes;
-#pragma unroll
-        for (int pl = 0; pl < kSplit; ++pl) a[0][mi][pl] = wv.raw_at(sb, pl * 1024);
-      }
-    }
-  } else {
-    load_a(0, 0);
-  }
-  load_b(0, 0, 0);
-  __builtin_amdgcn_sched_barrier(0);
-  pre();
-  __builtin_amdgcn_sched_barrier(0);
-  // The requests are pinned in front of the MFMAs they are to run under: left to the scheduler, the next block's
-  // fragment loads sank to their first use (load, s_waitcnt vmcnt(0), MFMA -- six to nine L2 round trips per block; the
-  // 128-channel qkv conv took 18.4 k cycles for 9.2 k of MFMAs).
-#pragma unroll
-  for (int kb = 0; kb < KB32; ++kb) {
-    if (kb + 1 < KB32) load_a((kb + 1) & 1, kb + 1);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int ni = 0; ni < NT; ++ni) {
-      const int step = kb * NT + ni, nxt = step + 1;
-      if (nxt < KB32 * NT) load_b(nxt & 1, nxt / NT, nxt % NT);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int mi = 0; mi < MT; ++mi) acc[mi][ni] = mfma_split(a[kb & 1][mi], bs[step & 1], acc[mi][ni]);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-}
-
-template <int NC, int L, int TAPS, int MT, int NT>
-__device__ __forceinline__ void gemm_fast(const Ctx &c, const float *__restrict__ wp, int cblocks, int mt0, int nt0,
-                                          const float *src, f32x4 (&acc)[MT][NT]) {
-  constexpr int PFMAX = (MT * TAPS > 6) ? 2 : (MT * TAPS > 4 ? 2 : 4);  // register budget
-  if constexpr (TAPS == 3) {
-    if ((cblocks & 1) == 0) {
-      gemm_fast_tap3<NC, L, MT, NT>(c, wp, cblocks, mt0, nt0, src, acc);
-      return;
-    }
-  }
-  if (PFMAX == 4 && (cblocks & 3) == 0) gemm_fast_pf<NC, L, TAPS, MT, NT, PFMAX>(c, wp, cblocks, mt0, nt0, src, acc);
-  else if ((cblocks & 1) == 0) gemm_fast_pf<NC, L, TAPS, MT, NT, 2>(c, wp, cblocks, mt0, nt0, src, acc);
-  else gemm_fast_pf<NC, L, TAPS, MT, NT, 1>(c, wp, cblocks, mt0, nt0, src, acc);
-}
-
-// Generic path (Cin % 16 != 0: the 4-channel level of the latent denoiser): masked reads.
-template <int NC, int L, int MT, int NT>
-__device__ __forceinline__ void gemm_small(const Ctx &c, const float *__restrict__ wp, int kblocks, int mt0, int nt0,
-                                           const float *src, int cin, int ktaps, f32x4 (&acc)[MT][NT]) {
-  const int col = c.lane & 15, kq = c.lane >> 4;
-  const WStream wv(wp, c.lane);
-  const lds_f *src3 = (const lds_f *)src;
-  int dk = 0, cib = 0;
-  const int pad = ktaps == 3 ? 1 : 0;
-  for (int kb = 0; kb < kblocks; ++kb) {
-    f32x4 a[MT];
-#pragma unroll
-    for (int mi = 0; mi < MT; ++mi) a[mi] = wv[((size_t)(mt0 + mi) * kblocks + kb) * 64];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int ci = cib + kq;
-      const int shift = dk - pad;
-      float b[NT];
-#pragma unroll
-      for (int ni = 0; ni < NT; ++ni) {
-        const int n = 16 * (nt0 + ni) + col;
-        const int p = (n & (L - 1)) + shift;
-        const bool ok = (dk < ktaps) && (ci < cin) && (p >= 0) && (p < L);
-        float v = src3[swz<NC>(ok ? ci : 0, ok ? n + shift : 0)];
-        asm volatile("" : "+v"(v));  // keep the LDS read unconditional (no branch + wait per element)
-        b[ni] = ok ? v : 0.f;
-      }
-#pragma unroll
-      for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mi][j], b[ni], acc[mi][ni], 0, 0, 0);
-      cib += 4;
-      if (cib >= cin) {
-        cib = 0;
-        ++dk;
-      }
-    }
-  }
-}
-
-template <int NC, int MT, int NT>
-__device__ __forceinline__ void store_tiles(const Ctx &c, const f32x4 (&acc)[MT][NT], int mt0, int nt0, float *dst,
-                                            int cout, int act) {
-  const int col = c.lane & 15, kq = c.lane >> 4;
-  lds_f *d3 = (lds_f *)dst;
-#pragma unroll
-  for (int mi = 0; mi < MT; ++mi) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 16 * (mt0 + mi) + 4 * kq + r;
-      if (row < cout) {
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni) {
-          const float v = acc[mi][ni][r];
-          d3[swz<NC>(row, 16 * (nt0 + ni) + col)] = act ? fmaxf(v, 0.f) : v;
-        }
-      }
-    }
-  }
-}
-
-// GroupNorm fused into the conv epilogue (Block: proj -> GroupNorm -> [scale/shift] -> SiLU,
-// resnets.py:104-122; ResnetBlock: time/cond MLP -> (scale, shift), residual add, :125-151).
-// The rows of a group always sit inside one wave's accumulators (4 groups; a wave owns a quarter of
-// the rows, or part of its single m-tile on narrow levels), so the statistics are reductions over
-// registers: in-lane over tiles and the 4 rows of a lane, DPP over the columns of the sample,
-// permlane swaps over the row quarters.  The scale/shift rows are not a table either: each wave
-// computes the ones for its own output rows with a few MFMAs against G (the per-sample embedding sum
-// in LDS) right here, in the accumulator layout of the conv tile.  No LDS round trip, no barrier.
-struct GnEpilogue {
-  int mode;            // 0: plain conv, 1: dst = act(GN(conv)), 2: res += act(GN(conv))
-  int gamma_off, beta_off;
-  int ss_w, ss_b, E;   // packed [2C x E] scale/shift Linear (A fragments) + combined bias, or ss_w < 0
-  int C, cpg;          // channels, channels per group (1, 4, 8, 16 or the rows of a wave)
-  float *res;          // residual stream (mode 2)
-  int tab_off = 0;     // this ResnetBlock's rows in the per-cloud scale/shift table (Ctx::ss_row)
-};
-
-// One wave's share of a GEMM: PASSES x MT m-tiles by NT n-tiles, one k-sweep per pass.  Passes keep
-// the register footprint of a sweep small (MT * TAPS <= 6 fragments per block) so that every variant
-// fits beside the other phases of the kernel without spilling; the extra cost of a pass is one
-// pipeline fill.  The bias is folded into the accumulator start value.
-template <int NC, int L, int TAPS, int MT, int NT, int PASSES>
-__device__ __forceinline__ void gemm_passes(const Ctx &c, const float *wp, int mt0, int nt0, bool active,
-                                            const float *src, int cin, float *dst, int cout, const float *bias,
-                                            bool alias, int act, const GnEpilogue &g) {
-  using GG = Geo<NC>;
-  f32x4 acc[PASSES][MT][NT];
-  const int kq = c.lane >> 4, col = c.lane & 15;
-  // ---- parameters of the GroupNorm epilogue.  Every load goes out in one batch: before the k-sweep when the
-  // variant is a single pass (registers to spare: the round trip hides behind the GEMM), else at the start of
-  // the epilogue, in the shadow of the statistics.
-  constexpr bool kEarlyParams = TAPS == 3 && NC == 32 && PASSES == 1;
-  const bool has_ss = g.ss_w >= 0;
-  const bool wide = g.C >= 16;  // else C = 4: one m-tile holds scale rows 0..3 (row quarter 0) and shift rows 4..7
-  const int ekb = g.E >> 4;
-  const WStream wss(c.w + (has_ss ? g.ss_w : 0), c.lane);
-  f32x4 ga[PASSES][MT], be[PASSES][MT], sc0[PASSES][MT], sh0[PASSES][MT], a_sc[PASSES][MT], a_sh[PASSES][MT];
-#define GLDM_LOAD_GN_PARAMS()                                                                                       \
-  _Pragma("unroll") for (int p = 0; p < PASSES; ++p) _Pragma("unroll") for (int mi = 0; mi < MT; ++mi) {            \
-    const int mt_ = mt0 + p * MT + mi;                                                                              \
-    const int row0_ = 16 * mt_ + 4 * kq;                                                                            \
-    const int prow_ = row0_ + 3 < cout ? row0_ : 0; /* rows past cout (narrow levels) are not stored */             \
-    ga[p][mi] = *reinterpret_cast<const f32x4 *>(c.w + g.gamma_off + prow_);                                        \
-    be[p][mi] = *reinterpret_cast<const f32x4 *>(c.w + g.beta_off + prow_);                                         \
-    sc0[p][mi] = f32x4{1.f, 1.f, 1.f, 1.f};                                                                         \
-    sh0[p][mi] = f32x4{0.f, 0.f, 0.f, 0.f};                                                                         \
-    if (has_ss) {                                                                                                   \
-      const float *sb_ = c.w + g.ss_b;                                                                              \
-      if (wide) { /* scale rows: m-tile mt, shift rows: m-tile C/16 + mt of the [2C x E] Linear */                  \
-        sc0[p][mi] = *reinterpret_cast<const f32x4 *>(sb_ + row0_);                                                 \
-        sh0[p][mi] = *reinterpret_cast<const f32x4 *>(sb_ + g.C + row0_);                                           \
-        a_sc[p][mi] = wss[(size_t)mt_ * ekb * 64];                                                                  \
-        a_sh[p][mi] = wss[(size_t)((g.C >> 4) + mt_) * ekb * 64];                                                   \
-      } else {                                                                                                      \
-        _Pragma("unroll") for (int r = 0; r < 4; ++r) sc0[p][mi][r] = sb_[4 * kq + r < 2 * g.C ? 4 * kq + r : 0];   \
-        a_sc[p][mi] = wss[0];                                                                                       \
-      }                                                                                                             \
-    }                                                                                                               \
-  }
-  if (kEarlyParams && g.mode && active) { GLDM_LOAD_GN_PARAMS() }
-#pragma unroll
-  for (int p = 0; p < PASSES; ++p) {
-#pragma unroll
-    for (int mi = 0; mi < MT; ++mi) {
-      f32x4 bv = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (bias) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = 16 * (mt0 + p * MT + mi) + 4 * kq + r;
-          bv[r] = bias[row < cout ? row : cout - 1];
-        }
-      }
-#pragma unroll
-      for (int ni = 0; ni < NT; ++ni) acc[p][mi][ni] = bv;
-    }
-    if (active) {
-      if ((cin & 15) == 0) gemm_fast<NC, L, TAPS, MT, NT>(c, wp, cin >> 4, mt0 + p * MT, nt0, src, acc[p]);
-      else gemm_small<NC, L, MT, NT>(c, wp, (TAPS * cin + 15) >> 4, mt0 + p * MT, nt0, src, cin, TAPS, acc[p]);
-    }
-  }
-  if constexpr (TAPS == 3 && NC == 32) {
-    if (g.mode) {
-      if (!active) return;
-      const float inv_cnt = 1.0f / (float)(g.cpg * L);  // a power of two: exact
-      lds_f *d3 = (lds_f *)(g.mode == 2 ? g.res : dst);
-      if (!kEarlyParams) { GLDM_LOAD_GN_PARAMS() }
-#pragma unroll
-      for (int ni = 0; ni < NT; ++ni) {
-        const int n = 16 * (nt0 + ni) + col;
-        const lds_f *Gs = (const lds_f *)(c.lds + GG::kMiscG) + (n / L) * g.E;  // this column's sample
-        // ---- statistics
-        float mean[PASSES][MT][4], rstd[PASSES][MT][4];
-        if (g.cpg >= 32) {  // the group is everything this wave accumulates
-          float s1 = 0.f;
-#pragma unroll
-          for (int p = 0; p < PASSES; ++p)
-#pragma unroll
-            for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) s1 += acc[p][mi][ni][r];
-          s1 = half_sum(row_pair_sum(group_sum<L>(s1)));
-          const float m = s1 * inv_cnt;
-          float s2 = 0.f;
-#pragma unroll
-          for (int p = 0; p < PASSES; ++p)
-#pragma unroll
-            for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const float dx = acc[p][mi][ni][r] - m;
-                s2 += dx * dx;
-              }
-          s2 = half_sum(row_pair_sum(group_sum<L>(s2)));
-          const float rs = __builtin_amdgcn_rsqf(s2 * inv_cnt + 1e-5f);
-#pragma unroll
-          for (int p = 0; p < PASSES; ++p)
-#pragma unroll
-            for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                mean[p][mi][r] = m;
-                rstd[p][mi][r] = rs;
-              }
-        } else {
-#pragma unroll
-          for (int p = 0; p < PASSES; ++p)
-#pragma unroll
-            for (int mi = 0; mi < MT; ++mi) {
-              if (g.cpg == 1) {  // every accumulator row is its own group
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                  const float x = acc[p][mi][ni][r];
-                  const float m = group_sum<L>(x) * inv_cnt;
-                  const float dx = x - m;
-                  mean[p][mi][r] = m;
-                  rstd[p][mi][r] = __builtin_amdgcn_rsqf(group_sum<L>(dx * dx) * inv_cnt + 1e-5f);
-                }
-              } else {  // 4, 8 or 16 rows of this m-tile: the lane's 4 rows, then row quarters
-                float s1 = acc[p][mi][ni][0] + acc[p][mi][ni][1] + acc[p][mi][ni][2] + acc[p][mi][ni][3];
-                s1 = group_sum<L>(s1);
-                if (g.cpg >= 8) s1 = row_pair_sum(s1);
-                if (g.cpg >= 16) s1 = half_sum(s1);
-                const float m = s1 * inv_cnt;
-                float s2 = 0.f;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                  const float dx = acc[p][mi][ni][r] - m;
-                  s2 += dx * dx;
-                }
-                s2 = group_sum<L>(s2);
-                if (g.cpg >= 8) s2 = row_pair_sum(s2);
-                if (g.cpg >= 16) s2 = half_sum(s2);
-                const float rs = __builtin_amdgcn_rsqf(s2 * inv_cnt + 1e-5f);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                  mean[p][mi][r] = m;
-                  rstd[p][mi][r] = rs;
-                }
-              }
-            }
-        }
-        // ---- scale/shift rows of this column's sample, normalise, SiLU, store / accumulate
-        float gb[4];
-        if (has_ss) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) gb[j] = Gs[4 * j + kq];
-        }
-#pragma unroll
-        for (int p = 0; p < PASSES; ++p)
-#pragma unroll
-          for (int mi = 0; mi < MT; ++mi) {
-            const int mt = mt0 + p * MT + mi;
-            const int row0 = 16 * mt + 4 * kq;
-            f32x4 sc = sc0[p][mi], sh = sh0[p][mi];
-            const float *tab = L == 16 ? (((nt0 + ni) & 1) ? c.ss_row[1] : c.ss_row[0]) : nullptr;  // wave uniform (a select: a run-time index keeps Ctx in scratch)
-            if (has_ss && wide && tab) {
-              // The pose decoder's embedding does not depend on the grasp: the rows were computed once per cloud
-              // (ss_table_kernel).  In here they cost 32 MFMAs per m-tile and SAMPLE (E = 64), 17 % on top of a
-              // 256-wide conv's own, 15 of every n-tile's 16 columns repeating the first.
-              sc = *reinterpret_cast<const f32x4 *>(tab + g.tab_off + row0);
-              sh = *reinterpret_cast<const f32x4 *>(tab + g.tab_off + g.C + row0);
-            } else if (has_ss) {
-              if (wide) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                  sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a_sc[p][mi][j], gb[j], sc, 0, 0, 0);
-                  sh = __builtin_amdgcn_mfma_f32_16x16x4f32(a_sh[p][mi][j], gb[j], sh, 0, 0, 0);
-                }
-                // (E = 64, the pose decoder: 32 of these per m-tile and sample, 17 % on top of a 256-wide conv's own
-                // MFMAs -- a 16-column n-tile is ONE sample there, so 15 of its 16 columns repeat the first.  Requesting
-                // the kb >= 1 fragments together instead of one round trip each changed nothing: it is MFMA time.)
-                for (int kb = 1; kb < ekb; ++kb) {  // wide embeddings
-                  const f32x4 a2 = wss[((size_t)mt * ekb + kb) * 64], a3 = wss[((size_t)((g.C >> 4) + mt) * ekb + kb) * 64];
-#pragma unroll
-                  for (int j = 0; j < 4; ++j) {
-                    const float bj = Gs[16 * kb + 4 * j + kq];
-                    sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a2[j], bj, sc, 0, 0, 0);
-                    sh = __builtin_amdgcn_mfma_f32_16x16x4f32(a3[j], bj, sh, 0, 0, 0);
-                  }
-                }
-              } else {
-                f32x4 t = sc;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) t = __builtin_amdgcn_mfma_f32_16x16x4f32(a_sc[p][mi][j], gb[j], t, 0, 0, 0);
-                for (int kb = 1; kb < ekb; ++kb) {
-                  const f32x4 a2 = wss[(size_t)kb * 64];
-#pragma unroll
-                  for (int j = 0; j < 4; ++j) t = __builtin_amdgcn_mfma_f32_16x16x4f32(a2[j], Gs[16 * kb + 4 * j + kq], t, 0, 0, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                  const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(t[r]), __float_as_uint(t[r]), false, false);
-                  sc[r] = t[r];                    // valid in row quarter 0, the only one that is stored
-                  sh[r] = __uint_as_float(sw[1]);  // quarter 1's value seen from quarter 0
-                }
-              }
-            }
-            // the four values of the lane, without wave-uniform branches between them (mode, scale/shift and the row
-            // bound are tested once per m-tile: tested per value they cut the exp / rcp chains into basic blocks)
-            auto finish4 = [&](auto mode_c, auto ss_c, auto full_c) {
-              constexpr int kMode = decltype(mode_c)::value;
-              constexpr bool kSS = decltype(ss_c)::value, kFull = decltype(full_c)::value;
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                float y = (acc[p][mi][ni][r] - mean[p][mi][r]) * rstd[p][mi][r] * ga[p][mi][r] + be[p][mi][r];
-                if (kSS) y = y * sc[r] + sh[r];
-                y = silu(y);
-                if (kFull || row0 + r < cout) {
-                  const int a = swz<NC>(row0 + r, n);
-                  d3[a] = kMode == 2 ? d3[a] + y : y;
-                }
-              }
-            };
-            using std::integral_constant;
-            typedef integral_constant<bool, true> T;
-            typedef integral_constant<bool, false> F;
-            const bool full = row0 + 3 < cout;
-            if (g.mode == 2) {
-              if (has_ss) { if (full) finish4(integral_constant<int, 2>{}, T{}, T{}); else finish4(integral_constant<int, 2>{}, T{}, F{}); }
-              else { if (full) finish4(integral_constant<int, 2>{}, F{}, T{}); else finish4(integral_constant<int, 2>{}, F{}, F{}); }
-            } else {
-              if (has_ss) { if (full) finish4(integral_constant<int, 1>{}, T{}, T{}); else finish4(integral_constant<int, 1>{}, T{}, F{}); }
-              else { if (full) finish4(integral_constant<int, 1>{}, F{}, T{}); else finish4(integral_constant<int, 1>{}, F{}, F{}); }
-            }
-          }
-      }
-      return;
-    }
-  }
-  if (alias) __syncthreads();
-  if (active) {
-#pragma unroll
-    for (int p = 0; p < PASSES; ++p) store_tiles<NC, MT, NT>(c, acc[p], mt0 + p * MT, nt0, dst, cout, act);
-  }
-}
-
-#undef GLDM_LOAD_GN_PARAMS
-
 constexpr int kOpInts = 12, kMaxOps = 84;  // op tape: 84 * 12 = 1008 ints; the op count lives in int 1023
 constexpr int kPmMaxOps = 8 * GLDM_R1D_MAX_LEVELS + 2;   // 64-column engines: at most 8 entries per level + the last ResnetBlock's 2
 
-// =========================================================================================================
-// Position-major engine pieces (L = 4, 64-column tiles = 16 samples x 4 positions, column = 16 * pos + sample,
+// ==== Position-major engine pieces (L = 4, 64-column tiles = 16 samples x 4 positions, column = 16 * pos + sample,
 // 8 waves, one workgroup per CU).  1x1 convs, LayerNorm and the final 1x1 are layout agnostic and shared with
 // the sample-major engine; what follows are the layout-aware phases.
-// =========================================================================================================
 
 // One wave's share of a k = 3 conv: MT m-tiles x out positions P0..P0+NP-1, with the GroupNorm / scale-shift /
 // SiLU / residual epilogue.  A group's rows no longer sit in one wave (8 waves share 16 m-tiles and the taps
@@ -1220,7 +308,6 @@ constexpr int kPmMaxOps = 8 * GLDM_R1D_MAX_LEVELS + 2;   // 64-column engines: a
 //   GK 0: partner = the adjacent wave (C = 256: 2 m-tiles per wave, C = 128: 1; all 4 positions)
 //   GK 1: partner = wave ^ 4 (C = 64: one m-tile = one group, positions split in two halves)
 //   GK 2: four waves (one per position) x two groups per m-tile (C = 32: 8 channels per group)
-struct NoHook { __device__ __forceinline__ void operator()() const {} };
 constexpr float sqrt_up(int n) {   // >= sqrt(n), n a power of two
   float r = 1.f;
   while (n >= 4) { r *= 2.f; n /= 4; }
@@ -1233,11 +320,10 @@ constexpr float sqrt_up(int n) {   // >= sqrt(n), n a power of two
 // wave's n-tiles of 4 positions x 4 samples; sample = lane & 3; GK 3: C = 16, one m-tile whose four row quarters are the
 // four groups, waves 0-3 one tile each -- waves 4-7 repeat their work with `live` false so that every wave meets the
 // barriers).  The statistics of a sample then also sum over the four positions inside a tile (DPP row rotations).
-template <int MT, int P0, int NP, int GK, int FIN = 0, class PRE = NoPreA, class HOOK = NoHook, int LL = 4>
+template <int MT, int P0, int NP, int GK, int FIN, class PRE, class HOOK, int LL>
 __device__ __forceinline__ void conv_pm3_wave(const Ctx &c, const float *wp, const float *bias, int mt0,
                                               const float *src, int cin, float *dst, int cout, bool alias,
-                                              const GnEpilogue &g, const PRE &pre = PRE(), const HOOK &hook = HOOK(),
-                                              bool live = true) {
+                                              const GnEpilogue &g, const PRE &pre, const HOOK &hook, bool live) {
   using GG = Geo<64>;
   using PGx = PG<LL>;
   const int kq = c.lane >> 4, cl = c.lane & 15;
@@ -1249,7 +335,7 @@ __device__ __forceinline__ void conv_pm3_wave(const Ctx &c, const float *wp, con
   const WStream wss(c.w + (has_ss ? g.ss_w : 0), c.lane);
   f32x4 ga[MT], be[MT], sc[MT], sh[MT], a_sc[MT], a_sh[MT];
   // Epilogue parameters are requested right after the k-sweep (measured: requesting them before it, live through
-  // the sweep, is 0-10 % slower on the narrow convs and no faster on the wide ones: tools/micro/gemm_pm_rate)
+  // the sweep, is 0-10 % slower on the narrow convs and no faster on the wide ones: the gemm_pm_rate probe of DESIGN_HISTORY.md)
   auto load_params = [&]() {
 #pragma unroll
     for (int mi = 0; mi < MT; ++mi) {
@@ -2043,7 +1129,6 @@ __device__ __forceinline__ void qkv_att_pm(const Ctx &c, int w_off, int s_off, c
   __syncthreads();
 }
 
-
 // ---- attention block of the 16-position 64-column engine: qkv_att16_pm (behind quad16_narrow.h, whose core it shares).
 // (Rounds 4-5: qkv_ln16_pm + attention16_pm, q | k | v through LDS as a [384][64] f32 block over both plane regions.)
 // The four zero entries either side of every plane row (8 blocks x 3 planes x 4 g rows x 8 entries) of the 16-position
@@ -2102,82 +1187,6 @@ __device__ __forceinline__ void resblock_pm(const Ctx &c, int w1, int b1, int w2
     else if (t == 2) resblock_pm_wave<1, 2, 1, 3, 16>(c, wp1, bp1, wp2, bp2, 0, X, H, C, g1, g2, stamp2, live);
     else resblock_pm_wave<1, 3, 1, 3, 16>(c, wp1, bp1, wp2, bp2, 0, X, H, C, g1, g2, stamp2, live);
   }
-  __syncthreads();
-}
-
-// dst[cout][NC] = W * im2col(src[cin][NC]) + bias: the waves split the output rows (all n-tiles each).
-// Ends with a barrier.  alias: dst overlaps src -> all reads complete (barrier) before any store.
-// Output widths are 16 x {1, 2, 4, 8, 12, 16} rows (validate() enforces it).
-// (Tried and dropped: running the <= 64-channel levels column-parallel, one wave per n-tile with no
-// barriers inside the level: those phases are bound by per-wave issue, not by the barriers, and with
-// half the waves active every op took 1.7-2x longer.  And the opposite, 8 waves per 32-column tile
-// with the statistics of a wide group exchanged between wave pairs: correct, but at 128 VGPRs per
-// wave the k-loops spill and the launch was 5-7 % slower than with 4 waves.)
-template <int NC, int L>
-__device__ __forceinline__ void conv_gemm(const Ctx &c, int w_off, int b_off, const float *src, int cin, int ktaps,
-                                          float *dst, int cout, bool alias, int act = 0,
-                                          const GnEpilogue &g = GnEpilogue{0, 0, 0, -1, 0, 0, 0, 0, nullptr}) {
-  if (GLDM_SKIP(c, 8)) return;
-  const float *wp = c.w + w_off;
-  const float *bias = b_off >= 0 ? c.w + b_off : nullptr;
-  const int mtiles = (cout + 15) >> 4;
-  const int w = c.wave;
-  // G3: k = 3 taps (<= 2 m-tiles per sweep), G1: 1x1
-#define GLDM_G3(MT, NT, P, mt0, nt0, on) gemm_passes<NC, L, 3, MT, NT, P>(c, wp, mt0, nt0, on, src, cin, dst, cout, bias, alias, act, g)
-#define GLDM_G1(MT, NT, P, mt0, nt0, on) gemm_passes<NC, L, 1, MT, NT, P>(c, wp, mt0, nt0, on, src, cin, dst, cout, bias, alias, act, g)
-  if constexpr (NC == 64) {
-    if (ktaps == 3) {
-      // 64-column engines: 8 waves share the m-tiles (L = 4: the three taps tie the 4 position tiles together; L = 16:
-      // tiles of 4 positions x 4 samples, taps by shifted plane reads).  Only the levels' down convs come this way.
-      constexpr int LL = L == 16 ? 16 : 4;
-      if (LL == 4 && (cin & 15)) conv_pm3_cin4(c, wp, bias, src, dst, cout, alias);
-      else if (mtiles == 16) conv_pm3_wave<2, 0, 4, 0, 0, NoPreA, NoHook, LL>(c, wp, bias, 2 * w, src, cin, dst, cout, alias, g);
-      else if (mtiles == 8) conv_pm3_wave<1, 0, 4, 0, 0, NoPreA, NoHook, LL>(c, wp, bias, w, src, cin, dst, cout, alias, g);
-      else if (mtiles == 4) {
-        if (w < 4) conv_pm3_wave<1, 0, 2, 1, 0, NoPreA, NoHook, LL>(c, wp, bias, w & 3, src, cin, dst, cout, alias, g);
-        else conv_pm3_wave<1, 2, 2, 1, 0, NoPreA, NoHook, LL>(c, wp, bias, w & 3, src, cin, dst, cout, alias, g);
-      } else {  // 2 m-tiles: wave = (m-tile, position / tile)
-        const int pw = w >> 1;
-        if (pw == 0) conv_pm3_wave<1, 0, 1, 2, 0, NoPreA, NoHook, LL>(c, wp, bias, w & 1, src, cin, dst, cout, alias, g);
-        else if (pw == 1) conv_pm3_wave<1, 1, 1, 2, 0, NoPreA, NoHook, LL>(c, wp, bias, w & 1, src, cin, dst, cout, alias, g);
-        else if (pw == 2) conv_pm3_wave<1, 2, 1, 2, 0, NoPreA, NoHook, LL>(c, wp, bias, w & 1, src, cin, dst, cout, alias, g);
-        else conv_pm3_wave<1, 3, 1, 2, 0, NoPreA, NoHook, LL>(c, wp, bias, w & 1, src, cin, dst, cout, alias, g);
-      }
-    }
-    // 1x1 layers (layout agnostic): 8 waves x 4 n-tiles; also the fused set abstraction
-    else if (mtiles == 16) GLDM_G1(2, 4, 1, 2 * w, 0, true);
-    else if (mtiles == 12) GLDM_G1(3, 2, 1, 3 * (w & 3), 2 * (w >> 2), true);
-    else if (mtiles == 8) GLDM_G1(1, 4, 1, w, 0, true);
-    else if (mtiles == 4) GLDM_G1(1, 2, 1, w & 3, 2 * (w >> 2), true);
-    else if (mtiles == 2) GLDM_G1(1, 1, 1, w & 1, w >> 1, true);
-    else GLDM_G1(1, 1, 1, 0, w & 3, w < 4);
-  } else if (ktaps == 3) {
-    if (c.nta == 1) {  // tail workgroup: only columns 0..15 are live
-      if (mtiles == 16) GLDM_G3(2, 1, 2, 4 * w, 0, true);
-      else if (mtiles == 12) GLDM_G3(1, 1, 3, 3 * w, 0, true);
-      else if (mtiles == 8) GLDM_G3(2, 1, 1, 2 * w, 0, true);
-      else GLDM_G3(1, 1, 1, w < mtiles ? w : 0, 0, w < mtiles);
-    } else if (mtiles == 16) GLDM_G3(2, 2, 2, 4 * w, 0, true);
-    else if (mtiles == 12) GLDM_G3(1, 2, 3, 3 * w, 0, true);
-    else if (mtiles == 8) GLDM_G3(2, 2, 1, 2 * w, 0, true);
-    else if (mtiles == 4) GLDM_G3(1, 2, 1, w, 0, true);
-    else if (mtiles == 2) GLDM_G3(1, 1, 1, w & 1, w >> 1, true);
-    else GLDM_G3(1, 1, 1, 0, w & 1, w < 2);
-  } else {
-    if (c.nta == 1) {
-      if (mtiles == 16) GLDM_G1(4, 1, 1, 4 * w, 0, true);
-      else if (mtiles == 12) GLDM_G1(3, 1, 1, 3 * w, 0, true);
-      else if (mtiles == 8) GLDM_G1(2, 1, 1, 2 * w, 0, true);
-      else GLDM_G1(1, 1, 1, w < mtiles ? w : 0, 0, w < mtiles);
-    } else if (mtiles == 16) GLDM_G1(4, 2, 1, 4 * w, 0, true);
-    else if (mtiles == 12) GLDM_G1(3, 2, 1, 3 * w, 0, true);
-    else if (mtiles == 8) GLDM_G1(2, 2, 1, 2 * w, 0, true);
-    else if (mtiles == 4) GLDM_G1(1, 2, 1, w, 0, true);
-    else if (mtiles == 2) GLDM_G1(1, 1, 1, w & 1, w >> 1, true);
-    else GLDM_G1(1, 1, 1, 0, w & 1, w < 2);
-  }
-#undef GLDM_G3
-#undef GLDM_G1
   __syncthreads();
 }
 
@@ -2455,7 +1464,6 @@ __device__ __forceinline__ void attention_pair(const Ctx &c, float *qkv, float *
   }
 }
 
-
 #include "quad_narrow.h"
 #include "quad16_narrow.h"
 
@@ -2667,7 +1675,6 @@ __device__ __forceinline__ void resblock4_valu(const Ctx &c, const int (&o)[kOpI
   for (int k = 0; k < 2; ++k) X[swz<NC>(2 * h + k, n)] = x[2 * h + k] + z[k];
 }
 
-
 // GroupNorm rides in the conv epilogue: the rows of a group must sit inside one wave's accumulators
 __host__ __device__ __forceinline__ bool gn_fusable(int C, int groups) {
   if (groups != 4 || C % 4) return false;
@@ -2864,7 +1871,6 @@ __device__ __forceinline__ void qkv_att16_pm(const Ctx &c, int w_off, int s_off,
   }
   __syncthreads();
 }
-
 
 template <int NC, int L>
 __device__ __forceinline__ void run_tape(const Ctx &c0, const gldm_r1d_desc &d, const int *tape, kernarg_int *ktape, int n_ops, int E, long long *stamps) {
@@ -3494,95 +2500,55 @@ __global__ void pose_prologue_kernel(const float *__restrict__ H, const float *_
 }
 #pragma clang fp contract(fast)
 
-
-// ====================================================================== fused SA ==
-// PointNetSAModule core (ext/pvcnn/modules/pointnet.py:100-111 without the FPS):
-//   grouped = cat(p[idx] - centre, f[idx])          (BallQuery.forward)
-//   out[b, :, j] = max_k  SharedMLP2d(grouped)[b, :, j, k]
-// One workgroup = one 64-column tile = 64/U centres x U neighbours (NC = 64 geometry).  The
-// grouped tensor ([B, 3+C, M, U], 4.3 MB per cloud at SSG-SA2) never exists in HBM: the
-// neighbour tile is gathered straight into LDS, the MLP layers (BatchNorm folded, ReLU) run on
-// the same f32-MFMA GEMM core as the ResNet1D engine with weights streamed from L2, and the max
-// over the U neighbours is taken on chip.  HBM traffic: 12N + 4CN + 12M + 4MU (idx) in,
-// 4 Cout M out per cloud.
-struct SaArgs {
-  const float *points, *centers, *feat;
-  const int32_t *idx;
-  const float *weights;
-  float *out;
-  int c, n, m, u, n_layers;
-  int cin_pad[4], cout[4], w_off[4], b_off[4];
-  // split-f16 kernel: range scales on (range_pow2).  gain_r / gain_b: per layer, the largest row sum of |W| and the largest
-  // |bias| (BatchNorm folded), from the packer: |layer output| <= gain_r * max |input| + gain_b
-  int ranged;
-  float gain_r[4], gain_b[4];
-  // split-f16 kernel, first layer hoisted (gldm_sa_mlp_forward_f16x2_pre): pre [b][n][c1] = W1b f + b1 per POINT (one
-  // pointwise GEMM per cloud instead of one per (centre, neighbour) pair: every point sits in ~16 balls), wa_off: float
-  // index in `weights` of W1a [c1][4] (the coordinate columns x, y, z, 0).  The MFMA layers are then layers 2.. of the module.
-  const float *pre;
-  int c1, wa_off;
-  int pre_bcast;   // pre is ONE row [c1] for every point (a module without features: the row is the folded bias b1)
-};
-
-__global__ __launch_bounds__(Geo<64>::kThreads, 2) void sa_mlp_kernel(const SaArgs a) {
-  using GG = Geo<64>;
-  constexpr int NC = 64;
-  extern __shared__ float lds[];
-  Ctx c{a.weights, lds, (int)threadIdx.x, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), (int)threadIdx.x & 63,
-        0, GG::kNT};
-  const int b = blockIdx.y, tile = blockIdx.x;
-  const int cpt = NC / a.u;                 // centres per tile
-  const int j0 = tile * cpt;
-  const float *pts = a.points + (size_t)b * 3 * a.n;
-  const float *ctr = a.centers + (size_t)b * 3 * a.m;
-  const float *feat = a.feat ? a.feat + (size_t)b * a.c * a.n : nullptr;
-  const int32_t *idx = a.idx + ((size_t)b * a.m + j0) * a.u;
-  float *X = lds + GG::kBufX, *H = lds + GG::kBufH;
-  // ---- gather the neighbour tile: rows 0..2 relative coords, 3..3+C features, zero pad
-  {
-    const int col = c.lane, jj = col / a.u;
-    const bool live = j0 + jj < a.m;
-    const int id = live ? idx[col] : 0;
-    const int rows = a.cin_pad[0];
-    // six rows per wave in flight at a time: every element is a scattered memory round trip, and issued one by one
-    // (load, wait, store) the gather took as long as the tile's MFMAs.  (Requesting the NEXT tile's rows before the
-    // MLP from a persistent workgroup was slower: the in-order vmcnt makes the first weight fragment wait for them.)
-    for (int r0 = c.wave; r0 < rows; r0 += 6 * GG::kWaves) {
-      float v[6];
-#pragma unroll
-      for (int q = 0; q < 6; ++q) {
-        const int r = r0 + q * GG::kWaves;
-        v[q] = 0.f;
-        if (live && r < rows) {
-          if (r < 3) v[q] = pts[r * a.n + id] - ctr[r * a.m + j0 + jj];
-          else if (r < 3 + a.c) v[q] = feat[(size_t)(r - 3) * a.n + id];
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 6; ++q) {
-        const int r = r0 + q * GG::kWaves;
-        if (r < rows) X[swz<NC>(r, col)] = v[q];
-      }
-    }
+// Scale / shift rows of every ResnetBlock for one conditioning cloud (ResnetBlock.mlp, resnets.py:125-151, when the
+// embedding has no time part: the pose decoder):  ss[rb][row] = comb_b[row] + sum_e W[row][e] G[e],  G = sum over the
+// cond rows of SiLU(cemb) -- the value the conv epilogue would compute with MFMAs for every sample and column.
+// Table layout per cloud: blocks in tape order, [scale rows (C) | shift rows (C)] each (build_tape's tab_off).
+__global__ __launch_bounds__(256) void ss_table_kernel(const gldm_r1d_desc d, const float *__restrict__ w,
+                                                       const float *__restrict__ cemb, int stride,
+                                                       float *__restrict__ tab) {
+  __shared__ float G[256];
+  const int cond = blockIdx.x, E = d.emb_dim, R = d.cond_rows, ekb = E >> 4;
+  for (int e = threadIdx.x; e < E; e += blockDim.x) {
+    float g = 0.f;
+    for (int r = 0; r < R; ++r) g += silu(cemb[((size_t)cond * R + r) * E + e]);
+    G[e] = g;
   }
   __syncthreads();
-  // ---- grouped MLP (1x1 convs + folded BN + ReLU), ping-pong X <-> H
-  float *src = X, *dst = H;
-  for (int l = 0; l < a.n_layers; ++l) {
-    conv_gemm<NC, 4>(c, a.w_off[l], a.b_off[l], src, a.cin_pad[l], 1, dst, a.cout[l], false, 1);   // 1x1 layers only (L is the k = 3 convs' layout)
-    float *t = src; src = dst; dst = t;
-  }
-  // ---- max over the U neighbours of each centre
-  const int cout = a.cout[a.n_layers - 1];
-  float *out = a.out + (size_t)b * cout * a.m;
-  for (int i = c.tid; i < cout * cpt; i += GG::kThreads) {
-    const int row = i / cpt, jj = i - row * cpt;
-    if (j0 + jj >= a.m) continue;
-    float mx = -3.0e38f;
-    for (int k = 0; k < a.u; ++k) mx = fmaxf(mx, src[swz<NC>(row, jj * a.u + k)]);
-    out[(size_t)row * a.m + j0 + jj] = mx;
+  float *out = tab + (size_t)cond * stride;
+  int off = 0;
+  const int n_rb = 2 * d.n_levels + 1;
+  for (int i = 0; i < n_rb; ++i) {
+    const int C = d.dims[i < 2 * d.n_levels ? i / 2 : d.n_levels];
+    const gldm_r1d_resblock &rb = d.rb[i];
+    for (int row = threadIdx.x; row < 2 * C; row += blockDim.x) {
+      // packed A fragments of the [2C x E] Linear: W[row][e] at ((mt * ekb + kb) * 64 + 16 kq + i) * 4 + j,
+      // row = 16 mt + i, e = 16 kb + 4 j + kq
+      const float *wr = w + rb.ss_w + (size_t)(row >> 4) * ekb * 256 + (row & 15) * 4;
+      float acc = w[rb.ss_b + row];
+      for (int kb = 0; kb < ekb; ++kb)
+        for (int j = 0; j < 4; ++j)
+          for (int kq = 0; kq < 4; ++kq) acc = fmaf(wr[kb * 256 + kq * 64 + j], G[16 * kb + 4 * j + kq], acc);
+      out[off + row] = acc;
+    }
+    off += 2 * C;
   }
 }
+
+}  // namespace
+
+// The generator on its own (n latents x L positions of one step), for the statistical tests: out [n][L]
+__global__ void philox_normal_kernel(unsigned long long seed, long long base, int step, int n, int L, float *out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * L) return;
+  const int gi = i / L, l = i - gi * L;
+  const unsigned long long g = (unsigned long long)(base + gi);
+  float z4[4];
+  philox_normal4(seed, (unsigned)g, (unsigned)(g >> 32), (unsigned)(l >> 2), (unsigned)step, z4);
+  out[i] = z4[l & 3];
+}
+
+namespace {
 
 bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
@@ -3728,9 +2694,7 @@ int launch_one(const RunArgs &a, int tiles, hipStream_t s) {
 #ifdef GLDM_DEBUG_KNOBS
   if (getenv("GLDM_R1D_ONE_WG") && lds_bytes < 100 * 1024) lds_bytes = 100 * 1024;  // one workgroup per CU: phases on their own
 #endif
-  struct Tag {};
-  gldm_dev::allow_dynamic_lds<Tag>(reinterpret_cast<const void *>(&r1d_kernel<NC, L>), (int)lds_bytes);
-  hipLaunchKernelGGL((r1d_kernel<NC, L>), dim3(tiles), dim3(Geo<NC>::kThreads), lds_bytes, s, a);
+  gldm_dev::launch_dynamic_lds<r1d_kernel<NC, L>>(dim3(tiles), dim3(Geo<NC>::kThreads), (int)lds_bytes, lds_bytes, s, a);
   return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
 }
 
@@ -3842,1213 +2806,19 @@ int launch_r1d(const RunArgs &a_in, hipStream_t s) {
   return rc;
 }
 
-
-// ============================================================== fused pointwise MLP layer ==
-// y[b, :, cols] = act(W x[b, :, cols] + bias) for a k = 1 Conv1d + folded BatchNorm + ReLU of SharedMLP
-// (ext/pvcnn/modules/shared_mlp.py:6-35) in the native [B, C, N] layout, and optionally, on the accumulators
-// before they are stored, the head  z[b, :, cols] = Wh y + bh  (PVCNNEncoder: conv_downscale + out_layer[0]
-// folded, pc_encoders.py:104-111).  With the head fused `y` may be NULL: the encoder's [B, 1536, N] tensor
-// (1.6 GB per 256 clouds) then never reaches HBM.
-// A persistent workgroup of 8 waves takes 32 points of one cloud at a time: the [cin][32] input tile is staged
-// once in LDS (swizzled like the engine's activations) and every wave sweeps its share of the output rows over it
-// with the engine's GEMM core, weights streamed as buffer-load fragments.  The head product uses each 16-row
-// block of y straight from the accumulators as the B operand (lane (kq, col) register r = row 4 kq + r = k-step
-// r of a 16x16x4 MFMA), against head weights packed in that k order; the waves' partial z tiles meet in LDS.
-struct PwArgs {
-  const float *x, *w, *bias, *head_w, *head_b;
-  float *y, *z;
-  int cin, cout, n, relu, hout, tiles_per_cloud, total_tiles;
-  // optional layer in front (x [b, cin0, n] -> relu(W0 x + b0) = the [cin][32] tile of the main layer, never in HBM)
-  const float *w0, *bias0;
-  int cin0;
-  int dyn_first;   // split-f16 kernel: units (pairs of m-tiles) >= dyn_first are handed out at run time
-  int ticket_off;  // ... from a ticket at this float index of the LDS plan
-  int x0_in_planes; // 48-column tiles: the front layer's f32 tile lies under the planes (see pointwise_mlp_sp_kernel)
-  // split-f16 kernel, ADD instantiation: an addend in front of the activation, add[cloud * add_bs + row * add_rs + col * add_cs]
-  // (a per-cloud bias: bs = cout, rs = 1, cs = 0; a [b, cout, n] tensor: bs = cout * n, rs = n, cs = 1)
-  const float *add;
-  long long add_bs, add_rs, add_cs;
-  // split-f16 kernel: range scales (range_pow2).  The staged input tile's is measured; the front layer's output planes take
-  // theirs from the bound gain0_r * max |x| + gain0_b (largest row sum of |W0|, largest |bias0|).  rng_off: float index of the
-  // eight per-wave range words in the LDS plan.  ranged == 0: operands are split as they are.
-  int ranged, rng_off;
-  float gain0_r, gain0_b;
-  int y_point_major;   // split-f16 kernel: y is [b, n, cout] (a lane's four consecutive rows of a column: one 16-byte store)
-  int cin_rows;        // split-f16 kernel without a front layer: rows x really has (cin = that padded to whole 128-deep trips
-                       // of the weight ring: the planes of the rows beyond are zero, like the weights' columns there)
-};
-
-__global__ __launch_bounds__(512, 2) void pointwise_mlp_kernel(const PwArgs a) {
-  constexpr int NC = 32;
-  extern __shared__ float lds[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  Ctx c{a.w, lds, tid, wave, lane, 0, 2};
-  const int col = lane & 15, kq = lane >> 4;
-  const int cblocks = a.cin >> 4, mtiles = a.cout >> 4, mt_per_wave = mtiles >> 3;
-  float *zpart = lds + a.cin * NC;  // [8 waves][16 rows][32 cols]
-  const WStream hw(a.head_w ? a.head_w : a.w, lane);
-  for (int tile = blockIdx.x; tile < a.total_tiles; tile += gridDim.x) {
-    const int b = tile / a.tiles_per_cloud, c0 = (tile - b * a.tiles_per_cloud) * NC;
-    __syncthreads();  // the previous tile's readers are done
-    if (a.w0) {
-      // layer in front: stage its [cin0][32] input tile behind the z partials, sweep its output rows (= the main
-      // layer's input rows) with the same GEMM core and leave them in LDS as the main layer's tile
-      float *x0 = zpart + 8 * 16 * NC;
-      const float *xb0 = a.x + (size_t)b * a.cin0 * a.n + c0;
-      for (int i = tid; i < a.cin0 * 8; i += 512) {
-        const int row = i >> 3, q = i & 7;
-        *reinterpret_cast<f32x4 *>(x0 + swz<NC>(row, 4 * q)) = *reinterpret_cast<const f32x4 *>(xb0 + (size_t)row * a.n + 4 * q);
-      }
-      __syncthreads();
-      const int cb0 = a.cin0 >> 4, mt_per_wave0 = a.cin >> 7;  // cin output rows = cin / 16 m-tiles over 8 waves
-      for (int ps = 0; ps < mt_per_wave0; ps += 2) {
-        const int mt0 = wave * mt_per_wave0 + ps;
-        f32x4 acc[2][2];
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi) {
-          const f32x4 bv = *reinterpret_cast<const f32x4 *>(a.bias0 + 16 * (mt0 + mi) + 4 * kq);
-          acc[mi][0] = bv;
-          acc[mi][1] = bv;
-        }
-        gemm_fast_pf<NC, 4, 1, 2, 2, 2>(c, a.w0, cb0, mt0, 0, x0, acc);
-        lds_f *d3 = (lds_f *)lds;
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni)
-              d3[swz<NC>(16 * (mt0 + mi) + 4 * kq + r, 16 * ni + col)] = fmaxf(acc[mi][ni][r], 0.f);
-      }
-    } else {
-      const float *xb = a.x + (size_t)b * a.cin * a.n + c0;
-      for (int i = tid; i < a.cin * 8; i += 512) {
-        const int row = i >> 3, q = i & 7;
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(xb + (size_t)row * a.n + 4 * q);
-        *reinterpret_cast<f32x4 *>(lds + swz<NC>(row, 4 * q)) = v;
-      }
-    }
-    __syncthreads();
-    f32x4 zacc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-    for (int ps = 0; ps < mt_per_wave; ps += 2) {
-      const int mt0 = wave * mt_per_wave + ps;
-      f32x4 acc[2][2];
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi) {
-        const f32x4 bv = *reinterpret_cast<const f32x4 *>(a.bias + 16 * (mt0 + mi) + 4 * kq);
-        acc[mi][0] = bv;
-        acc[mi][1] = bv;
-      }
-      if ((cblocks & 3) == 0) gemm_fast_pf<NC, 4, 1, 2, 2, 4>(c, a.w, cblocks, mt0, 0, lds, acc);
-      else gemm_fast_pf<NC, 4, 1, 2, 2, 2>(c, a.w, cblocks, mt0, 0, lds, acc);
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi) {
-        if (a.relu) {
-#pragma unroll
-          for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[mi][ni][r] = fmaxf(acc[mi][ni][r], 0.f);
-        }
-        if (a.y) {
-          float *yb = a.y + ((size_t)b * a.cout + 16 * (mt0 + mi) + 4 * kq) * a.n + c0 + col;
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni) __builtin_nontemporal_store(acc[mi][ni][r], yb + (size_t)r * a.n + 16 * ni);
-        }
-        if (a.head_w) {
-          const f32x4 ah = hw[(size_t)(mt0 + mi) * 64];
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni)
-              zacc[ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(ah[r], acc[mi][ni][r], zacc[ni], 0, 0, 0);
-        }
-      }
-    }
-    if (a.head_w) {
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) zpart[(wave * 16 + 4 * kq + r) * NC + 16 * ni + col] = zacc[ni][r];
-      __syncthreads();
-      for (int i = tid; i < a.hout * NC; i += 512) {
-        const int row = i / NC, cc = i - row * NC;
-        float v = a.head_b ? a.head_b[row] : 0.f;
-#pragma unroll
-        for (int w8 = 0; w8 < 8; ++w8) v += zpart[(w8 * 16 + row) * NC + cc];
-        a.z[((size_t)b * a.hout + row) * a.n + c0 + cc] = v;
-      }
-    }
-  }
+// gldm_decode / gldm_encode of a net with a per-cloud scale / shift table (ss_table_rows() > 0): ss_table_kernel fills it, behind
+// the hand-off granules of the workspace (gldm_r1d_workspace_bytes), and the engine is pointed at it.  false: the launch failed.
+bool launch_ss_table(RunArgs &a, hipStream_t s) {
+  const int rows = ss_table_rows(&a.d);
+  if (rows <= 0) return true;
+  float *tab = reinterpret_cast<float *>(reinterpret_cast<char *>(a.ws) + ws_layout(&a.d, a.n_samples).ss_off);
+  const int n_cond = (a.n_samples + a.samples_per_cond - 1) / a.samples_per_cond;
+  hipLaunchKernelGGL(ss_table_kernel, dim3(n_cond), dim3(256), 0, s, a.d, a.weights, a.cemb, rows, tab);
+  if (hipGetLastError() != hipSuccess) return false;
+  a.ss_tab = tab;
+  a.ss_stride = rows;
+  return true;
 }
-
-// ---- the same layer(s) on split-f16 operands -------------------------------------------------------------------------
-// pointwise_mlp_kernel with the main GEMM on v_mfma_f32_16x16x32_bf16 (6 partial products per f32 product, see the
-// split-f16 core of the position-major engine): weights pre-split on the host (mfma_a_fragments_f16x2), the [cin][32]
-// input tile split ONCE while it is staged and kept in LDS as B-fragment planes
-//   [32-channel block][plane hi|mid|lo][g][32 columns][8 bf16]      (6 KiB per block; cin = 768: 144 KiB)
-// so the eight waves' k-loops are ds_read_b128 + buffer loads + MFMA.  A 32-column tile re-uses a weight fragment
-// for two n-tiles only: 7 MB of fragments per tile, 62 B/clk if the MFMAs were never to wait -- above the 50 B/clk a CU
-// draws from L2 (tools/micro/l2_stream), so fragments are requested four blocks ahead (ring of four register sets: 24 KiB
-// in flight per wave) and the ring is kept full across the units of output rows.
-// (Measured and dropped: 64-column tiles with K walked in 256-channel chunks -- planes of a chunk in LDS, accumulators of
-// half the output rows kept across the chunks, two passes, front layer recomputed per pass on the bf16 pipe: half the
-// weight bytes per column, yet the same 0.97-1.04 ms per 329 clouds as this kernel's 1.04: the stream is not what it
-// waits for in the end.)
-// The optional layer in front (96 -> 768: an eighth of the FLOPs) runs on the same pipe (pw_front_split: 20-25 k cycles
-// per tile on the f32 pipe before) and writes its ReLU output straight into those planes; the head product is taken on the
-// accumulators exactly as in the f32 kernel (the C layout of the two MFMA shapes is the same).
-// f32 [row][NC] tile of the front layer: swz<32> on the first 32 columns (the two n-tiles trade places on odd rows), any
-// further n-tile in place
-template <int NC>
-__device__ __forceinline__ int pw_swz(int row, int col) { return row * NC + (col < 32 ? (col ^ ((row & 1) << 4)) : col); }
-template <int NC>   // columns of the tile: 32 or 48
-__device__ __forceinline__ void store_planes4_pw(float *planes, int c0, int n, float v0, float v1, float v2, float v3) {
-  unsigned h0, h1, l0, l1;
-  split_f16x2(v0, v1, h0, l0);
-  split_f16x2(v2, v3, h1, l1);
-  const int a = ((((c0 >> 5) * kSplit) * 4 + ((c0 >> 3) & 3)) * NC + n) * 4 + ((c0 >> 2) & 1) * 2;   // dwords
-  lds_u2 *d = (lds_u2 *)(planes + a);
-  d[0] = u32x2_t{h0, h1};
-  d[8 * NC] = u32x2_t{l0, l1};   // next plane: 4 * NC * 4 dwords
-}
-
-// The layer in front of the split-f16 main layer, on the same pipe: x0 = the f32 [cin0][32] tile (swizzled), w0s =
-// split fragments of W0 [cin x cin0], KB0 = cin0 / 32.  A wave splits the whole tile ONCE into registers (its B planes
-// serve all of the wave's m-tiles) and walks its m-tiles in pairs; the A registers of a (m-tile, block) are refilled
-// with the next pair's fragments as soon as its MFMAs have issued.  Output: ReLU, split, into the main layer's planes.
-// bsc = 1 / (range scale of the input tile), osc = that scale / the scale of the output planes (range_pow2; 1 and 1 for
-// ordinary data)
-template <int KB0, int NT>
-__device__ __forceinline__ void pw_front_split(const WStream &w0s, const float *bias0, const float *x0, float *planes,
-                                               int wave, int lane, int mt_per_wave0, bool x0_in_planes, float bsc, float osc) {
-  constexpr int NC = 16 * NT;
-  const int col = lane & 15, kq = lane >> 4;
-  u32x4 bp[KB0][NT][kSplit];
-#pragma unroll
-  for (int kb = 0; kb < KB0; ++kb)
-#pragma unroll
-    for (int ni = 0; ni < NT; ++ni) {
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = x0[pw_swz<NC>(32 * kb + 8 * kq + j, 16 * ni + col)] * bsc;
-      split_planes8(v, bp[kb][ni]);
-    }
-  if (x0_in_planes) __syncthreads();   // 48-column tiles: the f32 tile lies under the planes this layer is about to write
-  u32x4 af[2][KB0][kSplit];
-  const int mt_first = wave * mt_per_wave0, mt_last = mt_first + mt_per_wave0 - 2;
-  auto load_a = [&](int mi, int kb, int mt0) {
-#pragma unroll
-    for (int pl = 0; pl < kSplit; ++pl) af[mi][kb][pl] = w0s.raw_at(((mt0 + mi) * KB0 + kb) * kFragBytes, pl * 1024);
-  };
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int kb = 0; kb < KB0; ++kb) load_a(mi, kb, mt_first);
-  for (int mt0 = mt_first; mt0 <= mt_last; mt0 += 2) {
-    const int mtn = mt0 + 2 <= mt_last ? mt0 + 2 : mt_last;
-    f32x4 acc[2][NT];
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-      const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias0 + 16 * (mt0 + mi) + 4 * kq) * bsc;
-#pragma unroll
-      for (int ni = 0; ni < NT; ++ni) acc[mi][ni] = bv;
-    }
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-      for (int kb = 0; kb < KB0; ++kb) {
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni) acc[mi][ni] = mfma_split(af[mi][kb], bp[kb][ni], acc[mi][ni]);
-        __builtin_amdgcn_sched_barrier(0);
-        load_a(mi, kb, mtn);   // pinned here: the scheduler sinks such requests to their first use otherwise
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < NT; ++ni)
-        store_planes4_pw<NC>(planes, 16 * (mt0 + mi) + 4 * kq, 16 * ni + col, fmaxf(acc[mi][ni][0], 0.f) * osc,
-                             fmaxf(acc[mi][ni][1], 0.f) * osc, fmaxf(acc[mi][ni][2], 0.f) * osc, fmaxf(acc[mi][ni][3], 0.f) * osc);
-  }
-}
-
-#ifdef GLDM_DEBUG_KNOBS
-__device__ long long g_pw_stamp[64];
-#define GLDM_PW_STAMP(i) \
-  do { if (blockIdx.x == 5 && tile == 5 + 2 * (int)gridDim.x && (threadIdx.x & 63) == 0 && (wave == 0 || wave == 7)) \
-         g_pw_stamp[(wave ? 32 : 0) + (i)] = (long long)__builtin_readcyclecounter(); } while (0)
-#else
-#define GLDM_PW_STAMP(i) do {} while (0)
-#endif
-// NT: n-tiles per tile.  2 = 32 points (96 KiB of planes at cin = 768).  3 = 48 points (144 KiB): a weight fragment then
-// serves three n-tiles -- with three f16 products per block the kernel is bound by the CU's L2 rate (5 MB of fragments per
-// tile at 52 B/clk = 96 k cycles against 59 k of MFMAs at 32 points), so bytes per POINT are what counts.  n % 16 == 0: a
-// cloud's last tile holds 1-3 whole n-tiles (`ntv`); the others are computed on zeros and never stored.
-// MU: m-tiles per unit of output rows (2; 1 for layers of fewer than 256 rows, whose 4-7 two-tile units left waves idle:
-// the 128-row feature-propagation layers and the set-abstraction first layer per point)
-// (Tried for MU = 1: a 128-register bound, two workgroups per CU -- these launches are short tiles whose staging -> barrier
-// -> k-loop -> store chain is latency -- 96 spilled registers: the ring of four A sets and two B sets does not fit.)
-template <bool ADD, int NT, int MU = 2>
-__global__ __launch_bounds__(512, 2) void pointwise_mlp_sp_kernel(const PwArgs a) {
-  constexpr int NC = 16 * NT;
-  extern __shared__ float lds[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int col = lane & 15, kq = lane >> 4;
-  const int kb32 = a.cin >> 5, mtiles = a.cout >> 4;
-  float *planes = lds;                       // [kb32][kSplit][4][NC][4 dwords]
-  float *zpart = lds;                        // [8 waves][16 rows][NC cols], over the planes once they are dead
-  float *zdyn = lds + a.cin * (NC / 2) * kSplit;   // behind the planes: head products of the drawn units [unit - dyn_first][hout][NC]
-  // front layer's f32 input tile [cin0][NC]: behind the planes, under zdyn (dead by then); 48-column tiles have no room
-  // there -- it lies UNDER the planes and the front layer takes it into registers, then a barrier, before it writes them
-  float *x0 = a.x0_in_planes ? lds : zdyn;
-  int *ticket = (int *)(lds + a.ticket_off); // next unit of output rows to hand out (main layer)
-  const WStream hw(a.head_w ? a.head_w : a.w, lane);
-  const WStream wv(a.w, lane);
-  const lds_u4 *pl3 = (const lds_u4 *)planes + kq * NC + col;   // + ((kb * kSplit + plane) * 4) * NC + 16 ni
-  for (int tile = blockIdx.x; tile < a.total_tiles; tile += gridDim.x) {
-    const int b = tile / a.tiles_per_cloud, c0 = (tile - b * a.tiles_per_cloud) * NC;
-    const int ntv = min(NT, (a.n - c0) >> 4);   // whole n-tiles of this tile that exist
-    __syncthreads();  // the previous tile's readers are done
-    GLDM_PW_STAMP(0);
-    if (tid == 0) *ticket = a.dyn_first;
-    // range scale of the main layer's planes (range_pow2): the accumulators run in its units, `v = acc * s_main + bias` below
-    float s_main = 1.0f;
-    float *rng = lds + a.rng_off;   // [8]: the waves' largest staged magnitudes
-    auto range_publish = [&](float mx) {
-      mx = half_max(row_pair_max(row16_max(mx)));
-      if (lane == 0) rng[wave] = mx;
-    };
-    auto range_read = [&]() {
-      const f32x4 r0 = *reinterpret_cast<const f32x4 *>(rng), r1 = *reinterpret_cast<const f32x4 *>(rng + 4);
-      const float mx = fmaxf(fmaxf(fmaxf(r0[0], r0[1]), fmaxf(r0[2], r0[3])), fmaxf(fmaxf(r1[0], r1[1]), fmaxf(r1[2], r1[3])));
-      return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(mx)));
-    };
-    if (a.w0) {
-      const float *xb0 = a.x + (size_t)b * a.cin0 * a.n + c0;
-      float mx = 0.f;
-      for (int i = tid; i < a.cin0 * (NC / 4); i += 512) {
-        const int row = i / (NC / 4), q = i - row * (NC / 4);
-        f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (4 * q < 16 * ntv) v = *reinterpret_cast<const f32x4 *>(xb0 + (size_t)row * a.n + 4 * q);
-        *reinterpret_cast<f32x4 *>(x0 + pw_swz<NC>(row, 4 * q)) = v;
-        mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
-      }
-      if (a.ranged) range_publish(mx);
-      __syncthreads();
-      GLDM_PW_STAMP(1);
-      float bsc = 1.0f, osc = 1.0f;
-      if (a.ranged) {
-        const float m0 = range_read(), s0 = range_pow2(m0);
-        s_main = range_pow2(a.gain0_r * m0 + a.gain0_b);
-        bsc = pow2_inv(s0);
-        osc = s0 * pow2_inv(s_main);
-      }
-      const int mt_per_wave0 = a.cin >> 7;   // cin / 16 m-tiles over 8 waves
-      const WStream w0s(a.w0, lane);
-      switch (a.cin0 >> 5) {
-        case 1: pw_front_split<1, NT>(w0s, a.bias0, x0, planes, wave, lane, mt_per_wave0, a.x0_in_planes != 0, bsc, osc); break;
-        case 2: pw_front_split<2, NT>(w0s, a.bias0, x0, planes, wave, lane, mt_per_wave0, a.x0_in_planes != 0, bsc, osc); break;
-        default: pw_front_split<3, NT>(w0s, a.bias0, x0, planes, wave, lane, mt_per_wave0, a.x0_in_planes != 0, bsc, osc); break;
-      }
-    } else {
-      // stage + split: item = (8-channel group, column)
-      const float *xb = a.x + (size_t)b * a.cin_rows * a.n + c0;
-      // The tile's range scale needs its largest magnitude before anything is split.  Up to kHold items per thread (cin <=
-      // 256 at 32 points: the feature-propagation and per-point layers of the set-abstraction backbones) the staged values
-      // wait in registers across the exchange barrier: ONE pass over the input.  Wider tiles take a first pass for the maximum
-      // and read the tile again (from L2): measured on the feature-propagation layers of PointNet2SSG, the two-pass form alone
-      // cost 60-90 % of a launch.
-      constexpr int kHold = 2;
-      const int items = (a.cin >> 3) * NC;
-      auto stage_store = [&](int i, float (&v)[8], float inv) {
-        const int kg = i / NC, scol = i - kg * NC, row = 8 * kg;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] *= inv;
-        u32x4 pl[kSplit];
-        split_planes8(v, pl);
-        lds_u4 *d = (lds_u4 *)planes + (((row >> 5) * kSplit) * 4 + ((row >> 3) & 3)) * NC + scol;
-        d[0] = pl[0];
-        d[4 * NC] = pl[1];
-      };
-      auto stage_load = [&](int i, float (&v)[8]) {
-        const int kg = i / NC, scol = i - kg * NC, row = 8 * kg;
-        const bool in = scol < 16 * ntv && row < a.cin_rows;   // (cin_rows % 8 == 0: whole groups)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = in ? xb[(size_t)(row + j) * a.n + scol] : 0.f;
-      };
-      if (NT == 2 && a.ranged && items <= kHold * 512) {   // (48-point tiles exist for inputs of 640 rows and more only)
-        float hv[kHold][8];
-        float mx = 0.f;
-#pragma unroll
-        for (int q = 0; q < kHold; ++q) {
-          const int i = tid + 512 * q;
-          if (i < items) {
-            stage_load(i, hv[q]);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fabsf(hv[q][j]));
-          }
-        }
-        range_publish(mx);
-        __syncthreads();
-        s_main = range_pow2(range_read());
-        const float inv = pow2_inv(s_main);
-#pragma unroll
-        for (int q = 0; q < kHold; ++q) {
-          const int i = tid + 512 * q;
-          if (i < items) stage_store(i, hv[q], inv);
-        }
-      } else {
-        float inv = 1.0f;
-        if (a.ranged) {
-          float mx = 0.f;
-          for (int i = tid; i < items; i += 512) {
-            float v[8];
-            stage_load(i, v);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fabsf(v[j]));
-          }
-          range_publish(mx);
-          __syncthreads();
-          s_main = range_pow2(range_read());
-          inv = pow2_inv(s_main);
-        }
-        for (int i = tid; i < items; i += 512) {
-          float v[8];
-          stage_load(i, v);
-          stage_store(i, v, inv);
-        }
-      }
-    }
-    GLDM_PW_STAMP(2);
-    __syncthreads();
-    GLDM_PW_STAMP(3);
-    f32x4 zacc[NT];
-#pragma unroll
-    for (int ni = 0; ni < NT; ++ni) zacc[ni] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // ---- the output rows in units of two m-tiles, handed out at run time.  With a fixed share per wave the older wave
-    // of a SIMD gets the matrix pipe whenever it wants it, finishes its share at 95 % of the pair's rate and then idles
-    // at the tile's last barrier while its partner, alone, cannot hide its own LDS / weight latencies (stamps: wave 0
-    // done after 131 k cycles, wave 7 after 166 k, a lone wave at 58 % of the pipe).  A wave that is done takes the next
-    // unit off an LDS ticket instead; the unit after the current one is drawn before the current k-loop so that its
-    // first weight fragments are requested from inside that loop (the ring of four A sets never drains), and the B
-    // planes of block k + 1 are read in front of the MFMAs of block k.
-    const int units = mtiles / MU;
-    u32x4 af[4][MU][kSplit];
-    auto load_a = [&](int buf, int mt0, int kb) {
-#pragma unroll
-      for (int mi = 0; mi < MU; ++mi)
-#pragma unroll
-        for (int pl = 0; pl < kSplit; ++pl) af[buf][mi][pl] = wv.raw_at(((mt0 + mi) * kb32 + kb) * kFragBytes, pl * 1024);
-    };
-    u32x4 bs[2][NT][kSplit];
-    auto load_b = [&](int buf, int kb) {
-#pragma unroll
-      for (int ni = 0; ni < NT; ++ni)
-#pragma unroll
-        for (int pl = 0; pl < kSplit; ++pl) bs[buf][ni][pl] = pl3[(kb * kSplit + pl) * 4 * NC + 16 * ni];
-    };
-    auto draw = [&]() {
-      int t = 0;
-      if (lane == 0) t = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      return __builtin_amdgcn_readfirstlane(t);
-    };
-    // Units below dyn_first are dealt round robin (wave w: w, w + 8, ...), the rest drawn.  The head sum must not depend
-    // on who drew what: a drawn unit's head product goes to its own LDS slot (zdyn, over the dead front-layer tile), only
-    // the dealt ones accumulate in the wave's zacc, and the final sum walks waves, then slots, in index order.
-    const int dyn_first = a.dyn_first;
-    int unit = wave;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) load_a(u, MU * (unit < units ? unit : 0), u);   // a wave without a unit requests unit 0's (unused)
-    load_b(0, 0);
-    while (unit < units) {
-      const int mt0 = MU * unit;
-      const int nxt = unit + 8 < dyn_first ? unit + 8 : draw();
-      const int mtn = MU * (nxt < units ? nxt : unit);   // past the end: harmless re-reads of this unit's fragments
-      // bias and head fragments of this unit: requested now, used behind the k-loop (the bias is added last)
-      f32x4 acc[MU][NT], bv[MU], ah[MU];
-#pragma unroll
-      for (int mi = 0; mi < MU; ++mi) {
-        bv[mi] = *reinterpret_cast<const f32x4 *>(a.bias + 16 * (mt0 + mi) + 4 * kq);
-        ah[mi] = hw[(size_t)(a.head_w ? mt0 + mi : 0) * 64];
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-      for (int kb0 = 0; kb0 < kb32; kb0 += 4) {
-        const bool tail = kb0 + 4 >= kb32;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int kb = kb0 + u;
-          load_b((u + 1) & 1, kb + 1 < kb32 ? kb + 1 : 0);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int mi = 0; mi < MU; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < NT; ++ni) acc[mi][ni] = mfma_split(af[u][mi], bs[u & 1][ni], acc[mi][ni]);
-          __builtin_amdgcn_sched_barrier(0);
-          load_a(u, tail ? mtn : mt0, tail ? u : kb + 4);
-        }
-      }
-#pragma unroll
-      for (int mi = 0; mi < MU; ++mi) {
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            float v = __builtin_fmaf(acc[mi][ni][r], s_main, bv[mi][r]);   // s_main = 1: the plain sum, bit for bit
-            if constexpr (ADD)
-              v += a.add[(long long)b * a.add_bs + (long long)(16 * (mt0 + mi) + 4 * kq + r) * a.add_rs +
-                         (long long)(c0 + (ni < ntv ? 16 * ni + col : col)) * a.add_cs];
-            acc[mi][ni][r] = a.relu ? fmaxf(v, 0.f) : v;
-          }
-        if (a.y && a.y_point_major) {
-          float *yb = a.y + ((size_t)b * a.n + c0 + col) * a.cout + 16 * (mt0 + mi) + 4 * kq;
-#pragma unroll
-          for (int ni = 0; ni < NT; ++ni)
-            if (ni < ntv) *reinterpret_cast<f32x4 *>(yb + (size_t)16 * ni * a.cout) = acc[mi][ni];
-        } else if (a.y) {
-          float *yb = a.y + ((size_t)b * a.cout + 16 * (mt0 + mi) + 4 * kq) * a.n + c0 + col;
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int ni = 0; ni < NT; ++ni)
-              if (ni < ntv) __builtin_nontemporal_store(acc[mi][ni][r], yb + (size_t)r * a.n + 16 * ni);
-        }
-      }
-      if (a.head_w) {
-        const bool drawn = unit >= dyn_first;
-        f32x4 zu[NT];
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni) zu[ni] = drawn ? f32x4{0.f, 0.f, 0.f, 0.f} : zacc[ni];
-#pragma unroll
-        for (int mi = 0; mi < MU; ++mi) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int ni = 0; ni < NT; ++ni)
-              zu[ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(ah[mi][r], acc[mi][ni][r], zu[ni], 0, 0, 0);
-        }
-        if (drawn) {
-          float *slot = zdyn + (unit - dyn_first) * a.hout * NC;
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (4 * kq + r < a.hout) {
-#pragma unroll
-              for (int ni = 0; ni < NT; ++ni) slot[(4 * kq + r) * NC + 16 * ni + col] = zu[ni][r];
-            }
-        } else {
-#pragma unroll
-          for (int ni = 0; ni < NT; ++ni) zacc[ni] = zu[ni];
-        }
-      }
-      unit = nxt;
-    }
-    GLDM_PW_STAMP(16);
-    if (a.head_w) {
-      __syncthreads();  // every wave is done with the planes: the z partials go over them
-      GLDM_PW_STAMP(17);
-#pragma unroll
-      for (int ni = 0; ni < NT; ++ni)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) zpart[(wave * 16 + 4 * kq + r) * NC + 16 * ni + col] = zacc[ni][r];
-      __syncthreads();
-      // fixed summation tree: four lanes per output (waves 2p, 2p + 1 and every fourth slot from p), then the quad
-      const int nd = units - dyn_first;
-      for (int i0 = 0; i0 < a.hout * NC * 4; i0 += 512) {
-        const int i = i0 + tid, o = i >> 2, p = i & 3;
-        const bool live = o < a.hout * NC;
-        const int row = live ? o / NC : 0, cc = live ? o - row * NC : 0;
-        float v = zpart[((2 * p) * 16 + row) * NC + cc] + zpart[((2 * p + 1) * 16 + row) * NC + cc];
-        for (int d = p; d < nd; d += 4) v += zdyn[(d * a.hout + row) * NC + cc];
-        v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
-        v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
-        if (live && p == 0 && cc < 16 * ntv) a.z[((size_t)b * a.hout + row) * a.n + c0 + cc] = v + (a.head_b ? a.head_b[row] : 0.f);
-      }
-    }
-    GLDM_PW_STAMP(18);
-  }
-}
-
-
-// ======================================================== fused set abstraction, 128-column tiles ==
-// sa_mlp_kernel at twice the tile: 128 columns = 128 / U centres x U neighbours per workgroup (8 waves, one workgroup
-// per CU).  Every weight fragment then serves 8 n-tiles, a layer's fill / epilogue / barrier is paid once per 128
-// columns, and the last layer's output is never stored: max over a centre's neighbours is taken on the accumulators
-// (in-lane over the centre's n-tiles, DPP over the 16 columns of a tile; ReLU after the max, it is monotone) and only
-// [cout][centres] leaves the CU.  LDS: region A [max(cin_pad0, cout1)][128] (the gathered tile, later layer 2's
-// output) + region B [cout0][128] (+ [cout2] for 4 layers).  Shapes outside this plan run on sa_mlp_kernel.
-
-template <int MT, int NT>
-__device__ __forceinline__ void sa2_tiles(const Ctx &c, const SaArgs &a, int l, int mt0, int nt0, const float *src,
-                                          float *dst, bool last, int j0, float *outb) {
-  constexpr int NC = 128;
-  const int col = c.lane & 15, kq = c.lane >> 4;
-  const float *wp = a.weights + a.w_off[l], *bias = a.weights + a.b_off[l];
-  f32x4 acc[MT][NT];
-#pragma unroll
-  for (int mi = 0; mi < MT; ++mi) {
-    const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias + 16 * (mt0 + mi) + 4 * kq);
-#pragma unroll
-    for (int ni = 0; ni < NT; ++ni) acc[mi][ni] = bv;
-  }
-  const int cblocks = a.cin_pad[l] >> 4;
-  if ((cblocks & 3) == 0) gemm_fast_pf<NC, 16, 1, MT, NT, 4>(c, wp, cblocks, mt0, nt0, src, acc);
-  else gemm_fast_pf<NC, 16, 1, MT, NT, 2>(c, wp, cblocks, mt0, nt0, src, acc);  // the launcher checked: even
-  if (!last) {
-    lds_f *d3 = (lds_f *)dst;
-#pragma unroll
-    for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni)
-          d3[swz<NC>(16 * (mt0 + mi) + 4 * kq + r, 16 * (nt0 + ni) + col)] = fmaxf(acc[mi][ni][r], 0.f);
-    return;
-  }
-  // max over each centre's U columns: tpc = U / 16 n-tiles per centre (1, 2 or 4; NT is a multiple of it)
-  const int tpc = a.u >> 4;
-#pragma unroll
-  for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float m[NT];
-#pragma unroll
-      for (int ni = 0; ni < NT; ++ni) m[ni] = acc[mi][ni][r];
-      if (tpc >= 2) {
-#pragma unroll
-        for (int ni = 0; ni < NT; ni += 2) m[ni] = fmaxf(m[ni], m[ni + 1 < NT ? ni + 1 : ni]);
-      }
-      if (tpc >= 4) {
-#pragma unroll
-        for (int ni = 0; ni < NT; ni += 4) m[ni] = fmaxf(m[ni], m[ni + 2 < NT ? ni + 2 : ni]);
-      }
-#pragma unroll
-      for (int ni = 0; ni < NT; ++ni) {
-        if (ni % tpc) continue;  // wave uniform
-        const float v = fmaxf(row16_max(m[ni]), 0.f);
-        const int jj = (nt0 + ni) / tpc;  // centre of the tile
-        if (col == 0 && j0 + jj < a.m) outb[(size_t)(16 * (mt0 + mi) + 4 * kq + r) * a.m + j0 + jj] = v;
-      }
-    }
-}
-
-// The gather of tile t + 1 is requested in front of tile t's last layer and stored after it: its scattered round
-// trips (12 k cycles exposed per tile before) run under the longest GEMM of the tile.  Everything about it is
-// UNCONDITIONAL -- clamped tile index, clamped addresses, the store of a last redundant tile -- because a load behind a
-// branch, or one whose only consumer is behind a branch, is waited for on the spot.  (The in-order vmcnt makes the
-// layer's first weight fragment wait for the gather's loads: a few hundred cycles once per tile, measured.)
-constexpr int kSaFly = 32;  // feature rows per thread in flight: 4 row quarters x 32 = 128 feature channels
-
-struct SaTile {
-  const float *pts, *ctr, *feat;
-  int id, jj, j0;
-  bool live;
-};
-
-__device__ __forceinline__ SaTile sa2_tile(const SaArgs &a, int t, int tiles_per_cloud, int cpt, int col) {
-  const int b = t / tiles_per_cloud, tile = t - b * tiles_per_cloud;
-  SaTile s;
-  s.j0 = tile * cpt;
-  s.jj = col / a.u;
-  s.live = s.j0 + s.jj < a.m;
-  s.pts = a.points + (size_t)b * 3 * a.n;
-  s.ctr = a.centers + (size_t)b * 3 * a.m;
-  s.feat = a.feat ? a.feat + (size_t)b * a.c * a.n : a.points;
-  const int32_t *idx = a.idx + ((size_t)b * a.m + s.j0) * a.u;
-  s.id = idx[s.live ? col : 0];
-  s.id = s.live ? s.id : 0;
-  return s;
-}
-
-__device__ __forceinline__ void sa2_gather_load(const SaArgs &a, const SaTile &s, int rq, float &xyz, float (&v)[kSaFly]) {
-  const int r3 = rq < 3 ? rq : 0;
-  xyz = s.pts[r3 * a.n + s.id] - s.ctr[r3 * a.m + (s.live ? s.j0 + s.jj : 0)];
-  const int cmax = a.c > 0 ? a.c - 1 : 0;
-#pragma unroll
-  for (int q = 0; q < kSaFly; ++q) {
-    const int f = rq + 4 * q;
-    v[q] = s.feat[(size_t)(f < cmax ? f : cmax) * a.n + s.id];
-  }
-}
-
-__device__ __forceinline__ void sa2_gather_store(const SaArgs &a, const SaTile &s, int rq, int col, float xyz,
-                                                 const float (&v)[kSaFly], float *A) {
-  constexpr int NC = 128;
-  lds_f *A3 = (lds_f *)A;
-  const int rows = a.cin_pad[0];
-  if (rq < 3) A3[swz<NC>(rq, col)] = s.live ? xyz : 0.f;
-#pragma unroll
-  for (int q = 0; q < kSaFly; ++q) {
-    const int f = rq + 4 * q;
-    if (3 + f < rows) A3[swz<NC>(3 + f, col)] = (s.live && f < a.c) ? v[q] : 0.f;
-  }
-  for (int r = 3 + 4 * kSaFly + rq; r < rows; r += 4) A3[swz<NC>(r, col)] = 0.f;  // zero pad beyond 131 rows
-}
-
-__global__ __launch_bounds__(512, 1) void sa_mlp2_kernel(const SaArgs a, int rows_a, int tiles_per_cloud, int total_tiles) {
-  constexpr int NC = 128;
-  extern __shared__ float lds[];
-  Ctx c{a.weights, lds, (int)threadIdx.x, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), (int)threadIdx.x & 63,
-        0, 8};
-  const int cpt = NC / a.u;  // centres per tile
-  float *A = lds, *B = lds + (size_t)rows_a * NC;
-  const int w = c.wave, col = c.tid & (NC - 1), rq = c.tid >> 7;
-  auto layer = [&](int l, const float *src, float *dst, int j0, float *outb) {
-    const bool last = l == a.n_layers - 1;
-    const int mtiles = a.cout[l] >> 4;
-    // the lane ids are laundered per call: otherwise every variant's lane-derived LDS offsets are hoisted out of the
-    // tile loop as invariants and live (spilled) across the whole kernel
-    Ctx cl = c;
-    asm volatile("" : "+v"(cl.tid), "+v"(cl.lane));
-    if (mtiles >= 8) {  // one m-tile x all 8 n-tiles per pass: every weight fragment serves 128 columns
-      for (int p = 0; p < (mtiles >> 3); ++p) sa2_tiles<1, 8>(cl, a, l, w + 8 * p, 0, src, dst, last, j0, outb);
-    } else if (mtiles == 4) sa2_tiles<1, 4>(cl, a, l, w & 3, 4 * (w >> 2), src, dst, last, j0, outb);
-    else sa2_tiles<1, 2>(cl, a, l, w & 1, 2 * (w >> 1), src, dst, last, j0, outb);
-  };
-  // persistent workgroups (a tile is 45 us of work and a workgroup launch several)
-  int t = blockIdx.x;
-  {
-    const SaTile s = sa2_tile(a, t, tiles_per_cloud, cpt, col);
-    float xyz, v[kSaFly];
-    sa2_gather_load(a, s, rq, xyz, v);
-    sa2_gather_store(a, s, rq, col, xyz, v, A);
-  }
-  __syncthreads();
-  for (; t < total_tiles; t += gridDim.x) {
-    const int b = t / tiles_per_cloud, j0 = (t - b * tiles_per_cloud) * cpt;
-    float *outb = a.out + (size_t)b * a.cout[a.n_layers - 1] * a.m;
-    float *src = A, *dst = B;
-    for (int l = 0; l + 1 < a.n_layers; ++l) {
-      layer(l, src, dst, j0, outb);
-      __syncthreads();
-      float *tsw = src; src = dst; dst = tsw;
-    }
-    const int tn = t + (int)gridDim.x < total_tiles ? t + (int)gridDim.x : t;
-    const SaTile s = sa2_tile(a, tn, tiles_per_cloud, cpt, col);
-    float xyz, v[kSaFly];
-    sa2_gather_load(a, s, rq, xyz, v);
-    layer(a.n_layers - 1, src, dst, j0, outb);
-    __syncthreads();  // the last layer may have been reading region A
-    sa2_gather_store(a, s, rq, col, xyz, v, A);
-    __syncthreads();
-  }
-}
-
-
-// ======================================================== fused set abstraction on split-f16 planes ==
-// The same module core (gather + grouped MLP + max over the neighbours, ext/pvcnn/modules/pointnet.py:100-111) with the
-// GEMMs on the bf16 matrix pipe: every f32 product as six bf16 partial products (hi / mid / lo splits of both operands,
-// f32 accumulation: see the split-f16 core above), 6/16 of the f32-MFMA time.  A tile is 64 columns = 64 / U centres x U
-// neighbours; the gathered tile and every hidden layer's output live in LDS as pre-split planes in B-fragment order
-// (the position-major engine's geometry: 12 KiB per 32 channels), written once by their producer (the gather threads hold
-// four consecutive channels of a column; a layer's epilogue its accumulators' four consecutive rows), so the k-loops are
-// ds_read_b128 + buffer loads + MFMA (gemm1_pl).  Region A: the gathered tile, later the odd hidden layers' outputs;
-// region B: the even ones'.  The last layer is never stored: max over a centre's neighbours on the accumulators.
-// Persistent workgroups; the next tile's gather is requested in front of the last layer and stored behind it.
-// Shapes: cin_pad a multiple of 32 (zero weights beyond the real rows), hidden widths multiples of 32 up to 256, U in
-// {16, 32, 64}; anything else runs on the f32 kernels above.
-constexpr int kSaBlockFloats = PG<4>::kBlockFloats;   // one 32-channel block of a 64-column tile's planes
-constexpr int kSa3Quads = 9;   // row quads per gather thread: 8 threads per column x 9 x 4 rows >= 259 + padding
-template <int NT, class FIRST>
-__device__ __forceinline__ void sa3_gemm(const Ctx &c, const float *wp, int kb, int mt, int nt0, const float *planes,
-                                         f32x4 (&acc)[1][NT], const FIRST &first) {
-  switch (kb) {
-    case 1: gemm1_pl<1, 1, NT, NoPre, 1, 4, FIRST>(c, wp, mt, nt0, planes, acc, NoPre(), first); break;
-    case 2: gemm1_pl<2, 1, NT, NoPre, 1, 4, FIRST>(c, wp, mt, nt0, planes, acc, NoPre(), first); break;
-    case 3: gemm1_pl<3, 1, NT, NoPre, 1, 4, FIRST>(c, wp, mt, nt0, planes, acc, NoPre(), first); break;
-    case 4: gemm1_pl<4, 1, NT, NoPre, 1, 4, FIRST>(c, wp, mt, nt0, planes, acc, NoPre(), first); break;
-    case 5: gemm1_pl<5, 1, NT, NoPre, 1, 4, FIRST>(c, wp, mt, nt0, planes, acc, NoPre(), first); break;
-    case 6: gemm1_pl<6, 1, NT, NoPre, 1, 4, FIRST>(c, wp, mt, nt0, planes, acc, NoPre(), first); break;
-    case 9: gemm1_pl<9, 1, NT, NoPre, 1, 4, FIRST>(c, wp, mt, nt0, planes, acc, NoPre(), first); break;   // 259 + 3 -> 288 rows (PVCNN2 SA4)
-    default: gemm1_pl<8, 1, NT, NoPre, 1, 4, FIRST>(c, wp, mt, nt0, planes, acc, NoPre(), first); break;
-  }
-}
-// The wave's first m-tile of layer l (the mapping of sa_mlp3_kernel) and the request for its block-0 fragments: issued
-// right behind the previous layer's k-loop, in flight under its epilogue and the barrier (each layer of a tile used to
-// start with a cold L2 round trip: ~1.9 k cycles against 2-5 k of MFMAs).
-__device__ __forceinline__ int sa3_first_mt(const SaArgs &a, int l, int w) {
-  const int mtiles = a.cout[l] >> 4;
-  return (l + 1 < a.n_layers && mtiles < 8) ? (mtiles == 4 ? (w & 3) : (w & 1)) : w;
-}
-__device__ __forceinline__ Frag3 sa3_request(const Ctx &c, const SaArgs &a, int l) {
-  const WStream wv(a.weights + a.w_off[l], c.lane);
-  const int mt = sa3_first_mt(a, l, c.wave), kb = a.cin_pad[l] >> 5;
-  const int mtc = mt < (a.cout[l] >> 4) ? mt : 0;   // waves beyond a narrow last layer: any valid fragment
-  Frag3 f;
-#pragma unroll
-  for (int pl = 0; pl < kSplit; ++pl) f.p[pl] = wv.raw_at(mtc * kb * kFragBytes, pl * 1024);
-  return f;
-}
-// REQ: request the next layer's first fragments right behind this k-loop (in flight under the epilogue and the barrier)
-// bsc = 1 / (scale of the input planes): the accumulators run in the input's units; osc = that scale / the scale of the
-// output planes (both 1 for ordinary data: range_pow2)
-template <int NT, class FIRST, bool REQ>
-__device__ __forceinline__ Frag3 sa3_hidden(const Ctx &c, const SaArgs &a, int l, int mt, int nt0, const float *src, float *dst,
-                                            const FIRST &first, float bsc, float osc) {
-  const int col = c.lane & 15, kq = c.lane >> 4;
-  f32x4 acc[1][NT];
-  const f32x4 bv = *reinterpret_cast<const f32x4 *>(a.weights + a.b_off[l] + 16 * mt + 4 * kq) * bsc;
-#pragma unroll
-  for (int ni = 0; ni < NT; ++ni) acc[0][ni] = bv;
-  sa3_gemm<NT, FIRST>(c, a.weights + a.w_off[l], a.cin_pad[l] >> 5, mt, nt0, src, acc, first);
-  Frag3 nxt{};
-  if constexpr (REQ) nxt = sa3_request(c, a, l + 1);
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int ni = 0; ni < NT; ++ni)
-    store_planes4(dst, 16 * mt + 4 * kq, 16 * (nt0 + ni) + col, fmaxf(acc[0][ni][0], 0.f) * osc, fmaxf(acc[0][ni][1], 0.f) * osc,
-                  fmaxf(acc[0][ni][2], 0.f) * osc, fmaxf(acc[0][ni][3], 0.f) * osc);
-  return nxt;
-}
-// last layer: m-tile mt over all four n-tiles, max over each centre's U / 16 tiles and 16 columns, ReLU, one value per row
-// STAGED (the single-tile kernels): the pooled values are not stored here.  A workgroup walks RUNS of consecutive tiles,
-// i.e. 8 consecutive centres of a cloud; the pooled value of (row, centre s of the run) goes to stage[row][s] in LDS and,
-// at the end of the run, all threads write the rows' 32-byte runs (sa3_flush) -- where the unstaged form wrote every (row,
-// centre) as a 4-byte store of its own into its own 32-byte sector (268 MB of HBM writes per launch at SSG-SA2 for a
-// 33.5 MB tensor).  LDS, not registers, carries the run: values kept in registers across tiles were spilled to scratch, and
-// a scratch reload queues behind the next tile's gather in the in-order vmcnt (measured: 1.02 -> 1.26 ms).
-constexpr int kSaRun = 8;   // centres per staged run
-template <class FIRST, bool STAGED = false>
-__device__ __forceinline__ void sa3_last(const Ctx &c, const SaArgs &a, int l, int mt, const float *src, int j0, float *outb,
-                                         const FIRST &first, float bsc, float osc, float *stage = nullptr, int slot0 = 0) {
-  const int col = c.lane & 15, kq = c.lane >> 4;
-  f32x4 acc[1][4];
-  const f32x4 bv = *reinterpret_cast<const f32x4 *>(a.weights + a.b_off[l] + 16 * mt + 4 * kq) * bsc;
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) acc[0][ni] = bv;
-  sa3_gemm<4, FIRST>(c, a.weights + a.w_off[l], a.cin_pad[l] >> 5, mt, 0, src, acc, first);
-  const int tpc = a.u >> 4;   // n-tiles per centre: 1, 2 or 4
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    float m[4];
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) m[ni] = acc[0][ni][r];
-    if (tpc >= 2) { m[0] = fmaxf(m[0], m[1]); m[2] = fmaxf(m[2], m[3]); }
-    if (tpc >= 4) m[0] = fmaxf(m[0], m[2]);
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-      if (ni % tpc) continue;  // wave uniform
-      const float v = fmaxf(row16_max(m[ni]), 0.f) * osc;
-      const int jj = ni / tpc;
-      if constexpr (STAGED) {
-        if (col == 0 && j0 + jj < a.m) ((lds_f *)stage)[(16 * mt + 4 * kq + r) * kSaRun + slot0 + jj] = v;
-      } else {
-        if (col == 0 && j0 + jj < a.m) outb[(size_t)(16 * mt + 4 * kq + r) * a.m + j0 + jj] = v;
-      }
-    }
-  }
-}
-// the staged run -> out[b][row][jbase .. jbase + count) for every row of the last layer: thread = (row, half of the run)
-__device__ __forceinline__ void sa3_flush(const SaArgs &a, const float *stage, int tid, int b, int jbase, int count) {
-  const int rows = a.cout[a.n_layers - 1];
-  for (int i = tid; i < 2 * rows; i += 512) {
-    const int row = i >> 1, h4 = 4 * (i & 1), left = count - h4;
-    if (left <= 0) continue;
-    const f32x4 v = *reinterpret_cast<const lds_f4 *>((const lds_f *)stage + row * kSaRun + h4);
-    float *o = a.out + ((size_t)b * rows + row) * a.m + jbase + h4;
-    if (left >= 4 && (((size_t)o & 15) == 0)) *reinterpret_cast<f32x4 *>(o) = v;
-    else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (e < left) o[e] = v[e];
-    }
-  }
-}
-
-// One layer of the multi-tile form over all `sub` tiles of a workgroup pass: the m-tile's weight fragments (KB blocks x 3
-// planes) are requested ONCE and stay in registers while the tiles' planes stream through -- per tile only LDS reads,
-// MFMAs and the epilogue remain (through gemm1_pl every tile paid the fragments' round trip again: latency bound at 24-96
-// MFMAs per call).  LAST: max over the neighbours instead of the plane stores.
-template <int KB, int NT, bool LAST>
-__device__ __forceinline__ void sa3_layer_multi(const Ctx &c, const SaArgs &a, int l, int mt, int nt0, int sub, int per,
-                                                int src_off, int dst_off, int T, int tiles_per_cloud, int total_tiles,
-                                                float bsc, float osc) {
-  const int col = c.lane & 15, kq = c.lane >> 4, g = kq;
-  const WStream wv(a.weights + a.w_off[l], c.lane);
-  u32x4 af[KB][kSplit];
-#pragma unroll
-  for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-    for (int pl = 0; pl < kSplit; ++pl) af[kb][pl] = wv.raw_at((mt * KB + kb) * kFragBytes, pl * 1024);
-  const f32x4 bv = *reinterpret_cast<const f32x4 *>(a.weights + a.b_off[l] + 16 * mt + 4 * kq) * bsc;
-  const int cpt = 64 / a.u, tpc = a.u >> 4;
-  for (int st = 0; st < sub; ++st) {
-    const lds_u4 *pl3 = (const lds_u4 *)(c.lds + st * per + src_off) + g * 64 + 16 * nt0 + col;
-    f32x4 acc[NT];
-#pragma unroll
-    for (int ni = 0; ni < NT; ++ni) acc[ni] = bv;
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb) {
-      u32x4 bs[NT][kSplit];
-#pragma unroll
-      for (int ni = 0; ni < NT; ++ni)
-#pragma unroll
-        for (int pl = 0; pl < kSplit; ++pl) bs[ni][pl] = pl3[(kb * kSplit + pl) * 256 + 16 * ni];
-#pragma unroll
-      for (int ni = 0; ni < NT; ++ni) acc[ni] = mfma_split(af[kb], bs[ni], acc[ni]);
-    }
-    if constexpr (!LAST) {
-#pragma unroll
-      for (int ni = 0; ni < NT; ++ni)
-        store_planes4(c.lds + st * per + dst_off, 16 * mt + 4 * kq, 16 * (nt0 + ni) + col, fmaxf(acc[ni][0], 0.f) * osc,
-                      fmaxf(acc[ni][1], 0.f) * osc, fmaxf(acc[ni][2], 0.f) * osc, fmaxf(acc[ni][3], 0.f) * osc);
-    } else {
-      static_assert(!LAST || NT == 4, "the max runs over all four n-tiles of a tile");
-      const int t = T * sub + st;
-      if (t < total_tiles) {   // wave uniform
-        const int b = t / tiles_per_cloud, j0 = (t - b * tiles_per_cloud) * cpt;
-        float *outb = a.out + (size_t)b * a.cout[l] * a.m;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float m[4];
-#pragma unroll
-          for (int ni = 0; ni < 4; ++ni) m[ni] = acc[ni < NT ? ni : 0][r];
-          if (tpc >= 2) { m[0] = fmaxf(m[0], m[1]); m[2] = fmaxf(m[2], m[3]); }
-          if (tpc >= 4) m[0] = fmaxf(m[0], m[2]);
-#pragma unroll
-          for (int ni = 0; ni < 4; ++ni) {
-            if (ni % tpc) continue;  // wave uniform
-            const float v = fmaxf(row16_max(m[ni]), 0.f) * osc;
-            const int jj = ni / tpc;
-            if (col == 0 && j0 + jj < a.m) outb[(size_t)(16 * mt + 4 * kq + r) * a.m + j0 + jj] = v;
-          }
-        }
-      }
-    }
-  }
-}
-template <int NT, bool LAST>
-__device__ __forceinline__ void sa3_layer_multi_kb(const Ctx &c, const SaArgs &a, int l, int mt, int nt0, int sub, int per,
-                                                   int src_off, int dst_off, int T, int tiles_per_cloud, int total_tiles,
-                                                   float bsc, float osc) {
-  switch (a.cin_pad[l] >> 5) {
-    case 1: sa3_layer_multi<1, NT, LAST>(c, a, l, mt, nt0, sub, per, src_off, dst_off, T, tiles_per_cloud, total_tiles, bsc, osc); break;
-    case 2: sa3_layer_multi<2, NT, LAST>(c, a, l, mt, nt0, sub, per, src_off, dst_off, T, tiles_per_cloud, total_tiles, bsc, osc); break;
-    default: sa3_layer_multi<4, NT, LAST>(c, a, l, mt, nt0, sub, per, src_off, dst_off, T, tiles_per_cloud, total_tiles, bsc, osc); break;
-  }
-}
-
-// SUBMAX > 1: narrow nets (SSG SA1: 3 -> 64 -> 64 -> 128 over 512 centres per cloud) have 1.3 k cycles of MFMAs per
-// 64-column tile against ~13 k of per-tile cost (four barriers, three cold layer starts, the gather's round trip): a
-// workgroup then takes `sub` consecutive tiles at once -- their planes side by side in LDS, every layer swept over all of
-// them between two barriers, the weight fragments of the later ones coming from L1.  QUADS: row quads a gather thread
-// holds per tile (9 covers 288 input rows; the multi-tile form takes 32-row inputs: one quad).
-// PRE: the module's first layer is not a GEMM here.  W1 [x - c; f] = W1a (x - c) + W1b f, and W1b f + b1 depends on the
-// POINT only: the caller computes it once per cloud (a.pre), the gather threads fetch a neighbour's 4 rows of it instead of
-// 4 feature rows, add the three coordinate products and apply the ReLU -- the tile that goes into LDS is the first
-// layer's OUTPUT.  One k-loop, one plane-writing epilogue and one barrier per tile less, 29 % fewer MFMAs at SSG-SA2.
-// (The second launch bound is waves per SIMD: 4 = two co-resident workgroups, i.e. 128 registers.  The hoisted form with
-// up to four row quads per gather thread fits them; the general one holds nine quads and runs one workgroup per CU.)
-template <int SUBMAX, int QUADS, bool PRE = false>
-__global__ __launch_bounds__(512, (PRE && QUADS <= 4) ? 4 : 2) void sa_mlp3_kernel(const SaArgs a, int blocks_a, int blocks_b, int sub,
-                                                         int tiles_per_cloud, int total_tiles) {
-  extern __shared__ float lds[];
-  Ctx c{a.weights, lds, (int)threadIdx.x, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), (int)threadIdx.x & 63,
-        0, 4};
-  const int cpt = 64 / a.u;  // centres per tile
-  const int per = (blocks_a + blocks_b) * kSaBlockFloats;   // floats of one tile's two plane regions
-  const int w = c.wave, col = c.lane, qg = c.wave;   // gather: thread = (column, row-quad group)
-  const int nquads = a.cin_pad[0] >> 2;
-  const int supers = (total_tiles + sub - 1) / sub;
-  float gv[SUBMAX][QUADS][4];
-  float dxyz[SUBMAX][PRE ? 4 : 1];   // PRE: the column's x - c (3) and its live mask
-  // The neighbour index of a column is requested a tile ahead of the gather that dereferences it (idx_request at the end
-  // of the previous gather_load): read where it is used, every tile began with an exposed round trip for the index in
-  // front of the gather's own.
-  int id_pf[SUBMAX];
-  auto idx_request = [&](int T) {
-#pragma unroll
-    for (int st = 0; st < SUBMAX; ++st) {
-      const int t0 = T * sub + (st < sub ? st : 0);
-      const int t = t0 < total_tiles ? t0 : total_tiles - 1;
-      const int b = t / tiles_per_cloud, tile = t - b * tiles_per_cloud, j0 = tile * cpt, jj = col / a.u;
-      const bool live = j0 + jj < a.m;
-      id_pf[st] = (a.idx + ((size_t)b * a.m + j0) * a.u)[live ? col : 0];
-    }
-  };
-  auto gather_load = [&](int T) {   // idx_request(T) went before
-#pragma unroll
-    for (int st = 0; st < SUBMAX; ++st) {
-      const int t0 = T * sub + (st < sub ? st : 0);
-      const int t = t0 < total_tiles ? t0 : total_tiles - 1;   // clamped: every load stays unconditional
-      const int b = t / tiles_per_cloud, tile = t - b * tiles_per_cloud, j0 = tile * cpt, jj = col / a.u;
-      const bool live = j0 + jj < a.m;
-      const float *pts = a.points + (size_t)b * 3 * a.n, *ctr = a.centers + (size_t)b * 3 * a.m;
-      const float *feat = a.feat ? a.feat + (size_t)b * a.c * a.n : a.points;
-      const int id = live ? id_pf[st] : 0;
-      const int jc = live ? j0 + jj : 0, cmax = a.c > 0 ? a.c - 1 : 0;
-      if constexpr (PRE) {
-        // pre is POINT-major, [b][n][c1]: a neighbour's rows are one run of c1 floats, a thread's row quad one 16-byte load
-        // (channel-major, the 4-byte gathers of a tile were 8192 cache-line requests: the texture addresser, not the
-        // matrix pipe, bounded the kernel -- a layer less changed nothing)
-        const f32x4 *prow = reinterpret_cast<const f32x4 *>(a.pre + (a.pre_bcast ? (size_t)0 : ((size_t)b * a.n + id) * a.c1));
-#pragma unroll
-        for (int e = 0; e < 3; ++e) dxyz[st][e] = pts[e * a.n + id] - ctr[e * a.m + jc];
-        dxyz[st][3] = live ? 1.0f : 0.0f;
-        const int qmax = (a.c1 >> 2) - 1;
-#pragma unroll
-        for (int i = 0; i < QUADS; ++i) {
-          const int rq = qg + 8 * i;
-          const f32x4 v4 = prow[rq < qmax ? rq : qmax];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) gv[st][i][e] = v4[e];
-        }
-        continue;
-      }
-#pragma unroll
-      for (int i = 0; i < QUADS; ++i) {
-        const int rq = qg + 8 * i;   // rows 4 rq .. 4 rq + 3: [x y z f0] for quad 0, f[4 rq - 3 ..] after it
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int ch = 4 * rq + e;
-          float v;
-          if (ch < 3) v = pts[ch * a.n + id] - ctr[ch * a.m + jc];
-          else { const int f = ch - 3; v = feat[(size_t)(f < cmax ? f : cmax) * a.n + id]; v = f < a.c ? v : 0.f; }
-          gv[st][i][e] = live ? v : 0.f;
-        }
-      }
-    }
-  };
-  // PRE: gv holds the neighbours' rows of W1b f + b1; add W1a (x - c), ReLU -> the first layer's output (dead columns and
-  // rows beyond c1: zero).  W1a's rows are wave uniform (a wave's threads share their row quads).
-  auto gather_finish = [&]() {
-    if constexpr (PRE) {
-      const f32x4 *wa = reinterpret_cast<const f32x4 *>(a.weights + a.wa_off);
-#pragma unroll
-      for (int i = 0; i < QUADS; ++i) {
-        const int rq = qg + 8 * i;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int row = 4 * rq + e;
-          const f32x4 w4 = wa[row < a.c1 ? row : 0];
-#pragma unroll
-          for (int st = 0; st < SUBMAX; ++st) {
-            float h = gv[st][i][e];
-            h = __builtin_fmaf(w4[0], dxyz[st][0], h);
-            h = __builtin_fmaf(w4[1], dxyz[st][1], h);
-            h = __builtin_fmaf(w4[2], dxyz[st][2], h);
-            gv[st][i][e] = row < a.c1 ? fmaxf(h, 0.f) * dxyz[st][3] : 0.f;
-          }
-        }
-      }
-    }
-  };
-  // Range scale of the gathered tile(s) (range_pow2): every wave publishes the largest magnitude it holds in front of a
-  // barrier the tile needs anyway, all read the eight words behind it.  m_in / s_in: of the tile(s) about to be stored.
-  float *rng = lds + (size_t)sub * per;   // [8], behind the planes (the launcher adds the room)
-  float m_in = 0.f, s_in = 1.f;
-  auto range_publish = [&]() {
-    float mx = 0.f;
-#pragma unroll
-    for (int st = 0; st < SUBMAX; ++st)
-#pragma unroll
-      for (int i = 0; i < QUADS; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) mx = fmaxf(mx, fabsf(gv[st][i][e]));
-    mx = half_max(row_pair_max(row16_max(mx)));
-    if (c.lane == 0) rng[c.wave] = mx;
-  };
-  auto range_read = [&]() {
-    const f32x4 r0 = *reinterpret_cast<const f32x4 *>(rng), r1 = *reinterpret_cast<const f32x4 *>(rng + 4);
-    const float mx = fmaxf(fmaxf(fmaxf(r0[0], r0[1]), fmaxf(r0[2], r0[3])), fmaxf(fmaxf(r1[0], r1[1]), fmaxf(r1[2], r1[3])));
-    m_in = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(mx)));
-    s_in = range_pow2(m_in);
-  };
-  auto gather_store = [&]() {
-    const float inv = pow2_inv(s_in);
-#pragma unroll
-    for (int st = 0; st < SUBMAX; ++st) {
-      if (st < sub) {
-#pragma unroll
-        for (int i = 0; i < QUADS; ++i) {
-          const int rq = qg + 8 * i;
-          if (rq < nquads)
-            store_planes4(lds + st * per, 4 * rq, col, gv[st][i][0] * inv, gv[st][i][1] * inv, gv[st][i][2] * inv, gv[st][i][3] * inv);
-        }
-      }
-    }
-  };
-  Frag3 frag;   // block-0 fragments of the wave's first m-tile of the NEXT layer to run
-  // The request for the next layer's first fragments sits behind this layer's (first) k-loop, in front of its stores: in
-  // flight under the epilogue and the barrier.  Straight-line code: the fragments travel by value.
-  auto hidden = [&](int l, bool a_to_b, float bsc, float osc) {
-    const int mtiles = a.cout[l] >> 4;
-    Ctx cl = c;
-    asm volatile("" : "+v"(cl.tid), "+v"(cl.lane));
-    if constexpr (SUBMAX > 1) {   // weights once per layer, the tiles stream through (sa3_layer_multi)
-      const int so = a_to_b ? 0 : blocks_a * kSaBlockFloats, dof = a_to_b ? blocks_a * kSaBlockFloats : 0;
-      if (mtiles >= 8) {
-        for (int p = 0; p < (mtiles >> 3); ++p) sa3_layer_multi_kb<4, false>(cl, a, l, w + 8 * p, 0, sub, per, so, dof, 0, 1, 0, bsc, osc);
-      } else if (mtiles == 4) sa3_layer_multi_kb<2, false>(cl, a, l, w & 3, 2 * (w >> 2), sub, per, so, dof, 0, 1, 0, bsc, osc);
-      else sa3_layer_multi_kb<1, false>(cl, a, l, w & 1, w >> 1, sub, per, so, dof, 0, 1, 0, bsc, osc);
-      return;
-    }
-    const Frag3 cur = frag;
-    for (int st = 0; st < sub; ++st) {
-      const float *src = lds + st * per + (a_to_b ? 0 : blocks_a * kSaBlockFloats);
-      float *dst = lds + st * per + (a_to_b ? blocks_a * kSaBlockFloats : 0);
-      if (st == 0) {
-        if (mtiles == 8) frag = sa3_hidden<4, Frag3, true>(cl, a, l, w, 0, src, dst, cur, bsc, osc);
-        else if (mtiles == 16) {
-          sa3_hidden<4, Frag3, false>(cl, a, l, w, 0, src, dst, cur, bsc, osc);
-          frag = sa3_hidden<4, NoFirst, true>(cl, a, l, w + 8, 0, src, dst, NoFirst(), bsc, osc);
-        } else if (mtiles == 4) frag = sa3_hidden<2, Frag3, true>(cl, a, l, w & 3, 2 * (w >> 2), src, dst, cur, bsc, osc);
-        else frag = sa3_hidden<1, Frag3, true>(cl, a, l, w & 1, w >> 1, src, dst, cur, bsc, osc);
-      } else if constexpr (SUBMAX > 1) {
-        if (mtiles == 8) sa3_hidden<4, NoFirst, false>(cl, a, l, w, 0, src, dst, NoFirst(), bsc, osc);
-        else if (mtiles == 16) {
-          sa3_hidden<4, NoFirst, false>(cl, a, l, w, 0, src, dst, NoFirst(), bsc, osc);
-          sa3_hidden<4, NoFirst, false>(cl, a, l, w + 8, 0, src, dst, NoFirst(), bsc, osc);
-        } else if (mtiles == 4) sa3_hidden<2, NoFirst, false>(cl, a, l, w & 3, 2 * (w >> 2), src, dst, NoFirst(), bsc, osc);
-        else sa3_hidden<1, NoFirst, false>(cl, a, l, w & 1, w >> 1, src, dst, NoFirst(), bsc, osc);
-      }
-    }
-  };
-  // Tile order.  SUBMAX > 1: workgroup w takes super-tiles w, w + grid, ...  SUBMAX == 1: RUNS of consecutive tiles = 8
-  // consecutive centres of a cloud, so that the pooled rows leave as 32-byte runs (SaOutStage); the runs are dealt
-  // w, w + grid, ... in an order that gives the workgroups of one XCD (blockIdx % 8: the dispatcher's round robin)
-  // neighbouring runs: at any time the chip works on ~32 clouds and an XCD on four of them, whose features stay in its L2.
-  // (Measured and dropped: one contiguous range of 64 tiles per workgroup, 16-centre runs -- every workgroup on a cloud of
-  // its own, 256 clouds live at once: 1.02 -> 1.31 ms at SSG-SA2, the gathers miss L2.)
-  constexpr bool kRuns = SUBMAX == 1;
-  const int grid = gridDim.x;
-  const int run = !kRuns ? 1 : (supers < 8 * grid ? 1 : (cpt >= kSaRun ? 1 : kSaRun / cpt));   // small launches: a tile per workgroup at a time
-  const int w8 = !kRuns ? (int)blockIdx.x
-                        : ((grid & 7) == 0 ? ((int)blockIdx.x & 7) * (grid >> 3) + ((int)blockIdx.x >> 3) : (int)blockIdx.x);
-  auto tile_of = [&](int q) { return (w8 + (q / run) * grid) * run + q % run; };   // this workgroup's q-th (super-)tile
-  int q = 0, T = tile_of(0);
-  if (T >= supers) return;   // (whole workgroup: no barrier has been reached yet)
-  float *stage = rng + 16;   // [rows of the last layer][kSaRun] (kRuns; the launcher adds the room)
-  int st_count = 0, st_b = 0, st_jbase = 0;
-  idx_request(T);
-  gather_load(T);
-  {
-    const int T1 = tile_of(1);
-    idx_request(T1 < supers ? T1 : T);
-  }
-  frag = sa3_request(c, a, 0);
-  gather_finish();
-  if (a.ranged) {
-    range_publish();
-    __syncthreads();
-    range_read();
-  }
-  gather_store();
-  __syncthreads();
-  for (; T < supers; T = tile_of(++q)) {
-    bool a_to_b = true;
-    // scales of this tile's planes, layer by layer: the input's is measured, a hidden layer's follows from the bound
-    // |out| <= gain_r * max |in| + gain_b (true units)
-    float bnd = m_in, s_cur = s_in;
-    for (int l = 0; l + 1 < a.n_layers; ++l) {
-      bnd = a.gain_r[l] * bnd + a.gain_b[l];
-      const float s_nxt = a.ranged ? range_pow2(bnd) : 1.0f;
-      hidden(l, a_to_b, pow2_inv(s_cur), s_cur * pow2_inv(s_nxt));
-      s_cur = s_nxt;
-      __syncthreads();
-      a_to_b = !a_to_b;
-    }
-    const int Tq = tile_of(q + 1), Tn = Tq < supers ? Tq : T;
-    gather_load(Tn);
-    {
-      const int T2 = tile_of(q + 2);
-      idx_request(T2 < supers ? T2 : Tn);   // for the gather of the tile after next
-    }
-    {
-      const int l = a.n_layers - 1, mtiles = a.cout[l] >> 4;
-      const float bsc = pow2_inv(s_cur), osc = s_cur;
-      Ctx cl = c;
-      asm volatile("" : "+v"(cl.tid), "+v"(cl.lane));
-      if constexpr (SUBMAX > 1) {
-        const int so = a_to_b ? 0 : blocks_a * kSaBlockFloats;
-        for (int mt = w; mt < mtiles; mt += 8)
-          sa3_layer_multi_kb<4, true>(cl, a, l, mt, 0, sub, per, so, 0, T, tiles_per_cloud, total_tiles, bsc, osc);
-      }
-      const Frag3 cur = frag;
-      for (int st = 0; st < (SUBMAX > 1 ? 0 : sub); ++st) {
-        const int t = T * sub + st;
-        if (t >= total_tiles) break;   // wave uniform
-        const int b = t / tiles_per_cloud, j0 = (t - b * tiles_per_cloud) * cpt;
-        float *outb = a.out + (size_t)b * a.cout[l] * a.m;
-        const float *src = lds + st * per + (a_to_b ? 0 : blocks_a * kSaBlockFloats);
-        if constexpr (kRuns) {
-          const int live = a.m - j0 < cpt ? a.m - j0 : cpt;          // centres of this tile that exist
-          if (st_count == 0) { st_b = b; st_jbase = j0; }
-          if (w < mtiles) sa3_last<Frag3, true>(cl, a, l, w, src, j0, outb, cur, bsc, osc, stage, st_count);
-          for (int mt = w + 8; mt < mtiles; mt += 8) sa3_last<NoFirst, true>(cl, a, l, mt, src, j0, outb, NoFirst(), bsc, osc, stage, st_count);
-          st_count += live;
-        } else {
-        if (st == 0) {
-          if (w < mtiles) sa3_last<Frag3>(cl, a, l, w, src, j0, outb, cur, bsc, osc);
-        } else {
-          if (w < mtiles) sa3_last<NoFirst>(cl, a, l, w, src, j0, outb, NoFirst(), bsc, osc);
-        }
-        for (int mt = w + 8; mt < mtiles; mt += 8) sa3_last<NoFirst>(cl, a, l, mt, src, j0, outb, NoFirst(), bsc, osc);
-        }
-      }
-      frag = sa3_request(c, a, 0);   // the next tile's first layer
-    }
-    gather_finish();                 // the next tile's gathered values have long landed
-    if (a.ranged) range_publish();
-    __syncthreads();  // the last layer may have been reading region A
-    if constexpr (kRuns) {
-      // the run ends here unless the next tile continues it (same cloud, the next centres, room in the stage)
-      bool more = Tq < supers;
-      if (more) {
-        const int bn = Tq / tiles_per_cloud, jn = (Tq - bn * tiles_per_cloud) * cpt;
-        const int liven = a.m - jn < cpt ? a.m - jn : cpt;
-        more = bn == st_b && jn == st_jbase + st_count && st_count + liven <= kSaRun;
-      }
-      if (!more) {
-        sa3_flush(a, stage, c.tid, st_b, st_jbase, st_count);
-        st_count = 0;
-      }
-    }
-    if (a.ranged) range_read();
-    gather_store();
-    __syncthreads();
-  }
-}
-
-
-// Scale / shift rows of every ResnetBlock for one conditioning cloud (ResnetBlock.mlp, resnets.py:125-151, when the
-// embedding has no time part: the pose decoder):  ss[rb][row] = comb_b[row] + sum_e W[row][e] G[e],  G = sum over the
-// cond rows of SiLU(cemb) -- the value the conv epilogue would compute with MFMAs for every sample and column.
-// Table layout per cloud: blocks in tape order, [scale rows (C) | shift rows (C)] each (build_tape's tab_off).
-__global__ __launch_bounds__(256) void ss_table_kernel(const gldm_r1d_desc d, const float *__restrict__ w,
-                                                       const float *__restrict__ cemb, int stride,
-                                                       float *__restrict__ tab) {
-  __shared__ float G[256];
-  const int cond = blockIdx.x, E = d.emb_dim, R = d.cond_rows, ekb = E >> 4;
-  for (int e = threadIdx.x; e < E; e += blockDim.x) {
-    float g = 0.f;
-    for (int r = 0; r < R; ++r) g += silu(cemb[((size_t)cond * R + r) * E + e]);
-    G[e] = g;
-  }
-  __syncthreads();
-  float *out = tab + (size_t)cond * stride;
-  int off = 0;
-  const int n_rb = 2 * d.n_levels + 1;
-  for (int i = 0; i < n_rb; ++i) {
-    const int C = d.dims[i < 2 * d.n_levels ? i / 2 : d.n_levels];
-    const gldm_r1d_resblock &rb = d.rb[i];
-    for (int row = threadIdx.x; row < 2 * C; row += blockDim.x) {
-      // packed A fragments of the [2C x E] Linear: W[row][e] at ((mt * ekb + kb) * 64 + 16 kq + i) * 4 + j,
-      // row = 16 mt + i, e = 16 kb + 4 j + kq
-      const float *wr = w + rb.ss_w + (size_t)(row >> 4) * ekb * 256 + (row & 15) * 4;
-      float acc = w[rb.ss_b + row];
-      for (int kb = 0; kb < ekb; ++kb)
-        for (int j = 0; j < 4; ++j)
-          for (int kq = 0; kq < 4; ++kq) acc = fmaf(wr[kb * 256 + kq * 64 + j], G[16 * kb + 4 * j + kq], acc);
-      out[off + row] = acc;
-    }
-    off += 2 * C;
-  }
-}
-
 }  // namespace
 
 GLDM_API int gldm_r1d_cond_embed(const float *z_cond, const float *w, const float *b, int n_cond, int rows, int dc,
@@ -5116,16 +2886,6 @@ GLDM_API int gldm_denoise_rng(const gldm_r1d_desc *desc, const float *weights, c
   return launch_r1d(a, reinterpret_cast<hipStream_t>(stream));
 }
 
-// The generator on its own (n latents x L positions of one step), for the statistical tests: out [n][L]
-__global__ void philox_normal_kernel(unsigned long long seed, long long base, int step, int n, int L, float *out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n * L) return;
-  const int gi = i / L, l = i - gi * L;
-  const unsigned long long g = (unsigned long long)(base + gi);
-  float z4[4];
-  philox_normal4(seed, (unsigned)g, (unsigned)(g >> 32), (unsigned)(l >> 2), (unsigned)step, z4);
-  out[i] = z4[l & 3];
-}
 GLDM_API int gldm_step_noise_rng(unsigned long long noise_seed, long long noise_base, int step, int n_samples, int seq_len,
                                  float *out, gldm_stream_t stream) {
   if (!out || n_samples <= 0 || seq_len <= 0 || step < 0 || noise_base < 0) return GLDM_ERR_INVALID_ARG;
@@ -5148,17 +2908,7 @@ GLDM_API int gldm_decode(const gldm_r1d_desc *desc, const float *weights, const 
   a.weights = weights; a.temb = nullptr; a.cemb = cemb; a.samples_per_cond = samples_per_cond;
   a.x_in = z_h; a.n_samples = n_samples; a.n_steps = 1; a.sched_kind = GLDM_SCHED_NONE;
   a.out0 = tmrp; a.out1 = logit; a.ws = reinterpret_cast<float *>(workspace);
-  const int rows = ss_table_rows(desc);
-  if (rows > 0) {  // the table lives behind the hand-off granules of the workspace (gldm_r1d_workspace_bytes)
-    const long long off = ws_layout(desc, n_samples).ss_off;
-    float *tab = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + off);
-    const int n_cond = (n_samples + samples_per_cond - 1) / samples_per_cond;
-    hipLaunchKernelGGL(ss_table_kernel, dim3(n_cond), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *desc, weights,
-                       cemb, rows, tab);
-    if (hipGetLastError() != hipSuccess) return GLDM_ERR_LAUNCH;
-    a.ss_tab = tab;
-    a.ss_stride = rows;
-  }
+  if (!launch_ss_table(a, reinterpret_cast<hipStream_t>(stream))) return GLDM_ERR_LAUNCH;
   return launch_r1d(a, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -5179,17 +2929,7 @@ GLDM_API int gldm_encode(const gldm_r1d_desc *desc, const float *weights, const 
   a.x_in = h; a.n_samples = n_samples; a.n_steps = 1; a.sched_kind = GLDM_SCHED_NONE;
   a.out0 = mu; a.out1 = logvar; a.out2 = z; a.eps = eps; a.mix_mu = mix_mu; a.mix_eps = mix_eps;
   a.eps_times_std = eps_times_std; a.ws = reinterpret_cast<float *>(workspace);
-  const int rows = ss_table_rows(desc);
-  if (rows > 0) {  // as gldm_decode: the per-cloud scale/shift table behind the hand-off granules
-    const long long off = ws_layout(desc, n_samples).ss_off;
-    float *tab = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + off);
-    const int n_cond = (n_samples + samples_per_cond - 1) / samples_per_cond;
-    hipLaunchKernelGGL(ss_table_kernel, dim3(n_cond), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *desc, weights,
-                       cemb, rows, tab);
-    if (hipGetLastError() != hipSuccess) return GLDM_ERR_LAUNCH;
-    a.ss_tab = tab;
-    a.ss_stride = rows;
-  }
+  if (!launch_ss_table(a, reinterpret_cast<hipStream_t>(stream))) return GLDM_ERR_LAUNCH;
   return launch_r1d(a, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -5212,352 +2952,5 @@ GLDM_API int gldm_pose_epilogue(const float *tmrp, const float *logit, const flo
   if (confidence && !logit) return GLDM_ERR_INVALID_ARG;
   hipLaunchKernelGGL(pose_epilogue_kernel, dim3((n + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      tmrp, logit, grasp_mean, grasp_std, n, grasps_per_cloud, H, tmrp_unnorm, confidence);
-  return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
-}
-
-
-namespace {
-int launch_pointwise(const float *x, const float *w0, const float *b0, int cin0, const float *w, const float *bias, int b,
-                     int cin_arg, int cout, int n, int relu, const float *head_w, const float *head_b, int hout, float *y,
-                     float *z, hipStream_t stream, bool split_f16 = false, const float *add = nullptr, long long add_bs = 0,
-                     long long add_rs = 0, long long add_cs = 0, const float *front_gain = nullptr, bool y_point_major = false) {
-  if (y_point_major && (!split_f16 || !y)) return GLDM_ERR_UNSUPPORTED;
-  if (add && !split_f16) return GLDM_ERR_UNSUPPORTED;
-  // The split launch without a front layer takes any multiple of 8 input rows: K is padded to whole 128-deep trips of its
-  // weight ring (the caller's fragments carry zero columns there: r1d_pack.mfma_a_fragments_f16x2 of the padded matrix)
-  const int cin_rows = cin_arg;
-  const int cin = (split_f16 && !w0 && cin_arg > 0 && (cin_arg & 7) == 0) ? (cin_arg + 127) & ~127 : cin_arg;
-  if (!x || !w || !bias || b <= 0 || cin <= 0 || cout <= 0 || n <= 0) return GLDM_ERR_INVALID_ARG;
-  if (!y && !head_w) return GLDM_ERR_INVALID_ARG;
-  if (head_w && (!z || hout <= 0 || hout > 16)) return GLDM_ERR_INVALID_ARG;
-  // k-blocks in pairs, 32-point tiles; output rows: 2 m-tiles x 8 waves per round on the f32 kernel, units of two m-tiles on
-  // the split one (fewer than eight units -- 64 .. 224 output rows -- leave waves without a unit idle)
-  // the split launch hands out its output rows in units of two m-tiles, or of one where two would leave waves idle (fewer
-  // than 256 rows, no front layer / head): then any multiple of 16 rows
-  // (narrow inputs only: 32-point planes within half a CU's LDS, i.e. the 32-point tile form stays)
-  const int mu = (split_f16 && !w0 && !head_w && cout < 256 && ((size_t)cin * 32 * 2 * kSplit + 64) * 2 <= (size_t)160 * 1024) ? 1 : 2;
-  if ((cin & 31) || (split_f16 ? (n & 15) : (n & 31)) || (split_f16 ? (cout & (16 * mu - 1)) : (cout & 255))) return GLDM_ERR_UNSUPPORTED;
-  if ((w0 || head_w) && (cout & 255)) return GLDM_ERR_UNSUPPORTED;   // front layer / head: whole rounds of units only
-  if (w0 && (!b0 || cin0 <= 0 || (cin0 & 31) || (cin & 255))) return GLDM_ERR_UNSUPPORTED;
-  size_t lds_bytes = ((size_t)cin * 32 + 8 * 16 * 32 + (w0 ? (size_t)cin0 * 32 : 0)) * sizeof(float);
-  if (split_f16) {  // `w` and `w0` hold split-f16 fragments: planes of the tile + the front layer's f32 tile
-    if (cin & 127) return GLDM_ERR_UNSUPPORTED;  // the A ring walks four 32-deep blocks per trip
-    if (w0 && cin0 > 96) return GLDM_ERR_UNSUPPORTED;  // the front layer keeps its whole split tile in registers (72)
-  }
-  int dyn_first = 0, ticket_off = 0, nt = 2, x0_in_planes = 0;
-  if (split_f16) {
-    // LDS plan: planes | head products of the drawn units (the front layer's f32 tile lies under them: dead by then) |
-    // ticket.  As many units are drawn as have room for their head slot (all but the first round when there is no head).
-    // Tile width: 48 points where 32-point planes already take more than half a CU's LDS (one workgroup per CU either way)
-    // and the 48-point plan fits; the front tile then goes UNDER the planes (x0_in_planes).
-    const size_t cap = (size_t)160 * 1024 - 64;   // ticket + range words
-    const int units = cout / (16 * mu);
-    auto plan = [&](int ncol, bool x0_under, size_t &planes, size_t &region, int &first) {
-      planes = (size_t)cin * ncol * 2 * kSplit;   // bytes: cin x ncol x kSplit f16
-      region = (w0 && !x0_under) ? (size_t)cin0 * ncol * sizeof(float) : 0;
-      if (planes + region > cap) return false;
-      if (x0_under && (size_t)cin0 * ncol * sizeof(float) > planes) return false;
-      int drawn = units > 8 ? units - 8 : 0;
-      if (head_w) {
-        const size_t slot = (size_t)hout * ncol * sizeof(float);
-        const int room = (int)((cap - planes) / slot);
-        if (drawn > room) drawn = room;
-        if (planes < (size_t)8 * 16 * ncol * sizeof(float)) drawn = 0;   // z partials need the planes' space
-      }
-      first = (units - drawn + 7) & ~7;   // whole rounds are dealt
-      if (head_w && (size_t)(units - first) * hout * ncol * sizeof(float) > region)
-        region = (size_t)(units - first) * hout * ncol * sizeof(float);
-      return planes + region <= cap;
-    };
-    size_t planes = 0, region = 0;
-    if (!plan(32, false, planes, region, dyn_first)) return GLDM_ERR_UNSUPPORTED;
-    if ((planes + region + 64) * 2 > (size_t)160 * 1024 && n >= 48) {
-      size_t p3 = 0, r3 = 0;
-      int f3 = 0;
-      if (plan(48, w0 != nullptr, p3, r3, f3)) {
-        nt = 3; planes = p3; region = r3; dyn_first = f3; x0_in_planes = w0 ? 1 : 0;
-      }
-    }
-    ticket_off = (int)((planes + region) / sizeof(float));
-    lds_bytes = planes + region + 64;   // ticket (16 B) + the eight range words
-  }
-  if (lds_bytes > 160 * 1024) return GLDM_ERR_UNSUPPORTED;
-  struct PwTag { int site; };
-  struct PwBfTag { int site; };
-  struct PwBfAddTag { int site; };
-  struct PwBf3Tag { int site; };
-  struct PwBfAdd3Tag { int site; };
-  struct PwBf1Tag { int site; };
-  struct PwBfAdd1Tag { int site; };
-  if (split_f16 && mu == 1 && nt == 2) {
-    if (add) gldm_dev::allow_dynamic_lds<PwBfAdd1Tag>(reinterpret_cast<const void *>(&pointwise_mlp_sp_kernel<true, 2, 1>), 160 * 1024);
-    else gldm_dev::allow_dynamic_lds<PwBf1Tag>(reinterpret_cast<const void *>(&pointwise_mlp_sp_kernel<false, 2, 1>), 160 * 1024);
-  } else if (split_f16 && add && nt == 3) gldm_dev::allow_dynamic_lds<PwBfAdd3Tag>(reinterpret_cast<const void *>(&pointwise_mlp_sp_kernel<true, 3>), 160 * 1024);
-  else if (split_f16 && nt == 3) gldm_dev::allow_dynamic_lds<PwBf3Tag>(reinterpret_cast<const void *>(&pointwise_mlp_sp_kernel<false, 3>), 160 * 1024);
-  else if (split_f16 && add) gldm_dev::allow_dynamic_lds<PwBfAddTag>(reinterpret_cast<const void *>(&pointwise_mlp_sp_kernel<true, 2>), 160 * 1024);
-  else if (split_f16) gldm_dev::allow_dynamic_lds<PwBfTag>(reinterpret_cast<const void *>(&pointwise_mlp_sp_kernel<false, 2>), 160 * 1024);
-  else gldm_dev::allow_dynamic_lds<PwTag>(reinterpret_cast<const void *>(&pointwise_mlp_kernel), 160 * 1024);
-  PwArgs a{};
-  a.x = x; a.w = w; a.bias = bias; a.head_w = head_w; a.head_b = head_b; a.y = y; a.z = z;
-  a.cin = cin; a.cout = cout; a.n = n; a.relu = relu; a.hout = hout;
-  a.w0 = w0; a.bias0 = b0; a.cin0 = cin0;
-  a.dyn_first = dyn_first; a.ticket_off = ticket_off; a.x0_in_planes = x0_in_planes;
-  a.add = add; a.add_bs = add_bs; a.add_rs = add_rs; a.add_cs = add_cs;
-  // range scales: a lone layer measures its input tile; with a layer in front the caller's gain bounds its output
-  a.y_point_major = y_point_major ? 1 : 0;
-  a.cin_rows = cin_rows;
-  a.rng_off = ticket_off + 4;
-  a.ranged = split_f16 && (!w0 || front_gain);
-  if (w0 && front_gain) {
-    a.gain0_r = front_gain[0]; a.gain0_b = front_gain[1];
-    if (!(a.gain0_r >= 0.f) || !(a.gain0_b >= 0.f)) return GLDM_ERR_INVALID_ARG;
-  }
-  a.tiles_per_cloud = (n + 16 * nt - 1) / (16 * nt);
-  a.total_tiles = b * a.tiles_per_cloud;
-  const int per_cu = lds_bytes * 2 <= 160 * 1024 ? 2 : 1;
-  int grid = cu_count() * per_cu;
-  if (grid > a.total_tiles) grid = a.total_tiles;
-  if (split_f16 && mu == 1 && nt == 2) {
-    if (add) hipLaunchKernelGGL((pointwise_mlp_sp_kernel<true, 2, 1>), dim3(grid), dim3(512), lds_bytes, stream, a);
-    else hipLaunchKernelGGL((pointwise_mlp_sp_kernel<false, 2, 1>), dim3(grid), dim3(512), lds_bytes, stream, a);
-  } else if (split_f16 && add && nt == 3) hipLaunchKernelGGL((pointwise_mlp_sp_kernel<true, 3>), dim3(grid), dim3(512), lds_bytes, stream, a);
-  else if (split_f16 && nt == 3) hipLaunchKernelGGL((pointwise_mlp_sp_kernel<false, 3>), dim3(grid), dim3(512), lds_bytes, stream, a);
-  else if (split_f16 && add) hipLaunchKernelGGL((pointwise_mlp_sp_kernel<true, 2>), dim3(grid), dim3(512), lds_bytes, stream, a);
-  else if (split_f16) hipLaunchKernelGGL((pointwise_mlp_sp_kernel<false, 2>), dim3(grid), dim3(512), lds_bytes, stream, a);
-  else hipLaunchKernelGGL(pointwise_mlp_kernel, dim3(grid), dim3(512), lds_bytes, stream, a);
-#ifdef GLDM_DEBUG_KNOBS
-  if (split_f16 && getenv("GLDM_PW_STAMP")) {   // diagnostic builds: phase clocks of one steady-state tile (waves 0 and 7)
-    long long h[64];
-    (void)hipStreamSynchronize(stream);
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_pw_stamp), sizeof(h));
-    for (int w = 0; w < 2; ++w) {
-      const long long *q = h + 32 * w;
-      printf("pointwise split %d(%d)->%d b=%d wave %d: stage %lld front %lld barrier %lld |", cin, cin0, cout, b, w ? 7 : 0,
-             q[1] - q[0], q[2] - q[1], q[3] - q[2]);
-      printf(" main %lld wait %lld head %lld total %lld\n", q[16] - q[3], q[17] - q[16], q[18] - q[17], q[18] - q[0]);
-    }
-  }
-#endif
-  return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
-}
-}  // namespace
-
-GLDM_API int gldm_pointwise_mlp(const float *x, const float *w_packed, const float *bias, int b, int cin, int cout,
-                                int n, int relu, const float *head_w_packed, const float *head_bias, int hout,
-                                float *y, float *z, gldm_stream_t stream) {
-  return launch_pointwise(x, nullptr, nullptr, 0, w_packed, bias, b, cin, cout, n, relu, head_w_packed, head_bias, hout,
-                          y, z, reinterpret_cast<hipStream_t>(stream));
-}
-
-GLDM_API int gldm_pointwise_mlp2(const float *x, const float *w0_packed, const float *bias0, int cin0,
-                                 const float *w_packed, const float *bias, int b, int cin, int cout, int n,
-                                 const float *head_w_packed, const float *head_bias, int hout, float *y, float *z,
-                                 gldm_stream_t stream) {
-  if (!w0_packed) return GLDM_ERR_INVALID_ARG;
-  return launch_pointwise(x, w0_packed, bias0, cin0, w_packed, bias, b, cin, cout, n, 1, head_w_packed, head_bias,
-                          hout, y, z, reinterpret_cast<hipStream_t>(stream));
-}
-
-GLDM_API int gldm_pointwise_mlp_f16x2(const float *x, const float *w_split, const float *bias, int b, int cin, int cout,
-                                       int n, int relu, const float *head_w_packed, const float *head_bias, int hout,
-                                       float *y, float *z, gldm_stream_t stream) {
-  return launch_pointwise(x, nullptr, nullptr, 0, w_split, bias, b, cin, cout, n, relu, head_w_packed, head_bias, hout,
-                          y, z, reinterpret_cast<hipStream_t>(stream), true);
-}
-
-GLDM_API int gldm_pointwise_mlp_f16x2_pm(const float *x, const float *w_split, const float *bias, int b, int cin, int cout,
-                                          int n, int relu, float *y_point_major, gldm_stream_t stream) {
-  return launch_pointwise(x, nullptr, nullptr, 0, w_split, bias, b, cin, cout, n, relu, nullptr, nullptr, 0, y_point_major,
-                          nullptr, reinterpret_cast<hipStream_t>(stream), true, nullptr, 0, 0, 0, nullptr, true);
-}
-
-GLDM_API int gldm_pointwise_mlp_f16x2_add(const float *x, const float *w_split, const float *bias, const float *add,
-                                           long long add_cloud_stride, long long add_row_stride, long long add_col_stride, int b,
-                                           int cin, int cout, int n, int relu, float *y, gldm_stream_t stream) {
-  if (!add) return GLDM_ERR_INVALID_ARG;
-  return launch_pointwise(x, nullptr, nullptr, 0, w_split, bias, b, cin, cout, n, relu, nullptr, nullptr, 0, y, nullptr,
-                          reinterpret_cast<hipStream_t>(stream), true, add, add_cloud_stride, add_row_stride, add_col_stride);
-}
-
-GLDM_API int gldm_pointwise_mlp2_f16x2(const float *x, const float *w0_packed, const float *bias0, int cin0,
-                                        const float *w_split, const float *bias, int b, int cin, int cout, int n,
-                                        const float *head_w_packed, const float *head_bias, int hout,
-                                        const float *front_gain, float *y, float *z, gldm_stream_t stream) {
-  if (!w0_packed) return GLDM_ERR_INVALID_ARG;
-  return launch_pointwise(x, w0_packed, bias0, cin0, w_split, bias, b, cin, cout, n, 1, head_w_packed, head_bias,
-                          hout, y, z, reinterpret_cast<hipStream_t>(stream), true, nullptr, 0, 0, 0, front_gain);
-}
-
-namespace {
-// pre != nullptr: the first layer hoisted (sa_mlp3_kernel<.., PRE>): `features` unused, c = 0, cin_pad[0] = rows of pre
-int launch_sa3(const float *points, const float *centers, const float *features, const float *pre, int wa_off, int pre_bcast,
-               const int32_t *idx, const float *weights, int b, int c, int n, int m, int u,
-               int n_layers, const int32_t *cin_pad, const int32_t *cout, const int32_t *w3_off,
-               const int32_t *b_off, const float *range_gain, float *out, gldm_stream_t stream) {
-  if (!points || !centers || !idx || !weights || !out || !cin_pad || !cout || !w3_off || !b_off || b <= 0 || c < 0 ||
-      n <= 0 || m <= 0 || u <= 0)
-    return GLDM_ERR_INVALID_ARG;
-  if (c > 0 && !features) return GLDM_ERR_INVALID_ARG;
-  if (pre && (c != 0 || wa_off < 0 || (wa_off & 3))) return GLDM_ERR_INVALID_ARG;
-  if (n_layers < 1 || n_layers > 4 || !(u == 16 || u == 32 || u == 64)) return GLDM_ERR_UNSUPPORTED;
-  SaArgs a{};
-  a.points = points; a.centers = centers; a.feat = c > 0 ? features : nullptr; a.idx = idx; a.weights = weights;
-  a.out = out; a.c = c; a.n = n; a.m = m; a.u = u; a.n_layers = n_layers;
-  a.ranged = range_gain != nullptr;
-  a.pre = pre; a.c1 = pre ? cin_pad[0] : 0; a.wa_off = wa_off; a.pre_bcast = pre_bcast ? 1 : 0;
-  for (int l = 0; l < n_layers && range_gain; ++l) {
-    a.gain_r[l] = range_gain[2 * l];
-    a.gain_b[l] = range_gain[2 * l + 1];
-    if (!(a.gain_r[l] >= 0.f) || !(a.gain_b[l] >= 0.f)) return GLDM_ERR_INVALID_ARG;
-  }
-  int blocks_a = 0, blocks_b = 0;
-  for (int l = 0; l < n_layers; ++l) {
-    const int kb = cin_pad[l] >> 5, mt = cout[l] >> 4;
-    if (cin_pad[l] <= 0 || (cin_pad[l] & 31) || !(kb <= 6 || kb == 8 || kb == 9) || cout[l] <= 0 || (cout[l] & 15)) return GLDM_ERR_UNSUPPORTED;
-    if (l > 0 && cin_pad[l] != cout[l - 1]) return GLDM_ERR_INVALID_ARG;
-    if (l + 1 < n_layers) {   // hidden layer: its output is the next layer's planes
-      if ((cout[l] & 31) || !(mt == 2 || mt == 4 || mt == 8 || mt == 16)) return GLDM_ERR_UNSUPPORTED;
-      int &blk = (l & 1) ? blocks_a : blocks_b;
-      blk = blk > (cout[l] >> 5) ? blk : (cout[l] >> 5);
-    }
-    a.cin_pad[l] = cin_pad[l]; a.cout[l] = cout[l]; a.w_off[l] = w3_off[l]; a.b_off[l] = b_off[l];
-  }
-  if (!pre && (cin_pad[0] < 3 + c || cin_pad[0] > 32 * kSa3Quads)) return GLDM_ERR_UNSUPPORTED;
-  if (pre && cin_pad[0] > 256) return GLDM_ERR_UNSUPPORTED;
-  blocks_a = blocks_a > (cin_pad[0] >> 5) ? blocks_a : (cin_pad[0] >> 5);
-  const size_t tile_bytes = (size_t)(blocks_a + blocks_b) * kSaBlockFloats * sizeof(float);
-  // behind the planes: the eight range words and (single-tile kernels) the staged output rows of a run
-  const size_t kRngBytes = 64 + (size_t)cout[n_layers - 1] * kSaRun * sizeof(float);
-  if (tile_bytes + kRngBytes > 160 * 1024) return GLDM_ERR_UNSUPPORTED;
-  const int cpt = 64 / u, tpc = (m + cpt - 1) / cpt, total = tpc * b;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  // narrow nets (32-row inputs, every K in {32, 64, 128}): the multi-tile kernel -- the layer's weights once per
-  // workgroup pass, `sub` tiles' planes side by side in LDS (SSG SA1: three 48 KiB tiles, 2.52 -> 2.07 ms).  Two
-  // co-resident workgroups of one tile each (the kernel fits 128 registers) measured slower: 2.40 ms.
-  // one or two row quads per gather thread; the hoisted form (pre): the multi-tile kernel with two tiles per pass
-  bool kb_ok = cin_pad[0] == 32 || cin_pad[0] == 64;
-  for (int l = 0; l < n_layers; ++l) kb_ok = kb_ok && (cin_pad[l] == 32 || cin_pad[l] == 64 || cin_pad[l] == 128);
-  int sub = kb_ok ? (int)(((size_t)160 * 1024 - kRngBytes) / tile_bytes) : 1;
-  if (sub > 4) sub = 4;
-  // two workgroups of two tiles each rather than one of four where LDS allows (the kernel fits 128 registers): the phases of
-  // one overlap the other's (SSG-SA1 at 256 clouds: 1.55 -> 1.47 ms)
-  if (sub > 2 && (tile_bytes * 2 + kRngBytes) * 2 <= (size_t)160 * 1024) sub = 2;
-  if (pre && sub > 2) sub = 2;
-  while (sub > 1 && (total + sub - 1) / sub < 2 * cu_count()) --sub;
-  if (sub > 1) {
-    const int supers = (total + sub - 1) / sub;
-    const int per_cu_m = (tile_bytes * sub + kRngBytes) * 2 <= (size_t)160 * 1024 ? 2 : 1;
-    const int grid = supers < cu_count() * per_cu_m ? supers : cu_count() * per_cu_m;
-    if (pre) {
-      struct Sa3mPreTag { int site; };
-      gldm_dev::allow_dynamic_lds<Sa3mPreTag>(reinterpret_cast<const void *>(&sa_mlp3_kernel<2, 2, true>), 160 * 1024);
-      hipLaunchKernelGGL((sa_mlp3_kernel<2, 2, true>), dim3(grid), dim3(512), tile_bytes * sub + kRngBytes, s, a, blocks_a, blocks_b, sub, tpc, total);
-    } else if (cin_pad[0] == 32) {
-      struct Sa3mTag { int site; };
-      gldm_dev::allow_dynamic_lds<Sa3mTag>(reinterpret_cast<const void *>(&sa_mlp3_kernel<4, 1>), 160 * 1024);
-      hipLaunchKernelGGL((sa_mlp3_kernel<4, 1>), dim3(grid), dim3(512), tile_bytes * sub + kRngBytes, s, a, blocks_a, blocks_b, sub, tpc, total);
-    } else {
-      struct Sa3m2Tag { int site; };
-      gldm_dev::allow_dynamic_lds<Sa3m2Tag>(reinterpret_cast<const void *>(&sa_mlp3_kernel<4, 2>), 160 * 1024);
-      hipLaunchKernelGGL((sa_mlp3_kernel<4, 2>), dim3(grid), dim3(512), tile_bytes * sub + kRngBytes, s, a, blocks_a, blocks_b, sub, tpc, total);
-    }
-  } else {
-    const int per_cu = (tile_bytes + kRngBytes) * 2 <= 160 * 1024 ? 2 : 1;
-    int grid = cu_count() * per_cu;
-    if (grid > total) grid = total;
-    if (pre && cin_pad[0] <= 128) {
-      struct Sa3Pre4Tag { int site; };
-      gldm_dev::allow_dynamic_lds<Sa3Pre4Tag>(reinterpret_cast<const void *>(&sa_mlp3_kernel<1, 4, true>), 160 * 1024);
-      hipLaunchKernelGGL((sa_mlp3_kernel<1, 4, true>), dim3(grid), dim3(512), tile_bytes + kRngBytes, s, a, blocks_a, blocks_b, 1, tpc, total);
-    } else if (pre) {
-      struct Sa3PreTag { int site; };
-      gldm_dev::allow_dynamic_lds<Sa3PreTag>(reinterpret_cast<const void *>(&sa_mlp3_kernel<1, 8, true>), 160 * 1024);
-      hipLaunchKernelGGL((sa_mlp3_kernel<1, 8, true>), dim3(grid), dim3(512), tile_bytes + kRngBytes, s, a, blocks_a, blocks_b, 1, tpc, total);
-    } else {
-      struct Sa3Tag { int site; };
-      gldm_dev::allow_dynamic_lds<Sa3Tag>(reinterpret_cast<const void *>(&sa_mlp3_kernel<1, kSa3Quads>), 160 * 1024);
-      hipLaunchKernelGGL((sa_mlp3_kernel<1, kSa3Quads>), dim3(grid), dim3(512), tile_bytes + kRngBytes, s, a, blocks_a, blocks_b, 1, tpc, total);
-    }
-  }
-  return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
-}
-}  // namespace
-
-GLDM_API int gldm_sa_mlp_forward_f16x2(const float *points, const float *centers, const float *features,
-                                        const int32_t *idx, const float *weights, int b, int c, int n, int m, int u,
-                                        int n_layers, const int32_t *cin_pad, const int32_t *cout, const int32_t *w3_off,
-                                        const int32_t *b_off, const float *range_gain, float *out, gldm_stream_t stream) {
-  return launch_sa3(points, centers, features, nullptr, 0, 0, idx, weights, b, c, n, m, u, n_layers, cin_pad, cout, w3_off, b_off,
-                    range_gain, out, stream);
-}
-
-GLDM_API int gldm_sa_mlp_forward_f16x2_pre(const float *points, const float *centers, const float *pre, int pre_broadcast,
-                                            const int32_t *idx, const float *weights, int wa_off, int b, int n, int m, int u, int n_layers,
-                                            const int32_t *cin_pad, const int32_t *cout, const int32_t *w3_off,
-                                            const int32_t *b_off, const float *range_gain, float *out, gldm_stream_t stream) {
-  if (!pre) return GLDM_ERR_INVALID_ARG;
-  return launch_sa3(points, centers, nullptr, pre, wa_off, pre_broadcast, idx, weights, b, 0, n, m, u, n_layers, cin_pad, cout, w3_off,
-                    b_off, range_gain, out, stream);
-}
-
-
-GLDM_API int gldm_sa_mlp_forward(const float *points, const float *centers, const float *features,
-                                 const int32_t *idx, const float *weights, int b, int c, int n, int m, int u,
-                                 int n_layers, const int32_t *cin_pad, const int32_t *cout, const int32_t *w_off,
-                                 const int32_t *b_off, float *out, gldm_stream_t stream) {
-  if (!points || !centers || !idx || !weights || !out || !cin_pad || !cout || !w_off || !b_off || b <= 0 || c < 0 ||
-      n <= 0 || m <= 0 || u <= 0)
-    return GLDM_ERR_INVALID_ARG;
-  if (c > 0 && !features) return GLDM_ERR_INVALID_ARG;
-  if (n_layers < 1 || n_layers > 4) return GLDM_ERR_UNSUPPORTED;
-  if (u > 64 || (64 % u) != 0) return GLDM_ERR_UNSUPPORTED;
-  SaArgs a{};
-  a.points = points; a.centers = centers; a.feat = c > 0 ? features : nullptr; a.idx = idx; a.weights = weights;
-  a.out = out; a.c = c; a.n = n; a.m = m; a.u = u; a.n_layers = n_layers;
-  for (int l = 0; l < n_layers; ++l) {
-    const int mt = (cout[l] + 15) >> 4;
-    if (cin_pad[l] <= 0 || (cin_pad[l] & 15) || cin_pad[l] > kMaxC || cout[l] > kMaxC ||
-        !(mt == 1 || mt == 2 || mt == 4 || mt == 8 || mt == 12 || mt == 16) || (cout[l] & 15))
-      return GLDM_ERR_UNSUPPORTED;
-    if (l > 0 && cin_pad[l] != cout[l - 1]) return GLDM_ERR_INVALID_ARG;
-    a.cin_pad[l] = cin_pad[l]; a.cout[l] = cout[l]; a.w_off[l] = w_off[l]; a.b_off[l] = b_off[l];
-  }
-  if (cin_pad[0] < 3 + c) return GLDM_ERR_INVALID_ARG;
-  {  // 128-column tiles when the layer plan fits: widths 32 / 64 / 128 / 256 k, U a multiple of 16, both regions in LDS
-    bool ok = (u == 16 || u == 32 || u == 64) && n_layers >= 1 && c <= 4 * kSaFly;
-    int rows_a = cin_pad[0], rows_b = 0;
-    for (int l = 0; l < n_layers && ok; ++l) {
-      const int mt = cout[l] >> 4;
-      ok = (mt == 2 || mt == 4 || (mt >= 8 && (mt & 7) == 0)) && (cin_pad[l] & 31) == 0;
-      if (l + 1 < n_layers) {  // stored outputs: even layers -> B, odd layers -> A
-        if (l & 1) rows_a = rows_a > cout[l] ? rows_a : cout[l];
-        else rows_b = rows_b > cout[l] ? rows_b : cout[l];
-      } else if (ok) {  // the max runs on one wave's n-tiles: a centre's U / 16 tiles must not straddle two waves
-        const int nt = mt >= 8 ? 8 : (mt == 4 ? 4 : 2);
-        ok = (u >> 4) <= nt;
-      }
-    }
-    const size_t lds2 = (size_t)(rows_a + rows_b) * 128 * sizeof(float);
-#ifdef GLDM_DEBUG_KNOBS
-    static const bool tile64 = getenv("GLDM_SA_TILE64") != nullptr;  // diagnostic builds: force the 64-column kernel
-#else
-    constexpr bool tile64 = false;  // the shipped library reads no environment
-#endif
-    if (ok && lds2 <= 160 * 1024 && !tile64) {
-      struct Sa2Tag { int site; };
-      gldm_dev::allow_dynamic_lds<Sa2Tag>(reinterpret_cast<const void *>(&sa_mlp2_kernel), 160 * 1024);
-      const int cpt2 = 128 / u, tpc = (m + cpt2 - 1) / cpt2, total = tpc * b;
-      const int grid = total < cu_count() ? total : cu_count();
-      hipLaunchKernelGGL(sa_mlp2_kernel, dim3(grid), dim3(512), lds2, reinterpret_cast<hipStream_t>(stream), a, rows_a,
-                         tpc, total);
-      return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
-    }
-  }
-  const size_t lds_bytes = (size_t)(Geo<64>::kBufH + kMaxC * 64) * sizeof(float);
-  struct SaTag { int site; };
-  gldm_dev::allow_dynamic_lds<SaTag>(reinterpret_cast<const void *>(&sa_mlp_kernel), (int)lds_bytes);
-  const int cpt = 64 / u;
-  hipLaunchKernelGGL(sa_mlp_kernel, dim3((m + cpt - 1) / cpt, b), dim3(Geo<64>::kThreads), lds_bytes,
-                     reinterpret_cast<hipStream_t>(stream), a);
   return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
 }

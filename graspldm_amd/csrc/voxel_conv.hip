@@ -321,7 +321,7 @@ __global__ __launch_bounds__(kConvThreads, 2) void conv3d_k3_kernel(const float 
 // ---- the same conv on split-f16 operands (the shipped encoder's two shapes: 48 ch @ 24^3 and 96 ch @ 12^3) ------------
 // v_mfma_f32_16x16x32_bf16 with every f32 operand written as hi + mid + lo (three bf16 numbers, exact) and the six
 // partial products of weight >= 2^-16 accumulated in f32: the error of an f32 rounding per product at 6/16 of the
-// f32-MFMA time (see csrc/resnet1d.hip, "split-f16 GEMM core").  K is walked as (16-channel block, PAIR of taps):
+// f32-MFMA time (see csrc/mfma_core.h, "split-f16 GEMM core").  K is walked as (16-channel block, PAIR of taps):
 // lane group g of a fragment = (tap 2 p + (g >> 1), channels 8 (g & 1) .. + 7); 27 taps = 13 pairs + one half-empty
 // (zero weights).  Work is walked in groups of 3 m-tiles x 3 n-tiles so that the A sets (double buffered), the B planes
 // and the accumulators fit 256 registers.  Weights: graspldm_amd/voxel.py: pack_conv3d_f16x2.
@@ -357,7 +357,7 @@ __device__ __forceinline__ f32x4 c3_mfma3(const c3_u32x4 (&a)[kC3Split], const c
 
 constexpr int kPairs = 14;  // tap pairs per 16-channel block (the last one holds tap 26 and zeros)
 
-// Range scale of a staged brick (see csrc/resnet1d.hip, "range scale of split operands"): f16 has 5 exponent bits, the
+// Range scale of a staged brick (see csrc/mfma_core.h, "range scale of split operands"): f16 has 5 exponent bits, the
 // grid's magnitude is the data's (voxel averages of raw features).  s = 1 while 2^-8 <= m < 2^14: every bit as without it.
 __device__ __forceinline__ float c3_range_pow2(float m) {
   int e = (int)((__float_as_uint(m) >> 23) & 0xffu) - 127;

@@ -13,7 +13,7 @@ using wstream_u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 // offset as the SCALAR offset, the lane's 16 bytes as a constant 32-bit vector offset.  A global_load of
 // the same bytes carries a 64-bit address per lane; issuing it between MFMAs costs the SIMD ~60 cycles of
 // matrix issue per instruction (measured: 256x256 k3 conv 84 % -> 95 % of the MFMA-bound time,
-// tools/micro/gemm_pm_rate).  `i` must be wave uniform.
+// the gemm_pm_rate probe of DESIGN_HISTORY.md).  `i` must be wave uniform.
 struct WStream {
   __amdgpu_buffer_rsrc_t r;
   int v;

@@ -1,7 +1,7 @@
-// Per-shape rate of the engine's conv_gemm (the real code, included below) in isolation:
+// Per-shape rate of conv_gemm (the real code: csrc/mfma_core.h, included below) in isolation:
 // cycles per call vs the MFMA-bound ideal, with 1 or 2 workgroups per CU.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include tools/micro/gemm_rate.hip -o tools/micro/build/gemm_rate
-#include "../../graspldm_amd/csrc/resnet1d.hip"
+#include "../../graspldm_amd/csrc/mfma_core.h"
 #include <vector>
 
 namespace {
@@ -32,7 +32,8 @@ __global__ __launch_bounds__(Geo<NC>::kThreads, 2) void gemm_probe(const float *
 #ifdef GLDM_PROBE_COLD
     cc.w = w + (size_t)(i % 48) * (1 << 19);  // 48 x 2 MiB apart: every call streams weights that left L2 (96 MiB cycle)
 #endif
-    conv_gemm<NC, L>(cc, 0, 1 << 18, lds + GG::kBufX, ci, tp, lds + GG::kBufH, co, false);
+    // 64 columns: 1x1 layers only (main() asks for nothing else; the k = 3 convs of that geometry are the engine's own)
+    conv_gemm<NC, L>(cc, 0, 1 << 18, lds + GG::kBufX, ci, NC == 64 ? 1 : tp, lds + GG::kBufH, co, false);
   }
   const long long t1 = __builtin_readcyclecounter();
   if (c.tid == 0) cycles[blockIdx.x] = t1 - t0;

@@ -1,7 +1,7 @@
 // How long does a short batch of loads take on a CU whose other workgroup streams conv weights?
 // Even workgroups (blockIdx / 256 even) run the engine's 256x256 k=3 conv in a loop; odd ones time a batch of
 // `nload` 16-byte loads (L2-hot, like the parameters of a short op).  Build as tools/micro/gemm_rate.hip.
-#include "../../graspldm_amd/csrc/resnet1d.hip"
+#include "../../graspldm_amd/csrc/mfma_core.h"
 #include <vector>
 
 namespace {
