@@ -33,3 +33,25 @@ def publish(device):
     device = torch.device(device)
     if device.type == "cuda":
         torch.cuda.current_stream(device).synchronize()
+
+
+def cached(owner, slot, key, build, device):
+    """The entry `slot` of `owner` (an nn.Module or a plan object: the entry lives and dies with it), rebuilt by `build()`
+    when `key` differs from the key it was stored under and published once per build.  A build that cannot be made in the
+    split-f16 range (r1d_pack.SplitRangeError) is an entry like any other: None is stored under the key and returned until
+    the key changes, so a weight version that does not fit the split is decided once."""
+    hit = owner.__dict__.get(slot)
+    if hit is None or hit[0] != key:
+        from .r1d_pack import SplitRangeError
+        try:
+            value = build()
+        except SplitRangeError:
+            value = None
+        hit = owner.__dict__[slot] = (key, value)
+        publish(device)
+    return hit[1]
+
+
+def cached_key(owner, slot):
+    """The key `slot` of `owner` is stored under: the key of an entry derived from that one."""
+    return owner.__dict__[slot][0]

@@ -7,8 +7,11 @@ longer sets MIOPEN_FIND_MODE.  Voxel convs have no library path either (csrc/vox
 for shapes without an MFMA instantiation).  Never a CPU path: CPU tensors are rejected like everywhere else in this package.
 """
 import ctypes
+from typing import NamedTuple, Optional
 
 import torch
+
+LDS_BYTES = 160 * 1024   # a CU's LDS: the dynamic-LDS limit every launcher plans against
 
 
 def range_gain(w2d, bias):
@@ -67,15 +70,25 @@ def pack_head(wh):
 SPLIT_PAD_MIN_CIN = 32   # narrowest input the split launch takes with K padded to 128 (below: the lane-per-point kernel)
 
 
+def _tiles_ok(x):
+    """x is [B, C, N], contiguous, N in whole 32-point tiles.  None: the channel half of a predicate alone (what a packer asks)."""
+    return x is None or (x.ndim == 3 and x.is_contiguous() and x.shape[-1] % 32 == 0)
+
+
+def _f32_units(cin, cout):
+    """Units of the f32 launch: K in pairs of 16-deep blocks, output rows in rounds of two m-tiles on eight waves."""
+    return cin % 32 == 0 and cout % 256 == 0
+
+
 def split_supported(cin, cin0=0):
-    """The split-f16 form of the fused launch (gldm_pointwise_mlp*_f16x2): A ring of four 32-deep blocks, the tile
-    as planes (48 floats per channel) + the front layer's f32 tile (split once per wave into registers: cin0 <= 96).
-    Without a front layer any multiple of 8 input rows from 32 up: K is zero-padded to whole trips of the ring
-    (split_fragments)."""
+    """Channel rules of launch_pointwise's split-f16 form (csrc/pointwise_mlp.hip; gldm_pointwise_mlp*_f16x2): A ring of
+    four 32-deep blocks, the tile as planes (48 floats per channel) + the front layer's f32 tile (split once per wave into
+    registers: cin0 <= 96).  Without a front layer any multiple of 8 input rows from 32 up: K is zero-padded to whole
+    trips of the ring (split_fragments)."""
     from .numerics import split_enabled
     kpad = (cin + 127) // 128 * 128
     ok_k = cin % 128 == 0 or (cin0 == 0 and cin % 8 == 0 and cin >= SPLIT_PAD_MIN_CIN)
-    return split_enabled() and ok_k and cin0 % 32 == 0 and cin0 <= 96 and 4 * (48 * kpad + 32 * cin0) + 16 <= 160 * 1024
+    return split_enabled() and ok_k and cin0 % 32 == 0 and cin0 <= 96 and 4 * (48 * kpad + 32 * cin0) + 16 <= LDS_BYTES
 
 
 def split_fragments(w2d):
@@ -90,25 +103,28 @@ def split_fragments(w2d):
 
 
 def fused_mlp_supported(x, cin, cout):
-    return (x.ndim == 3 and x.is_contiguous() and cin % 32 == 0 and cout % 256 == 0 and x.shape[-1] % 32 == 0
-            and 4 * (32 * cin + 4096) <= 160 * 1024)
+    """launch_pointwise's f32 form, one layer (csrc/pointwise_mlp.hip; gldm_pointwise_mlp)."""
+    return _tiles_ok(x) and _f32_units(cin, cout) and 4 * (32 * cin + 4096) <= LDS_BYTES
 
 
 def split_mlp_supported(x, cin, cout):
-    """The split-f16 launch on its own (gldm_pointwise_mlp_f16x2): output rows in units of 32 (fewer than 256 leave waves
-    idle, still several times the any-shape kernel's rate: the 128-row feature-propagation layers of PointNet++ / PVCNN2)."""
-    rows_ok = cout >= 64 and (cout % 32 == 0 or (cout < 256 and cout % 16 == 0))
-    return x.ndim == 3 and x.is_contiguous() and rows_ok and x.shape[-1] % 32 == 0 and split_supported(cin)
+    """launch_pointwise's split-f16 form without a front layer or head (csrc/pointwise_mlp.hip; gldm_pointwise_mlp_f16x2
+    and its _pm / _add forms): output rows in units of two m-tiles, or of one where two would leave waves idle (fewer than
+    256 rows) and the 32-point planes fit half a CU's LDS.  Fewer than 256 rows still run several times the any-shape
+    kernel's rate: the 128-row feature-propagation layers of PointNet++ / PVCNN2."""
+    kpad = (cin + 127) // 128 * 128
+    one_tile_units = cout < 256 and (kpad * 128 + 64) * 2 <= LDS_BYTES
+    return _tiles_ok(x) and cout >= 64 and cout % (16 if one_tile_units else 32) == 0 and split_supported(cin)
 
 
 def fused_mlp2_supported(x, cin0, cin, cout):
-    """Two layers in one launch (gldm_pointwise_mlp2): cin0 -> cin -> cout."""
-    return (x.ndim == 3 and x.is_contiguous() and cin0 % 32 == 0 and cin % 256 == 0 and cout % 256 == 0
-            and x.shape[-1] % 32 == 0 and 4 * (32 * (cin + cin0) + 4096) <= 160 * 1024)
+    """launch_pointwise's f32 form with a front layer (csrc/pointwise_mlp.hip; gldm_pointwise_mlp2): cin0 -> cin -> cout."""
+    return (_tiles_ok(x) and _f32_units(cin0, cin) and _f32_units(cin, cout)
+            and 4 * (32 * (cin + cin0) + 4096) <= LDS_BYTES)
 
 
 def pointwise_mlp(x, w_packed, bias, cout, relu, head=None, keep_y=True, front=None, split=False):
-    """One fused launch: y = act(W x + b) over [B, Cin, N] (hand-written MFMA GEMM, csrc/resnet1d.hip:
+    """One fused launch: y = act(W x + b) over [B, Cin, N] (hand-written MFMA GEMM, csrc/pointwise_mlp.hip:
     pointwise_mlp_kernel / pointwise_mlp_sp_kernel) and optionally z = Wh y + bh on the accumulators.
     head = (packed Wh, bh, hout).  front = (packed W0, b0, cin[, gain]): a ReLU layer x -> relu(W0 x + b0) in front, its
     output kept in LDS only; gain = range_gain(W0, b0) lets the split launch scale that layer's planes into the f16 range.
@@ -154,39 +170,54 @@ def pointwise_conv(x, conv):
     return _gemm_bias_act(x.float(), conv.weight.reshape(conv.weight.shape[0], -1), conv.bias, False)
 
 
+def fold_conv_bn(conv, bn):
+    """BatchNorm(eval) folded into a k = 1 conv: W' = diag(s) W, b' = (b - mean) s + beta with s = gamma / sqrt(var + eps),
+    in f32 on the module's device.  The one fold of the package (dense layers and sa_pack's set-abstraction tables)."""
+    w = conv.weight.detach().float().reshape(conv.weight.shape[0], -1)
+    s = bn.weight.detach().float() * torch.rsqrt(bn.running_var.detach().float() + bn.eps)
+    cb = conv.bias.detach().float() if conv.bias is not None else torch.zeros_like(s)
+    return (w * s.view(-1, 1)).contiguous(), ((cb - bn.running_mean.detach().float()) * s + bn.bias.detach().float()).contiguous()
+
+
+class FoldedLayer(NamedTuple):
+    """A conv + BatchNorm folded and packed for the launches its shape has."""
+    w: torch.Tensor                 # W' [cout, cin]
+    b: torch.Tensor                 # b' [cout]
+    wp: Optional[torch.Tensor]      # f32 A fragments (gldm_pointwise_mlp / mlp2), or None
+    ws: Optional[torch.Tensor]      # split-f16 A fragments over ws_k columns, or None
+    ws_k: int                       # a multiple of 128: a main layer of the split launch; cin <= 96: a front layer only
+    gain: ctypes.Array              # range_gain(W', b')
+
+    @property
+    def ws_main(self):
+        """The split fragments where they carry whole trips of the weight ring (the main layer of a split launch), else None."""
+        return self.ws if self.ws_k % 128 == 0 else None
+
+
+def _pack_folded(conv, bn, device):
+    from .r1d_pack import SplitRangeError, mfma_a_fragments, mfma_a_fragments_f16x2
+    w, b = fold_conv_bn(conv, bn)
+    cout, cin = w.shape
+    wp = ws = None
+    ws_k = 0
+    try:   # a folded weight beyond the f16 range (|w| >= 65504: a huge BatchNorm gain) keeps the f32-pipe kernels
+        if _f32_units(cin, cout):
+            wp = mfma_a_fragments(w.cpu()).to(device)
+            # split fragments, K as it is: main layers of the split launch (cin % 128 == 0) and its narrow front layers
+            if split_supported(cin) or cin <= 128:
+                ws, ws_k = mfma_a_fragments_f16x2(w.cpu()).to(device), cin
+        elif split_mlp_supported(None, cin, cout):
+            ws, ws_k = split_fragments(w).to(device), (cin + 127) // 128 * 128   # K padded to the ring: split launch only
+    except SplitRangeError:
+        ws, ws_k = None, 0
+    return FoldedLayer(w, b, wp, ws, ws_k, range_gain(w, b))
+
+
 def folded_conv_bn(conv, bn, device):
-    """BatchNorm(eval) folded into the k = 1 conv: (W', b', W' packed for gldm_pointwise_mlp or None, W' as split-f16
-    fragments or None), on `device`, computed once per (weights, statistics) version and kept on the conv module."""
-    from ._cache import params_key, publish
+    """The FoldedLayer of (conv, bn) on `device`, computed once per (weights, statistics) version and kept on the conv."""
+    from ._cache import cached, params_key
     src = [conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var] + ([conv.bias] if conv.bias is not None else [])
-    key = params_key(src, device)
-    hit = conv.__dict__.get("_gldm_folded")  # lives and dies with the module
-    if hit is None or hit[0] != key:
-        from .r1d_pack import SplitRangeError, mfma_a_fragments, mfma_a_fragments_f16x2
-        s = bn.weight * torch.rsqrt(bn.running_var + bn.eps)
-        w = (conv.weight.reshape(conv.weight.shape[0], -1) * s.view(-1, 1)).contiguous()
-        cb = conv.bias if conv.bias is not None else torch.zeros_like(bn.running_mean)
-        b = ((cb - bn.running_mean) * s + bn.bias).contiguous()
-        wp = ws = None
-        try:   # a folded weight beyond the f16 range (|w| >= 65504: a huge BatchNorm gain) keeps the f32-pipe kernels
-            if w.shape[1] % 32 == 0 and w.shape[0] % 256 == 0:
-                wp = mfma_a_fragments(w.detach().float().cpu()).to(device)
-                # split fragments: main layers of the split launch (cin % 128 == 0) and its narrow front layers (cin <= 128)
-                if split_supported(w.shape[1]) or w.shape[1] <= 128:
-                    ws = mfma_a_fragments_f16x2(w.detach().float().cpu()).to(device)
-            elif w.shape[0] % 16 == 0 and w.shape[0] >= 64 and split_supported(w.shape[1]):
-                ws = split_fragments(w).to(device)   # 64 .. 240 output rows / K padded to the ring: split launch only
-        except SplitRangeError:
-            ws = None
-        hit = (key, w, b, wp, ws, range_gain(w, b))
-        conv.__dict__["_gldm_folded"] = hit
-        publish(device)
-    return hit[1], hit[2], hit[3], hit[4]
-
-
-def folded_range_gain(conv):
-    """range_gain of the layer folded_conv_bn packed last (same weight version)."""
-    return conv.__dict__["_gldm_folded"][5]
+    return cached(conv, "_gldm_folded", params_key(src, device), lambda: _pack_folded(conv, bn, device), device)
 
 
 def pointwise_conv_bn_relu(x, conv, bn):
@@ -194,15 +225,33 @@ def pointwise_conv_bn_relu(x, conv, bn):
     cout % 256 == 0) run as ONE hand-written MFMA launch (GEMM + bias + ReLU in the native layout); the others in the
     narrow lane-per-point kernel or the any-shape f32-MFMA kernel (_gemm_bias_act)."""
     _need_cuda(x)
-    w, b, wp, ws = folded_conv_bn(conv, bn, x.device)
+    f = folded_conv_bn(conv, bn, x.device)
+    cout, cin = f.w.shape
     x = x.float()
-    if wp is not None and fused_mlp_supported(x, w.shape[1], w.shape[0]):
-        if ws is not None and w.shape[1] % 128 == 0 and split_supported(w.shape[1]):   # (narrow layers keep UNPADDED fragments, as front layers)
-            return pointwise_mlp(x, ws, b, w.shape[0], True, split=True)[0]
-        return pointwise_mlp(x, wp, b, w.shape[0], True)[0]
-    if wp is None and ws is not None and split_mlp_supported(x, w.shape[1], w.shape[0]):
-        return pointwise_mlp(x, ws, b, w.shape[0], True, split=True)[0]
-    return _gemm_bias_act(x, w, b, True)
+    if f.wp is not None and fused_mlp_supported(x, cin, cout):
+        if f.ws_main is not None and split_supported(cin):
+            return pointwise_mlp(x, f.ws_main, f.b, cout, True, split=True)[0]
+        return pointwise_mlp(x, f.wp, f.b, cout, True)[0]
+    if f.wp is None and f.ws_main is not None and split_mlp_supported(x, cin, cout):
+        return pointwise_mlp(x, f.ws_main, f.b, cout, True, split=True)[0]
+    return _gemm_bias_act(x, f.w, f.b, True)
+
+
+class ConcatLayer(NamedTuple):
+    """A folded layer over cat([xa, xb]) packed as its two column blocks (concat_conv_bn_relu)."""
+    w3: torch.Tensor                 # split fragments of the wide part
+    w_other: torch.Tensor            # the other part: a matrix, or split fragments when both parts are wide
+    zero_b: torch.Tensor
+    wa3: Optional[torch.Tensor]      # broadcast form: split fragments of Wa where its width allows the split launch
+
+
+def _pack_concat(f, ca, broadcast, both_wide, device):
+    wa, wb = f.w[:, :ca].contiguous(), f.w[:, ca:].contiguous()
+    w3 = split_fragments(wb if broadcast else wa).to(device)
+    w_other = wa if broadcast else (split_fragments(wb).to(device) if both_wide else wb)
+    # broadcast form: Wa xa over the clouds is itself a wide GEMM ([1, Ca, B] columns = clouds) where Ca allows
+    wa3 = split_fragments(wa).to(device) if broadcast and split_supported(ca) else None
+    return ConcatLayer(w3, w_other, torch.zeros_like(f.b), wa3)
 
 
 def concat_conv_bn_relu(xa, xb, conv, bn):
@@ -232,44 +281,30 @@ def concat_conv_bn_relu(xa, xb, conv, bn):
     both_wide = not broadcast and cb >= 128 and ca >= 128 and split_supported(ca) and split_supported(cb)
     if not split_supported(wide_c) or (not broadcast and cb not in SMALL_CIN and not both_wide):
         return None
-    from ._cache import params_key, publish
-    src = [conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var] + ([conv.bias] if conv.bias is not None else [])
-    key = (params_key(src, xa.device), ca, broadcast, both_wide)
-    hit = conv.__dict__.get("_gldm_concat")
-    if hit is None or hit[0] != key:
-        from .r1d_pack import SplitRangeError, mfma_a_fragments_f16x2
-        w, b = folded_conv_bn(conv, bn, xa.device)[:2]
-        wa, wb = w[:, :ca].contiguous(), w[:, ca:].contiguous()
-        wide = wb if broadcast else wa
-        try:
-            w3 = split_fragments(wide).to(xa.device)
-            w_other = wa if broadcast else (split_fragments(wb).to(xa.device) if both_wide else wb)
-            # broadcast form: Wa xa over the clouds is itself a wide GEMM ([1, Ca, B] columns = clouds) where Ca allows
-            wa3 = split_fragments(wa).to(xa.device) if broadcast and split_supported(ca) else None
-        except SplitRangeError:
-            return None   # a weight beyond the f16 range: the caller concatenates and takes the plain (f32) path
-        hit = (key, w3, w_other, b, torch.zeros_like(b), wa3)
-        conv.__dict__["_gldm_concat"] = hit
-        publish(xa.device)
-    _, w3, w_other, b, zero_b, wa3 = hit
+    from ._cache import cached, cached_key
+    f = folded_conv_bn(conv, bn, xa.device)
+    c = cached(conv, "_gldm_concat", (cached_key(conv, "_gldm_folded"), ca, broadcast, both_wide),
+               lambda: _pack_concat(f, ca, broadcast, both_wide, xa.device), xa.device)
+    if c is None:
+        return None   # a weight beyond the f16 range: the caller concatenates and takes the plain (f32) path
     y = torch.empty((bsz, cout, n), dtype=torch.float32, device=xa.device)
     if broadcast:
         # Wa xa for every cloud at once: [1, Ca, B] columns = clouds (the split launch where the cloud count is a multiple of
         # 32 and Ca of 128, else the any-shape kernel)
         x1 = xa[:, :, 0].t().contiguous().unsqueeze(0)
-        if wa3 is not None and split_mlp_supported(x1, ca, cout):
-            g = pointwise_mlp(x1, wa3, zero_b, cout, False, split=True)[0][0].t().contiguous()                      # [B, Cout]
+        if c.wa3 is not None and split_mlp_supported(x1, ca, cout):
+            g = pointwise_mlp(x1, c.wa3, c.zero_b, cout, False, split=True)[0][0].t().contiguous()                      # [B, Cout]
         else:
-            g = _gemm_bias_act(x1, w_other, None, False)[0].t().contiguous()
-        xw, add, strides, bias = xb.contiguous(), g, (cout, 1, 0), b
+            g = _gemm_bias_act(x1, c.w_other, None, False)[0].t().contiguous()
+        xw, add, strides, bias = xb.contiguous(), g, (cout, 1, 0), f.b
     elif both_wide:
-        add = pointwise_mlp(xb.contiguous(), w_other, b, cout, False, split=True)[0]                             # [B, Cout, N] = Wb xb + b
-        xw, strides, bias = xa.contiguous(), (cout * n, n, 1), zero_b
+        add = pointwise_mlp(xb.contiguous(), c.w_other, f.b, cout, False, split=True)[0]                             # [B, Cout, N] = Wb xb + b
+        xw, strides, bias = xa.contiguous(), (cout * n, n, 1), c.zero_b
     else:
-        add = _gemm_bias_act(xb.contiguous(), w_other, b, False)                                                   # [B, Cout, N]
-        xw, strides, bias = xa.contiguous(), (cout * n, n, 1), zero_b
+        add = _gemm_bias_act(xb.contiguous(), c.w_other, f.b, False)                                                   # [B, Cout, N]
+        xw, strides, bias = xa.contiguous(), (cout * n, n, 1), c.zero_b
     with torch.cuda.device(xa.device):
-        L.call("gldm_pointwise_mlp_f16x2_add", L.ptr(xw), L.ptr(w3), L.ptr(bias), L.ptr(add), *strides, bsz, wide_c, cout, n, 1,
+        L.call("gldm_pointwise_mlp_f16x2_add", L.ptr(xw), L.ptr(c.w3), L.ptr(bias), L.ptr(add), *strides, bsz, wide_c, cout, n, 1,
                L.ptr(y), L.current_stream(xa.device))
     return y
 

@@ -60,36 +60,31 @@ class PVCNNEncoder(nn.Module):
             for layer in layers[: -2 if two else -1]:
                 feats, _ = layer((feats, coords))
             feats = feats.contiguous().float()
+            if w.shape[0] <= 16 and two and dense.fused_mlp2_supported(feats, prev.layers[0].weight.shape[1], cin, cout):
+                f0 = dense.folded_conv_bn(prev.layers[0], prev.layers[1], feats.device)
+                f = dense.folded_conv_bn(conv, bn, feats.device)
+                if f.ws is not None and f0.ws is not None and dense.split_supported(cin, f0.w.shape[1]):
+                    # both GEMMs on the f16 matrix pipe (split-f32 operands)
+                    return dense.pointwise_mlp(feats, f.ws, f.b, cout, True, head=self._packed_head(w, b), keep_y=False,
+                                               front=(f0.ws, f0.b, cin, f0.gain), split=True)[1]
+                return dense.pointwise_mlp(feats, f.wp, f.b, cout, True, head=self._packed_head(w, b), keep_y=False,
+                                           front=(f0.wp, f0.b, cin))[1]
             if two:
-                conv0, bn0 = prev.layers[0], prev.layers[1]
-                if w.shape[0] <= 16 and dense.fused_mlp2_supported(feats, conv0.weight.shape[1], cin, cout):
-                    _, b0, wp0, ws0 = dense.folded_conv_bn(conv0, bn0, feats.device)
-                    _, bf, wp, ws = dense.folded_conv_bn(conv, bn, feats.device)
-                    if ws is not None and ws0 is not None and dense.split_supported(cin, conv0.weight.shape[1]):
-                        # both GEMMs on the f16 matrix pipe (split-f32 operands)
-                        return dense.pointwise_mlp(feats, ws, bf, cout, True, head=self._packed_head(w, b), keep_y=False,
-                                                   front=(ws0, b0, cin, dense.folded_range_gain(conv0)), split=True)[1]
-                    return dense.pointwise_mlp(feats, wp, bf, cout, True, head=self._packed_head(w, b), keep_y=False,
-                                               front=(wp0, b0, cin))[1]
                 feats = prev(feats).contiguous()
             if w.shape[0] <= 16 and dense.fused_mlp_supported(feats, cin, cout):
-                _, bf, wp, ws = dense.folded_conv_bn(conv, bn, feats.device)
-                if ws is not None:
-                    return dense.pointwise_mlp(feats, ws, bf, cout, True, head=self._packed_head(w, b), keep_y=False,
-                                               split=True)[1]
-                return dense.pointwise_mlp(feats, wp, bf, cout, True, head=self._packed_head(w, b), keep_y=False)[1]
+                f = dense.folded_conv_bn(conv, bn, feats.device)
+                split = f.ws_main is not None and dense.split_supported(cin)
+                return dense.pointwise_mlp(feats, f.ws_main if split else f.wp, f.b, cout, True, head=self._packed_head(w, b),
+                                           keep_y=False, split=split)[1]
             feats = last(feats)
             return dense.pointwise_gemm(feats, w, b)
         return dense.pointwise_gemm(bb(x, cond=cond), w, b)
 
     def _packed_head(self, w, b):
-        from ._cache import publish
-        hit = self.__dict__.get("_head_packed")
-        if hit is None or hit[0] is not w:
-            hit = (w, dense.pack_head(w).to(w.device), b.contiguous(), int(w.shape[0]))
-            self.__dict__["_head_packed"] = hit
-            publish(w.device)
-        return hit[1], hit[2], hit[3]
+        """(packed W, b, rows) of the folded head for the launches that take it on their accumulators; rebuilt with it."""
+        from ._cache import cached, cached_key
+        return cached(self, "_head_packed", cached_key(self, "_head_cache"),
+                      lambda: (dense.pack_head(w).to(w.device), b.contiguous(), int(w.shape[0])), w.device)
 
     def _folded_head(self):
         """conv_downscale (C -> C/2, k=1) and out_layer[0] (C/2 -> out_channels, k=1) have nothing between them
@@ -97,19 +92,15 @@ class PVCNNEncoder(nn.Module):
         [out_channels x C] GEMM over the points instead of a 2 C^2/2 FLOP-per-point one.  Folded in f64 once per
         weight version."""
         cd, o0 = self.conv_downscale, self.out_layer[0]
-        from ._cache import params_key, publish
-        key = params_key([cd.weight, cd.bias, o0.weight, o0.bias], cd.weight.device)
-        hit = self.__dict__.get("_head_cache")
-        if hit is None or hit[0] != key:
+        from ._cache import cached, params_key
+        dev = cd.weight.device
+
+        def fold():
             # folded on the HOST (f64 there; on the device this product was the path's last library GEMM, once per weight version)
-            dev = cd.weight.device
             wo, wd = o0.weight[:, :, 0].detach().double().cpu(), cd.weight[:, :, 0].detach().double().cpu()
-            w = (wo @ wd).float().contiguous().to(dev)
-            b = (wo @ cd.bias.detach().double().cpu() + o0.bias.detach().double().cpu()).float().contiguous().to(dev)
-            hit = (key, w, b)
-            self.__dict__["_head_cache"] = hit
-            publish(cd.weight.device)
-        return hit[1], hit[2]
+            return ((wo @ wd).float().contiguous().to(dev),
+                    (wo @ cd.bias.detach().double().cpu() + o0.bias.detach().double().cpu()).float().contiguous().to(dev))
+        return cached(self, "_head_cache", params_key([cd.weight, cd.bias, o0.weight, o0.bias], dev), fold, dev)
 
     def load_ckpt_and_freeze(self, ckpt_path, fine_tune=False):
         ckpt = torch.load(ckpt_path, map_location="cpu")

@@ -209,19 +209,13 @@ class PointNetSAModule(nn.Module):
         self.groupers = nn.ModuleList(groupers)
         self.mlps = nn.ModuleList(mlps)
 
-    def _fused(self, g, grouper, mlp, coords, centers, features):
+    def _fused(self, grouper, mlp, coords, centers, features):
         """ball query -> ONE fused launch (gather + grouped MLP on MFMA + max): the grouped
         [B, 3+C, M, U] tensor is never materialised."""
+        from ._cache import cached, params_key
         from .sa_pack import SaMlpPlan
-        plans = self.__dict__.setdefault("_plans", {})
-        from ._cache import params_key, publish
         key = params_key(mlp.state_dict(keep_vars=True).values(), coords.device)
-        plan = plans.get(g)
-        if plan is None or plan.key_dev != key:
-            plan = SaMlpPlan(mlp, coords.device)
-            plan.key_dev = key
-            plans[g] = plan
-            publish(coords.device)
+        plan = cached(mlp, "_sa_plan", key, lambda: SaMlpPlan(mlp, coords.device), coords.device)
         feats = features.contiguous() if features is not None and features.shape[1] > 0 else None
         idx = ball_query(centers, coords, grouper.radius, grouper.num_neighbors)
         return plan.run(coords.contiguous(), centers.contiguous(), feats, idx)
@@ -231,9 +225,9 @@ class PointNetSAModule(nn.Module):
         features, coords = inputs
         centers = furthest_point_sample(coords, self.num_centers)
         outs = []
-        for g, (grouper, mlp) in enumerate(zip(self.groupers, self.mlps)):
+        for grouper, mlp in zip(self.groupers, self.mlps):
             if grouper.include_coordinates and not self.training and fusable(mlp, grouper.num_neighbors):
-                outs.append(self._fused(g, grouper, mlp, coords, centers, features))
+                outs.append(self._fused(grouper, mlp, coords, centers, features))
             else:  # wide (> 256 channel) or U > 64 stages: gather kernel + GEMMs + max
                 outs.append(mlp(grouper(coords, centers, features)).max(dim=-1).values)
         return (torch.cat(outs, dim=1) if len(outs) > 1 else outs[0]), centers
@@ -355,14 +349,9 @@ class PVConv(nn.Module):
         # hand-written path: implicit-GEMM conv3d on MFMA (shapes with an instantiation) or the direct any-shape kernel
         # (every other width / resolution, partial edge bricks included), GN+Swish, SE gate folded into the devoxelize
         # pass together with the point-branch add
-        plan = self.__dict__.get("_voxel_plan")
-        from ._cache import params_key, publish
-        key = params_key([c.weight for c in convs], vox.device)
-        if plan is None or plan.key != key:
-            plan = voxel.VoxelBranchPlan(convs, vox.device, self.resolution)
-            plan.key = key
-            self.__dict__["_voxel_plan"] = plan
-            publish(vox.device)
+        from ._cache import cached, params_key
+        plan = cached(self, "_voxel_plan", params_key([c.weight for c in convs], vox.device),
+                      lambda: voxel.VoxelBranchPlan(convs, vox.device, self.resolution), vox.device)
         return voxel.run(plan, convs, norms, se, vox, norm_coords, pf, self.resolution), coords
 
 

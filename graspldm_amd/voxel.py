@@ -16,6 +16,7 @@ SPLIT_SHAPES = {(48, 24), (96, 12), (32, 32), (64, 32), (32, 16), (64, 16), (128
 
 
 def conv_supported(cout, r):
+    """Shapes launch_conv / launch_conv_halves have an f32-MFMA instantiation for (csrc/voxel_conv.hip; gldm_conv3d_k3[_cl])."""
     return cout % 16 == 0 and r % 4 == 0 and (cout // 16, r // 4) in SUPPORTED
 
 
@@ -29,8 +30,8 @@ def pack_conv3d(weight):
 
 
 def split_conv_supported(cin, cout, r):
-    """Shapes gldm_conv3d_k3_f16x2 is built for (SPLIT_SHAPES with cin % 16 == 0, and the shipped encoder's first conv
-    3 -> 48 @ 24^3 with K = 81 packed into three 32-deep blocks)."""
+    """Shapes conv3d_k3_f16x2_impl dispatches (csrc/voxel_conv.hip; gldm_conv3d_k3_f16x2[_gn]: SPLIT_SHAPES with cin % 16 == 0,
+    and the shipped encoder's first conv 3 -> 48 @ 24^3 with K = 81 packed into three 32-deep blocks)."""
     if (cin, cout, r) == (3, 48, 24):
         from .numerics import split_enabled
         return split_enabled()   # under f32_only() its f32 form runs (K padded to 27 x 16: slower, exact f32 products)
@@ -83,7 +84,6 @@ class VoxelBranchPlan:
                 except SplitRangeError:   # a weight beyond the f16 range: this conv keeps an f32 kernel
                     self.split[i] = False
             self.w.append((c.weight.detach().float().contiguous() if self.generic[i] else pack_conv3d(c.weight)).to(device))
-        self.key = None  # set by the owner (PVConv.forward) from _cache.params_key
 
 
 def run(plan, convs, norms, se, vox, norm_coords, point_feat, r):

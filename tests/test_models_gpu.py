@@ -201,16 +201,18 @@ def test_fused_sa_mlp_equals_unfused_oracle(b, c, n, m, u, chans, split, monkeyp
     ball_group -> shared_mlp -> max on the same weights.  split=True: every case runs on the split-f16 64-column kernel
     (sa_mlp3_kernel: 1 / 2 / 4 centres per tile, ragged last tiles, more tiles than persistent workgroups, 2-4 layers,
     1-6 and 9 input blocks, 16-wide hidden layers packed as zero-padded 32-wide ones, the narrow-net form with one and
-    with two row quads per gather thread).  split=False forces the f32 kernels: cases 1-3, 5, 6 on the
+    with two row quads per gather thread); the predicate is asked about the tables the launch gets (the last case's
+    259 -> 128 -> 256 fits the CU's LDS only with its first layer hoisted: 9 + 4 plane blocks + the staged output rows).  split=False forces the f32 kernels: cases 1-3, 5, 6 on the
     128-column one (sa_mlp2_kernel), cases 4 and 7 on the 64-column one (sa_mlp_kernel)."""
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     from graspldm_amd import sa_pack
     if not split:
         monkeypatch.setattr(sa_pack, "split_plan_ok", lambda *a, **k: False)
+    elif len(chans) >= 2 and (m * u >= 2 * n if c else sa_pack.PRE_WITHOUT_FEATURES):
+        assert sa_pack.split_plan_ok(list(chans[:-1]), list(chans[1:]), u)   # first layer hoisted: the tables behind it
     else:
-        cins = [c + 3] + list(chans[:-1])
-        assert sa_pack.split_plan_ok(cins, list(chans), u)
+        assert sa_pack.split_plan_ok([c + 3] + list(chans[:-1]), list(chans), u)
     from graspldm_amd.pvcnn import PointNetSAModule
     from graspldm_amd.synthetic import load_synthetic_weights
     from oracle import torch_ref as R

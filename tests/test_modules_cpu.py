@@ -174,7 +174,7 @@ def test_decoder_workspace_holds_the_scale_shift_table():
 def test_folded_prenorm_qkv_block_of_the_descriptor(fpc_state_dict):
     """ABI 4: per level, to_qkv with the PreNorm LayerNorm gain folded in (W' = W diag(g), to_qkv's own row order,
     MFMA fragment order) and its row sums s = W' 1, so that W LN(x) = rstd (W' x - mean s) (csrc/resnet1d.hip:
-    qkv_ln_pm).  Checked entry by entry against the state dict, and the identity itself against torch's LayerNorm form
+    qkv_att_pm).  Checked entry by entry against the state dict, and the identity itself against torch's LayerNorm form
     (resnets.py:104-124)."""
     from graspldm_amd.r1d_pack import pack_resnet1d
     pre = "diffusion_model.model."
@@ -301,7 +301,10 @@ def test_pad_cin32_and_16_position_descriptors():
 
 def test_f32_only_switch_changes_what_is_packed_and_chosen(fpc_state_dict):
     """numerics.f32_only(): descriptors name no split copy (-> sample-major f32 engine), the split shape predicates say no
-    wherever an f32 kernel exists, and the switch restores itself."""
+    wherever an f32 kernel exists, and the switch restores itself.  In the default mode the predicates say what the C
+    launchers take: launch_sa3 reserves 64 + 32 cout_last bytes behind the planes (13 plane blocks + a 256-row output do
+    not fit the CU's 160 KiB), and launch_pointwise hands out one-m-tile units (cout % 16) only where cout < 256 and the
+    32-point planes fit half the LDS ((128 K + 64) 2 <= 160 KiB, K padded to 128: K <= 512), units of 32 rows otherwise."""
     from graspldm_amd import numerics, voxel, dense
     from graspldm_amd.r1d_pack import pack_resnet1d
     from graspldm_amd.sa_pack import split_plan_ok
@@ -309,6 +312,12 @@ def test_f32_only_switch_changes_what_is_packed_and_chosen(fpc_state_dict):
     on = pack_resnet1d(sd, "diffusion_model.model.", groups=4, seq_len=4, num_steps=1000)["desc"]
     assert on.rb[2].c1_w3 > 0 and on.rb[2].c1_wq > 0 and on.lv[1].qkvn_wq > 0
     assert voxel.split_conv_supported(48, 48, 24) and dense.split_supported(768, 96) and split_plan_ok([131], [128, 128, 256], 64)
+    assert not split_plan_ok([259], [128, 256], 16) and not split_plan_ok([259], [128, 128, 256], 32)
+    assert split_plan_ok([128], [256], 32) and split_plan_ok([163], [128, 128], 64)
+    x640, x512 = torch.zeros(1, 640, 32), torch.zeros(1, 512, 32)
+    assert not any(dense.split_mlp_supported(x640, 640, cout) for cout in (80, 112, 144, 176, 208, 240))
+    assert dense.split_mlp_supported(x640, 640, 96) and dense.split_mlp_supported(x640, 640, 128)
+    assert dense.split_mlp_supported(x512, 512, 80) and not dense.split_mlp_supported(x512[:, :, :16], 512, 80)
     with numerics.f32_only():
         assert not numerics.split_enabled()
         off = pack_resnet1d(sd, "diffusion_model.model.", groups=4, seq_len=4, num_steps=1000)["desc"]
@@ -347,3 +356,45 @@ def test_sixteen_position_nets_carry_the_wave_local_copies(fpc_state_dict):
     x = torch.arange(2 * 96, dtype=torch.float32).reshape(2, 96)
     assert torch.equal(quad_perm32(x)[:, 8 * 1 + 5], x[:, 16 * 1 + 4 * 1 + 1])      # block 0, g = 1, j = 5
     assert mfma_a_fragments_f16x2(quad_perm32(pad_cin32(torch.ones(16, 48), 16, 3))).numel() == 3 * 512
+
+
+def test_derived_weight_cache_decides_once_per_weight_version(monkeypatch):
+    """_cache.cached: one build per key, a build beyond the f16 range is an entry too (decided once, not on every forward),
+    and the key follows in-place weight updates, invalidate_caches() and the arithmetic mode."""
+    import graspldm_amd
+    from graspldm_amd import dense, numerics, r1d_pack
+    from graspldm_amd.pvcnn import SharedMLP
+    from graspldm_amd.sa_pack import SaMlpPlan
+    calls = []
+    split = r1d_pack.split_f16x2
+    monkeypatch.setattr(r1d_pack, "split_f16x2", lambda w: (calls.append(tuple(w.shape)), split(w))[1])
+    conv, bn = torch.nn.Conv1d(256, 256, 1), torch.nn.BatchNorm1d(256).eval()
+    with torch.no_grad():
+        conv.weight[3, 5] = 1.0e5          # folded: beyond 65504
+    cpu = torch.device("cpu")
+    f = dense.folded_conv_bn(conv, bn, cpu)
+    assert f.wp is not None and f.ws is None and f.ws_main is None and len(calls) == 1
+    assert dense.folded_conv_bn(conv, bn, cpu) is f and len(calls) == 1            # unchanged weights: no second split
+    with torch.no_grad():
+        conv.weight.mul_(1.0)                                                       # in-place update: a new version
+    f2 = dense.folded_conv_bn(conv, bn, cpu)
+    assert f2 is not f and len(calls) == 2
+    graspldm_amd.invalidate_caches()
+    f3 = dense.folded_conv_bn(conv, bn, cpu)
+    assert f3 is not f2 and len(calls) == 3
+    with numerics.f32_only():
+        f4 = dense.folded_conv_bn(conv, bn, cpu)
+        assert f4 is not f3 and f4.ws is None and len(calls) == 3                   # repacked without a split copy
+    with torch.no_grad():
+        conv.weight[3, 5] = 0.0
+    ok = dense.folded_conv_bn(conv, bn, cpu)
+    assert ok.ws is not None and ok.ws_main is ok.ws and ok.ws_k == 256
+    # the set-abstraction tables: the out-of-range decision is stored on the plan, not retried by every run()
+    mlp = SharedMLP(6, (32, 64), dim=2).eval()
+    with torch.no_grad():
+        mlp.layers[3].weight[0, 0] = 1.0e5
+    plan = SaMlpPlan(mlp, cpu)
+    del calls[:]
+    assert plan._split_plan() is None and plan._pre_plan() is None
+    n = len(calls)
+    assert n >= 2 and plan._split_plan() is None and plan._pre_plan() is None and len(calls) == n
