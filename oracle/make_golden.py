@@ -26,6 +26,10 @@ Fixtures hold inputs and expected outputs only (data, no reference source).
                            end to end on 2 partial clouds (`python -m oracle.make_golden ppc`)
      pvcnn2.npz            PVCNN2 forward on one cloud (every 16th point kept); `python -m oracle.make_golden pvcnn2`
                            writes only this one
+     pvcnn2_b.npz          the same PVCNN2 (seed-4 weights) on the normalised cloud synthetic_batch(1, 1024)[0][0]: the second
+                           cloud of the set-abstraction end-to-end test (`python -m oracle.make_golden pvcnn2_b`)
+     bench_objects.npz     bench.py's 32 distinct objects (rank 0): encoder latents and GraspLatentDDM.generate_grasps
+                           B=32 G=20, 100 DDIM steps (`python -m oracle.make_golden bench_objects`)
 """
 import os
 import sys
@@ -176,16 +180,25 @@ def main():
 
 
 @torch.no_grad()
-def pvcnn2_golden(cloud=None):
-    """G8: PVCNN2 (set abstraction + PVConv + feature propagation, pvcnn_base.py:147-279) on one cloud."""
+def pvcnn2_golden(cloud=None, name="pvcnn2.npz"):
+    """G8: PVCNN2 (set abstraction + PVConv + feature propagation, pvcnn_base.py:147-279) on one cloud.  Only the default
+    fixture name writes the schema (the weights are the same seed-4 recipe under every name)."""
     from grasp_ldm.models.modules.ext.pvcnn.pvcnn_base import PVCNN2
     if cloud is None:
         pcs, _ = synthetic.synthetic_batch(2, 1024)
         cloud = pcs[:1].transpose(1, 2).contiguous() * 0.05 / 0.12
     net = PVCNN2().eval()
     synthetic.load_synthetic_weights(net, seed=4)
-    _schema("schema_pvcnn2.json", net)
-    _save("pvcnn2.npz", coords=cloud, out=net(cloud)[:, :, ::16])
+    if name == "pvcnn2.npz":
+        _schema("schema_pvcnn2.json", net)
+    _save(name, coords=cloud, out=net(cloud)[:, :, ::16])
+
+
+def pvcnn2_b_golden():
+    """The second cloud of test_ldm_end_to_end_with_the_set_abstraction_encoder: the normalised synthetic cloud 0 as the
+    encoder sees it (no rescaling to unit radius, unlike pvcnn2.npz's), channels first."""
+    pcs, _ = synthetic.synthetic_batch(1, 1024)
+    pvcnn2_golden(pcs.transpose(1, 2).contiguous(), name="pvcnn2_b.npz")
 
 
 def front_end_golden():
@@ -301,6 +314,29 @@ def c5_golden():
           tmrp=tm, logit=lg, H=H, confidence=torch.sigmoid(lg.view(1, G, 1)), seed=SEED, num_grasps=G)
 
 
+BENCH_SEED = 4321
+
+
+@torch.no_grad()
+def bench_objects_golden():
+    """The benchmark's regime on the reference's own graph: the 32 distinct objects bench.py tiles to its 256-cloud batch
+    (rank 0: synthetic_batch(32, 1024, first_index=0)), G = 20, 100 DDIM steps of GaussianDiffusion1D.sample + the decoder.
+    x_T is NOT stored: it is torch.manual_seed(BENCH_SEED) followed by torch.randn(640, 1, 4), the reference's only draw
+    (gaussian_diffusion.py:253).  The clouds are not stored either (tests regenerate them from the recipe); `pc_probe`
+    keeps every 64th point so a test can assert that what it regenerated is what the reference saw."""
+    ref_import.install_shims()
+    ldm = ref_import.build_reference_ldm(noise_scheduler_type="ddim")
+    synthetic.load_synthetic_weights(ldm, seed=0)
+    ldm.set_inference_timesteps(100)
+    pcs, metas = synthetic.synthetic_batch(32, 1024, first_index=0)
+    z = ldm.vae_model.encode_pc(pcs)
+    torch.manual_seed(BENCH_SEED)
+    (tm, lg), _ = ldm.generate_grasps(pcs, num_grasps=20, device="cpu")
+    assert tm.shape == (640, 6) and lg.shape == (640, 1) and z.shape == (32, 3, 64)
+    _save("bench_objects.npz", z=z, tmrp=tm, logit=lg, grasp_mean=metas["grasp_mean"], grasp_std=metas["grasp_std"],
+          seed=BENCH_SEED, pc_probe=pcs[:, ::64])
+
+
 @torch.no_grad()
 def ppc_golden():
     """The reference's second shipped experiment, the partial-cloud config
@@ -343,10 +379,16 @@ if __name__ == "__main__":
         os.makedirs(OUT, exist_ok=True)
         class_cond_golden()
         sys.exit(0)
-    if len(sys.argv) > 1 and sys.argv[1] in ("c5", "ppc"):
+    if len(sys.argv) > 1 and sys.argv[1] in ("c5", "ppc", "bench_objects"):
         os.makedirs(OUT, exist_ok=True)
         torch.set_num_threads(8)
-        {"c5": c5_golden, "ppc": ppc_golden}[sys.argv[1]]()
+        {"c5": c5_golden, "ppc": ppc_golden, "bench_objects": bench_objects_golden}[sys.argv[1]]()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "pvcnn2_b":
+        os.makedirs(OUT, exist_ok=True)
+        torch.set_num_threads(8)
+        ref_import.install_shims()
+        pvcnn2_b_golden()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "front_end":
         os.makedirs(OUT, exist_ok=True)

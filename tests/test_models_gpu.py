@@ -769,8 +769,8 @@ def test_voxel_conv_without_mfma_instantiation_runs_the_direct_kernel():
 def test_ldm_end_to_end_with_the_set_abstraction_encoder():
     """GraspLatentDDM.generate_grasps conditioned by the SET-ABSTRACTION encoder family (north star: FPS / ball query /
     grouped set-abstraction MLPs conditioning the VAE): PVCNN2Encoder in its repaired form.  Backbone weights = the golden's,
-    which test_g8_pvcnn2_golden pins to the reference's own PVCNN2 graph (checked again here on the golden cloud); the
-    expectation continues from the backbone's features on the CPU: the encoder head in f64 (pc_encoders.py:104-111), then
+    which test_g8_pvcnn2_golden pins to the reference's own PVCNN2 graph (checked again here on both clouds of the batch:
+    pvcnn2.npz's and, as the encoder sees it, the normalised synthetic one of pvcnn2_b.npz); the expectation continues from the backbone's features on the CPU: the encoder head in f64 (pc_encoders.py:104-111), then
     the oracle's 100 DDIM steps and decoder (grasp_ldm.py:189-233).  Poses 1e-4."""
     import torch.nn.functional as F
     from graspldm_amd.pipeline import build_fpc_ldm
@@ -792,6 +792,9 @@ def test_ldm_end_to_end_with_the_set_abstraction_encoder():
         feat = enc.pvcnn_modules(pc.transpose(1, 2).contiguous().cuda())
         z_hip = enc(pc.cuda())
     assert _err(feat[:1, :, ::16], g["out"]) < 1e-4                       # the reference's backbone
+    gb = load_golden("pvcnn2_b.npz")                                      # ... and on the second cloud, from which the
+    assert torch.equal(gb["coords"], pc[1:2].transpose(1, 2))             # expectation below continues
+    assert _err(feat[1:2, :, ::16], gb["out"]) < 1e-4, _err(feat[1:2, :, ::16], gb["out"])
     sd = {k: v.detach().cpu() for k, v in ldm.state_dict().items()}
     p = "vae_model.encoder.pc_encoder."
     h = F.conv1d(feat.cpu().double(), sd[p + "conv_downscale.weight"].double(), sd[p + "conv_downscale.bias"].double())

@@ -152,3 +152,26 @@ def test_config5_end_to_end(fpc_spec):
     _close(logit, g["logit"], atol=2e-5)
     out = R.pose_epilogue(tmrp, logit, dict(grasp_mean=g["grasp_mean"], grasp_std=g["grasp_std"]), 1, G)
     _close(out["grasps"], g["H"], atol=2e-5)
+
+
+def test_bench_objects_fixture(fpc_state_dict, fpc_spec):
+    """bench.py's 32 distinct objects (bench_objects.npz: the reference's encoder latents and 100-step DDIM poses, G = 20):
+    the oracle reproduces objects 0, 13 and 31 from the regenerated clouds and each object's own 20 x_T rows (clouds and
+    samples are independent, so three objects stand for the recipe; the GPU suite checks all 32)."""
+    from graspldm_amd.synthetic import synthetic_batch
+    g = load_golden("bench_objects.npz")
+    G = 20
+    pcs, metas = synthetic_batch(32, 1024, first_index=0)
+    assert torch.equal(pcs[:, ::64], g["pc_probe"])          # the clouds the reference saw
+    assert torch.equal(metas["grasp_mean"], g["grasp_mean"]) and torch.equal(metas["grasp_std"], g["grasp_std"])
+    torch.manual_seed(int(g["seed"]))
+    x_T = torch.randn(32 * G, 1, 4)
+    obj = torch.tensor([0, 13, 31])
+    rows = (obj[:, None] * G + torch.arange(G)).reshape(-1)
+    z = R.pvcnn_encoder_forward(fpc_state_dict, "vae_model.encoder.pc_encoder.", pcs[obj], fpc_spec)
+    _close(z, g["z"][obj], atol=1e-5)
+    sched = R.make_scheduler("ddim")
+    sched.set_timesteps(100)
+    tmrp, logit = R.ldm_generate(fpc_state_dict, pcs[obj], G, sched, fpc_spec, x_T=x_T[rows])
+    _close(tmrp, g["tmrp"][rows], atol=2e-5)
+    _close(logit, g["logit"][rows], atol=2e-5)
