@@ -10,7 +10,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # GLDM_LIB: another build of the same library (diagnostic builds: make -C graspldm_amd/csrc EXTRA=... OUT=...)
 LIB_PATH = os.environ.get("GLDM_LIB") or os.path.join(_PKG, "libgldm_hip.so")
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 class GldmError(RuntimeError):
@@ -70,6 +70,10 @@ _SIGNATURES = {
     "gldm_pointwise_mlp_f16x2_pm": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
     "gldm_pointwise_mlp_f16x2_add": [_vp, _vp, _vp, _vp, _ll, _ll, _ll, _i, _i, _i, _i, _i, _vp, _vp],
     "gldm_pointwise_mlp2_f16x2": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp],
+    "gldm_point_attention": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _ll, _vp, _vp],
+    "gldm_point_attention_workspace_bytes": [_i, _i, _i],   # returns long long (restype set in lib())
+    "gldm_groupnorm_swish_points": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp],
+    "gldm_pointwise_rows": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
     "gldm_sa_mlp_forward": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "gldm_sa_mlp_forward_f16x2": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "gldm_sa_mlp_forward_f16x2_pre": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -123,6 +127,7 @@ def lib():
     h.gldm_r1d_tile_columns.restype = _i
     h.gldm_conv3d_partial_floats.argtypes = [_i, _i, _i]
     h.gldm_conv3d_partial_floats.restype = ctypes.c_longlong
+    h.gldm_point_attention_workspace_bytes.restype = ctypes.c_longlong
     h.gldm_squeeze_parts.argtypes = []
     h.gldm_squeeze_parts.restype = _i
     _lib = h

@@ -170,6 +170,27 @@ def pointwise_conv(x, conv):
     return _gemm_bias_act(x.float(), conv.weight.reshape(conv.weight.shape[0], -1), conv.bias, False)
 
 
+ROWS_MAX = 8   # output rows gldm_pointwise_rows keeps per point
+
+
+def pointwise_rows(x, conv):
+    """A k = 1 conv with a few output rows (the encoder's out_layer[0], C -> out_channels, where global attention keeps it
+    from folding into conv_downscale): one pass over x (gldm_pointwise_rows); more than ROWS_MAX rows or n % 4: pointwise_conv."""
+    _need_cuda(x)
+    hout, n = conv.weight.shape[0], x.shape[-1]
+    if x.ndim != 3 or hout > ROWS_MAX or n % 4:
+        return pointwise_conv(x, conv)
+    from . import _lib as L
+    xf = x.contiguous().float()
+    b, cin, _ = xf.shape
+    w = conv.weight.detach().reshape(hout, cin).float().contiguous()
+    bias = conv.bias.detach().float().contiguous() if conv.bias is not None else None
+    y = torch.empty((b, hout, n), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        L.call("gldm_pointwise_rows", L.ptr(xf), L.ptr(w), L.ptr(bias), b, cin, hout, n, L.ptr(y), L.current_stream(x.device))
+    return y
+
+
 def fold_conv_bn(conv, bn):
     """BatchNorm(eval) folded into a k = 1 conv: W' = diag(s) W, b' = (b - mean) s + beta with s = gamma / sqrt(var + eps),
     in f32 on the module's device.  The one fold of the package (dense layers and sa_pack's set-abstraction tables)."""

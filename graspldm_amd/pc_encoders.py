@@ -13,21 +13,23 @@ class PVCNNEncoder(nn.Module):
                  scale_voxel_resolution=0.75, num_blocks=(1, 1, 1, 1), is_conditioned=False, cond_dims=None,
                  extra_block_channels=None, use_global_attention=False, out_channels=1, load_from_ckpt_path=None):
         super().__init__()
-        if use_global_attention:
-            raise NotImplementedError("global attention is off in the shipped configs and not on the hot path")
         self.pvcnn_modules = PVCNN(extra_feature_channels=extra_feature_channels, scale_channels=scale_channels,
                                    scale_voxel_resolution=scale_voxel_resolution, num_blocks=num_blocks,
                                    is_conditioned=is_conditioned, cond_dims=cond_dims,
                                    extra_block_channels=extra_block_channels)
-        self._finish(in_features, out_features, n_points, out_channels)
+        self._finish(in_features, out_features, n_points, out_channels, use_global_attention)
         if load_from_ckpt_path is not None:
             self.load_ckpt_and_freeze(load_from_ckpt_path)
 
-    def _finish(self, in_features, out_features, n_points, out_channels):
+    def _finish(self, in_features, out_features, n_points, out_channels, use_global_attention=False):
         self.in_features, self.out_features = in_features, out_features
         mid = int(self.pvcnn_modules.out_channels / 2)
         self.conv_downscale = nn.Conv1d(self.pvcnn_modules.out_channels, mid, kernel_size=1)
         self.global_attention = None
+        if use_global_attention:   # pc_encoders.py:65-69: every point attends to every point at the downscaled width
+            from .attention import Attention, check_supported
+            check_supported(mid, n_points, 8)
+            self.global_attention = Attention(mid, 8, D=1)
         self.out_layer = nn.Sequential(nn.Conv1d(mid, out_channels, kernel_size=1),
                                        nn.Linear(n_points, self.out_features))
 
@@ -37,13 +39,24 @@ class PVCNNEncoder(nn.Module):
         if not out.is_cuda:
             raise RuntimeError("pointcloud must be a CUDA tensor (graspldm_amd has no CPU path)")
         x = torch.transpose(out, 1, 2).contiguous()
-        w, b = self._folded_head()
-        x = self._backbone_and_head(x, cond, w, b)
+        if self.global_attention is not None:
+            x = self._attention_tail(self._backbone_and_head(x, cond, None, None))
+        else:
+            w, b = self._folded_head()
+            x = self._backbone_and_head(x, cond, w, b)
         x = dense.linear(x, self.out_layer[1])
         return x.squeeze(1) if x.shape[-2] == 1 else x
 
+    def _attention_tail(self, feats):
+        """conv_downscale -> global attention -> out_layer[0] (pc_encoders.py:104-111 with the switch on).  The attention
+        block sits between the two convs, so they cannot fold into one head: the backbone keeps its [B, C, N] output,
+        conv_downscale runs as a k = 1 GEMM of its own and the attention block at half the width."""
+        from .attention import conv1x1
+        x = self.global_attention(conv1x1(feats.contiguous().float(), self.conv_downscale))
+        return dense.pointwise_rows(x, self.out_layer[0])
+
     def _backbone_and_head(self, x, cond, w, b):
-        """backbone -> head.  When the backbone ends in wide SharedMLP layers (PVCNN: 96 -> 768 -> 1536), they and the
+        """backbone -> head; w = None: the backbone's features [B, C, N] themselves (the global-attention tail follows).  When the backbone ends in wide SharedMLP layers (PVCNN: 96 -> 768 -> 1536), they and the
         folded head run as ONE launch: the 768-row tile is produced in LDS, the head product is taken on the last
         layer's accumulators, and neither [B, 768, N] (0.8 GB per 256 clouds) nor [B, 1536, N] (1.6 GB) is written."""
         from .pvcnn import PVCNN, SharedMLP
@@ -60,25 +73,28 @@ class PVCNNEncoder(nn.Module):
             for layer in layers[: -2 if two else -1]:
                 feats, _ = layer((feats, coords))
             feats = feats.contiguous().float()
-            if w.shape[0] <= 16 and two and dense.fused_mlp2_supported(feats, prev.layers[0].weight.shape[1], cin, cout):
+            head = (lambda: self._packed_head(w, b)) if w is not None else (lambda: None)   # packed only where a launch takes it
+            pick = 0 if w is None else 1   # (y, z) of a fused launch: the features without a head, the head's rows with one
+            if (w is None or w.shape[0] <= 16) and two and dense.fused_mlp2_supported(feats, prev.layers[0].weight.shape[1], cin, cout):
                 f0 = dense.folded_conv_bn(prev.layers[0], prev.layers[1], feats.device)
                 f = dense.folded_conv_bn(conv, bn, feats.device)
                 if f.ws is not None and f0.ws is not None and dense.split_supported(cin, f0.w.shape[1]):
                     # both GEMMs on the f16 matrix pipe (split-f32 operands)
-                    return dense.pointwise_mlp(feats, f.ws, f.b, cout, True, head=self._packed_head(w, b), keep_y=False,
-                                               front=(f0.ws, f0.b, cin, f0.gain), split=True)[1]
-                return dense.pointwise_mlp(feats, f.wp, f.b, cout, True, head=self._packed_head(w, b), keep_y=False,
-                                           front=(f0.wp, f0.b, cin))[1]
+                    return dense.pointwise_mlp(feats, f.ws, f.b, cout, True, head=head(), keep_y=w is None,
+                                               front=(f0.ws, f0.b, cin, f0.gain), split=True)[pick]
+                return dense.pointwise_mlp(feats, f.wp, f.b, cout, True, head=head(), keep_y=w is None,
+                                           front=(f0.wp, f0.b, cin))[pick]
             if two:
                 feats = prev(feats).contiguous()
-            if w.shape[0] <= 16 and dense.fused_mlp_supported(feats, cin, cout):
+            if (w is None or w.shape[0] <= 16) and dense.fused_mlp_supported(feats, cin, cout):
                 f = dense.folded_conv_bn(conv, bn, feats.device)
                 split = f.ws_main is not None and dense.split_supported(cin)
-                return dense.pointwise_mlp(feats, f.ws_main if split else f.wp, f.b, cout, True, head=self._packed_head(w, b),
-                                           keep_y=False, split=split)[1]
+                return dense.pointwise_mlp(feats, f.ws_main if split else f.wp, f.b, cout, True, head=head(),
+                                           keep_y=w is None, split=split)[pick]
             feats = last(feats)
-            return dense.pointwise_gemm(feats, w, b)
-        return dense.pointwise_gemm(bb(x, cond=cond), w, b)
+            return feats if w is None else dense.pointwise_gemm(feats, w, b)
+        feats = bb(x, cond=cond)
+        return feats if w is None else dense.pointwise_gemm(feats, w, b)
 
     def _packed_head(self, w, b):
         """(packed W, b, rows) of the folded head for the launches that take it on their accumulators; rebuilt with it."""
@@ -122,8 +138,8 @@ class PVCNN2Encoder(PVCNNEncoder):
                  scale_voxel_resolution=0.75, num_blocks=(1, 1, 1, 1), is_conditioned=False, cond_dims=None,
                  extra_block_channels=None, use_global_attention=False, use_local_attention=False, out_channels=1):
         nn.Module.__init__(self)
-        if use_global_attention or use_local_attention:
-            raise NotImplementedError("attention variants are not on the hot path")
+        if use_local_attention:
+            raise NotImplementedError("local (voxel) attention inside PVConv is not on the hot path")
         if tuple(num_blocks) != (1, 1, 1, 1):
             raise NotImplementedError("PVCNN2 fixes its block counts in sa_blocks / fp_blocks (pvcnn_base.py:186-202); "
                                       f"num_blocks={tuple(num_blocks)} cannot be honoured")
@@ -131,4 +147,4 @@ class PVCNN2Encoder(PVCNNEncoder):
             raise NotImplementedError("PVCNN2 takes no conditioning / extra block channels (pvcnn_base.py:204-212)")
         self.pvcnn_modules = PVCNN2(extra_feature_channels=extra_feature_channels, width_multiplier=scale_channels,
                                     voxel_resolution_multiplier=scale_voxel_resolution, use_attention=False)
-        self._finish(in_features, out_features, n_points, out_channels)
+        self._finish(in_features, out_features, n_points, out_channels, use_global_attention)

@@ -563,6 +563,43 @@ int gldm_devoxelize_gn_cl_fused(const float *coords /*[b,3,n]*/, const float *fe
 int gldm_bias_act(float *y /*[b,c,n]*/, const float *bias /*[c]*/, int b, int c, long long n, int relu,
                   gldm_stream_t stream);
 
+/* ------------------------------------------------ point attention (ABI 12) */
+
+/* ref: grasp_ldm/models/modules/modules.py:10-54 (the PVD `Attention` block) between its k = 1 convs: dense softmax
+ * attention of every point over every point, WITHOUT a 1 / sqrt(c) factor (modules.py:42):
+ *   out[b,c,i] = sum_j v[b,c,j] softmax_j( sum_c' q[b,c',i] k[b,c',j] ).
+ * q, k, v are [b,c,n] f32 and may alias one another (with the k and v projections folded into q and the out conv, k = v =
+ * the block's input).  c % 16 == 0, 16 <= c <= 1024; n % 32 == 0, 32 <= n <= 4096; GLDM_ERR_UNSUPPORTED otherwise.
+ * Default arithmetic: both products as three v_mfma_f32_16x16x32_f16 over hi / lo f16 pieces, f32 accumulation; every
+ * 16-row group of an operand is split as x / s (s a power of two from the group's largest magnitude, folded back on the
+ * accumulators) and P is split as 2^14 P.  exact_f32 != 0: the same stages on v_mfma_f32_16x16x4_f32.  Softmax subtracts
+ * the row maximum and divides once per row.  Deterministic (fixed summation order, no atomics); a cloud's result does
+ * not depend on b or on its position in the batch.
+ * `workspace`: at least gldm_point_attention_workspace_bytes(b, c, n) bytes (at most 256 MiB, or one cloud's need where
+ * that is more: operand fragments, scores and probabilities of a chunk of clouds; the entry point loops over chunks),
+ * 16-byte aligned, private to the stream until the call's work has finished.  A missing / smaller workspace or a
+ * pointer that is not 16-byte aligned: GLDM_ERR_INVALID_ARG, nothing launched.  The bytes query returns -1 for an
+ * unsupported shape. */
+long long gldm_point_attention_workspace_bytes(int b, int c, int n);
+int gldm_point_attention(const float *q /*[b,c,n]*/, const float *k /*[b,c,n]*/, const float *v /*[b,c,n]*/,
+                         int b, int c, int n, int exact_f32, void *workspace, long long workspace_bytes,
+                         float *out /*[b,c,n]*/, gldm_stream_t stream);
+
+/* ref: modules.py:50-52 (`x = h + x; x = nonlin(norm(x))`): out = swish(GroupNorm(groups, eps, affine)(x + add)) over
+ * [b,c,n]; add may be NULL, out may be x.  Statistics from the tensor itself, combined in f64 in a fixed order (as
+ * gldm_groupnorm_swish does for voxel grids).  c % groups == 0, c / groups <= 128, n % 4 == 0, b <= 65535
+ * (GLDM_ERR_UNSUPPORTED otherwise); x, add and out 16-byte aligned (GLDM_ERR_INVALID_ARG otherwise). */
+int gldm_groupnorm_swish_points(const float *x /*[b,c,n]*/, const float *add /*[b,c,n] or NULL*/, const float *gamma /*[c]*/,
+                                const float *beta /*[c]*/, int b, int c, int n, int groups, float eps,
+                                float *out /*[b,c,n]*/, gldm_stream_t stream);
+
+/* ref: grasp_ldm/models/modules/pc_encoders.py:72-77,111 (out_layer[0] = Conv1d(C -> out_channels, k = 1)) where it cannot be
+ * folded into conv_downscale (global attention on): y = W x + bias for a FEW output rows, hout <= 8, over [b, cin, n]; W
+ * [hout, cin] row major.  One pass over x, k-ordered fma chain from the bias.  n % 4 == 0, b <= 65535
+ * (GLDM_ERR_UNSUPPORTED otherwise); x and y 16-byte aligned (GLDM_ERR_INVALID_ARG otherwise). */
+int gldm_pointwise_rows(const float *x /*[b,cin,n]*/, const float *w /*[hout,cin]*/, const float *bias /*[hout] or NULL*/,
+                        int b, int cin, int hout, int n, float *y /*[b,hout,n]*/, gldm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
