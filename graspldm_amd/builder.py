@@ -1,9 +1,11 @@
 """String -> class registry and recursive config builder: mirror of
-`grasp_ldm/models/builder.py:28-116` for the models on the generation path."""
+`grasp_ldm/models/builder.py:28-116` for the models on the generation path and the grasp success
+classifier (builder.py:24)."""
 from torch import nn
 
 from .config import ConfigDict, _wrap
 from .diffusion import GaussianDiffusion1D
+from .grasp_classifier import PointsBasedGraspClassifier
 from .grasp_ldm import GraspLatentDDM
 from .grasp_vae import GraspCVAE
 from .resnets import ClassTimeConditionedResNet1D, ResNet1D, TimeConditionedResNet1D
@@ -11,7 +13,8 @@ from .resnets import ClassTimeConditionedResNet1D, ResNet1D, TimeConditionedResN
 DIFFUSION_MODELS = {"GaussianDiffusion1D": GaussianDiffusion1D, "TimeConditionedResNet1D": TimeConditionedResNet1D,
                     "ClassTimeConditionedResNet1D": ClassTimeConditionedResNet1D}
 STANDARD_MODULES = {"ResNet1D": ResNet1D}
-ALL_MODELS = {"GraspCVAE": GraspCVAE, "GraspLatentDDM": GraspLatentDDM, **STANDARD_MODULES, **DIFFUSION_MODELS}
+ALL_MODELS = {"GraspCVAE": GraspCVAE, "GraspLatentDDM": GraspLatentDDM, "PointsBasedGraspClassifier": PointsBasedGraspClassifier,
+              **STANDARD_MODULES, **DIFFUSION_MODELS}
 
 
 def build_model(model_cfg) -> nn.Module:

@@ -47,6 +47,8 @@ class _InferenceBase:
             raise RuntimeError("graspldm_amd runs on the GPU only (no CPU path)")
         self.model = None
         self.dataset = None
+        self.classifier = None
+        self.gripper_points = None
 
     def _results(self, pc, metas, tmrp, cls_logit, num_pcs, num_grasps, all_steps=()):
         # before anything leaves the device: a lost hand-off inside the fused sampling launch raises here
@@ -77,9 +79,40 @@ class _InferenceBase:
             for step in all_steps:  # [tmrp [G,6], logit [G,1]] on the CPU (grasp_ldm.py:223-227)
                 Hs, _, _ = pose_epilogue(step[0].to(self.device), None, mean, std, num_grasps)
                 steps_H.append(Hs.view(1, num_grasps, 4, 4).cpu())
-        return dict(grasps=H.view(num_pcs, num_grasps, 4, 4), grasp_tmrp=un.view(num_pcs, num_grasps, 6),
-                    confidence=conf.view(num_pcs, num_grasps, 1), qualities=None, pc=unnormalize_pc(pc, metas),
-                    all_steps_grasps=steps_H)
+        out = dict(grasps=H.view(num_pcs, num_grasps, 4, 4), grasp_tmrp=un.view(num_pcs, num_grasps, 6),
+                   confidence=conf.view(num_pcs, num_grasps, 1), qualities=None, pc=unnormalize_pc(pc, metas),
+                   all_steps_grasps=steps_H)
+        if self.classifier is not None:   # additive: the key exists only with a classifier set
+            out["success"] = self.score_grasps(pc, metas, out["grasps"]).unsqueeze(-1)
+        return out
+
+    def set_classifier(self, model, gripper_points=None):
+        """Attach a PointsBasedGraspClassifier: every result dict then carries `success` [B, G, 1], the classifier's
+        probability for each returned pose (score_grasps).  gripper_points [Ng, 3]: the points the classifier was trained
+        with (default: gripper.control_points(num_pc_points - N) for a cloud of N points).  None detaches it."""
+        self.classifier = None if model is None else model.to(self.device).eval()
+        self.gripper_points = None if gripper_points is None else gripper_points.to(self.device).float()
+
+    @torch.no_grad()
+    def score_grasps(self, pc, metas, H):
+        """Success probability [B, G] of poses H [B, G, 4, 4] (or [G, 4, 4] for one cloud; un-normalised cloud frame, as
+        generate_grasps returns them) against the normalised cloud(s) pc: the gripper points go through the cloud's own
+        normalisation, (x - metas["pc_mean"]) / pc_scale.  metas["pc_mean"] is the total shift (centring mean + pc_shift,
+        acronym_grasp_points.py:121), so the instance's pc_shift is already part of it."""
+        if self.classifier is None:
+            raise RuntimeError("no classifier attached: call set_classifier(model) first")
+        batch = (pc.unsqueeze(0) if pc.ndim == 2 else pc).to(self.device)
+        H = H.to(self.device)
+        if H.ndim == 3:
+            H = H.unsqueeze(0)
+        if H.ndim != 4 or H.shape[-2:] != (4, 4) or H.shape[0] != batch.shape[0]:
+            raise RuntimeError(f"grasps must be [B,G,4,4] with B = {batch.shape[0]} clouds (or [G,4,4] for one), not {tuple(H.shape)}")
+        scale = torch.as_tensor((getattr(self, "_norm", None) or {}).get("pc_scale", PC_STD), dtype=torch.float32).reshape(-1)
+        if not bool((scale == scale[0]).all()):
+            raise NotImplementedError("the classifier front takes one translation scale for the three axes")
+        mean = metas["pc_mean"].to(self.device).float().reshape(-1, 3)
+        return self.classifier.score_poses(batch, H, gripper_points=self.gripper_points, pc_mean=mean, pc_shift=0.0,
+                                           pc_scale=float(scale[0]))
 
     def set_normalization_params(self, norm_config):
         """grasp_ldm/inference/inference_base.py:103-130: pc_shift, grasp_shift, translation_scale, rotation_scale."""

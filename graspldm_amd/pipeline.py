@@ -51,3 +51,25 @@ def build_fpc_ldm(n_points=1024, scheduler="ddim", seed=0, device=None, **kw):
     ldm.eval()
     return ldm.to(device) if device is not None else ldm
 
+
+
+def classifier_model_config(n_cloud_points=1024, n_gripper_points=64, backbone="PVCNN", backbone_args=None):
+    """A reference-style config of the grasp success classifier (grasp_classifier.py:18-52): `num_pc_points` counts the
+    merged scene, cloud + gripper points; the backbone sees one extra feature channel, the cloud / gripper label."""
+    if backbone == "PVCNN":
+        args = dict(extra_feature_channels=1, scale_channels=0.25, scale_voxel_resolution=0.75, num_blocks=(1, 1, 1, 1))
+    elif backbone == "PVCNN2":
+        args = dict(extra_feature_channels=1)
+    else:
+        raise ValueError(f"backbone must be PVCNN or PVCNN2, not {backbone!r}")
+    args.update(backbone_args or {})
+    return dict(model=dict(type="PointsBasedGraspClassifier", args=dict(
+        num_pc_points=n_cloud_points + n_gripper_points, points_backbone_config=dict(type=backbone, args=args),
+        loss_config=dict(classification_loss=dict(type="BCEClassificationLoss", args={})))))
+
+
+def build_classifier(n_cloud_points=1024, n_gripper_points=64, backbone="PVCNN", seed=0, device=None, backbone_args=None):
+    model = build_model_from_cfg(classifier_model_config(n_cloud_points, n_gripper_points, backbone, backbone_args))
+    load_synthetic_weights(model, seed=seed)
+    model.eval()
+    return model.to(device) if device is not None else model

@@ -600,6 +600,39 @@ int gldm_groupnorm_swish_points(const float *x /*[b,c,n]*/, const float *add /*[
 int gldm_pointwise_rows(const float *x /*[b,cin,n]*/, const float *w /*[hout,cin]*/, const float *bias /*[hout] or NULL*/,
                         int b, int cin, int hout, int n, float *y /*[b,hout,n]*/, gldm_stream_t stream);
 
+/* ------------------------------------------------ grasp success classifier (ABI 13) */
+
+/* ref: grasp_ldm/dataset/acronym/acronym_grasp_points.py:25-28,107,117 (gripper points placed at a pose, centred on the
+ * cloud's mean, normalised) + grasp_ldm/models/grasp_classifier.py:71-80 (label channel, merge, channel-first): the input of
+ * every (cloud, pose) scene in one pass.  pc [bc,np,3] normalised clouds; H [bc*g,4,4] row-major poses in the un-normalised
+ * cloud frame, row c*g + i belongs to cloud c (repeat_interleave order); gripper [ng,3] control points; pc_mean [bc,3] or
+ * NULL (the points are then placed in the frame as given).  x [bc*g, 4, np+ng]: columns < np hold the cloud's xyz (bit
+ * copies) and label 0, columns >= np hold (R p + t - pc_mean - pc_shift) / pc_scale and label 1,
+ * evaluated in the reference's order (k-ordered fma chain of R p, then + t, - pc_mean, - pc_shift, one IEEE division).  pc_scale zero or NaN,
+ * a null pointer or a non-positive count: GLDM_ERR_INVALID_ARG. */
+int gldm_grasp_scene(const float *pc /*[bc,np,3]*/, const float *H /*[bc*g,4,4]*/, const float *gripper /*[ng,3]*/,
+                     const float *pc_mean /*[bc,3] or NULL*/, float pc_shift, float pc_scale, int bc, int g, int np, int ng,
+                     float *x /*[bc*g,4,np+ng]*/, gldm_stream_t stream);
+
+/* ref: grasp_ldm/models/grasp_classifier.py:40-52,86-92: the `classifier` Sequential (SharedMLP(c -> rows) with its
+ * BatchNorm(eval) folded, Dropout(eval), Conv1d(rows -> 1), Linear(n -> 1)) and the sigmoid on features x [b,c,n]:
+ *   logit[b] = c0 + sum_n l[n] (w2 . relu(W1' x[b,:,n] + b1')),   prob = 1 / (1 + exp(-logit)),
+ * c0 = lb + b2 sum_n l[n] from the caller.  `w1`: exact_f32 == 0: split-f16 A fragments of W1' with K zero-padded to a
+ * multiple of 32 ([rows/16][K/32][plane][lane][8 f16], see "Split-f16 weight fragments"); exact_f32 != 0: f32 A fragments
+ * [rows/16][c/16][lane][4].  16-byte aligned.  The GEMM runs on the matrix pipe (three f16 products per f32 product, the
+ * 64-point tile split as x / s with s the power of two that brings its largest magnitude into [2^13, 2^14); or
+ * v_mfma_f32_16x16x4_f32); ReLU, w2 and
+ * l[n] are applied on the accumulators, neither [b,rows,n] nor [b,1,n] is written.  The sum over points runs in a fixed
+ * order (lanes, waves, then one partial per 64-point tile in `workspace`, added in tile order by a second launch): no
+ * atomics, bitwise repeatable, independent of b and of a scene's position.
+ * c % 16 == 0, 16 <= c <= 2048; rows % 16 == 0, 16 <= rows <= 512; 1 <= n <= 2^20 (any n: tail columns are masked), b *
+ * ceil(n / 64) < 2^31: GLDM_ERR_UNSUPPORTED otherwise.  `workspace`: gldm_cls_head_workspace_bytes(b, c, rows, n) bytes
+ * (-1 for an unsupported shape), private to the stream until the work has finished; smaller: GLDM_ERR_WORKSPACE. */
+long long gldm_cls_head_workspace_bytes(int b, int c, int rows, int n);
+int gldm_cls_head(const float *x /*[b,c,n]*/, const void *w1, const float *b1 /*[rows]*/, const float *w2 /*[rows]*/,
+                  const float *l /*[n]*/, float c0, int b, int c, int rows, int n, int exact_f32, void *workspace,
+                  long long workspace_bytes, float *logit /*[b]*/, float *prob /*[b]*/, gldm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

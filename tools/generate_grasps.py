@@ -7,7 +7,8 @@ Additive flags: --pc_file FILE [--num_points N] (generate on a sensor cloud read
 the reference's `generate_on_pointcloud`, grasp_ldm/inference/inference_base.py:161-212, which its own CLI does not
 reach -- it only iterates ACRONYM items, tools/generate_grasps.py:109-131), --device, --seed, --synthetic N (run on N-point synthetic object clouds with
 the synthetic weight recipe when no experiment directory / ACRONYM data is available; there is
-no network here for either), --out FILE.npz, --refine_from FILE [--refine_strength S] (start from given grasps instead of
+no network here for either), --out FILE.npz, --classifier_config FILE [--classifier_ckpt FILE] [--sort_by_success] (score every
+generated grasp with a PointsBasedGraspClassifier: the results and the written file gain `success`), --refine_from FILE [--refine_strength S] (start from given grasps instead of
 from noise: with --mode VAE the file's grasps are reconstructed through the VAE, with --mode LDM they are encoded, diffused
 forward to `S` of the schedule and denoised again; FILE is .npy / .npz key `grasps`, [G,4,4] or [B,G,4,4] -- one set per
 sample / cloud file in order --, un-normalised, in the cloud's frame; --num_grasps is taken from the file then).  `--inference_steps` is honoured (the reference
@@ -55,6 +56,13 @@ def parse_args(argv=None):
     p.add_argument("--refine_strength", type=float, default=0.3,
                    help="with --refine_from and --mode LDM: the share of the schedule to diffuse forward and denoise again "
                         "(0 = decode the encoder's mean, 1 = the whole schedule)")
+    p.add_argument("--classifier_config", type=str, default=None, metavar="FILE",
+                   help="reference-style config whose `model` is a PointsBasedGraspClassifier: every generated grasp is "
+                        "scored against its cloud and the results gain `success`")
+    p.add_argument("--classifier_ckpt", type=str, default=None, metavar="FILE",
+                   help="the classifier's checkpoint (optional with --synthetic: the synthetic weight recipe is used)")
+    p.add_argument("--sort_by_success", action="store_true",
+                   help="with --classifier_config: order each cloud's grasps by falling success probability in --out")
     p.add_argument("--out", type=str, default=None, help="write results of all samples to this .npz")
     return p.parse_args(argv)
 
@@ -78,6 +86,42 @@ def setup_model(args):
         return model
     return InferenceVAE(exp_name=exp_name, exp_out_root=exp_root, data_root=args.data_root, data_split=args.split,
                         use_ema_model=args.use_ema_model, device=args.device)
+
+
+def find_classifier_section(cfg):
+    """The {type, args} dict of the classifier inside a reference-style config: `model` (or `models`) itself, its
+    `classifier` entry, or a `model` key below either."""
+    for key in ("model", "models"):
+        node = cfg.get(key) if isinstance(cfg, dict) else None
+        for _ in range(3):
+            if not isinstance(node, dict):
+                break
+            if node.get("type") == "PointsBasedGraspClassifier":
+                return node
+            node = node.get("classifier", node.get("model"))
+    raise SystemExit("--classifier_config: no model of type PointsBasedGraspClassifier under `model` / `models`")
+
+
+def setup_classifier(args, model):
+    """Build the classifier of --classifier_config, load --classifier_ckpt (or recipe weights under --synthetic), attach."""
+    if not args.classifier_config:
+        if args.classifier_ckpt or args.sort_by_success:
+            raise SystemExit("--classifier_ckpt / --sort_by_success need --classifier_config")
+        return model
+    from graspldm_amd.builder import build_model
+    from graspldm_amd.config import Config
+    section = find_classifier_section(Config.fromfile(args.classifier_config))
+    clf = build_model(section)
+    if args.classifier_ckpt:
+        from graspldm_amd.checkpoint import load_weights
+        load_weights(clf, args.classifier_ckpt, args.use_ema_model)
+    elif args.synthetic:
+        from graspldm_amd.synthetic import load_synthetic_weights
+        load_synthetic_weights(clf, seed=0)
+    else:
+        raise SystemExit("--classifier_ckpt is required (recipe weights are used under --synthetic only)")
+    model.set_classifier(clf.eval())
+    return model
 
 
 def read_grasp_file(path):
@@ -125,7 +169,7 @@ def main(argv=None):
     if args.seed is not None:
         torch.manual_seed(args.seed)
         np.random.seed(args.seed)
-    model = setup_model(args)
+    model = setup_classifier(args, setup_model(args))
     from graspldm_amd.synthetic import normalize_cloud, synthetic_cloud
     results = []
     if args.pc_file:
@@ -171,8 +215,15 @@ def encoder_points(model):
 
 
 def finish(args, results):
+    if args.sort_by_success:   # every per-grasp array of a cloud in the order of falling success
+        for r in results:
+            order = torch.argsort(r["success"][..., 0], dim=1, descending=True, stable=True)
+            for k in ("grasps", "grasp_tmrp", "confidence", "success", "latent_mu", "latent_logvar"):
+                if k in r:
+                    idx = order.view(*order.shape, *([1] * (r[k].ndim - 2))).expand_as(r[k])
+                    r[k] = torch.gather(r[k], 1, idx)
     if args.out:
-        extra = {k: torch.cat([r[k] for r in results]).cpu().numpy() for k in ("latent_mu", "latent_logvar")
+        extra = {k: torch.cat([r[k] for r in results]).cpu().numpy() for k in ("latent_mu", "latent_logvar", "success")
                  if all(k in r for r in results)}
         np.savez_compressed(args.out, grasps=torch.cat([r["grasps"] for r in results]).cpu().numpy(),
                             grasp_tmrp=torch.cat([r["grasp_tmrp"] for r in results]).cpu().numpy(),
