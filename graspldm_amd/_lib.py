@@ -10,7 +10,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # GLDM_LIB: another build of the same library (diagnostic builds: make -C graspldm_amd/csrc EXTRA=... OUT=...)
 LIB_PATH = os.environ.get("GLDM_LIB") or os.path.join(_PKG, "libgldm_hip.so")
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 class GldmError(RuntimeError):
@@ -74,6 +74,9 @@ _SIGNATURES = {
     "gldm_point_attention_workspace_bytes": [_i, _i, _i],   # returns long long (restype set in lib())
     "gldm_groupnorm_swish_points": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp],
     "gldm_pointwise_rows": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    "gldm_point_attention_fused": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    "gldm_groupnorm_affine": [_vp, _vp, _i, _i, _i, _vp, _vp],
+    "gldm_groupnorm_swish_points_sum": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp],
     "gldm_grasp_scene": [_vp, _vp, _vp, _vp, _f, _f, _i, _i, _i, _i, _vp, _vp],
     "gldm_cls_head_workspace_bytes": [_i, _i, _i, _i],   # returns long long (restype set in lib())
     "gldm_cls_head": [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _vp, _ll, _vp, _vp, _vp],

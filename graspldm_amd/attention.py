@@ -8,7 +8,11 @@ Two folds, exact algebra (only rounding changes), done in f64 on the host once p
   * rows of P sum to 1, so  Wo (v P^T) + bo = (Wo Wv)(x P^T) + (Wo bv + bo): the v projection disappears (V = x).
 The block is then two weight GEMMs (the package's k = 1 launches), the attention core reading ONE tensor as K and V
 (gldm_point_attention, csrc/point_attention.hip) and one GroupNorm + Swish launch that adds the residual on its way
-(gldm_groupnorm_swish_points).  No CPU path."""
+(gldm_groupnorm_swish_points).  No CPU path.
+
+Voxel attention inside PVConv (pvconv.py:68-69: the block in place of the second Swish, tokens = the r^3 voxels) runs the
+same algebra from voxel.run: `check_voxel_supported` is the one gate of its shapes, `attention_core` its dispatch between
+the fused kernel (gldm_point_attention_fused: c <= 128, no n x n tensor) and the materialised core above."""
 from typing import NamedTuple, Optional
 
 import torch
@@ -28,6 +32,28 @@ def check_supported(c, n=None, num_groups=None):
     if not supported(c, n) or (num_groups is not None and c // num_groups > MAX_GROUP_CHANNELS):
         raise NotImplementedError(f"point attention over (C, N) = ({c}, {n}) has no kernel: C % 16 == 0 in 16..1024, "
                                   f"N % 32 == 0 in 32..4096, C / groups <= {MAX_GROUP_CHANNELS}")
+
+
+VOXEL_MIN_C, VOXEL_MAX_C = 32, 1024   # voxel attention: channels (C = 16 would pad half of every 32-deep f16 MFMA)
+VOXEL_MIN_R, VOXEL_MAX_R = 4, 16       # resolutions, r % 4 == 0: n = r^3 is a multiple of 64 in 64 .. 4096
+FUSED_MAX_C = 128                      # gldm_point_attention_fused: 32 <= c <= 128
+
+
+def voxel_supported(c, r):
+    return (c % 16 == 0 and VOXEL_MIN_C <= c <= VOXEL_MAX_C and r % 4 == 0 and VOXEL_MIN_R <= r <= VOXEL_MAX_R)
+
+
+def check_voxel_supported(c, r):
+    """The one gate of PVConv(use_attention=True): out_channels c and voxel resolution r."""
+    if not voxel_supported(c, r):
+        raise NotImplementedError(f"voxel attention over (C, n) = ({c}, {r ** 3}) at resolution {r} has no kernel: C % 16 == 0 in "
+                                  f"{VOXEL_MIN_C}..{VOXEL_MAX_C}, r % 4 == 0 in {VOXEL_MIN_R}..{VOXEL_MAX_R} (n = r^3, a multiple "
+                                  f"of 64 in 64..4096)")
+
+
+def fused_supported(c, n):
+    """Shapes gldm_point_attention_fused is built for: c % 16 == 0 in 32 .. 128, n % 32 == 0 in 32 .. 4096."""
+    return c % 16 == 0 and 32 <= c <= FUSED_MAX_C and n % 32 == 0 and 32 <= n <= 4096
 
 
 def fold_attention(wq, bq, wk, wv, bv, wo, bo):
@@ -96,6 +122,44 @@ def point_attention(q, k, v):
         L.call("gldm_point_attention", L.ptr(q), L.ptr(k), L.ptr(v), b, c, n, int(not split_enabled()), L.ptr(ws), nbytes,
                L.ptr(out), L.current_stream(q.device))
     return out
+
+
+def point_attention_fused(q, k, v):
+    """point_attention's contract in one launch without a workspace (gldm_point_attention_fused): c <= 128."""
+    from . import _lib as L
+    from .numerics import split_enabled
+    for t in (q, k, v):
+        if not t.is_cuda:
+            raise RuntimeError("attention inputs must be CUDA tensors (graspldm_amd has no CPU path)")
+    q, k, v = (t if t.is_contiguous() and t.dtype == torch.float32 else t.contiguous().float() for t in (q, k, v))
+    b, c, n = q.shape
+    if not fused_supported(c, n):
+        raise NotImplementedError(f"fused point attention over (C, N) = ({c}, {n}) has no kernel: C % 16 == 0 in 32..{FUSED_MAX_C}, "
+                                  f"N % 32 == 0 in 32..4096")
+    out = torch.empty_like(q)
+    with torch.cuda.device(q.device):
+        L.call("gldm_point_attention_fused", L.ptr(q), L.ptr(k), L.ptr(v), b, c, n, int(not split_enabled()), L.ptr(out),
+               L.current_stream(q.device))
+    return out
+
+
+def attention_core(q, k, v):
+    """The core of the voxel path, by width and under both arithmetics: c <= 128 takes the fused kernel, wider tensors
+    the materialised core (measured at three shapes: DESIGN.md 4.6)."""
+    return point_attention_fused(q, k, v) if q.shape[1] <= FUSED_MAX_C else point_attention(q, k, v)
+
+
+def groupnorm_swish_sum(x, norm, add=None):
+    """(swish(GroupNorm(x + add)), its per-(cloud, channel) sums over N) over [B, C, N], one launch."""
+    from . import _lib as L
+    b, c, n = x.shape
+    out = torch.empty_like(x)
+    chan_sum = torch.empty((b, c), dtype=torch.float32, device=x.device)
+    gamma, beta = norm.weight.detach().float().contiguous(), norm.bias.detach().float().contiguous()
+    with torch.cuda.device(x.device):
+        L.call("gldm_groupnorm_swish_points_sum", L.ptr(x), L.ptr(add), L.ptr(gamma), L.ptr(beta), b, c, n, int(norm.num_groups),
+               float(norm.eps), L.ptr(out), L.ptr(chan_sum), L.current_stream(x.device))
+    return out, chan_sum
 
 
 def groupnorm_swish(x, norm, add=None):

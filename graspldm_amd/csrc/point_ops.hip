@@ -785,7 +785,7 @@ int ilog2_ceil(int v) {
 
 // =========================================================== C ABI =========
 
-GLDM_API int gldm_abi_version(void) { return 13; }
+GLDM_API int gldm_abi_version(void) { return 14; }
 
 // ---------------------------------------------------------------- row max --
 // out[row] = max over n of x[row][0..n): the global pooling of PointNetAModule (pointnet.py:40-44, `.max(dim=-1)`) over

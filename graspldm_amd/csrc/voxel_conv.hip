@@ -980,8 +980,8 @@ __global__ __launch_bounds__(64) void groupnorm_coef_kernel(const float *__restr
   }
   const double n = (double)cpg * r3, mean_d = s / n;
   const float mean = (float)mean_d, rstd = (float)(1.0 / sqrt(fmax(s2 / n - mean_d * mean_d, 0.0) + (double)eps));
-  if (tid < cpg) {
-    const int ch = g * cpg + tid;
+  for (int i = tid; i < cpg; i += 64) {   // one trip up to 64 channels per group; the voxel attention stack goes to 128
+    const int ch = g * cpg + i;
     const float a = gamma[ch] * rstd;
     coef[((size_t)b * c + ch) * 2] = a;
     coef[((size_t)b * c + ch) * 2 + 1] = beta[ch] - mean * rstd * gamma[ch];
@@ -1533,7 +1533,7 @@ GLDM_API int gldm_conv3d_k3_f16x2_gn(const float *x, const float *in_coef, const
 
 GLDM_API int gldm_groupnorm_coef(const float *partial, const float *gamma, const float *beta, int b, int c, int r, int groups,
                                  float eps, float *coef, gldm_stream_t stream) {
-  if (!partial || !gamma || !beta || !coef || b <= 0 || c <= 0 || r <= 0 || groups <= 0 || c % groups || c / groups > 64)
+  if (!partial || !gamma || !beta || !coef || b <= 0 || c <= 0 || r <= 0 || groups <= 0 || c % groups || c / groups > 128)
     return GLDM_ERR_INVALID_ARG;
   const int nbricks = ((r + kBrick - 1) / kBrick) * ((r + kBrick - 1) / kBrick);
   hipLaunchKernelGGL(groupnorm_coef_kernel, dim3(groups, b), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), partial, gamma,

@@ -132,19 +132,21 @@ class PVCNN2Encoder(PVCNNEncoder):
     feature-propagation) backbone.  The two scale arguments mean what they mean for PVCNNEncoder and are mapped onto
     the arguments PVCNN2 does take (scale_channels -> width_multiplier, scale_voxel_resolution ->
     voxel_resolution_multiplier); the ones PVCNN2 has no counterpart for are rejected instead of silently dropped
-    (its block counts live in the class tables sa_blocks / fp_blocks, and it has no conditioning inputs)."""
+    (its block counts live in the class tables sa_blocks / fp_blocks, and it has no conditioning inputs).
+    use_local_attention is PVCNN2's use_attention: voxel attention inside the PVConv of the second set-abstraction stage,
+    C = int(64 scale_channels) channels over int(16 scale_voxel_resolution)^3 voxels; shapes outside
+    attention.check_voxel_supported (the quarter-width default: C = 16) raise NotImplementedError at construction."""
 
     def __init__(self, in_features=3, out_features=32, n_points=1024, extra_feature_channels=0, scale_channels=0.25,
                  scale_voxel_resolution=0.75, num_blocks=(1, 1, 1, 1), is_conditioned=False, cond_dims=None,
                  extra_block_channels=None, use_global_attention=False, use_local_attention=False, out_channels=1):
         nn.Module.__init__(self)
-        if use_local_attention:
-            raise NotImplementedError("local (voxel) attention inside PVConv is not on the hot path")
         if tuple(num_blocks) != (1, 1, 1, 1):
             raise NotImplementedError("PVCNN2 fixes its block counts in sa_blocks / fp_blocks (pvcnn_base.py:186-202); "
                                       f"num_blocks={tuple(num_blocks)} cannot be honoured")
         if is_conditioned or cond_dims is not None or extra_block_channels is not None:
             raise NotImplementedError("PVCNN2 takes no conditioning / extra block channels (pvcnn_base.py:204-212)")
         self.pvcnn_modules = PVCNN2(extra_feature_channels=extra_feature_channels, width_multiplier=scale_channels,
-                                    voxel_resolution_multiplier=scale_voxel_resolution, use_attention=False)
+                                    voxel_resolution_multiplier=scale_voxel_resolution,
+                                    use_attention=bool(use_local_attention))
         self._finish(in_features, out_features, n_points, out_channels, use_global_attention)

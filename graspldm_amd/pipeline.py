@@ -7,13 +7,17 @@ from .synthetic import load_synthetic_weights
 
 
 def fpc_model_config(n_points=1024, scheduler="ddim", latent=4, pc_latent=64, pc_channels=3, encoder="PVCNNEncoder",
-                     encoder_scale=None, use_global_attention=False):
+                     encoder_scale=None, use_global_attention=False, use_local_attention=False):
     """configs/generation/fpc/fpc_1a_latentc3_z4_pc64_180k.py:25-153 as data.  encoder="PVCNN2Encoder": the same
     experiment conditioned by the SET-ABSTRACTION encoder family of the registry (pc_encoders.py:139-197 in its repaired
     form: PointNet++ set abstraction + PVConv + feature propagation, then the same head); encoder_scale =
     (scale_channels, scale_voxel_resolution), default the shipped (0.75, 0.75) / PVCNN2's own width (1, 1).
-    use_global_attention: the encoder's attention block over all points (pc_encoders.py:65-69), off in the shipped config."""
+    use_global_attention: the encoder's attention block over all points (pc_encoders.py:65-69), off in the shipped config.
+    use_local_attention (PVCNN2Encoder only): voxel attention inside the PVConv of the second set-abstraction stage
+    (pc_encoders.py:152-153, ext/pvcnn/utils.py:123); the key is absent from the config when the flag is off."""
     rn = dict(block_channels=(32, 64, 128, 256), input_conditioning_dims=pc_latent, resnet_block_groups=4, dropout=0.1)
+    if use_local_attention and encoder != "PVCNN2Encoder":
+        raise ValueError("use_local_attention is an argument of PVCNN2Encoder only")
     if encoder == "PVCNNEncoder":
         sc, sv = encoder_scale or (0.75, 0.75)
         enc = dict(type="PVCNNEncoder", args=dict(
@@ -23,7 +27,8 @@ def fpc_model_config(n_points=1024, scheduler="ddim", latent=4, pc_latent=64, pc
         sc, sv = encoder_scale or (1, 1)
         enc = dict(type="PVCNN2Encoder", args=dict(
             in_features=3, n_points=n_points, scale_channels=sc, scale_voxel_resolution=sv, out_channels=pc_channels,
-            **(dict(use_global_attention=True) if use_global_attention else {})))
+            **(dict(use_global_attention=True) if use_global_attention else {}),
+            **(dict(use_local_attention=True) if use_local_attention else {})))
     else:
         raise ValueError(f"encoder must be PVCNNEncoder or PVCNN2Encoder, not {encoder!r}")
     vae = dict(model=dict(type="GraspCVAE", args=dict(

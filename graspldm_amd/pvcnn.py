@@ -317,13 +317,15 @@ class SE3d(nn.Module):
 
 
 class PVConv(nn.Module):
-    """pvconv.py:13-84 (inference; `use_attention` voxel attention is off in every shipped config)."""
+    """pvconv.py:13-84 (inference).  use_attention=True: voxel_layers[6] is the PVD Attention block over the r^3 voxels in
+    place of the second Swish (pvconv.py:68-69), SE behind it; shapes by attention.check_voxel_supported."""
 
     def __init__(self, in_channels, out_channels, kernel_size, resolution, use_attention=False, dropout=0.1,
                  with_se=False, with_se_relu=False, normalize=True, eps=0):
         super().__init__()
         if use_attention:
-            raise NotImplementedError("voxel attention is not on the generation hot path")
+            from .attention import check_voxel_supported
+            check_voxel_supported(out_channels, int(resolution))
         self.in_channels, self.out_channels = in_channels, out_channels
         self.kernel_size, self.resolution = kernel_size, resolution
         self.voxelization = Voxelization(resolution, normalize=normalize, eps=eps)
@@ -331,7 +333,12 @@ class PVConv(nn.Module):
                   nn.GroupNorm(num_groups=8, num_channels=out_channels), Swish()]
         layers += [nn.Dropout(dropout)] if dropout is not None else []
         layers += [nn.Conv3d(out_channels, out_channels, kernel_size, stride=1, padding=kernel_size // 2),
-                   nn.GroupNorm(num_groups=8, num_channels=out_channels), Swish()]
+                   nn.GroupNorm(num_groups=8, num_channels=out_channels)]
+        if use_attention:
+            from .attention import Attention
+            layers.append(Attention(out_channels, 8))
+        else:
+            layers.append(Swish())
         if with_se:
             layers.append(SE3d(out_channels, use_relu=with_se_relu))
         self.voxel_layers = nn.Sequential(*layers)
@@ -345,6 +352,8 @@ class PVConv(nn.Module):
         norms = [m for m in mods if isinstance(m, nn.GroupNorm)]
         se = mods[-1] if isinstance(mods[-1], SE3d) else None
         from . import voxel
+        from .attention import Attention
+        attn = next((m for m in mods if isinstance(m, Attention)), None)
         pf = self.point_features(features)
         # hand-written path: implicit-GEMM conv3d on MFMA (shapes with an instantiation) or the direct any-shape kernel
         # (every other width / resolution, partial edge bricks included), GN+Swish, SE gate folded into the devoxelize
@@ -352,6 +361,8 @@ class PVConv(nn.Module):
         from ._cache import cached, params_key
         plan = cached(self, "_voxel_plan", params_key([c.weight for c in convs], vox.device),
                       lambda: voxel.VoxelBranchPlan(convs, vox.device, self.resolution), vox.device)
+        if attn is not None:
+            return voxel.run_attention(plan, convs, norms, attn, se, vox, norm_coords, pf, self.resolution), coords
         return voxel.run(plan, convs, norms, se, vox, norm_coords, pf, self.resolution), coords
 
 
@@ -478,7 +489,8 @@ def create_pointnet2_fp_modules(fp_blocks, in_channels, sa_in_channels, embed_di
                                 with_se=False, normalize=True, eps=0, width_multiplier=1,
                                 voxel_resolution_multiplier=1):
     """utils.py:185-247 -> (fp_layers, out_channels), via fp_plan (attention inside the propagation stages is off in every
-    configuration this package builds; PVConv rejects use_attention=True itself)."""
+    configuration this package builds; `use_attention` is accepted and has no effect, as in the reference, whose
+    `c < len(fp_blocks) - 1` reads the shadowed local list and is never true: utils.py:217-222)."""
     stages, width = fp_plan(fp_blocks, in_channels, sa_in_channels, embed_dim, width_multiplier, voxel_resolution_multiplier)
     layers = []
     for st in stages:

@@ -1,6 +1,7 @@
 """Voxel branch of PVConv on the HIP path: Conv3d(k3) -> GroupNorm(8) -> Swish -> Conv3d(k3) ->
 GroupNorm(8) -> Swish -> SE -> trilinear devoxelize (+ point branch), pvconv.py:47-84, as
-gldm_conv3d_k3 / gldm_groupnorm_swish / gldm_se_gate / gldm_devoxelize_fused launches."""
+gldm_conv3d_k3 / gldm_groupnorm_swish / gldm_se_gate / gldm_devoxelize_fused launches (`run`); with use_attention=True
+the PVD Attention block over the voxels stands in place of the second Swish (pvconv.py:68-69; `run_attention`)."""
 import torch
 
 from . import _lib as L
@@ -86,6 +87,42 @@ class VoxelBranchPlan:
             self.w.append((c.weight.detach().float().contiguous() if self.generic[i] else pack_conv3d(c.weight)).to(device))
 
 
+def _launch_conv(plan, i, conv, x, coef, b, r, cl, st):
+    """Conv i of a voxel stack on the kernel its shape has -> (raw output, per-brick statistics).  coef: the (a, s) of the
+    GroupNorm + Swish this conv applies to x while it stages its bricks, or None; cl: write the output channel-last."""
+    cin, cout = conv.in_channels, conv.out_channels
+    y = torch.empty((b, cout, r, r, r), dtype=torch.float32, device=x.device)
+    nf = L.lib().gldm_conv3d_partial_floats(b, cout, r)
+    partial = torch.empty(int(nf), dtype=torch.float32, device=x.device)
+    staged = plan.split[i] and cin % 16 == 0
+    if staged and (coef is not None or cl):
+        L.call("gldm_conv3d_k3_f16x2_gn", L.ptr(x), L.ptr(coef), L.ptr(plan.w[i]), L.ptr(conv.bias), b, cin, cout, r,
+               L.ptr(y), L.ptr(partial), 1 if cl else 0, st)
+    elif cl:
+        assert coef is None
+        L.call("gldm_conv3d_k3_cl", L.ptr(x), L.ptr(plan.w[i]), L.ptr(conv.bias), b, cin, cout, r, L.ptr(y), L.ptr(partial), st)
+    else:
+        assert coef is None
+        entry = "gldm_conv3d_k3_generic" if plan.generic[i] else ("gldm_conv3d_k3_f16x2" if plan.split[i] else "gldm_conv3d_k3")
+        L.call(entry, L.ptr(x), L.ptr(plan.w[i]), L.ptr(conv.bias), b, cin, cout, r, L.ptr(y), L.ptr(partial), st)
+    return y, partial
+
+
+def _next_conv_stages_norm(plan, convs, i, r):
+    """Conv i + 1 applies conv i's GroupNorm + Swish while it stages its planes (a cin % 16 == 0 split kernel on a large grid).
+    Measured per 256 clouds: at 24^3 the pass costs 0.26 ms and the staged form 0.1 ms; at 12^3 the pass is 0.06 ms and the
+    staged form 0.25 ms -- six channel blocks of exp / rcp in front of short tap loops -- so small grids keep the pass
+    between their convs."""
+    return plan.split[i + 1] and convs[i + 1].in_channels % 16 == 0 and r >= 16
+
+
+def _groupnorm_coef(partial, gn, b, c, r, st):
+    coef = torch.empty((b, c, 2), dtype=torch.float32, device=partial.device)
+    L.call("gldm_groupnorm_coef", L.ptr(partial), L.ptr(gn.weight), L.ptr(gn.bias), b, c, r, gn.num_groups, float(gn.eps),
+           L.ptr(coef), st)
+    return coef
+
+
 def run(plan, convs, norms, se, vox, norm_coords, point_feat, r):
     """vox [B, Cin, r, r, r] -> fused features [B, Cout, N] = gate * devox(voxel stack) + point_feat.
 
@@ -108,36 +145,18 @@ def run(plan, convs, norms, se, vox, norm_coords, point_feat, r):
     with torch.cuda.device(dev):
         for i, (conv, gn) in enumerate(zip(convs, norms)):
             cin, cout = conv.in_channels, conv.out_channels
-            y = torch.empty((b, cout, r, r, r), dtype=torch.float32, device=dev)
-            nf = L.lib().gldm_conv3d_partial_floats(b, cout, r)
-            partial = torch.empty(int(nf), dtype=torch.float32, device=dev)
             last = i == len(convs) - 1
             staged = plan.split[i] and cin % 16 == 0          # the plane-staging kernels: folded input, channel-last output
             mfma32 = not plan.split[i] and not plan.generic[i]   # the f32-MFMA kernels: channel-last output
             # the last conv's readers (squeeze, devoxelize) take a voxel's channels as one run
             cl = last and (staged or mfma32) and cout % 4 == 0 and cout <= 256 and cout // gn.num_groups <= 64
-            if staged and (coef is not None or cl):
-                L.call("gldm_conv3d_k3_f16x2_gn", L.ptr(x), L.ptr(coef), L.ptr(plan.w[i]), L.ptr(conv.bias), b, cin, cout, r,
-                       L.ptr(y), L.ptr(partial), 1 if cl else 0, st)
-            elif cl:
-                assert coef is None
-                L.call("gldm_conv3d_k3_cl", L.ptr(x), L.ptr(plan.w[i]), L.ptr(conv.bias), b, cin, cout, r, L.ptr(y), L.ptr(partial), st)
-            else:
-                assert coef is None
-                entry = "gldm_conv3d_k3_generic" if plan.generic[i] else ("gldm_conv3d_k3_f16x2" if plan.split[i] else "gldm_conv3d_k3")
-                L.call(entry, L.ptr(x), L.ptr(plan.w[i]), L.ptr(conv.bias), b, cin, cout, r, L.ptr(y), L.ptr(partial), st)
+            y, partial = _launch_conv(plan, i, conv, x, coef, b, r, cl, st)
             x_cl = cl
-            # the consumer of this conv's GroupNorm + Swish: the next conv if it stages planes (cin % 16 == 0 split kernel),
+            # the consumer of this conv's GroupNorm + Swish: the next conv if it stages planes (_next_conv_stages_norm),
             # else the SE pass + devoxelize (last conv), else a pass of its own
-            # (measured per 256 clouds: at 24^3 the pass costs 0.26 ms and the staged form 0.1 ms; at 12^3 the pass is
-            # 0.06 ms and the staged form 0.25 ms -- six channel blocks of exp / rcp in front of short tap loops -- so small
-            # grids keep the pass between their convs)
-            foldable = (last or (plan.split[i + 1] and convs[i + 1].in_channels % 16 == 0 and r >= 16)) \
-                and cout // gn.num_groups <= 64
+            foldable = (last or _next_conv_stages_norm(plan, convs, i, r)) and cout // gn.num_groups <= 64
             if foldable:
-                coef = torch.empty((b, cout, 2), dtype=torch.float32, device=dev)
-                L.call("gldm_groupnorm_coef", L.ptr(partial), L.ptr(gn.weight), L.ptr(gn.bias), b, cout, r, gn.num_groups,
-                       float(gn.eps), L.ptr(coef), st)
+                coef = _groupnorm_coef(partial, gn, b, cout, r, st)
             else:
                 coef = None
                 if last and se is not None:
@@ -173,4 +192,53 @@ def run(plan, convs, norms, se, vox, norm_coords, point_feat, r):
                    L.ptr(out), st)
         else:
             L.call("gldm_devoxelize_fused", L.ptr(norm_coords), L.ptr(x), L.ptr(gate), L.ptr(pf), b, c, n, r, L.ptr(out), st)
+    return out
+
+
+def run_attention(plan, convs, norms, attn, se, vox, norm_coords, point_feat, r):
+    """`run` for PVConv(use_attention=True), pvconv.py:57-83 with `Attention` in place of the second Swish (modules.py:34-54):
+    Conv3d -> GroupNorm -> Swish -> Conv3d -> GroupNorm -> Attention -> SE -> devoxelize (+ point branch).
+
+    The first conv and its GroupNorm + Swish run as in `run`.  The second conv writes channel-major; its GroupNorm feeds the
+    block RAW, so gldm_groupnorm_coef + gldm_groupnorm_affine make x [B, C, r^3] (the residual and, with the block's two
+    folds, K and V at once).  Then the folded q' conv, the attention core (attention.attention_core: the fused kernel up to
+    128 channels), the folded out conv, and ONE GroupNorm + Swish launch that adds the residual and leaves the SE squeeze
+    sums (gldm_groupnorm_swish_points_sum); gldm_se_gate and gldm_devoxelize_fused close the stack."""
+    from . import attention as A
+    dev = vox.device
+    b = vox.shape[0]
+    st = L.current_stream(dev)
+    x = vox.contiguous()
+    coef = None
+    with torch.cuda.device(dev):
+        for i, (conv, gn) in enumerate(zip(convs, norms)):
+            cout, last = conv.out_channels, i == len(convs) - 1
+            y, partial = _launch_conv(plan, i, conv, x, coef, b, r, False, st)
+            # the first conv's GroupNorm + Swish: staged by the second conv where `run` stages it, else a pass of its own;
+            # the last conv's GroupNorm has no Swish: coefficients for the affine launch
+            if last or (_next_conv_stages_norm(plan, convs, i, r) and cout // gn.num_groups <= 64):
+                coef = _groupnorm_coef(partial, gn, b, cout, r, st)
+            else:
+                coef = None
+                L.call("gldm_groupnorm_swish", L.ptr(y), L.ptr(partial), L.ptr(gn.weight), L.ptr(gn.bias), b, cout, r,
+                       gn.num_groups, float(gn.eps), None, st)
+            x = y
+        c = x.shape[1]
+        xa = torch.empty((b, c, r ** 3), dtype=torch.float32, device=dev)
+        L.call("gldm_groupnorm_affine", L.ptr(x), L.ptr(coef), b, c, r, L.ptr(xa), st)
+        pq, po = attn._packed(dev)
+        h = A.run_conv(A.attention_core(A.run_conv(xa, pq), xa, xa), po)
+        gate = None
+        if se is not None:
+            feat, chan_sum = A.groupnorm_swish_sum(h, attn.norm, add=xa)
+            gate = torch.empty((b, c), dtype=torch.float32, device=dev)
+            w1, w2 = se.fc[0].weight, se.fc[2].weight
+            L.call("gldm_se_gate", L.ptr(chan_sum), L.ptr(w1), L.ptr(w2), b, c, w1.shape[0], r, 1 if se.use_relu else 0,
+                   L.ptr(gate), st)
+        else:
+            feat = A.groupnorm_swish(h, attn.norm, add=xa)
+        n = norm_coords.shape[2]
+        out = torch.empty((b, c, n), dtype=torch.float32, device=dev)
+        pf = point_feat.contiguous() if point_feat is not None else None
+        L.call("gldm_devoxelize_fused", L.ptr(norm_coords), L.ptr(feat), L.ptr(gate), L.ptr(pf), b, c, n, r, L.ptr(out), st)
     return out

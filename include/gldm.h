@@ -512,7 +512,7 @@ int gldm_conv3d_k3_f16x2_gn(const float *x /*[b,cin,r^3] raw*/, const float *in_
 
 /* ref: pvconv.py:57-66 (nn.GroupNorm(8, c)) as per-(cloud, channel) coefficients: GN(x) = a x + s, a = gamma rstd,
  * s = beta - mean a, statistics from a conv's `partial` (combined in f64 in a fixed order, as gldm_groupnorm_swish).
- * c / groups <= 64. */
+ * c / groups <= 128. */
 int gldm_groupnorm_coef(const float *partial, const float *gamma, const float *beta, int b, int c, int r, int groups,
                         float eps, float *coef /*[b,c,2]*/, gldm_stream_t stream);
 
@@ -599,6 +599,39 @@ int gldm_groupnorm_swish_points(const float *x /*[b,c,n]*/, const float *add /*[
  * (GLDM_ERR_UNSUPPORTED otherwise); x and y 16-byte aligned (GLDM_ERR_INVALID_ARG otherwise). */
 int gldm_pointwise_rows(const float *x /*[b,cin,n]*/, const float *w /*[hout,cin]*/, const float *bias /*[hout] or NULL*/,
                         int b, int cin, int hout, int n, float *y /*[b,hout,n]*/, gldm_stream_t stream);
+
+/* ------------------------------------------------ voxel attention inside PVConv (ABI 14) */
+
+/* ref: grasp_ldm/models/modules/modules.py:39-48 (the PVD `Attention` block between its k = 1 convs) where the tokens are the
+ * r^3 voxels of a PVConv (ext/pvcnn/modules/pvconv.py:68-69): the contract of gldm_point_attention,
+ *   out[b,c,i] = sum_j v[b,c,j] softmax_j( sum_c' q[b,c',i] k[b,c',j] ),   no 1 / sqrt(c) factor,
+ * for many tokens at few channels, in ONE launch that never writes an n x n tensor and takes no workspace: a workgroup
+ * keeps the q of 128 queries in registers, walks the keys in staged tiles of 32 and carries a running maximum and sum per
+ * query (online softmax; one division per row at the end).  q, k, v are [b,c,n] f32 and may alias one another; out may
+ * not alias them.  c % 16 == 0, 32 <= c <= 128; n % 32 == 0, 32 <= n <= 4096; b <= 65535 (GLDM_ERR_UNSUPPORTED otherwise).
+ * Default arithmetic: both products as three v_mfma_f32_16x16x32_f16 over hi / lo f16 pieces with f32 accumulation; q is
+ * split as q / s per 16-query tile, every staged tile of k and of v as x / s (s a power of two from the tile's largest
+ * magnitude, 1 for anything ordinary, folded back on the accumulators), probabilities as 2^14 p.  exact_f32 != 0: the same
+ * stages on v_mfma_f32_16x16x4_f32.  Deterministic (fixed summation order, no atomics, nothing waits on another
+ * workgroup); a cloud's result does not depend on b, on its position in the batch or on the stream.  A null or not
+ * 16-byte aligned pointer, or a non-positive size: GLDM_ERR_INVALID_ARG, nothing launched.  Those two are the only
+ * statuses the entry decides itself; a launch the runtime refuses is GLDM_ERR_LAUNCH, as for every entry point here. */
+int gldm_point_attention_fused(const float *q /*[b,c,n]*/, const float *k /*[b,c,n]*/, const float *v /*[b,c,n]*/,
+                               int b, int c, int n, int exact_f32, float *out /*[b,c,n]*/, gldm_stream_t stream);
+
+/* ref: pvconv.py:64-69 (the second conv's nn.GroupNorm(8, c) where `Attention` follows it instead of Swish): x = a y + s per
+ * (cloud, channel) over a channel-major voxel grid, (a, s) = coef [b,c,2] from gldm_groupnorm_coef; no activation.
+ * r^3 % 4 == 0, r <= 64 (GLDM_ERR_UNSUPPORTED otherwise); y and x 16-byte aligned (GLDM_ERR_INVALID_ARG otherwise); x may
+ * be y. */
+int gldm_groupnorm_affine(const float *y /*[b,c,r^3] raw*/, const float *coef /*[b,c,2]*/, int b, int c, int r,
+                          float *x /*[b,c,r^3]*/, gldm_stream_t stream);
+
+/* ref: modules.py:50-52 followed by se.py:12-25: gldm_groupnorm_swish_points with the SE squeeze on its way:
+ * chan_sum[b,c] = sum over n of the OUTPUT, a wave per channel, lanes in index order (f64), a fixed tree over the lanes.
+ * Same shapes and statuses as gldm_groupnorm_swish_points; chan_sum must not be NULL. */
+int gldm_groupnorm_swish_points_sum(const float *x /*[b,c,n]*/, const float *add /*[b,c,n] or NULL*/, const float *gamma /*[c]*/,
+                                    const float *beta /*[c]*/, int b, int c, int n, int groups, float eps,
+                                    float *out /*[b,c,n]*/, float *chan_sum /*[b,c]*/, gldm_stream_t stream);
 
 /* ------------------------------------------------ grasp success classifier (ABI 13) */
 
