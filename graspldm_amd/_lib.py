@@ -83,6 +83,8 @@ _SIGNATURES = {
     "gldm_sa_mlp_forward": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "gldm_sa_mlp_forward_f16x2": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "gldm_sa_mlp_forward_f16x2_pre": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "gldm_ball_query_multi": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "gldm_group_max_concat": [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp],
 }
 
 

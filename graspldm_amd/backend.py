@@ -8,6 +8,8 @@ inputs are borrowed.  Every launch goes to torch's current HIP stream (the
 reference launches half of its kernels on the default stream: SURVEY.md §5).
 Backward entry points exist by name and raise (inference-only scope).
 """
+import ctypes
+
 import torch
 
 from . import _lib as L
@@ -47,6 +49,38 @@ class _HipBackend:
         with torch.cuda.device(out.device):
             L.call("gldm_ball_query", L.ptr(centers_coords), L.ptr(points_coords), b, n, m, float(radius),
                    int(num_neighbors), L.ptr(out), _stream(out))
+        return out
+
+    # ---- ball_query/ball_query.cpp:6-30 once per radius, as one launch (not a reference name: multi-scale modules)
+    @staticmethod
+    def ball_query_multi(centers_coords, points_coords, radii, num_neighbors):
+        """-> [idx_s [B, M, u_s] int32 per scale], each bit-identical to ball_query(radii[s], num_neighbors[s])."""
+        _f32(centers_coords, "centers_coords")
+        _f32(points_coords, "points_coords")
+        s = len(radii)
+        if s != len(num_neighbors) or not 1 <= s <= 4:
+            raise RuntimeError("ball_query_multi takes one to four (radius, num_neighbors) pairs")
+        b, _, m = centers_coords.shape
+        n = points_coords.shape[2]
+        outs = [torch.empty((b, m, int(u)), dtype=torch.int32, device=centers_coords.device) for u in num_neighbors]
+        with torch.cuda.device(centers_coords.device):
+            L.call("gldm_ball_query_multi", L.ptr(centers_coords), L.ptr(points_coords), b, n, m, s,
+                   (ctypes.c_float * s)(*[float(r) for r in radii]), (ctypes.c_int32 * s)(*[int(u) for u in num_neighbors]),
+                   (ctypes.c_void_p * s)(*[o.data_ptr() for o in outs]), _stream(centers_coords))
+        return outs
+
+    # ---- modules/pointnet.py:104-109: the max over h sub-centres and the concatenation of the scales
+    @staticmethod
+    def group_max_concat(part, h, out, c0):
+        """out[:, c0 : c0 + C, j] = max over part[:, :, j h : (j + 1) h]; part [B, C, M h], out [B, Ctot, M] (in place)."""
+        _f32(part, "part")
+        _f32(out, "out")
+        b, c, mh = part.shape
+        m = out.shape[2]
+        if mh != m * int(h) or out.shape[0] != b:
+            raise RuntimeError("group_max_concat: part must be [B, C, M h] for out [B, Ctot, M]")
+        with torch.cuda.device(out.device):
+            L.call("gldm_group_max_concat", L.ptr(part), b, c, m, int(h), L.ptr(out), int(c0), out.shape[1], _stream(out))
         return out
 
     # ---- grouping/grouping.cpp:6-24

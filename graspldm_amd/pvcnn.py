@@ -1,6 +1,6 @@
 """Point-cloud backbones of the GraspLDM encoder on MI355X: host-side mirror of
 `grasp_ldm/models/modules/ext/pvcnn/**` (functional wrappers, nn.Modules and the
-three backbones PVCNN / PVCNN2 / PointNet2SSG) with the reference's class names,
+backbones PVCNN / PVCNN2 / PointNet2SSG / PointNet2MSG) with the reference's class names,
 constructor arguments and state_dict keys, so reference checkpoints load with
 `strict=True`.
 
@@ -220,10 +220,46 @@ class PointNetSAModule(nn.Module):
         idx = ball_query(centers, coords, grouper.radius, grouper.num_neighbors)
         return plan.run(coords.contiguous(), centers.contiguous(), feats, idx)
 
+    def _multi_scale_path(self):
+        """More than one scale; or ONE scale of more than 64 neighbours that folds onto the 64-column kernels
+        (sa_pack.msg_fold) -- no single-scale kernel takes those, they ran grouped.  One scale of up to 64 neighbours keeps
+        the single-scale dispatch below."""
+        from .sa_pack import msg_fusable
+        if len(self.groupers) > 1:
+            return len(self.groupers) <= 4
+        return self.groupers[0].num_neighbors > 64 and msg_fusable(self.mlps[0], self.groupers[0].num_neighbors)
+
+    def _forward_multi_scale(self, coords, centers, features):
+        """More than one scale, or one scale of more than 64 neighbours (_multi_scale_path), eval mode: ONE ball query over all radii (gldm_ball_query_multi), per scale the fused MLP, and
+        every scale's rows written straight into the module's [B, sum C, M] output (gldm_group_max_concat) -- no grouped
+        [B, 3 + C, M, U] tensor and no torch.cat.  A branch sa_pack.msg_fusable rejects takes the grouped path."""
+        from ._cache import cached, params_key
+        from .sa_pack import SaMlpPlan, msg_fusable
+        coords, centers = coords.contiguous(), centers.contiguous()
+        feats = features.contiguous().float() if features is not None and features.shape[1] > 0 else None
+        out = torch.empty((coords.shape[0], self.out_channels, self.num_centers), dtype=torch.float32, device=coords.device)
+        fused = [msg_fusable(mlp, g.num_neighbors) for g, mlp in zip(self.groupers, self.mlps)]
+        todo = [g for g, ok in zip(self.groupers, fused) if ok]
+        idx = iter(_backend.ball_query_multi(centers, coords, [g.radius for g in todo], [g.num_neighbors for g in todo])
+                   if todo else ())
+        c0 = 0
+        for grouper, mlp, ok in zip(self.groupers, self.mlps, fused):
+            width = mlp.layers[-3].weight.shape[0]
+            if ok:
+                key = params_key(mlp.state_dict(keep_vars=True).values(), coords.device)
+                plan = cached(mlp, "_sa_plan", key, lambda: SaMlpPlan(mlp, coords.device), coords.device)
+                plan.run_msg(coords, centers, feats, next(idx), out, c0)
+            else:
+                out[:, c0:c0 + width] = mlp(grouper(coords, centers, features)).max(dim=-1).values
+            c0 += width
+        return out
+
     def forward(self, inputs):
         from .sa_pack import fusable
         features, coords = inputs
         centers = furthest_point_sample(coords, self.num_centers)
+        if not self.training and all(g.include_coordinates for g in self.groupers) and self._multi_scale_path():
+            return self._forward_multi_scale(coords, centers, features), centers
         outs = []
         for grouper, mlp in zip(self.groupers, self.mlps):
             if grouper.include_coordinates and not self.training and fusable(mlp, grouper.num_neighbors):
@@ -624,4 +660,20 @@ class PointNet2SSG(PointNet2):
     def __init__(self, num_shapes=0, extra_feature_channels=3, width_multiplier=1, voxel_resolution_multiplier=1):
         super().__init__(num_shapes=num_shapes, sa_blocks=self.sa_blocks, fp_blocks=self.fp_blocks,
                          with_one_hot_shape_id=False, extra_feature_channels=extra_feature_channels,
+                         width_multiplier=width_multiplier, voxel_resolution_multiplier=voxel_resolution_multiplier)
+
+
+class PointNet2MSG(PointNet2):
+    """pointnet2.py:126-159, repaired: the reference's constructor passes `num_classes=` on to PointNet2.__init__, which does
+    not take it, so the class cannot be built there.  `num_classes` is accepted and ignored (the classifier head it sized is
+    commented out in the reference); the state_dict keys are those of the reference's PointNet2 built with these tables."""
+    sa_blocks = [(None, (512, [0.1, 0.2, 0.4], [32, 64, 128], [(32, 32, 64), (64, 64, 128), (64, 96, 128)])),
+                 (None, (128, [0.4, 0.8], [64, 128], [(128, 128, 256), (128, 196, 256)])),
+                 (None, (None, None, None, (256, 512, 1024)))]
+    fp_blocks = [((256, 256), None), ((256, 128), None), ((128, 128, 128), None)]
+
+    def __init__(self, num_classes=None, num_shapes=0, extra_feature_channels=3, width_multiplier=1,
+                 voxel_resolution_multiplier=1):
+        super().__init__(num_shapes=num_shapes, sa_blocks=self.sa_blocks, fp_blocks=self.fp_blocks,
+                         with_one_hot_shape_id=True, extra_feature_channels=extra_feature_channels,
                          width_multiplier=width_multiplier, voxel_resolution_multiplier=voxel_resolution_multiplier)

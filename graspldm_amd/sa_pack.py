@@ -32,24 +32,108 @@ def fusable(shared_mlp, num_neighbors):
     return (layers[0].weight.shape[1] + 31) // 32 * 32 <= 256
 
 
+_PLANE_WIDTHS = (32, 64, 128, 256)   # hidden widths launch_sa3 takes (m-tile counts 2 / 4 / 8 / 16)
+_SA_BLOCK_BYTES = 2 * 1024 * 4       # one 32-row block of a 64-column tile's hi + lo planes (csrc/mfma_core.h: PG<4>::kBlockFloats)
+_SA_BLOCK_BYTES_PLANNED = 3072 * 4   # the figure split_plan_ok has always planned with (three planes): never the more permissive
+
+
+def _sa3_shape_ok(kpad0, couts, num_neighbors, block_bytes, kpad0_max=288):
+    """launch_sa3's shape checks (csrc/sa_mlp.hip) for widths as the tables hold them: kpad0 = rows of the first layer's
+    input, couts = every layer's (padded) rows.  LDS: the two plane regions at `block_bytes` per 32-row block, and behind
+    them the eight range words and the staged output rows of a run (64 + cout_last * 8 * 4 bytes), in a CU's 160 KiB."""
+    if int(num_neighbors) not in (16, 32, 64) or not 1 <= len(couts) <= 4:
+        return False
+    kpad = [kpad0] + list(couts[:-1])
+    if any(k <= 0 or k % 32 or not (k // 32 <= 6 or k // 32 in (8, 9)) for k in kpad) or any(c <= 0 or c % 16 for c in couts):
+        return False
+    if any(c not in _PLANE_WIDTHS for c in couts[:-1]) or kpad0 > kpad0_max:
+        return False
+    blocks_a = max([kpad0 // 32] + [couts[l] // 32 for l in range(1, len(couts) - 1, 2)])
+    blocks_b = max([0] + [couts[l] // 32 for l in range(0, len(couts) - 1, 2)])
+    return (blocks_a + blocks_b) * block_bytes + 64 + couts[-1] * _SA_RUN * 4 <= dense.LDS_BYTES
+
+
 def split_plan_ok(cins, couts, num_neighbors):
     """Shapes launch_sa3 takes (csrc/sa_mlp.hip; gldm_sa_mlp_forward_f16x2 and, with the tables of the layers behind a
     hoisted first one, gldm_sa_mlp_forward_f16x2_pre): 64-column tiles on split-f16 planes."""
     from .numerics import split_enabled
-    if not split_enabled() or int(num_neighbors) not in (16, 32, 64) or not 1 <= len(couts) <= 4:
+    if not split_enabled() or not 1 <= len(couts) <= 4:
         return False
     # hidden widths are packed padded to the 32-row plane blocks (zero weight rows, zero bias: ReLU leaves zeros, and the
     # next layer's weights over those rows are zero): a 16-wide hidden layer (half-width PVCNN2) runs as a 32-wide one
     couts = [(c + 31) // 32 * 32 for c in couts[:-1]] + [couts[-1]]
-    kpad = [(cins[0] + 31) // 32 * 32] + list(couts[:-1])
-    if any(k % 32 or not (k // 32 <= 6 or k // 32 in (8, 9)) for k in kpad) or any(c % 16 for c in couts):
+    return _sa3_shape_ok((cins[0] + 31) // 32 * 32, couts, num_neighbors, _SA_BLOCK_BYTES_PLANNED)
+
+
+
+
+def _plane_width(c):
+    """A hidden width as the split tables pack it: the next width the kernels take (96 -> 128, 196 -> 256; zero weight rows
+    and zero bias, ReLU leaves zeros, the next layer's weights over those rows are zero); beyond 256: whole plane blocks."""
+    return next((w for w in _PLANE_WIDTHS if w >= c), (c + 31) // 32 * 32)
+
+
+def _f32_width(c):
+    """The same for the f32 tables: the next width gldm_sa_mlp_forward has an m-tile count for (_OK_MTILES)."""
+    return next((16 * t for t in _OK_MTILES if 16 * t >= c), c)
+
+
+def sa3_takes(kpad0, couts, num_neighbors, pre=False):
+    """What launch_sa3 itself takes, at its own LDS figure (8192 bytes per plane block): kpad0 = rows of the first layer's
+    input, or of the per-point layer's output when `pre`.  split_plan_ok asks the same helper with its larger figure."""
+    return _sa3_shape_ok(kpad0, couts, num_neighbors, _SA_BLOCK_BYTES, 256 if pre else 288)
+
+
+def msg_fold(num_neighbors):
+    """(u the fused kernels run with, h): a neighbourhood of U = 64 h runs as h centres of 64 columns and is folded by
+    gldm_group_max_concat -- exact: every tile's maximum is final, max is associative."""
+    u = int(num_neighbors)
+    return (64, u // 64) if u in (128, 256) else (u, 1)
+
+
+def msg_route(cin, couts, num_neighbors, hoist=True):
+    """Which fused launch one branch of a multi-scale set-abstraction module takes (SaMlpPlan.run_msg), or None (the
+    grouped tensor + GEMMs).  cin: rows of the grouped input (3 + C); couts: the SharedMLP's widths.
+      'pre'      gldm_sa_mlp_forward_f16x2_pre: first layer per point, hidden widths padded to _plane_width
+      'split'    gldm_sa_mlp_forward_f16x2
+      'f32'      gldm_sa_mlp_forward, hidden widths padded to _f32_width
+      'f32_pre'  gldm_sa_mlp_forward with the first layer hoisted (inputs wider than its 256 rows)
+    The split routes are what launch_sa3 takes (sa3_takes: its width sets and its LDS bound, planes + 64 + cout_last * 8 * 4
+    bytes)."""
+    from .numerics import split_enabled
+    u, _ = msg_fold(num_neighbors)
+    couts = [int(c) for c in couts]
+    n = len(couts)
+    if not 1 <= n <= 4 or u < 1 or 64 % u or couts[-1] > 256:   # pooled rows wider than 256: no fused kernel has run them
+        return None
+    if split_enabled():
+        pc = [_plane_width(c) for c in couts[:-1]] + couts[-1:]
+        split_ok = sa3_takes((cin + 31) // 32 * 32, pc, u)
+        if n >= 2 and (hoist or not split_ok) and sa3_takes((couts[0] + 31) // 32 * 32, pc[1:], u, pre=True):
+            return "pre"
+        if split_ok:
+            return "split"
+    fc = [_f32_width(c) for c in couts[:-1]] + couts[-1:]
+    if any(c % 16 or c > 256 or (c // 16) not in _OK_MTILES for c in fc):
+        return None
+    if (cin + 31) // 32 * 32 <= 256:
+        return "f32"
+    if n >= 2 and cin > 3 and (3 + fc[0] + 31) // 32 * 32 <= 256:
+        return "f32_pre"
+    return None
+
+
+def msg_fusable(shared_mlp, num_neighbors):
+    """Next to `fusable` / `split_plan_ok`: the branches of a multi-scale module that run fused (either hoisting choice)."""
+    layers = shared_mlp.layers
+    couts = [layers[i].weight.shape[0] for i in range(0, len(layers), 3)]
+    cin = layers[0].weight.shape[1]
+    if msg_route(cin, couts, num_neighbors) is None:
         return False
-    if any(c not in (32, 64, 128, 256) for c in couts[:-1]):
-        return False
-    blocks_a = max([kpad[0] // 32] + [couts[l] // 32 for l in range(1, len(couts) - 1, 2)])
-    blocks_b = max([0] + [couts[l] // 32 for l in range(0, len(couts) - 1, 2)])
-    # behind the planes: the eight range words and the staged output rows of a run
-    return (blocks_a + blocks_b) * 3072 * 4 + 64 + couts[-1] * _SA_RUN * 4 <= dense.LDS_BYTES
+    # ... and an f32 launch behind it: a folded weight beyond the f16 range sends run_msg there (as SaMlpPlan.run always can)
+    from .numerics import f32_only
+    with f32_only():
+        return msg_route(cin, couts, num_neighbors) is not None
 
 
 class LayerTable(NamedTuple):
@@ -83,15 +167,15 @@ def _table(buf, device, cin_pad, cout, w_off, b_off, gain=None):
 
 
 def pack_split_table(folded, device, behind=None):
-    """Split-f16 fragments [cout x K padded to 32] + biases of the folded (W, b) layers; hidden widths padded to whole
-    plane blocks.  `behind`: a tensor stored after the tables.  -> (LayerTable, offset of `behind`)."""
+    """Split-f16 fragments [cout x K padded to 32] + biases of the folded (W, b) layers; hidden widths padded to the
+    next width the kernels take (_plane_width).  `behind`: a tensor stored after the tables.  -> (LayerTable, offset of `behind`)."""
     buf = _Buf()
     cin_pad, cout, w_off, b_off, gain = [], [], [], [], []
     for i, (w, b) in enumerate(folded):
         # |layer output| <= gain_r max|input| + gain_b: the kernel scales the hidden layers' planes from this bound
         gain += [float(w.double().abs().sum(dim=1).max()), float(b.double().abs().max())]
-        kpad = (w.shape[1] + 31) // 32 * 32
-        rows = w.shape[0] if i == len(folded) - 1 else (w.shape[0] + 31) // 32 * 32
+        kpad = (w.shape[1] + 31) // 32 * 32 if i == 0 else cout[-1]   # later layers: the padded rows of the one in front
+        rows = w.shape[0] if i == len(folded) - 1 else _plane_width(w.shape[0])
         wp = torch.zeros(rows, kpad)
         wp[: w.shape[0], : w.shape[1]] = w.cpu()
         bp = torch.zeros(rows)
@@ -104,6 +188,27 @@ def pack_split_table(folded, device, behind=None):
     return _table(buf, device, cin_pad, cout, w_off, b_off, gain), off
 
 
+def pack_f32_table(folded, device):
+    """f32 A fragments + biases of the folded (W, b) layers (gldm_sa_mlp_forward); hidden widths padded to the next width
+    the kernel has an m-tile count for (_f32_width: zero rows, zero bias)."""
+    buf = _Buf()
+    cin_pad, cout, w_off, b_off = [], [], [], []
+    for i, (w, b) in enumerate(folded):
+        # K in pairs of 16-deep blocks: the kernels' weight-fragment pipeline runs two blocks per trip (an odd count
+        # would fall back to load-wait-compute per block); the padding rows are zero in the weights and the tile
+        kpad = (w.shape[1] + 31) // 32 * 32 if i == 0 else (cout[-1] + 15) // 16 * 16  # later layers: cin = (padded) cout of the previous one
+        rows = w.shape[0] if i == len(folded) - 1 else _f32_width(w.shape[0])
+        wp = torch.zeros(rows, kpad)
+        wp[: w.shape[0], : w.shape[1]] = w.cpu()
+        bp = torch.zeros(rows)
+        bp[: w.shape[0]] = b.cpu()
+        cin_pad.append(kpad)
+        cout.append(rows)
+        w_off.append(buf.add(mfma_a_fragments(wp)))
+        b_off.append(buf.add(bp))
+    return _table(buf, device, cin_pad, cout, w_off, b_off)
+
+
 class SaMlpPlan:
     """Packed weights of one SharedMLP(dim=2) on the device + the layer tables, for one weight version (the owner keys
     the plan; its lazily packed tables are entries of the plan and are decided once).  Where the layer plan fits the
@@ -114,19 +219,7 @@ class SaMlpPlan:
         layers = shared_mlp.layers
         self._folded = [dense.fold_conv_bn(layers[i], layers[i + 1]) for i in range(0, len(layers) - 2, 3)]
         self._device = device
-        buf = _Buf()
-        cin_pad, cout, w_off, b_off = [], [], [], []
-        for i, (w, b) in enumerate(self._folded):
-            # K in pairs of 16-deep blocks: the kernels' weight-fragment pipeline runs two blocks per trip (an odd count
-            # would fall back to load-wait-compute per block); the padding rows are zero in the weights and the tile
-            kpad = (w.shape[1] + 31) // 32 * 32 if i == 0 else (w.shape[1] + 15) // 16 * 16  # later layers: cin = cout of the previous one
-            wp = torch.zeros(w.shape[0], kpad)
-            wp[:, : w.shape[1]] = w.cpu()
-            cin_pad.append(kpad)
-            cout.append(w.shape[0])
-            w_off.append(buf.add(mfma_a_fragments(wp)))
-            b_off.append(buf.add(b.cpu()))
-        self.f32 = _table(buf, device, cin_pad, cout, w_off, b_off)
+        self.f32 = pack_f32_table(self._folded, device)
 
     def _split_plan(self):
         """The split LayerTable of every layer, packed on first use; None: a folded weight beyond the f16 range."""
@@ -191,3 +284,68 @@ class SaMlpPlan:
             L.call(entry, L.ptr(points), L.ptr(centers), L.ptr(features), L.ptr(idx), L.ptr(table.weights), b, c, n, m, u,
                    *table.args(), L.ptr(out), st)
         return out
+
+    def _f32_pre_plan(self):
+        """'f32_pre': y = W1b f + b1 per point (rows padded to _f32_width), then the f32 kernel with y as its features and
+        [W1a | I] as its first layer: W1 [x - c; f] + b1 = W1a (x - c) + y, in exact f32 products."""
+        def pack():
+            w1, b1 = self._folded[0]
+            c1, c1p = w1.shape[0], _f32_width(w1.shape[0])
+            w1b = torch.zeros(c1p, w1.shape[1] - 3)
+            w1b[:c1] = w1[:, 3:].cpu()
+            b1p = torch.zeros(c1p)
+            b1p[:c1] = b1.cpu()
+            first = torch.zeros(c1p, 3 + c1p)
+            first[:c1, :3] = w1[:, :3].cpu()
+            first[:, 3:] = torch.eye(c1p)
+            table = pack_f32_table([(first, torch.zeros(c1p))] + list(self._folded[1:]), self._device)
+            return table, w1b.to(self._device), b1p.to(self._device)
+        return cached(self, "_f32_pre", None, pack, self._device)
+
+    def run_msg(self, points, centers, features, idx, out, c0):
+        """One branch of a multi-scale module: the fused MLP on the route msg_route names, its [B, C, M] rows written into
+        rows c0.. of the module's output `out` [B, sum C, M] by gldm_group_max_concat (no grouped tensor, no torch.cat).
+        U = 64 h: idx [B, M, 64 h] viewed as [B, M h, 64] with every centre repeated h times, folded by the same launch."""
+        from .backend import _backend
+        b, _, n = points.shape
+        m, u_all = idx.shape[1], idx.shape[2]
+        u, h = msg_fold(u_all)
+        if h > 1:
+            idx = idx.view(b, m * h, u)
+            centers = centers.repeat_interleave(h, dim=2)
+        mh = m * h
+        c = 0 if features is None else features.shape[1]
+        couts = [w.shape[0] for w, _ in self._folded]
+        hoist = (c > 0 and mh * u >= 2 * n) or (c == 0 and PRE_WITHOUT_FEATURES)
+        route = msg_route(3 + c, couts, u, hoist)
+        pre = split = None
+        if route == "pre":
+            pre = self._pre_plan()
+        elif route == "split":
+            split = self._split_plan()
+        if pre is None and split is None and route in ("pre", "split"):   # a folded weight beyond the f16 range
+            from .numerics import f32_only
+            with f32_only():
+                route = msg_route(3 + c, couts, u, hoist)
+        if route is None:
+            raise L.GldmError("run_msg: no fused launch takes this branch (msg_route)")
+        # the per-point layer first: its temporaries are gone before the pooled rows are allocated
+        row = None if pre is None else (self._first_layer_per_point(features, pre) if c > 0 else pre.b1)
+        part = torch.empty((b, couts[-1], mh), dtype=torch.float32, device=points.device)
+        st = L.current_stream(points.device)
+        with torch.cuda.device(points.device):
+            if pre is not None:
+                L.call("gldm_sa_mlp_forward_f16x2_pre", L.ptr(points), L.ptr(centers), L.ptr(row), 0 if c > 0 else 1, L.ptr(idx),
+                       L.ptr(pre.table.weights), pre.wa_off, b, n, mh, u, *pre.table.args(), L.ptr(part), st)
+            elif split is not None:
+                L.call("gldm_sa_mlp_forward_f16x2", L.ptr(points), L.ptr(centers), L.ptr(features), L.ptr(idx),
+                       L.ptr(split.weights), b, c, n, mh, u, *split.args(), L.ptr(part), st)
+            elif route == "f32":
+                L.call("gldm_sa_mlp_forward", L.ptr(points), L.ptr(centers), L.ptr(features), L.ptr(idx), L.ptr(self.f32.weights),
+                       b, c, n, mh, u, *self.f32.args(), L.ptr(part), st)
+            else:
+                table, w1b, b1 = self._f32_pre_plan()
+                y = dense._gemm_bias_act(features.contiguous().float(), w1b, b1, False)
+                L.call("gldm_sa_mlp_forward", L.ptr(points), L.ptr(centers), L.ptr(y), L.ptr(idx), L.ptr(table.weights),
+                       b, y.shape[1], n, mh, u, *table.args(), L.ptr(part), st)
+        return _backend.group_max_concat(part, h, out, c0)

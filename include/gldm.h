@@ -133,6 +133,19 @@ int gldm_sa_group(const float *points /*[b,3,n]*/, const float *centers /*[b,3,m
                   int b, int c, int n, int m, float radius, int u,
                   float *out /*[b,3+c,m,u]*/, int32_t *idx_out, gldm_stream_t stream);
 
+/* Multi-scale set abstraction (pointnet.py:49-114 with lists of radii): replaces ball_query.cu:19-59 run once per
+ * scale.  ONE scan of a cloud's points per centre for n_scales radii (1..4); out[s] [b,m,u[s]] is bit-identical to
+ * gldm_ball_query(radius[s], u[s]).  radius, u and out are HOST arrays of n_scales entries (out: device pointers). */
+int gldm_ball_query_multi(const float *centers /*[b,3,m]*/, const float *points /*[b,3,n]*/, int b, int n, int m,
+                          int n_scales, const float *radius, const int32_t *u, int32_t *const *out,
+                          gldm_stream_t stream);
+
+/* Replaces pointnet.py:104-109 (the max over a scale's neighbours where a U = 64 h neighbourhood ran as h centres of
+ * 64, and the torch.cat of the scales): out[b, c0 + r, j] = max over part[b, r, j h .. j h + h - 1], h in {1, 2, 4};
+ * the other rows of out [b,ctot,m] are not touched. */
+int gldm_group_max_concat(const float *part /*[b,c,m*h]*/, int b, int c, int m, int h,
+                          float *out /*[b,ctot,m]*/, int c0, int ctot, gldm_stream_t stream);
+
 
 /* ------------------------------------- 1-D ResNet engine (denoiser, decoder) */
 

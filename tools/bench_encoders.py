@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from graspldm_amd.pvcnn import PVCNN, PVCNN2, PointNet2SSG  # noqa: E402
+from graspldm_amd.pvcnn import PVCNN, PVCNN2, PointNet2MSG, PointNet2SSG, fp_plan, sa_plan  # noqa: E402
 from graspldm_amd.synthetic import load_synthetic_weights  # noqa: E402
 
 
@@ -64,6 +64,38 @@ def benchmark_model(model, batch_sizes, num_points, in_channels, num_iterations,
     return out
 
 
+MSG_SHAPES = 4   # one-hot rows of the PointNet2MSG row
+
+
+def msg_flop_per_cloud(points, extra_feature_channels=3, num_shapes=MSG_SHAPES):
+    """FLOP of one PointNet2MSG forward on the reference's graph (2 per multiply-add of every 1x1 conv, as
+    oracle/count_flops.py counts the other rows), from the class's own tables: every branch's grouped MLP over
+    centres x neighbours, the global module over the last stage's points, the propagation MLPs over the points they
+    interpolate onto.  -> (total, the share of the grouped MLPs' layers behind the first one, which run as split-f16
+    products whatever the first layer's form)."""
+    def mlp(cols, chans):
+        return 2 * cols * sum(a * b for a, b in zip(chans[:-1], chans[1:]))
+    stages, sa_in, width, _ = sa_plan(PointNet2MSG.sa_blocks, extra_feature_channels)
+    total, grouped, n, counts = 0, 0, points, []
+    for st in stages:
+        pool = st["pool"]
+        counts.append(n)
+        cin = pool["in_channels"] + 3
+        if pool["num_centers"] is None:
+            total += mlp(n, [cin] + list(pool["out_channels"]))
+            n = 1
+        else:
+            for u, widths in zip(pool["num_neighbors"], pool["out_channels"]):
+                total += mlp(pool["num_centers"] * u, [cin] + list(widths))
+                grouped += mlp(pool["num_centers"] * u, list(widths))   # behind the first layer: always split-f16 products
+            n = pool["num_centers"]
+    sa_in = [sa_in[0] + num_shapes] + sa_in[1:]
+    fps, _ = fp_plan(PointNet2MSG.fp_blocks, width, sa_in)
+    for st, cols in zip(fps, reversed(counts)):
+        total += mlp(cols, [st["fp"]["in_channels"]] + list(st["fp"]["out_channels"]))
+    return total, grouped
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch-sizes", type=int, nargs="+", default=[1, 4, 16, 64, 256])
@@ -72,6 +104,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--shipped", action="store_true", help="also time PVCNNEncoder of the shipped fpc config")
     ap.add_argument("--full-pvcnn2", action="store_true", help="also time PVCNN2 at width / resolution multiplier 1")
+    ap.add_argument("--msg", action="store_true", help="also time PointNet2MSG (3 extra channels + 4 one-hot rows: 10 input rows)")
     ap.add_argument("--only", type=str, default=None, help="run only this model (kernel traces)")
     ap.add_argument("--out", type=str, default=None)
     args = ap.parse_args()
@@ -97,10 +130,16 @@ def main():
                                                        num_blocks=(1, 1, 1, 1), out_channels=3))
     if args.full_pvcnn2:
         models["PVCNN2(full)"] = PVCNN2(in_channels=3, extra_feature_channels=0)
+    in_channels = {}
+    if args.msg:
+        models["PointNet2MSG"] = PointNet2MSG(num_shapes=MSG_SHAPES, extra_feature_channels=3)
+        in_channels["PointNet2MSG"] = 3 + 3 + MSG_SHAPES
     if args.only:
         models = {k: v for k, v in models.items() if k == args.only}
     with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "encoder_flops.json")) as f:
         flops = {k: v["flop_per_cloud"] for k, v in json.load(f)["models"].items()}
+    if args.msg:
+        flops["PointNet2MSG"], msg_split = msg_flop_per_cloud(args.points)   # counted here from the tables, not by the flop counter
     PEAK = 157.3                      # f32 MFMA, dense
     PEAK_SPLIT = 2500.0 / 3           # f32 products as three f16 partial products on the f16 matrix pipe
     # Executed FLOP per cloud by the pipe they run on, where part of a model runs as split-f16 products: the shipped
@@ -115,6 +154,7 @@ def main():
     pv2_split = sa(1024, 32, (19, 16, 32)) + sa(256, 32, (35, 32, 64)) + sa(64, 32, (67, 64, 128))
     split_exec = {"PVCNNEncoder(fpc)": (2 * 1024 * (96 * 768 + 768 * 1536) + 2 * 27 * ((3 * 48 + 48 * 48) * 24 ** 3 + 48 * 96 * 12 ** 3 + 96 * 96 * 12 ** 3),
                                         8.115050112e9 - 2 * 768 * 1536 * 1024 - 2 * 3 * 768 * 1024 + 2 * 3 * 1536 * 1024),
+                  **({"PointNet2MSG": (msg_split, flops["PointNet2MSG"])} if args.msg else {}),
                   "PointNet2": (ssg_split, flops.get("PointNet2", 0)), "PVCNN2": (pv2_split, flops.get("PVCNN2", 0))}
     # Models without a hand-written entry above: the split-f16 share of one forward is COUNTED from the launches themselves
     # (a shim around _lib.call adds up 2 cin cout n / 2 * 27 cin cout r^3 / ... of every `*_f16x2*` entry point of ONE cloud).
@@ -147,7 +187,7 @@ def main():
         if name in ("PVCNN", "PVCNN2", "PVCNN2(full)") and name in flops:   # + the set-abstraction share entered by hand above
             base = split_exec.get(name, (0, flops[name]))
             split_exec[name] = (base[0] + split_flop_of_forward(m, args.points), base[1])
-        results[name] = benchmark_model(m, args.batch_sizes, args.points, 3, args.iterations, args.warmup)
+        results[name] = benchmark_model(m, args.batch_sizes, args.points, in_channels.get(name, 3), args.iterations, args.warmup)
         for b, r in results[name].items():
             fl = flops.get(name) if args.points == 1024 else None
             r["reference_gflop_per_cloud"] = fl / 1e9 if fl else None
