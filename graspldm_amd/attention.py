@@ -8,7 +8,7 @@ Two folds, exact algebra (only rounding changes), done in f64 on the host once p
   * rows of P sum to 1, so  Wo (v P^T) + bo = (Wo Wv)(x P^T) + (Wo bv + bo): the v projection disappears (V = x).
 The block is then two weight GEMMs (the package's k = 1 launches), the attention core reading ONE tensor as K and V
 (gldm_point_attention, csrc/point_attention.hip) and one GroupNorm + Swish launch that adds the residual on its way
-(gldm_groupnorm_swish_points).  No CPU path.
+(gldm_groupnorm_swish_points, csrc/voxel_norm.hip).  No CPU path.
 
 Voxel attention inside PVConv (pvconv.py:68-69: the block in place of the second Swish, tokens = the r^3 voxels) runs the
 same algebra from voxel.run: `check_voxel_supported` is the one gate of its shapes, `attention_core` its dispatch between

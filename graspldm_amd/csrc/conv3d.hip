@@ -1,33 +1,23 @@
-// voxel_conv.hip -- the voxel branch of PVConv (ext/pvcnn/modules/pvconv.py:47-84) on gfx950:
-//   Conv3d(k=3, p=1)  as an implicit GEMM on v_mfma_f32_16x16x4_f32   (gldm_conv3d_k3)
-//   GroupNorm(8) + Swish (+ per-channel sums for the SE gate)          (gldm_groupnorm_swish)
-//   SE gate (se.py:12-25)                                              (gldm_se_gate)
-//   trilinear devoxelize x gate + point-branch features                (gldm_devoxelize_fused)
+// conv3d.hip -- the Conv3d(k = 3, p = 1) of PVConv's voxel branch (ext/pvcnn/modules/pvconv.py:47-84) on gfx950:
+//   conv3d_k3_kernel            implicit GEMM on v_mfma_f32_16x16x4_f32                     (gldm_conv3d_k3[_cl])
+//   conv3d_k3_pl_kernel         the same conv on split-f16 operands, brick pre-split in LDS  (gldm_conv3d_k3_f16x2[_gn])
+//   conv3d_k3_fewch_sp_kernel   split-f16, a few input channels (3 -> 48 at 24^3)            (gldm_conv3d_k3_f16x2)
+//   conv3d_k3_generic_kernel    any shape, direct form on the VALU                           (gldm_conv3d_k3_generic)
+// What follows the convs (GroupNorm, SE gate, devoxelize) is voxel_norm.hip.
 //
-// conv3d mapping: a workgroup (4 waves) owns a 4 x 4 x r brick of output voxels (16 r outputs =
+// Mapping of the f32 kernel: a workgroup (4 waves) owns a 4 x 4 x r brick of output voxels (16 r outputs =
 // r n-tiles of 16) for ALL output channels.  Per 16-input-channel block the input brick with
 // its one-voxel halo (6 x 6 x (r+2), zero padded at the grid border) is staged in LDS once and
 // serves all 27 taps: a tap is a constant LDS offset, so the k-loop is LDS reads + MFMA only.
 // Weights (fragment order, k = tap * Cin_pad + ci) stream from L2 one tap ahead.  The LDS row
 // stride is = 16 (mod 32) dwords so the 4-row x 16-voxel B-fragment reads are conflict free.
 // Two workgroups fit per CU (62 KiB LDS each): one stages while the other computes.
-// The conv epilogue also emits per-brick per-channel (sum, sum of squares) so GroupNorm needs
+// Every conv's epilogue also emits per-brick per-channel (sum, sum of squares) (voxel_geom.h) so GroupNorm needs
 // no extra pass over the tensor for its statistics (combined in f64, fixed order).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-
-#include "gldm.h"
-#include "wstream.h"
-#include "devstate.h"
-
-#define GLDM_API extern "C" __attribute__((visibility("default")))
+#include "mfma_core.h"
+#include "voxel_geom.h"
 
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-typedef __attribute__((address_space(3))) float lds_f;
 
 #ifdef GLDM_DEBUG_KNOBS
 __device__ long long g_c3_stamp[32];
@@ -37,20 +27,23 @@ __device__ long long g_c3_stamp[32];
 #define GLDM_C3_STAMP(i) do {} while (0)
 #endif
 
+// Not mfma_core.h's dpp_mov: that one is __builtin_amdgcn_mov_dpp, this one update_dpp(0, ...), which has the compiler clear
+// the destination with a v_mov_b32 in front of each.  Swapping it in changes the code of every conv kernel (fewer
+// v_mov_b32, more s_nop around the epilogue's DPP adds); whether that is faster has not been measured, so the form the
+// convs were tuned with stays.
 template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float x) {
+__device__ __forceinline__ float c3_dpp_mov(float x) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, false));
 }
 __device__ __forceinline__ float row16_sum(float x) {  // every lane of a 16-lane DPP row ends with the row's sum
-  x += dpp_mov<0xB1>(x);   // quad_perm [1,0,3,2]
-  x += dpp_mov<0x4E>(x);   // quad_perm [2,3,0,1]
-  x += dpp_mov<0x141>(x);  // row_half_mirror
-  x += dpp_mov<0x140>(x);  // row_mirror
+  x += c3_dpp_mov<0xB1>(x);   // quad_perm [1,0,3,2]
+  x += c3_dpp_mov<0x4E>(x);   // quad_perm [2,3,0,1]
+  x += c3_dpp_mov<0x141>(x);  // row_half_mirror
+  x += c3_dpp_mov<0x140>(x);  // row_mirror
   return x;
 }
 
 constexpr int kConvThreads = 256;
-constexpr int kBrick = 4;  // brick is kBrick x kBrick x r output voxels
 
 // z extent of a brick row in LDS: r + 2, or, where the brick is staged four z at a time, r + 8: float4 slots aligned with
 // the grid's own z (slot k = z 4 k - 4 .. 4 k - 1), so that every load is a 16-byte aligned dwordx4 inside the grid and
@@ -319,53 +312,20 @@ __global__ __launch_bounds__(kConvThreads, 2) void conv3d_k3_kernel(const float 
 }
 
 // ---- the same conv on split-f16 operands (the shipped encoder's two shapes: 48 ch @ 24^3 and 96 ch @ 12^3) ------------
-// v_mfma_f32_16x16x32_bf16 with every f32 operand written as hi + mid + lo (three bf16 numbers, exact) and the six
-// partial products of weight >= 2^-16 accumulated in f32: the error of an f32 rounding per product at 6/16 of the
-// f32-MFMA time (see csrc/mfma_core.h, "split-f16 GEMM core").  K is walked as (16-channel block, PAIR of taps):
+// v_mfma_f32_16x16x32_f16 with every f32 operand written as hi + lo (two f16 numbers, x = hi + lo up to 2^-22 |x|) and
+// the three partial products a_hi b_lo + a_lo b_hi + a_hi b_hi accumulated in f32 (mfma_split): 3/16 of the
+// f32-MFMA time (csrc/mfma_core.h, "split-f16 GEMM core": the measured accuracy is recorded there).  K is walked as (16-channel block, PAIR of taps):
 // lane group g of a fragment = (tap 2 p + (g >> 1), channels 8 (g & 1) .. + 7); 27 taps = 13 pairs + one half-empty
 // (zero weights).  Work is walked in groups of 3 m-tiles x 3 n-tiles so that the A sets (double buffered), the B planes
 // and the accumulators fit 256 registers.  Weights: graspldm_amd/voxel.py: pack_conv3d_f16x2.
 // (First form, measured and replaced: the brick kept f32 in LDS, every lane splitting its 8 channels of a voxel again
 // for each (tap pair, n-tile): 2.4 / 0.9 ms per launch at 256 clouds against 2.1 / 0.8 with the pre-split planes below,
 // 3.55 / 1.25 on the f32 pipe.)
-typedef __attribute__((ext_vector_type(8))) _Float16 c3_f16x8;
-typedef __attribute__((ext_vector_type(2))) _Float16 c3_f16x2;
-typedef __attribute__((ext_vector_type(2))) float c3_f32x2;
-typedef __attribute__((ext_vector_type(4))) unsigned c3_u32x4;
-constexpr int kC3Split = 2;   // planes per operand: hi | lo (f16)
-
-// x[0..7] -> the hi and lo planes of a fragment: x = hi + lo up to 2^-22 |x| (the matrix pipe keeps f16 subnormals)
-__device__ __forceinline__ void c3_split(const float (&x)[8], c3_u32x4 (&pl)[kC3Split]) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float a = x[2 * q], b = x[2 * q + 1];
-    const c3_f16x2 h = __builtin_convertvector(c3_f32x2{a, b}, c3_f16x2);
-    const float ra = __builtin_fmaf((float)h[0], -1.0f, a), rb = __builtin_fmaf((float)h[1], -1.0f, b);
-    pl[0][q] = __builtin_bit_cast(unsigned, h);
-    pl[1][q] = __builtin_bit_cast(unsigned, __builtin_convertvector(c3_f32x2{ra, rb}, c3_f16x2));
-  }
-}
-__device__ __forceinline__ f32x4 c3_mfma(const c3_u32x4 &a, const c3_u32x4 &b, const f32x4 &c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(c3_f16x8, a), __builtin_bit_cast(c3_f16x8, b), c, 0, 0, 0);
-}
-// acc += A B, both operands split: the three partial products, small terms first
-__device__ __forceinline__ f32x4 c3_mfma3(const c3_u32x4 (&a)[kC3Split], const c3_u32x4 (&b)[kC3Split], f32x4 acc) {
-  acc = c3_mfma(a[0], b[1], acc);
-  acc = c3_mfma(a[1], b[0], acc);
-  return c3_mfma(a[0], b[0], acc);
-}
 
 constexpr int kPairs = 14;  // tap pairs per 16-channel block (the last one holds tap 26 and zeros)
 
-// Range scale of a staged brick (see csrc/mfma_core.h, "range scale of split operands"): f16 has 5 exponent bits, the
-// grid's magnitude is the data's (voxel averages of raw features).  s = 1 while 2^-8 <= m < 2^14: every bit as without it.
-__device__ __forceinline__ float c3_range_pow2(float m) {
-  int e = (int)((__float_as_uint(m) >> 23) & 0xffu) - 127;
-  if ((e >= -8 && e < 14) || e < -100 || e > 100) return 1.0f;
-  e = e < -40 ? -40 : e;
-  return __uint_as_float((unsigned)(e - 13 + 127) << 23);   // m / s in [2^13, 2^14)
-}
-__device__ __forceinline__ float c3_pow2_inv(float s) { return __uint_as_float((254u << 23) - __float_as_uint(s)); }
+// Not mfma_core.h's wave_max: this one walks the offsets 32 .. 1, the shared one 1 .. 32 -- the same value, but the
+// shared one reorders instructions in the twelve kernels that range a brick, and their code is to stay as measured.
 __device__ __forceinline__ float c3_wave_max(float x) {   // x >= 0: every lane ends with the wave's maximum
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) x = fmaxf(x, __shfl_xor(x, off, 64));
@@ -375,15 +335,17 @@ __device__ __forceinline__ float c3_wave_max(float x) {   // x >= 0: every lane 
 // ---- split-f16 conv with the brick PRE-SPLIT in LDS --------------------------------------------------------------------
 // Splitting a lane's 8 channels of a voxel for every (tap pair, n-tile) that touches it means ~27 splits per element
 // and wave, 36 VALU instructions per 18-36 MFMAs, with the two waves of a SIMD doing it in lock step.  Here the
-// staging threads split each brick element ONCE and keep the three bf16 planes in LDS, channel-minor:
-//   [plane hi|mid|lo][channel half][voxel of the 6 x 6 x (r + 2) haloed brick][8 channels]   (16 B per voxel, half and plane)
+// staging threads split each brick element ONCE and keep the two f16 planes in LDS, channel-minor:
+//   [plane hi|lo][channel half][voxel of the 6 x 6 x (r + 2) haloed brick][8 channels]   (16 B per voxel, half and plane)
 // so a B fragment plane is ONE ds_read_b128 per lane (voxel of its column + the tap of its lane group, channel half)
-// and the tap loop is LDS reads + buffer loads + MFMA.  96 B per voxel instead of 64: the 24^3 brick takes 90 KiB, one
-// workgroup of 8 waves per CU (3 n-tiles each); the 12^3 brick 48 KiB, 4 waves, three workgroups per CU.
-// Staging: an item = (voxel, 8-channel half): 8 dword loads one channel apart (coalesced along z), 36 VALU, three
-// ds_write_b128; the next block's raw values are requested before the tap loop and split / stored after it.
-// R: grid resolution; ZB: z extent of the brick (R, or a divisor of it: the 24^3 grid runs as two 4 x 4 x 12 half bricks per
-// (x, y) -- 48 KiB of planes instead of 90, three workgroups of 4 waves per CU instead of one of 8, so that one brick's
+// and the tap loop is LDS reads + buffer loads + MFMA.  64 B per voxel and 16-channel block, what the f32 brick takes: the
+// 24^3 brick is 59 KiB a plane set and keeps two sets (kDB below), one workgroup of 8 waves per CU (3 n-tiles each); the
+// 12^3 brick 32 KiB, 4 waves.
+// Staging: an item = (voxel, 8-channel half): 8 dword loads one channel apart (coalesced along z), the split
+// (split_planes8), two ds_write_b128; the next block's raw values are requested before the tap loop and split / stored
+// after it.
+// R: grid resolution; ZB: z extent of the brick (R, or a divisor of it: the 24^3 grid can run as two 4 x 4 x 12 half bricks
+// per (x, y) -- 32 KiB of planes, several workgroups of 4 waves per CU instead of one of 8, so that one brick's
 // staging, barriers and epilogue run under another's MFMAs, like the 12^3 conv always did; the two halves of a brick add
 // their GroupNorm partials into one zeroed slot with atomics: two addends, so the sum does not depend on their order).
 // ACT: the input is the RAW output of the previous conv and GroupNorm + Swish are applied while the brick is staged:
@@ -419,7 +381,7 @@ __global__ __launch_bounds__(64 * WAVES, (ZB * 16 / WAVES / 16 >= 6) ? 1 : 2) vo
   // stores, then a second barrier); one barrier per block is left.
   constexpr bool kDB = R == 24 && ZB == 24;
   // Range scale (raw input only: an activated one is bounded by the norm's affine).  Every 16-channel block is split as
-  // x / s_run, s_run the largest power-of-two scale any block so far has asked for (c3_range_pow2 of the block's largest
+  // x / s_run, s_run the largest power-of-two scale any block so far has asked for (range_pow2 of the block's largest
   // staged magnitude: the waves publish theirs in front of the block's first barrier); when it grows the accumulators --
   // bias included -- are rescaled, and the epilogue multiplies them back.  Ordinary data: s_run = 1 throughout.
   constexpr bool kRanged = !ACT;
@@ -436,9 +398,8 @@ __global__ __launch_bounds__(64 * WAVES, (ZB * 16 / WAVES / 16 >= 6) ? 1 : 2) vo
   x += (size_t)b * cin * r3;
   y += (size_t)b * cout * r3;
   const WStream wv(wp3, lane);
-  typedef __attribute__((address_space(3))) c3_u32x4 lds_c4;
-  constexpr int kSet = kC3Split * 2 * hs;   // 16-byte units of one plane set
-  lds_c4 *pl0 = (lds_c4 *)lds;   // 16-byte units: plane * 2 hs + half * hs + voxel.  A ds_read_b128 is served in 16-lane groups
+  constexpr int kSet = kSplit * 2 * hs;   // 16-byte units of one plane set
+  lds_u4 *pl0 = (lds_u4 *)lds;   // 16-byte units: plane * 2 hs + half * hs + voxel.  A ds_read_b128 is served in 16-lane groups
                                 // that mix columns 0-3, 12-15 of one lane row with columns 4-11 of the next (the other channel
                                 // half): with hs a multiple of 16 units the two sets fall on disjoint banks
 
@@ -475,16 +436,16 @@ __global__ __launch_bounds__(64 * WAVES, (ZB * 16 / WAVES / 16 >= 6) ? 1 : 2) vo
         s_glb[q] = (gx * r + gy) * r + gz + 8 * h * r3;
     }
   }
-  // halo voxels outside the grid stay zero for the whole kernel: written once, all three planes
+  // halo voxels outside the grid stay zero for the whole kernel: written once, both planes
   {
-    const c3_u32x4 z4 = c3_u32x4{0u, 0u, 0u, 0u};
+    const u32x4 z4 = u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
     for (int q = 0; q < kRounds; ++q)
       if (s_lds[q] >= 0 && s_glb[q] < 0) {
 #pragma unroll
-        for (int p3 = 0; p3 < kC3Split; ++p3) {
-          pl0[p3 * 2 * hs + s_lds[q]] = z4;
-          if constexpr (kDB) pl0[kSet + p3 * 2 * hs + s_lds[q]] = z4;
+        for (int k = 0; k < kSplit; ++k) {
+          pl0[k * 2 * hs + s_lds[q]] = z4;
+          if constexpr (kDB) pl0[kSet + k * 2 * hs + s_lds[q]] = z4;
         }
       }
   }
@@ -507,7 +468,7 @@ __global__ __launch_bounds__(64 * WAVES, (ZB * 16 / WAVES / 16 >= 6) ? 1 : 2) vo
   unsigned s_run_u = 0x3f800000u;   // s_run's bits, kept on the scalar side
   float *rng = s_coef;   // [WAVES] (raw input: no coefficients there; the launcher adds the room)
   auto stage_store = [&](int cb) {
-    lds_c4 *pl = pl0 + (kDB ? (cb & 1) * kSet : 0);
+    lds_u4 *pl = pl0 + (kDB ? (cb & 1) * kSet : 0);
 #pragma unroll
     for (int q = 0; q < kRounds; ++q)
       if (s_glb[q] >= 0) {
@@ -527,10 +488,10 @@ __global__ __launch_bounds__(64 * WAVES, (ZB * 16 / WAVES / 16 >= 6) ? 1 : 2) vo
             stg[q][2 * j2 + 1] = t1 * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896340736f * t1));
           }
         }
-        c3_u32x4 p3[kC3Split];
-        c3_split(stg[q], p3);
+        u32x4 planes[kSplit];
+        split_planes8(stg[q], planes);
 #pragma unroll
-        for (int k = 0; k < kC3Split; ++k) pl[k * 2 * hs + s_lds[q]] = p3[k];
+        for (int k = 0; k < kSplit; ++k) pl[k * 2 * hs + s_lds[q]] = planes[k];
       }
   };
   GLDM_C3_STAMP(1);
@@ -553,10 +514,10 @@ __global__ __launch_bounds__(64 * WAVES, (ZB * 16 / WAVES / 16 >= 6) ? 1 : 2) vo
       float mx = 0.f;
 #pragma unroll
       for (int w8 = 0; w8 < WAVES; ++w8) mx = fmaxf(mx, rng[w8]);
-      const unsigned need = __builtin_amdgcn_readfirstlane(__float_as_uint(c3_range_pow2(mx)));
+      const unsigned need = __builtin_amdgcn_readfirstlane(__float_as_uint(range_pow2(mx)));
       const unsigned s_new = (cb == 0 || need > s_run_u) ? need : s_run_u;   // positive floats order like their bits
       if (s_new != s_run_u) {   // wave uniform, never taken on ordinary data
-        const float f = __uint_as_float(s_run_u) * c3_pow2_inv(__uint_as_float(s_new));
+        const float f = __uint_as_float(s_run_u) * pow2_inv(__uint_as_float(s_new));
 #pragma unroll
         for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
@@ -571,22 +532,22 @@ __global__ __launch_bounds__(64 * WAVES, (ZB * 16 / WAVES / 16 >= 6) ? 1 : 2) vo
     if (cb < 3) GLDM_C3_STAMP(4 + 4 * cb);
     __syncthreads();   // two sets: also "everyone is through block cb - 1's taps", so block cb + 1 may overwrite its set
     if (cb < 3) GLDM_C3_STAMP(5 + 4 * cb);
-    const lds_c4 *pl = pl0 + (kDB ? (cb & 1) * kSet : 0);
-    c3_u32x4 a[2][GM][kC3Split];
+    const lds_u4 *pl = pl0 + (kDB ? (cb & 1) * kSet : 0);
+    u32x4 a[2][GM][kSplit];
     auto load_a = [&](int buf, int step) {   // step = pair * MG + mg
       const int p = step / MG, mg = step - p * MG;
 #pragma unroll
       for (int mi = 0; mi < GM; ++mi)
 #pragma unroll
-        for (int k = 0; k < kC3Split; ++k)
-          a[buf][mi][k] = wv.raw_at((((GM * mg + mi) * kblocks + cb * kPairs + p) * kC3Split) * 1024, k * 1024);
+        for (int k = 0; k < kSplit; ++k)
+          a[buf][mi][k] = wv.raw_at((((GM * mg + mi) * kblocks + cb * kPairs + p) * kSplit) * 1024, k * 1024);
     };
     load_a(0, 0);
     __builtin_amdgcn_s_setprio(0);
     constexpr int kSteps = kPairs * MG;
     constexpr int kUnits = kPairs * NG;   // (pair, n-group) units: the B planes of unit u + 1 are requested during unit u
     constexpr bool kBPre = NG > 1;   // a second B set costs 36 registers: only where a wave has two n-groups
-    c3_u32x4 bs[kBPre ? 2 : 1][GN][kC3Split];
+    u32x4 bs[kBPre ? 2 : 1][GN][kSplit];
     auto load_b = [&](int buf, int unit) {
       const int p = unit / NG, ng = unit - p * NG;
       const int ta = 2 * p, tb = 2 * p + 1 < 27 ? 2 * p + 1 : 26;
@@ -595,7 +556,7 @@ __global__ __launch_bounds__(64 * WAVES, (ZB * 16 / WAVES / 16 >= 6) ? 1 : 2) vo
 #pragma unroll
       for (int q = 0; q < GN; ++q)
 #pragma unroll
-        for (int k = 0; k < kC3Split; ++k) bs[buf][q][k] = pl[k * 2 * hs + vb[GN * ng + q] + toff];
+        for (int k = 0; k < kSplit; ++k) bs[buf][q][k] = pl[k * 2 * hs + vb[GN * ng + q] + toff];
     };
     if (kBPre) load_b(0, 0);
     for (int p0 = 0; p0 < kPairs; p0 += 2) {
@@ -619,7 +580,7 @@ __global__ __launch_bounds__(64 * WAVES, (ZB * 16 / WAVES / 16 >= 6) ? 1 : 2) vo
             for (int mi = 0; mi < GM; ++mi)
 #pragma unroll
               for (int q = 0; q < GN; ++q)
-                acc[GM * mg + mi][GN * ng + q] = c3_mfma3(a[cur][mi], bs[bcur][q], acc[GM * mg + mi][GN * ng + q]);
+                acc[GM * mg + mi][GN * ng + q] = mfma_split(a[cur][mi], bs[bcur][q], acc[GM * mg + mi][GN * ng + q]);
             __builtin_amdgcn_sched_barrier(0);
           }
         }
@@ -713,10 +674,10 @@ __global__ __launch_bounds__(64 * WAVES, (ZB * 16 / WAVES / 16 >= 6) ? 1 : 2) vo
 // With k = tap * 16 + ci (conv3d_k3_kernel, JN = 1) a 3-channel input pays 27 k-steps of 4 on the f32 pipe for 81 real
 // products per output: 0.49 ms per 256 clouds at 0.55 matrix-pipe occupancy, for a tensor whose store takes 0.1 ms.  Here
 // K is packed tap-major, channel-minor without padding between taps: k = tap * CIN + ci < 27 CIN, rounded up ONCE to a
-// multiple of 32 (CIN = 3: 81 -> 96 = three k-blocks of v_mfma_f32_16x16x32_bf16), six bf16 partial products per f32
+// multiple of 32 (CIN = 3: 81 -> 96 = three k-blocks of v_mfma_f32_16x16x32_f16), three f16 partial products per f32
 // product as everywhere else.  Lane (g, col) of a B fragment gathers its 8 consecutive k = (tap, ci) pairs of its voxel
 // from the f32 brick in LDS (8 ds_read_b32 at per-lane offsets, one n-tile ahead of their use) and splits them; the A
-// planes of a k-block (MT m-tiles x 3 planes) are read once per workgroup.  A workgroup of 8 waves owns a 4 x 4 x R
+// planes of a k-block (MT m-tiles x 2 planes) are read once per wave.  A workgroup of 8 waves owns a 4 x 4 x R
 // brick, R / 8 n-tiles per wave, 117 registers: two workgroups per CU; the haloed input brick is CIN x 6 x 6 x (R + 2)
 // floats (11 KiB at R = 24).  0.32 ms.  (Measured and dropped: persistent workgroups with the weight planes in LDS and the
 // next brick's input requested under the current k-loop -- 216 registers, one workgroup per CU: 0.41 ms; the same with
@@ -739,7 +700,7 @@ __global__ __launch_bounds__(64 * WAVES, 4) void conv3d_k3_fewch_sp_kernel(const
   const int b = blockIdx.y;
   x += (size_t)b * CIN * r3;
   y += (size_t)b * cout * r3;
-  // ---- the haloed brick, f32, zero outside the grid; its largest magnitude for the range scale (c3_range_pow2: the
+  // ---- the haloed brick, f32, zero outside the grid; its largest magnitude for the range scale (range_pow2: the
   // grid holds voxel averages of raw coordinates / features)
   float mx = 0.f;
   for (int i = tid; i < CIN * nvox; i += kThreads) {
@@ -771,9 +732,9 @@ __global__ __launch_bounds__(64 * WAVES, 4) void conv3d_k3_fewch_sp_kernel(const
     float m8 = 0.f;
 #pragma unroll
     for (int w8 = 0; w8 < WAVES; ++w8) m8 = fmaxf(m8, rng[w8]);
-    s_in = c3_range_pow2(__uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(m8))));
+    s_in = range_pow2(__uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(m8))));
   }
-  const float inv_in = c3_pow2_inv(s_in);
+  const float inv_in = pow2_inv(s_in);
   f32x4 acc[MT][NTW];
 #pragma unroll
   for (int mi = 0; mi < MT; ++mi) {
@@ -783,11 +744,11 @@ __global__ __launch_bounds__(64 * WAVES, 4) void conv3d_k3_fewch_sp_kernel(const
   }
 #pragma unroll
   for (int kb = 0; kb < KB; ++kb) {
-    c3_u32x4 a[MT][kC3Split];
+    u32x4 a[MT][kSplit];
 #pragma unroll
     for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
-      for (int pl = 0; pl < kC3Split; ++pl) a[mi][pl] = wv.raw_at(((mi * KB + kb) * kC3Split) * 1024, pl * 1024);
+      for (int pl = 0; pl < kSplit; ++pl) a[mi][pl] = wv.raw_at(((mi * KB + kb) * kSplit) * 1024, pl * 1024);
     int off[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -806,12 +767,12 @@ __global__ __launch_bounds__(64 * WAVES, 4) void conv3d_k3_fewch_sp_kernel(const
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[(ni + 1) & 1][j] = l3[vb[ni + 1] + off[j]];
       }
-      c3_u32x4 b3[kC3Split];
+      u32x4 b3[kSplit];
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[ni & 1][j] *= inv_in;
-      c3_split(v[ni & 1], b3);
+      split_planes8(v[ni & 1], b3);
 #pragma unroll
-      for (int mi = 0; mi < MT; ++mi) acc[mi][ni] = c3_mfma3(a[mi], b3, acc[mi][ni]);
+      for (int mi = 0; mi < MT; ++mi) acc[mi][ni] = mfma_split(a[mi], b3, acc[mi][ni]);
     }
   }
   if (s_in != 1.0f) {   // wave uniform
@@ -864,287 +825,6 @@ __global__ __launch_bounds__(64 * WAVES, 4) void conv3d_k3_fewch_sp_kernel(const
     }
 }
 
-// GroupNorm(groups) + Swish over [B, C, r^3]; statistics from the conv's per-brick partials.
-// grid = (groups, B); optional per-channel sum of the OUTPUT (for the SE squeeze).
-__global__ __launch_bounds__(512) void groupnorm_swish_kernel(float *__restrict__ y, const float *__restrict__ partial,
-                                                              const float *__restrict__ gamma,
-                                                              const float *__restrict__ beta, int c, int r3,
-                                                              int nbricks, int groups, float eps,
-                                                              float *__restrict__ chan_sum) {
-  __shared__ double s_stat[2];
-  __shared__ float s_red[8];
-  const int g = blockIdx.x, b = blockIdx.y, cpg = c / groups;
-  const int tid = threadIdx.x;
-  if (tid < 64) {
-    double s = 0.0, s2 = 0.0;
-    for (int i = tid; i < nbricks * cpg; i += 64) {
-      const int br = i / cpg, ch = g * cpg + i % cpg;
-      const float *p = partial + (((size_t)b * nbricks + br) * c + ch) * 2;
-      s += (double)p[0];
-      s2 += (double)p[1];
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-      s += __shfl_xor(s, off, 64);
-      s2 += __shfl_xor(s2, off, 64);
-    }
-    if (tid == 0) {
-      const double n = (double)cpg * r3, mean = s / n;
-      s_stat[0] = mean;
-      s_stat[1] = 1.0 / sqrt(fmax(s2 / n - mean * mean, 0.0) + (double)eps);
-    }
-  }
-  __syncthreads();
-  const float mean = (float)s_stat[0], rstd = (float)s_stat[1];
-  for (int cc = 0; cc < cpg; ++cc) {
-    const int ch = g * cpg + cc;
-    float *row = y + ((size_t)b * c + ch) * r3;
-    const float ga = gamma[ch] * rstd, be = beta[ch] - mean * rstd * gamma[ch];
-    float acc = 0.f;
-    const int n4 = (r3 & 3) ? 0 : r3 >> 2;   // rows are 16-byte aligned only when r^3 is a multiple of 4
-    if (r3 & 3) {
-      for (int i = tid; i < r3; i += 512) {
-        const float t = row[i] * ga + be;
-        const float o = t / (1.0f + __expf(-t));
-        acc += o;
-        row[i] = o;
-      }
-    }
-    for (int i = tid; i < n4; i += 512) {
-      float4 v = reinterpret_cast<float4 *>(row)[i];
-      float o[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float t = o[q] * ga + be;
-        o[q] = t / (1.0f + __expf(-t));
-        acc += o[q];
-      }
-      reinterpret_cast<float4 *>(row)[i] = make_float4(o[0], o[1], o[2], o[3]);
-    }
-    if (chan_sum) {
-      for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
-      __syncthreads();
-      if ((tid & 63) == 0) s_red[tid >> 6] = acc;
-      __syncthreads();
-      if (tid == 0) {
-        float t = 0.f;
-        for (int w = 0; w < 8; ++w) t += s_red[w];
-        chan_sum[(size_t)b * c + ch] = t;
-      }
-    }
-  }
-}
-
-// SE gate: gate = sigmoid(W2 act(W1 mean)), W1 [c/red, c], W2 [c, c/red]; one block per cloud.
-__global__ void se_gate_kernel(const float *__restrict__ chan_sum, const float *__restrict__ w1,
-                               const float *__restrict__ w2, int c, int hid, int r3, int use_relu,
-                               float *__restrict__ gate, int parts) {
-  extern __shared__ float s[];  // mean[c], h[hid]
-  const int b = blockIdx.x, tid = threadIdx.x;
-  float *mean = s, *h = s + c;
-  // chan_sum [b][parts][c]: partial sums of the squeeze, added in index order
-  for (int i = tid; i < c; i += blockDim.x) {
-    float t = chan_sum[(size_t)b * parts * c + i];
-    for (int p = 1; p < parts; ++p) t += chan_sum[((size_t)b * parts + p) * c + i];
-    mean[i] = t / (float)r3;
-  }
-  __syncthreads();
-  for (int i = tid; i < hid; i += blockDim.x) {
-    float a = 0.f;
-    for (int q = 0; q < c; ++q) a += w1[i * c + q] * mean[q];
-    h[i] = use_relu ? fmaxf(a, 0.f) : a / (1.0f + expf(-a));
-  }
-  __syncthreads();
-  for (int i = tid; i < c; i += blockDim.x) {
-    float a = 0.f;
-    for (int q = 0; q < hid; ++q) a += w2[i * hid + q] * h[q];
-    gate[(size_t)b * c + i] = 1.0f / (1.0f + expf(-a));
-  }
-}
-
-// GroupNorm as per-(cloud, channel) coefficients: y = a x + s with a = gamma rstd, s = beta - mean a; statistics from the
-// conv's per-brick partials, combined in f64 in a fixed order exactly as groupnorm_swish_kernel does.  grid = (groups, B).
-__global__ __launch_bounds__(64) void groupnorm_coef_kernel(const float *__restrict__ partial, const float *__restrict__ gamma,
-                                                            const float *__restrict__ beta, int c, int r3, int nbricks,
-                                                            int groups, float eps, float *__restrict__ coef) {
-  const int g = blockIdx.x, b = blockIdx.y, cpg = c / groups, tid = threadIdx.x;
-  double s = 0.0, s2 = 0.0;
-  for (int i = tid; i < nbricks * cpg; i += 64) {
-    const int br = i / cpg, ch = g * cpg + i % cpg;
-    const float *p = partial + (((size_t)b * nbricks + br) * c + ch) * 2;
-    s += (double)p[0];
-    s2 += (double)p[1];
-  }
-  for (int off = 32; off >= 1; off >>= 1) {
-    s += __shfl_xor(s, off, 64);
-    s2 += __shfl_xor(s2, off, 64);
-  }
-  const double n = (double)cpg * r3, mean_d = s / n;
-  const float mean = (float)mean_d, rstd = (float)(1.0 / sqrt(fmax(s2 / n - mean_d * mean_d, 0.0) + (double)eps));
-  for (int i = tid; i < cpg; i += 64) {   // one trip up to 64 channels per group; the voxel attention stack goes to 128
-    const int ch = g * cpg + i;
-    const float a = gamma[ch] * rstd;
-    coef[((size_t)b * c + ch) * 2] = a;
-    coef[((size_t)b * c + ch) * 2 + 1] = beta[ch] - mean * rstd * gamma[ch];
-  }
-}
-
-__device__ __forceinline__ float swish_fast(float t) {
-  return t * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896340736f * t));
-}
-
-// chan_sum[b][ch] = sum over the voxels of swish(a x + s): the SE squeeze of a GroupNorm + Swish output that is never
-// written (read-only pass; the consumers apply the same map on the fly).  grid = (C, B), rows of r^3 floats.
-__global__ __launch_bounds__(256) void gn_swish_sum_kernel(const float *__restrict__ y, const float *__restrict__ coef, int c,
-                                                           int r3, float *__restrict__ chan_sum) {
-  __shared__ float s_red[4];
-  const int ch = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const float *row = y + ((size_t)b * c + ch) * r3;
-  const float a = coef[((size_t)b * c + ch) * 2], s = coef[((size_t)b * c + ch) * 2 + 1];
-  float acc = 0.f;
-  if ((r3 & 3) == 0) {
-    const float4 *row4 = reinterpret_cast<const float4 *>(row);
-    for (int i = tid; i < (r3 >> 2); i += 256) {
-      const float4 v = row4[i];
-      acc += swish_fast(fmaf(v.x, a, s)) + swish_fast(fmaf(v.y, a, s)) + swish_fast(fmaf(v.z, a, s)) + swish_fast(fmaf(v.w, a, s));
-    }
-  } else {
-    for (int i = tid; i < r3; i += 256) acc += swish_fast(fmaf(row[i], a, s));
-  }
-  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
-  if ((tid & 63) == 0) s_red[tid >> 6] = acc;
-  __syncthreads();
-  if (tid == 0) chan_sum[(size_t)b * c + ch] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
-}
-
-// The same squeeze over a channel-LAST tensor [b][r^3][c]: block (part, b) sums its share of the voxels for every channel
-// (thread = (voxel stripe, channel quad), 16-byte loads), parts[b][part][c] leaves; se_gate_kernel adds the parts in order.
-constexpr int kSumParts = 8;
-__global__ __launch_bounds__(256) void gn_swish_sum_cl_kernel(const float *__restrict__ y, const float *__restrict__ coef, int c,
-                                                              int r3, float *__restrict__ parts) {
-  __shared__ f32x4 s_acc[256];
-  const int part = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const int quads = c >> 2, stripes = 256 / quads;          // threads beyond stripes * quads idle
-  const int qd = tid % quads, stripe = tid / quads;
-  const int v0 = (int)((long long)r3 * part / kSumParts), v1 = (int)((long long)r3 * (part + 1) / kSumParts);
-  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (stripe < stripes) {
-    const f32x4 *cf = reinterpret_cast<const f32x4 *>(coef + ((size_t)b * c + 4 * qd) * 2);
-    const f32x4 c01 = cf[0], c23 = cf[1];   // (a0, s0, a1, s1), (a2, s2, a3, s3)
-    const f32x4 *row = reinterpret_cast<const f32x4 *>(y + (size_t)b * r3 * c) + qd;
-    for (int v = v0 + stripe; v < v1; v += stripes) {
-      const f32x4 x = row[(size_t)v * quads];
-      acc[0] += swish_fast(fmaf(x[0], c01[0], c01[1]));
-      acc[1] += swish_fast(fmaf(x[1], c01[2], c01[3]));
-      acc[2] += swish_fast(fmaf(x[2], c23[0], c23[1]));
-      acc[3] += swish_fast(fmaf(x[3], c23[2], c23[3]));
-    }
-  }
-  s_acc[tid] = acc;
-  __syncthreads();
-  if (tid < quads) {
-    f32x4 t = s_acc[tid];
-    for (int st = 1; st < stripes; ++st) {
-      const f32x4 o = s_acc[st * quads + tid];
-      t[0] += o[0]; t[1] += o[1]; t[2] += o[2]; t[3] += o[3];
-    }
-    *reinterpret_cast<f32x4 *>(parts + ((size_t)b * kSumParts + part) * c + 4 * tid) = t;
-  }
-}
-
-// devoxelize_fused_kernel over a channel-LAST raw conv output [b][r^3][c] (coef required): a point's corner is ONE run of
-// c floats, read as 16-byte loads by c / 4 neighbouring lanes, instead of c dword gathers from c cache lines (the
-// channel-major form is bound by the address path: 64 lines per wave instruction, 0.24 ms per 48 x 24^3 x 256 clouds).
-// Block = 64 points; item = (point, channel quad); the results cross LDS so that the stores (and the reads of `add`) run
-// along the points.  c % 4 == 0, c <= 256.
-__global__ __launch_bounds__(256) void devoxelize_cl_kernel(const float *__restrict__ coords, const float *__restrict__ feat,
-                                                            const float *__restrict__ coef, const float *__restrict__ gate,
-                                                            const float *__restrict__ add, int c, int n, int r,
-                                                            float *__restrict__ outs) {
-  extern __shared__ float s_tile[];   // [c][65]
-  const int b = blockIdx.y, p0 = blockIdx.x * 64, tid = threadIdx.x;
-  const int r2 = r * r, r3 = r2 * r, quads = c >> 2;
-  coords += (size_t)b * 3 * n;
-  const f32x4 *f4 = reinterpret_cast<const f32x4 *>(feat + (size_t)b * r3 * c);
-  for (int it = tid; it < 64 * quads; it += 256) {
-    const int pt = it / quads, qd = it - pt * quads;
-    const int i = min(p0 + pt, n - 1);
-    const float x = coords[i], y = coords[i + n], z = coords[i + 2 * n];
-    const float xl = floorf(x), yl = floorf(y), zl = floorf(z);
-    const float xd1 = x - xl, yd1 = y - yl, zd1 = z - zl;
-    const float xd0 = 1.0f - xd1, yd0 = 1.0f - yd1, zd0 = 1.0f - zd1;
-    const float w[8] = {xd0 * yd0 * zd0, xd0 * yd0 * zd1, xd0 * yd1 * zd0, xd0 * yd1 * zd1,
-                        xd1 * yd0 * zd0, xd1 * yd0 * zd1, xd1 * yd1 * zd0, xd1 * yd1 * zd1};
-    const int i000 = (int)xl * r2 + (int)yl * r + (int)zl;
-    const int zh = zd1 > 0 ? 1 : 0, yh = yd1 > 0 ? r : 0, xh = xd1 > 0 ? r2 : 0;
-    const int idx[8] = {i000, i000 + zh, i000 + yh, i000 + yh + zh, i000 + xh, i000 + xh + zh, i000 + xh + yh, i000 + xh + yh + zh};
-    f32x4 v[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = f4[(size_t)idx[k] * quads + qd];
-    const f32x4 *cf = reinterpret_cast<const f32x4 *>(coef + ((size_t)b * c + 4 * qd) * 2);
-    const f32x4 c01 = cf[0], c23 = cf[1];
-    const float ca[4] = {c01[0], c01[2], c23[0], c23[2]}, cs[4] = {c01[1], c01[3], c23[1], c23[3]};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float o = 0.f;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o += w[k] * swish_fast(fmaf(v[k][q], ca[q], cs[q]));
-      s_tile[(4 * qd + q) * 65 + pt] = o;
-    }
-  }
-  __syncthreads();
-  for (int e = tid; e < c * 64; e += 256) {
-    const int ch = e >> 6, pt = e & 63;
-    if (p0 + pt < n) {
-      const float gt = gate ? gate[(size_t)b * c + ch] : 1.0f;
-      const size_t o = ((size_t)b * c + ch) * n + p0 + pt;
-      outs[o] = gt * s_tile[ch * 65 + pt] + (add ? add[o] : 0.f);
-    }
-  }
-}
-
-// out[b,c,i] = gate[b,c] * trilinear(V[b,c], coords[b,:,i]) + add[b,c,i]
-__global__ __launch_bounds__(256) void devoxelize_fused_kernel(const float *__restrict__ coords,
-                                                               const float *__restrict__ feat,
-                                                               const float *__restrict__ gate,
-                                                               const float *__restrict__ add, int c, int n, int r,
-                                                               float *__restrict__ outs,
-                                                               const float *__restrict__ coef) {
-  // coef != NULL: `feat` is a raw conv output and GroupNorm + Swish are applied to the 8 corners on the fly
-  // (swish(a f + s), (a, s) per cloud and channel: groupnorm_coef_kernel)
-  const int b = blockIdx.z;
-  const int r2 = r * r, r3 = r2 * r;
-  coords += (size_t)b * 3 * n;
-  feat += (size_t)b * c * r3;
-  outs += (size_t)b * c * n;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const float x = coords[i], y = coords[i + n], z = coords[i + 2 * n];
-  const float xl = floorf(x), yl = floorf(y), zl = floorf(z);
-  const float xd1 = x - xl, yd1 = y - yl, zd1 = z - zl;
-  const float xd0 = 1.0f - xd1, yd0 = 1.0f - yd1, zd0 = 1.0f - zd1;
-  const float w000 = xd0 * yd0 * zd0, w001 = xd0 * yd0 * zd1, w010 = xd0 * yd1 * zd0, w011 = xd0 * yd1 * zd1;
-  const float w100 = xd1 * yd0 * zd0, w101 = xd1 * yd0 * zd1, w110 = xd1 * yd1 * zd0, w111 = xd1 * yd1 * zd1;
-  const int i000 = (int)xl * r2 + (int)yl * r + (int)zl;
-  const int zh = zd1 > 0 ? 1 : 0, yh = yd1 > 0 ? r : 0, xh = xd1 > 0 ? r2 : 0;
-  const int i001 = i000 + zh, i010 = i000 + yh, i011 = i010 + zh;
-  const int i100 = i000 + xh, i101 = i100 + zh, i110 = i100 + yh, i111 = i110 + zh;
-  const int c0 = blockIdx.y * 16, c1 = min(c0 + 16, c);
-  for (int l = c0; l < c1; ++l) {
-    const float *f = feat + (size_t)l * r3;
-    float f0 = f[i000], f1 = f[i001], f2 = f[i010], f3 = f[i011], f4 = f[i100], f5 = f[i101], f6 = f[i110], f7 = f[i111];
-    if (coef) {
-      const float a = coef[((size_t)b * c + l) * 2], s = coef[((size_t)b * c + l) * 2 + 1];
-      f0 = swish_fast(fmaf(f0, a, s)); f1 = swish_fast(fmaf(f1, a, s)); f2 = swish_fast(fmaf(f2, a, s));
-      f3 = swish_fast(fmaf(f3, a, s)); f4 = swish_fast(fmaf(f4, a, s)); f5 = swish_fast(fmaf(f5, a, s));
-      f6 = swish_fast(fmaf(f6, a, s)); f7 = swish_fast(fmaf(f7, a, s));
-    }
-    const float v = w000 * f0 + w001 * f1 + w010 * f2 + w011 * f3 + w100 * f4 + w101 * f5 + w110 * f6 + w111 * f7;
-    const float gt = gate ? gate[(size_t)b * c + l] : 1.0f;
-    const float ad = add ? add[((size_t)b * c + l) * n + i] : 0.f;
-    outs[(size_t)l * n + i] = gt * v + ad;
-  }
-}
-
 template <int MT, int NTW, int JN>
 int launch_conv_jn(const float *x, const float *wp, const float *bias, int b, int cin, int cout, int r, float *y,
                 float *partial, hipStream_t s, int cout_total, int co0, int out_cl) {
@@ -1157,151 +837,6 @@ int launch_conv_jn(const float *x, const float *wp, const float *bias, int b, in
   return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
 }
 
-// y[b, c, :] = act(y[b, c, :] + bias[c]) in place: the epilogue of the k = 1 convs that run as plain
-// library GEMMs (one pass instead of a bias pass and an activation pass).
-__global__ __launch_bounds__(256) void bias_act_kernel(float *__restrict__ y, const float *__restrict__ bias, int c,
-                                                       long long n, int relu) {
-  const long long row = blockIdx.y;  // b * c + channel
-  const float bv = bias[row % c];
-  float *p = y + row * n;
-  const long long n4 = n >> 2;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-    float4 v = reinterpret_cast<float4 *>(p)[i];
-    v.x += bv; v.y += bv; v.z += bv; v.w += bv;
-    if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-    reinterpret_cast<float4 *>(p)[i] = v;
-  }
-}
-
-// ---- narrow k = 1 convs and the Linear over the point axis (the pieces of the shipped encoder that used to go to
-// MIOpen / rocBLAS: SharedMLP 3 -> 48 and 48 -> 96 of the PVConv point branches, shared_mlp.py:6-35, and
-// out_layer[1] = Linear(n_points -> latent) over the POINT axis, pc_encoders.py:60-82,104-111).  Too small for the
-// matrix pipe (<= 4.6 k MAC per point): lane = point, the point's cin inputs in registers, weights wave-uniform on the
-// scalar path, fma chain in k order from the bias.
-template <int CIN>
-__global__ __launch_bounds__(256) void pointwise_small_kernel(const float *__restrict__ x, const float *__restrict__ w,
-                                                              const float *__restrict__ bias, int cout, long long n,
-                                                              int relu, float *__restrict__ y) {
-  const int b = blockIdx.y;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const float *xb = x + (size_t)b * CIN * n + i;
-  float v[CIN];
-#pragma unroll
-  for (int ci = 0; ci < CIN; ++ci) v[ci] = xb[(size_t)ci * n];
-  float *yb = y + (size_t)b * cout * n + i;
-  // eight output channels at a time: eight independent fma chains per lane (one chain per pass left the vector pipe waiting
-  // on its own result: 0.106 ms for 48 -> 96 over 256 x 1024 points, three times its instruction count)
-  constexpr int kCh = 8;
-  int co = 0;
-  for (; co + kCh <= cout; co += kCh) {
-    const float *wr = w + (size_t)co * CIN;
-    float acc[kCh];
-#pragma unroll
-    for (int k = 0; k < kCh; ++k) acc[k] = bias ? bias[co + k] : 0.f;
-#pragma unroll
-    for (int ci = 0; ci < CIN; ++ci)
-#pragma unroll
-      for (int k = 0; k < kCh; ++k) acc[k] = fmaf(wr[k * CIN + ci], v[ci], acc[k]);
-#pragma unroll
-    for (int k = 0; k < kCh; ++k) yb[(size_t)(co + k) * n] = relu ? fmaxf(acc[k], 0.f) : acc[k];
-  }
-  for (; co < cout; ++co) {
-    const float *wr = w + (size_t)co * CIN;
-    float acc = bias ? bias[co] : 0.f;
-#pragma unroll
-    for (int ci = 0; ci < CIN; ++ci) acc = fmaf(wr[ci], v[ci], acc);
-    yb[(size_t)co * n] = relu ? fmaxf(acc, 0.f) : acc;
-  }
-}
-
-// ---- any-shape k = 1 conv (SharedMLP / feature-propagation layers outside the fused launches' shape sets) --------------
-// y[b, co, i] = act(bias[co] + sum_ci W[co][ci] x[b, ci, i]) for ANY (cin, cout, n), weights as stored by nn.Conv1d
-// ([cout][cin], BatchNorm folded by the caller): exact f32 products on v_mfma_f32_16x16x4_f32.  A 256-thread workgroup
-// owns a 64-row x 64-point output tile (wave = m-tile, four n-tiles); K is staged 16 channels at a time through LDS with
-// bounds masks (W rows padded to 17 words, x rows to 80: both fragment reads conflict free).  Replaces the library GEMM
-// (rocBLAS / MIOpen through F.conv1d) + bias / activation pass these layers used to take: PointNet++ / PVCNN2 widths such
-// as 384 -> 256 over 128 centres.  Not a speed-of-light kernel (one 16-deep stage per barrier pair); the shipped encoder
-// never comes here.
-__global__ __launch_bounds__(256) void pointwise_any_kernel(const float *__restrict__ x, const float *__restrict__ w,
-                                                            const float *__restrict__ bias, int cin, int cout, long long n,
-                                                            int relu, float *__restrict__ y) {
-  __shared__ float Ws[64 * 17];
-  __shared__ float Xs[16 * 80];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 15, kq = lane >> 4;
-  const long long c0 = (long long)blockIdx.x * 64;
-  const int r0 = blockIdx.y * 64, b = blockIdx.z;
-  x += (size_t)b * cin * n;
-  y += (size_t)b * cout * n;
-  f32x4 acc[4];
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) acc[ni] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int wr = tid >> 2, wk = (tid & 3) * 4;          // W stage: row, first k of the thread's four
-  const int xk = tid >> 4, xc = (tid & 15) * 4;         // x stage: channel, first point of the thread's four
-  for (int k0 = 0; k0 < cin; k0 += 16) {
-    float wv[4], xv[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const bool okw = r0 + wr < cout && k0 + wk + q < cin;
-      wv[q] = okw ? w[(size_t)(r0 + wr) * cin + k0 + wk + q] : 0.f;
-      const bool okx = k0 + xk < cin && c0 + xc + q < n;
-      xv[q] = okx ? x[(size_t)(k0 + xk) * n + c0 + xc + q] : 0.f;
-    }
-    __syncthreads();   // the previous stage's readers are done
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      Ws[wr * 17 + wk + q] = wv[q];
-      Xs[xk * 80 + xc + q] = xv[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float a = Ws[(16 * wave + col) * 17 + 4 * j + kq];
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-        acc[ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, Xs[(4 * j + kq) * 80 + 16 * ni + col], acc[ni], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int row = r0 + 16 * wave + 4 * kq + r;
-    if (row < cout) {
-      const float bv = bias ? bias[row] : 0.f;
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) {
-        const long long i = c0 + 16 * ni + col;
-        if (i < n) {
-          const float v = acc[ni][r] + bv;
-          y[(size_t)row * n + i] = relu ? fmaxf(v, 0.f) : v;
-        }
-      }
-    }
-  }
-}
-
-// y[row, o] = bias[o] + sum_n W[o, n] x[row, n]: one workgroup per row (rows = batch x channels: a few hundred),
-// the row staged in LDS, thread = output feature, four interleaved k-ordered fma chains.
-__global__ __launch_bounds__(256) void linear_rows_kernel(const float *__restrict__ x, const float *__restrict__ w,
-                                                          const float *__restrict__ bias, int n, int nout,
-                                                          float *__restrict__ y) {
-  extern __shared__ float xs[];
-  const int row = blockIdx.x;
-  for (int i = threadIdx.x; i < n; i += 256) xs[i] = x[(size_t)row * n + i];
-  __syncthreads();
-  for (int o = threadIdx.x; o < nout; o += 256) {
-    const float *wr = w + (size_t)o * n;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;   // four interleaved chains: shorter dependency and error chains
-    for (int i = 0; i < n; i += 4) {
-      const float4 wv = *reinterpret_cast<const float4 *>(wr + i);
-      a0 = fmaf(wv.x, xs[i], a0);
-      a1 = fmaf(wv.y, xs[i + 1], a1);
-      a2 = fmaf(wv.z, xs[i + 2], a2);
-      a3 = fmaf(wv.w, xs[i + 3], a3);
-    }
-    y[(size_t)row * nout + o] = ((a0 + a1) + (a2 + a3)) + (bias ? bias[o] : 0.f);
-  }
-}
-
 // ---- any-shape Conv3d(k = 3, p = 1) for voxel shapes without an MFMA instantiation (PVCNN2's 256 ch @ 8^3 and
 // 128 ch @ 16^3 feature-propagation convs: 16 m-tiles of accumulators do not fit a wave).  Direct form on the VALU: a
 // workgroup owns a 4 x 4 x r brick like the MFMA kernels (so the GroupNorm partials have the same layout), a thread a
@@ -1311,7 +846,7 @@ __global__ __launch_bounds__(256) void conv3d_k3_generic_kernel(const float *__r
                                                                 const float *__restrict__ bias, int cin, int cout, int r,
                                                                 float *__restrict__ y, float *__restrict__ partial) {
   __shared__ float s_red[2][4];
-  const int bpr = (r + kBrick - 1) / kBrick, r3 = r * r * r, nvox = 16 * r;   // any r: the last brick row / column may be partial
+  const int bpr = bricks_per_axis(r), r3 = r * r * r, nvox = 16 * r;   // any r: the last brick row / column may be partial
   const int bx0 = (blockIdx.x / bpr) * kBrick, by0 = (blockIdx.x % bpr) * kBrick, b = blockIdx.y;
   x += (size_t)b * cin * r3;
   y += (size_t)b * cout * r3;
@@ -1355,7 +890,7 @@ __global__ __launch_bounds__(256) void conv3d_k3_generic_kernel(const float *__r
 
 GLDM_API long long gldm_conv3d_partial_floats(int b, int cout, int r) {
   if (b <= 0 || cout <= 0 || r <= 0) return -1;
-  const long long bpr = (r + kBrick - 1) / kBrick;   // a resolution that is not a multiple of the brick has partial edge bricks
+  const long long bpr = bricks_per_axis(r);
   return (long long)b * bpr * bpr * cout * 2;
 }
 
@@ -1445,7 +980,7 @@ GLDM_API int gldm_conv3d_k3_cl(const float *x, const float *w_packed, const floa
 template <int MT, int R, int ZB, int WAVES, bool ACT>
 int launch_conv_pl_act(const float *x, const float *wp3, const float *bias, int b, int cin, int cout, float *y, float *partial,
                        const float *in_coef, int out_cl, hipStream_t s) {
-  const size_t lds_bytes = (size_t)(R == 24 && ZB == 24 ? 2 : 1) * kC3Split * 2 * ((36 * (ZB + 2) + 15) & ~15) * 16 +
+  const size_t lds_bytes = (size_t)(R == 24 && ZB == 24 ? 2 : 1) * kSplit * 2 * ((36 * (ZB + 2) + 15) & ~15) * 16 +
                            (ACT ? (size_t)2 * cin * sizeof(float) : 64 /* the waves' range words */);
   struct Tag {};
   gldm_dev::allow_dynamic_lds<Tag>(reinterpret_cast<const void *>(&conv3d_k3_pl_kernel<MT, R, ZB, WAVES, ACT>), (int)lds_bytes);
@@ -1492,8 +1027,8 @@ static int conv3d_k3_f16x2_impl(const float *x, const float *in_coef, const floa
     }
   } dump{s, cin, cout, r, b};
 #endif
-  // (4 x 4 x 12 half bricks at 24^3 -- <3, 24, 12, 4>: 48 KiB of planes, two co-resident workgroups of 4 waves -- measured
-  // 2.12 ms against 2.05 for the full-z brick: the kernel's 220 registers allow two waves per SIMD either way, and the
+  // (4 x 4 x 12 half bricks at 24^3 -- <3, 24, 12, 4>, two co-resident workgroups of 4 waves -- measured before round 6, on three
+  // bf16 planes (48 KiB a half brick), 2.12 ms against 2.05 for the full-z brick: the kernel's 220 registers allow two waves per SIMD either way, and the
   // halves pay a z halo and the weight stream twice.  Kept as an instantiable option, not used.  Round 6, with three f16
   // products instead of six bf16 ones: A/B of the whole encoder on one box 4.69 / 4.72 ms (full brick) against 4.63 / 4.84
   // (halves) -- inside the run-to-run spread, still not used.)
@@ -1531,135 +1066,10 @@ GLDM_API int gldm_conv3d_k3_f16x2_gn(const float *x, const float *in_coef, const
   return conv3d_k3_f16x2_impl(x, in_coef, w_split, bias, b, cin, cout, r, y, partial, out_channel_last ? 1 : 0, stream);
 }
 
-GLDM_API int gldm_groupnorm_coef(const float *partial, const float *gamma, const float *beta, int b, int c, int r, int groups,
-                                 float eps, float *coef, gldm_stream_t stream) {
-  if (!partial || !gamma || !beta || !coef || b <= 0 || c <= 0 || r <= 0 || groups <= 0 || c % groups || c / groups > 128)
-    return GLDM_ERR_INVALID_ARG;
-  const int nbricks = ((r + kBrick - 1) / kBrick) * ((r + kBrick - 1) / kBrick);
-  hipLaunchKernelGGL(groupnorm_coef_kernel, dim3(groups, b), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), partial, gamma,
-                     beta, c, r * r * r, nbricks, groups, eps, coef);
-  return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
-}
-
-GLDM_API int gldm_gn_swish_chan_sum(const float *y, const float *coef, int b, int c, int r, float *chan_sum,
-                                    gldm_stream_t stream) {
-  if (!y || !coef || !chan_sum || b <= 0 || c <= 0 || r <= 0) return GLDM_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(gn_swish_sum_kernel, dim3(c, b), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), y, coef, c,
-                     r * r * r, chan_sum);
-  return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
-}
-
-GLDM_API int gldm_groupnorm_swish(float *y, const float *partial, const float *gamma, const float *beta, int b, int c,
-                                  int r, int groups, float eps, float *chan_sum, gldm_stream_t stream) {
-  if (!y || !partial || !gamma || !beta || b <= 0 || c <= 0 || r <= 0 || groups <= 0 || c % groups)
-    return GLDM_ERR_INVALID_ARG;
-  const int nbricks = ((r + kBrick - 1) / kBrick) * ((r + kBrick - 1) / kBrick);
-  hipLaunchKernelGGL(groupnorm_swish_kernel, dim3(groups, b), dim3(512), 0, reinterpret_cast<hipStream_t>(stream), y,
-                     partial, gamma, beta, c, r * r * r, nbricks, groups, eps, chan_sum);
-  return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
-}
-
-GLDM_API int gldm_se_gate(const float *chan_sum, const float *w1, const float *w2, int b, int c, int hidden, int r,
-                          int use_relu, float *gate, gldm_stream_t stream) {
-  if (!chan_sum || !w1 || !w2 || !gate || b <= 0 || c <= 0 || hidden <= 0 || r <= 0) return GLDM_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(se_gate_kernel, dim3(b), dim3(128), (size_t)(c + hidden) * sizeof(float),
-                     reinterpret_cast<hipStream_t>(stream), chan_sum, w1, w2, c, hidden, r * r * r, use_relu, gate, 1);
-  return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
-}
-
-GLDM_API int gldm_se_gate_parts(const float *chan_parts, int parts, const float *w1, const float *w2, int b, int c, int hidden,
-                                int r, int use_relu, float *gate, gldm_stream_t stream) {
-  if (!chan_parts || !w1 || !w2 || !gate || b <= 0 || c <= 0 || hidden <= 0 || r <= 0 || parts <= 0) return GLDM_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(se_gate_kernel, dim3(b), dim3(128), (size_t)(c + hidden) * sizeof(float),
-                     reinterpret_cast<hipStream_t>(stream), chan_parts, w1, w2, c, hidden, r * r * r, use_relu, gate, parts);
-  return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
-}
-
-GLDM_API int gldm_squeeze_parts(void) { return kSumParts; }
-
-GLDM_API int gldm_gn_swish_chan_sum_cl(const float *y, const float *coef, int b, int c, int r, float *chan_parts,
-                                       gldm_stream_t stream) {
-  if (!y || !coef || !chan_parts || b <= 0 || c <= 0 || r <= 0) return GLDM_ERR_INVALID_ARG;
-  if (c % 4 || c > 1024) return GLDM_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(gn_swish_sum_cl_kernel, dim3(kSumParts, b), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), y, coef, c,
-                     r * r * r, chan_parts);
-  return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
-}
-
-GLDM_API int gldm_devoxelize_gn_cl_fused(const float *coords, const float *features_cl, const float *coef, const float *gate,
-                                         const float *add, int b, int c, int n, int r, float *out, gldm_stream_t stream) {
-  if (!coords || !features_cl || !coef || !out || b <= 0 || c <= 0 || n <= 0 || r <= 0) return GLDM_ERR_INVALID_ARG;
-  if (c % 4 || c > 256) return GLDM_ERR_UNSUPPORTED;
-  struct DevoxClTag { int site; };
-  gldm_dev::allow_dynamic_lds<DevoxClTag>(reinterpret_cast<const void *>(&devoxelize_cl_kernel), 256 * 65 * (int)sizeof(float));
-  hipLaunchKernelGGL(devoxelize_cl_kernel, dim3((n + 63) / 64, b), dim3(256), (size_t)c * 65 * sizeof(float),
-                     reinterpret_cast<hipStream_t>(stream), coords, features_cl, coef, gate, add, c, n, r, out);
-  return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
-}
-
-GLDM_API int gldm_devoxelize_fused(const float *coords, const float *features, const float *gate, const float *add,
-                                   int b, int c, int n, int r, float *out, gldm_stream_t stream) {
-  if (!coords || !features || !out || b <= 0 || c <= 0 || n <= 0 || r <= 0) return GLDM_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(devoxelize_fused_kernel, dim3((n + 255) / 256, (c + 15) / 16, b), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), coords, features, gate, add, c, n, r, out, nullptr);
-  return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
-}
-
-GLDM_API int gldm_devoxelize_gn_fused(const float *coords, const float *features, const float *coef, const float *gate,
-                                      const float *add, int b, int c, int n, int r, float *out, gldm_stream_t stream) {
-  if (!coords || !features || !coef || !out || b <= 0 || c <= 0 || n <= 0 || r <= 0) return GLDM_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(devoxelize_fused_kernel, dim3((n + 255) / 256, (c + 15) / 16, b), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), coords, features, gate, add, c, n, r, out, coef);
-  return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
-}
-
 GLDM_API int gldm_conv3d_k3_generic(const float *x, const float *w, const float *bias, int b, int cin, int cout, int r,
                                     float *y, float *partial, gldm_stream_t stream) {
   if (!x || !w || !bias || !y || !partial || b <= 0 || cin <= 0 || cout <= 0 || r <= 0) return GLDM_ERR_INVALID_ARG;
-  const int bpr = (r + kBrick - 1) / kBrick;
-  hipLaunchKernelGGL(conv3d_k3_generic_kernel, dim3(bpr * bpr, b), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, w,
+  hipLaunchKernelGGL(conv3d_k3_generic_kernel, dim3(bricks_per_cloud(r), b), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, w,
                      bias, cin, cout, r, y, partial);
-  return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
-}
-
-GLDM_API int gldm_pointwise_small(const float *x, const float *w, const float *bias, int b, int cin, int cout, long long n,
-                                  int relu, float *y, gldm_stream_t stream) {
-  if (!x || !w || !y || b <= 0 || cin <= 0 || cout <= 0 || n <= 0) return GLDM_ERR_INVALID_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)((n + 255) / 256), b);
-#define GLDM_PS_CASE(C) \
-  if (cin == C) { hipLaunchKernelGGL(pointwise_small_kernel<C>, grid, dim3(256), 0, s, x, w, bias, cout, n, relu, y); \
-                  return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH; }
-  GLDM_PS_CASE(3) GLDM_PS_CASE(6) GLDM_PS_CASE(16) GLDM_PS_CASE(24) GLDM_PS_CASE(32) GLDM_PS_CASE(48) GLDM_PS_CASE(64)
-#undef GLDM_PS_CASE
-  return GLDM_ERR_UNSUPPORTED;
-}
-
-GLDM_API int gldm_pointwise_any(const float *x, const float *w, const float *bias, int b, int cin, int cout, long long n,
-                                int relu, float *y, gldm_stream_t stream) {
-  if (!x || !w || !y || b <= 0 || cin <= 0 || cout <= 0 || n <= 0) return GLDM_ERR_INVALID_ARG;
-  const long long tiles = (n + 63) / 64;
-  if (tiles > 0x7fffffffLL || b > 65535 || (cout + 63) / 64 > 65535) return GLDM_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(pointwise_any_kernel, dim3((unsigned)tiles, (cout + 63) / 64, b), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), x, w, bias, cin, cout, n, relu, y);
-  return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
-}
-
-GLDM_API int gldm_linear_rows(const float *x, const float *w, const float *bias, int rows, int n, int nout, float *y,
-                              gldm_stream_t stream) {
-  if (!x || !w || !y || rows <= 0 || n <= 0 || nout <= 0) return GLDM_ERR_INVALID_ARG;
-  if ((n & 3) || (size_t)n * 4 > 64 * 1024) return GLDM_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(linear_rows_kernel, dim3(rows), dim3(256), (size_t)n * sizeof(float),
-                     reinterpret_cast<hipStream_t>(stream), x, w, bias, n, nout, y);
-  return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
-}
-
-GLDM_API int gldm_bias_act(float *y, const float *bias, int b, int c, long long n, int relu, gldm_stream_t stream) {
-  if (!y || !bias || b <= 0 || c <= 0 || n <= 0) return GLDM_ERR_INVALID_ARG;
-  if (n & 3) return GLDM_ERR_UNSUPPORTED;  // rows must stay 16-byte aligned
-  const long long n4 = n >> 2;
-  const int bx = (int)((n4 + 255) / 256 < 1 ? 1 : ((n4 + 255) / 256 > 64 ? 64 : (n4 + 255) / 256));
-  hipLaunchKernelGGL(bias_act_kernel, dim3(bx, b * c), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), y, bias, c, n,
-                     relu);
   return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
 }

@@ -43,12 +43,6 @@ __device__ __forceinline__ float head_pow2(float m) {
   return __uint_as_float((unsigned)(e - 13 + 127) << 23);
 }
 
-__device__ __forceinline__ float head_wave_sum(float x) {   // fixed tree: the same bits on every run
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) x += __shfl_xor(x, o);
-  return x;
-}
-
 // ---- scene assembly -----------------------------------------------------------------------------------------------------
 // A thread per (scene, column): four stores, each coalesced along the columns.
 __global__ __launch_bounds__(256) void grasp_scene_kernel(const float *__restrict__ pc, const float *__restrict__ H,
@@ -231,7 +225,7 @@ __global__ __launch_bounds__(256) void cls_head_kernel(const float *__restrict__
   if (wave == 0) {
     float s = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
     s = n0 + lane < n ? s * l[n0 + lane] : 0.f;
-    s = head_wave_sum(s);
+    s = wave_sum(s);
     if (lane == 0) part[(size_t)scene * tiles + tile] = s;
   }
 }

@@ -1,10 +1,10 @@
-// mfma_core.h -- what the dense kernel sources share (resnet1d.hip, sa_mlp.hip, pointwise_mlp.hip; the probes under
-// tools/micro include it too).  Device code only, __forceinline__ in an anonymous namespace: nothing here is a symbol.
+// mfma_core.h -- what the kernel sources share (all but point_ops.hip and sa_msg.hip; the probes under tools/micro include
+// it too).  Device code only, __forceinline__ in an anonymous namespace: nothing here is a symbol.
 //   * types and LDS maps: Geo<NC> (a workgroup's NC activation columns as [channel][column] f32 rows, XOR-swizzled: swz),
 //     PG<LL> (the same tensors as pre-split f16 planes in B-fragment order), Ctx;
 //   * split-f16 arithmetic: an f32 operand travels as hi + lo f16 (kSplit = 2), a product is three v_mfma_f32_16x16x32_f16
 //     (mfma_split); split_f16x2 / split_planes8 / store_planes4 make the planes, range_pow2 / pow2_inv their range scale;
-//   * cross-lane reductions on the VALU (DPP, permlane swaps);
+//   * cross-lane reductions on the VALU (DPP, permlane swaps), and over all 64 lanes by shuffles (wave_max, wave_sum);
 //   * GEMM cores, weights streamed L2 -> VGPR as whole fragments (wstream.h).  f32 pipe (v_mfma_f32_16x16x4_f32):
 //     gemm_fast_pf / gemm_fast_tap3 / gemm_fast / gemm_small, store_tiles, gemm_passes with the GroupNorm + scale/shift + SiLU
 //     + residual epilogue, conv_gemm dealing a layer's output tiles over the waves.  Split-f16 pipe: gemm1_pl (1x1, B from planes).
@@ -215,6 +215,19 @@ __device__ __forceinline__ float row_pair_max(float x) {
 __device__ __forceinline__ float half_max(float x) {
   const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
   return vmax(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+
+// All 64 lanes, where the reduction is not the hot path (one per tile or row): shuffles, offsets 1, 2, .. 32.  The
+// sum's order is part of its result: a fixed tree, the same bits on every run.
+__device__ __forceinline__ float wave_max(float x) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) x = fmaxf(x, __shfl_xor(x, o));
+  return x;
+}
+__device__ __forceinline__ float wave_sum(float x) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) x += __shfl_xor(x, o);
+  return x;
 }
 
 __device__ __forceinline__ float row16_max(float x) {  // max over the 16 lanes of a DPP row

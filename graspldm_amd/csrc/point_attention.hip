@@ -1,5 +1,6 @@
 // point_attention.hip -- dense softmax attention of every point over every point (the PVD Attention block of
-// grasp_ldm/models/modules/modules.py:10-54, without its k = 1 convs) and the GroupNorm + Swish over [b, c, n] behind it.
+// grasp_ldm/models/modules/modules.py:10-54, without its k = 1 convs; the GroupNorm + Swish behind it is voxel_norm.hip's
+// gldm_groupnorm_swish_points, the few-row out_layer conv pointwise_small.hip's gldm_pointwise_rows).
 //
 //   out[b, c, i] = sum_j v[b, c, j] softmax_j( sum_c' q[b, c', i] k[b, c', j] )          (no 1 / sqrt(c) factor)
 //
@@ -52,17 +53,6 @@ inline AttnWs attn_ws(int c, int n) {
 inline int attn_chunk(int b, int c, int n) {
   const long long fit = kAttnWsCap / attn_ws(c, n).total;
   return (int)(fit < 1 ? 1 : (fit < b ? fit : b));
-}
-
-__device__ __forceinline__ float wave_max(float x) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) x = fmaxf(x, __shfl_xor(x, o));
-  return x;
-}
-__device__ __forceinline__ float wave_sum(float x) {   // fixed tree: the same bits on every run
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) x += __shfl_xor(x, o);
-  return x;
 }
 
 // ---- pack: K on the SLOW axis (q and k of the scores product: x [c][n], a group = 16 points, K = channels) -------------
@@ -265,98 +255,6 @@ __global__ __launch_bounds__(256) void attn_softmax_kernel(const float *__restri
   }
 }
 
-// ---- GroupNorm + Swish over [b, c, n] (+ a residual in front) -----------------------------------------------------------
-// A workgroup per (cloud, group): the group's channels are one contiguous run of (c / groups) n floats.  Statistics of
-// x (+ add) in f64, per-thread partial sums in index order and a fixed tree over the threads.
-__global__ __launch_bounds__(256) void gn_swish_points_kernel(const float *x, const float *add, const float *__restrict__ gamma,
-                                                              const float *__restrict__ beta, int c, int n, int groups, float eps,
-                                                              float *out) {
-  __shared__ double red[2][256];
-  const int cg = c / groups, tid = threadIdx.x;
-  const size_t base = ((size_t)blockIdx.y * c + (size_t)blockIdx.x * cg) * n;
-  const int quads = cg * (n / 4);
-  const f32x4 *x4 = (const f32x4 *)(x + base), *a4 = add ? (const f32x4 *)(add + base) : nullptr;
-  double s1 = 0.0, s2 = 0.0;
-  for (int i = tid; i < quads; i += 256) {
-    f32x4 v = x4[i];
-    if (a4) v += a4[i];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      s1 += (double)v[e];
-      s2 += (double)v[e] * (double)v[e];
-    }
-  }
-  red[0][tid] = s1;
-  red[1][tid] = s2;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) {
-      red[0][tid] += red[0][tid + o];
-      red[1][tid] += red[1][tid + o];
-    }
-    __syncthreads();
-  }
-  const double cnt = (double)cg * n, mean = red[0][0] / cnt;
-  double var = red[1][0] / cnt - mean * mean;
-  var = var > 0.0 ? var : 0.0;
-  const double rstd = 1.0 / sqrt(var + (double)eps);
-  f32x4 *o4 = (f32x4 *)(out + base);
-  const int qpc = n / 4;   // a 16-byte run stays inside one channel
-  for (int i = tid; i < quads; i += 256) {
-    const int ch = blockIdx.x * cg + i / qpc;
-    const float a = (float)((double)gamma[ch] * rstd), s = (float)((double)beta[ch] - mean * (double)gamma[ch] * rstd);
-    f32x4 v = x4[i];
-    if (a4) v += a4[i];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float t = __builtin_fmaf(a, v[e], s);
-      v[e] = t / (1.0f + expf(-t));
-    }
-    o4[i] = v;
-  }
-}
-
-// ---- a few output rows of a k = 1 conv over [b, cin, n]: out_layer[0] behind the attention block (768 -> 3) ---------------
-// Memory bound (one pass over x): a thread owns four consecutive points, walks the channels with 16-byte loads and keeps
-// HO accumulators per point; k-ordered fma chain from the bias.  (The any-shape MFMA kernel pads 3 rows to a 64-row tile.)
-template <int HO>
-__global__ __launch_bounds__(256) void pointwise_rows_kernel(const float *__restrict__ x, const float *__restrict__ w,
-                                                             const float *__restrict__ bias, int cin, int n, float *__restrict__ y) {
-  const int q = blockIdx.x * 256 + threadIdx.x, nq = n / 4;
-  if (q >= nq) return;
-  const f32x4 *xp = (const f32x4 *)(x + (size_t)blockIdx.y * cin * n) + q;
-  f32x4 acc[HO];
-#pragma unroll
-  for (int o = 0; o < HO; ++o) {
-    const float b0 = bias ? bias[o] : 0.f;
-    acc[o] = f32x4{b0, b0, b0, b0};
-  }
-#pragma unroll 8
-  for (int ch = 0; ch < cin; ++ch) {
-    const f32x4 v = xp[(size_t)ch * nq];
-#pragma unroll
-    for (int o = 0; o < HO; ++o) {
-      const float wv = w[o * cin + ch];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[o][e] = __builtin_fmaf(wv, v[e], acc[o][e]);
-    }
-  }
-  f32x4 *yp = (f32x4 *)(y + (size_t)blockIdx.y * HO * n) + q;
-#pragma unroll
-  for (int o = 0; o < HO; ++o) yp[(size_t)o * nq] = acc[o];
-}
-
-template <int HO>
-int launch_rows(const float *x, const float *w, const float *bias, int b, int cin, int hout, int n, float *y, hipStream_t st) {
-  if constexpr (HO > 8) {
-    return GLDM_ERR_UNSUPPORTED;
-  } else {
-    if (hout != HO) return launch_rows<HO + 1>(x, w, bias, b, cin, hout, n, y, st);
-    hipLaunchKernelGGL(pointwise_rows_kernel<HO>, dim3((n / 4 + 255) / 256, b), dim3(256), 0, st, x, w, bias, cin, n, y);
-    return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
-  }
-}
-
 template <bool EX>
 int launch_attention(const float *q, const float *k, const float *v, int b, int c, int n, char *ws, float *out, hipStream_t st) {
   const AttnWs w = attn_ws(c, n);
@@ -407,22 +305,4 @@ GLDM_API int gldm_point_attention(const float *q, const float *k, const float *v
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   return exact_f32 ? launch_attention<true>(q, k, v, b, c, n, (char *)workspace, out, st)
                    : launch_attention<false>(q, k, v, b, c, n, (char *)workspace, out, st);
-}
-
-GLDM_API int gldm_groupnorm_swish_points(const float *x, const float *add, const float *gamma, const float *beta, int b, int c,
-                                         int n, int groups, float eps, float *out, gldm_stream_t stream) {
-  if (!x || !gamma || !beta || !out || b <= 0 || c <= 0 || n <= 0 || groups <= 0) return GLDM_ERR_INVALID_ARG;
-  if ((((size_t)x | (size_t)add | (size_t)out) & 15)) return GLDM_ERR_INVALID_ARG;   // 16-byte vector accesses
-  if (c % groups || c / groups > 128 || n % 4 || b > 65535) return GLDM_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(gn_swish_points_kernel, dim3(groups, b), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, add, gamma,
-                     beta, c, n, groups, eps, out);
-  return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
-}
-
-GLDM_API int gldm_pointwise_rows(const float *x, const float *w, const float *bias, int b, int cin, int hout, int n, float *y,
-                                 gldm_stream_t stream) {
-  if (!x || !w || !y || b <= 0 || cin <= 0 || hout <= 0 || n <= 0) return GLDM_ERR_INVALID_ARG;
-  if ((((size_t)x | (size_t)y) & 15)) return GLDM_ERR_INVALID_ARG;
-  if (hout > 8 || n % 4 || b > 65535) return GLDM_ERR_UNSUPPORTED;
-  return launch_rows<1>(x, w, bias, b, cin, hout, n, y, reinterpret_cast<hipStream_t>(stream));
 }

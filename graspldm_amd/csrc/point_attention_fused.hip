@@ -1,5 +1,6 @@
 // point_attention_fused.hip -- the attention core for MANY tokens at FEW channels (voxel attention inside PVConv: n = r^3
-// up to 4096 at c <= 128), and the two small launches the voxel attention stack needs around it.
+// up to 4096 at c <= 128).  The norms of the voxel attention stack around it (gldm_groupnorm_affine,
+// gldm_groupnorm_swish_points_sum) are voxel_norm.hip's.
 //
 //   out[b, c, i] = sum_j v[b, c, j] softmax_j( sum_c' q[b, c', i] k[b, c', j] )          (no 1 / sqrt(c) factor)
 //
@@ -46,12 +47,6 @@ struct FusedLds {
   static constexpr int kBytes = kSlots + 2 * 4 * 2 * 4;
 };
 static_assert(FusedLds<8, false>::kBytes * 2 <= 160 * 1024 && FusedLds<8, true>::kBytes * 2 <= 160 * 1024, "two workgroups per CU");
-
-__device__ __forceinline__ float fwave_max(float x) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) x = fmaxf(x, __shfl_xor(x, o));
-  return x;
-}
 
 template <int CT, bool EX>
 __global__ __launch_bounds__(256) void attn_fused_kernel(const float *__restrict__ q, const float *k, const float *v, int n,
@@ -103,8 +98,8 @@ __global__ __launch_bounds__(256) void attn_fused_kernel(const float *__restrict
             mk = fmaxf(mk, fabsf(kr[c2][h][e]));
             mv = fmaxf(mv, fabsf(vr[c2][h][e]));
           }
-      mk = fwave_max(mk);
-      mv = fwave_max(mv);
+      mk = wave_max(mk);
+      mv = wave_max(mv);
       if (lane == 0) {
         slots[(par * 4 + wave) * 2] = mk;
         slots[(par * 4 + wave) * 2 + 1] = mv;
@@ -202,7 +197,7 @@ __global__ __launch_bounds__(256) void attn_fused_kernel(const float *__restrict
             val[kb][t] = ch < C ? qp[(size_t)ch * n] : 0.f;
             m = fmaxf(m, fabsf(val[kb][t]));
           }
-        const float s = range_pow2(fwave_max(m)), inv = pow2_inv(s);
+        const float s = range_pow2(wave_max(m)), inv = pow2_inv(s);
         sq[nt] = s;
 #pragma unroll
         for (int kb = 0; kb < KB; ++kb) {
@@ -362,79 +357,6 @@ int launch_fused(const float *q, const float *k, const float *v, int b, int c, i
   }
 }
 
-// ---- x = a y + s per (cloud, channel) over a voxel grid: GroupNorm WITHOUT the activation ---------------------------------
-__global__ __launch_bounds__(256) void gn_affine_kernel(const float *__restrict__ y, const float *__restrict__ coef, int quads,
-                                                        float *__restrict__ x) {
-  const size_t row = blockIdx.x;   // cloud * c + channel
-  const float a = coef[2 * row], s = coef[2 * row + 1];
-  const f32x4 *y4 = (const f32x4 *)y + row * quads;
-  f32x4 *x4 = (f32x4 *)x + row * quads;
-  for (int i = blockIdx.y * 256 + threadIdx.x; i < quads; i += gridDim.y * 256) {
-    f32x4 t = y4[i];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) t[e] = __builtin_fmaf(a, t[e], s);
-    x4[i] = t;
-  }
-}
-
-// ---- GroupNorm + Swish over [b, c, n] (+ a residual in front) with the per-channel sums of the OUTPUT ------------------------
-// gn_swish_points_kernel's statistics (a workgroup per (cloud, group), f64, fixed tree); the second pass is a wave per
-// channel, so that a channel's sum is one wave's: lanes add their quads in index order (f64), then a fixed shuffle tree.
-__global__ __launch_bounds__(256) void gn_swish_points_sum_kernel(const float *x, const float *add, const float *__restrict__ gamma,
-                                                                  const float *__restrict__ beta, int c, int n, int groups, float eps,
-                                                                  float *out, float *__restrict__ chan_sum) {
-  __shared__ double red[2][256];
-  const int cg = c / groups, tid = threadIdx.x;
-  const size_t base = ((size_t)blockIdx.y * c + (size_t)blockIdx.x * cg) * n;
-  const int quads = cg * (n / 4);
-  const f32x4 *x4 = (const f32x4 *)(x + base), *a4 = add ? (const f32x4 *)(add + base) : nullptr;
-  double s1 = 0.0, s2 = 0.0;
-  for (int i = tid; i < quads; i += 256) {
-    f32x4 v = x4[i];
-    if (a4) v += a4[i];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      s1 += (double)v[e];
-      s2 += (double)v[e] * (double)v[e];
-    }
-  }
-  red[0][tid] = s1;
-  red[1][tid] = s2;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) {
-      red[0][tid] += red[0][tid + o];
-      red[1][tid] += red[1][tid + o];
-    }
-    __syncthreads();
-  }
-  const double cnt = (double)cg * n, mean = red[0][0] / cnt;
-  double var = red[1][0] / cnt - mean * mean;
-  var = var > 0.0 ? var : 0.0;
-  const double rstd = 1.0 / sqrt(var + (double)eps);
-  f32x4 *o4 = (f32x4 *)(out + base);
-  const int qpc = n / 4, wave = tid >> 6, lane = tid & 63;
-  for (int cl = wave; cl < cg; cl += 4) {
-    const int ch = blockIdx.x * cg + cl;
-    const float a = (float)((double)gamma[ch] * rstd), s = (float)((double)beta[ch] - mean * (double)gamma[ch] * rstd);
-    double sum = 0.0;
-    for (int i = lane; i < qpc; i += 64) {
-      f32x4 v = x4[cl * qpc + i];
-      if (a4) v += a4[cl * qpc + i];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float t = __builtin_fmaf(a, v[e], s);
-        v[e] = t / (1.0f + expf(-t));
-        sum += (double)v[e];
-      }
-      o4[cl * qpc + i] = v;
-    }
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) sum += __shfl_xor(sum, o);
-    if (lane == 0) chan_sum[(size_t)blockIdx.y * c + ch] = (float)sum;
-  }
-}
-
 }  // namespace
 
 GLDM_API int gldm_point_attention_fused(const float *q, const float *k, const float *v, int b, int c, int n, int exact_f32,
@@ -444,25 +366,4 @@ GLDM_API int gldm_point_attention_fused(const float *q, const float *k, const fl
   if ((((size_t)q | (size_t)k | (size_t)v | (size_t)out) & 15)) return GLDM_ERR_INVALID_ARG;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   return exact_f32 ? launch_fused<2, true>(q, k, v, b, c, n, out, st) : launch_fused<2, false>(q, k, v, b, c, n, out, st);
-}
-
-GLDM_API int gldm_groupnorm_affine(const float *y, const float *coef, int b, int c, int r, float *x, gldm_stream_t stream) {
-  if (!y || !coef || !x || b <= 0 || c <= 0 || r <= 0) return GLDM_ERR_INVALID_ARG;
-  if ((((size_t)y | (size_t)x) & 15)) return GLDM_ERR_INVALID_ARG;
-  const long long vox = (long long)r * r * r;
-  if (vox % 4 || r > 64 || (long long)b * c > 0x7fffffffll) return GLDM_ERR_UNSUPPORTED;
-  const int quads = (int)(vox / 4);
-  const int gx = quads >= 4096 ? 4 : 1;
-  hipLaunchKernelGGL(gn_affine_kernel, dim3(b * c, gx), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), y, coef, quads, x);
-  return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
-}
-
-GLDM_API int gldm_groupnorm_swish_points_sum(const float *x, const float *add, const float *gamma, const float *beta, int b, int c,
-                                             int n, int groups, float eps, float *out, float *chan_sum, gldm_stream_t stream) {
-  if (!x || !gamma || !beta || !out || !chan_sum || b <= 0 || c <= 0 || n <= 0 || groups <= 0) return GLDM_ERR_INVALID_ARG;
-  if ((((size_t)x | (size_t)add | (size_t)out) & 15)) return GLDM_ERR_INVALID_ARG;   // 16-byte vector accesses
-  if (c % groups || c / groups > 128 || n % 4 || b > 65535) return GLDM_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(gn_swish_points_sum_kernel, dim3(groups, b), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, add,
-                     gamma, beta, c, n, groups, eps, out, chan_sum);
-  return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
 }

@@ -3,7 +3,7 @@ PVCNN encoder: the wide SharedMLP layers + head (gldm_pointwise_mlp*: MFMA GEMMs
 operands), the narrow point-branch convs (gldm_pointwise_small) and the Linear over the point axis (gldm_linear_rows).
 Layer shapes outside those kernels' sets (PVCNN2 / PointNet++ widths such as 384 -> 256 over 128 centres) run in the
 any-shape f32-MFMA kernel (gldm_pointwise_any); since round 4 nothing here reaches rocBLAS / MIOpen, and the package no
-longer sets MIOPEN_FIND_MODE.  Voxel convs have no library path either (csrc/voxel_conv.hip, with a direct VALU kernel
+longer sets MIOPEN_FIND_MODE.  Voxel convs have no library path either (csrc/conv3d.hip, with a direct VALU kernel
 for shapes without an MFMA instantiation).  Never a CPU path: CPU tensors are rejected like everywhere else in this package.
 """
 import ctypes

@@ -8,7 +8,7 @@ from . import _lib as L
 from .r1d_pack import mfma_a_fragments
 
 SUPPORTED = {(3, 6), (6, 3), (2, 8), (4, 4), (8, 2), (4, 8), (2, 4), (4, 2), (1, 4), (2, 2), (4, 1), (8, 1),
-             (16, 2), (8, 4)}  # (cout/16, r/4) instantiated in voxel_conv.hip (the last two as two half-width launches)
+             (16, 2), (8, 4)}  # (cout/16, r/4) instantiated in conv3d.hip (the last two as two half-width launches)
 
 
 # (cout, r) of the plane-staging split-f16 kernel (gldm_conv3d_k3_f16x2; cin % 16 == 0): the shipped encoder's two shapes
@@ -17,7 +17,7 @@ SPLIT_SHAPES = {(48, 24), (96, 12), (32, 32), (64, 32), (32, 16), (64, 16), (128
 
 
 def conv_supported(cout, r):
-    """Shapes launch_conv / launch_conv_halves have an f32-MFMA instantiation for (csrc/voxel_conv.hip; gldm_conv3d_k3[_cl])."""
+    """Shapes launch_conv / launch_conv_halves have an f32-MFMA instantiation for (csrc/conv3d.hip; gldm_conv3d_k3[_cl])."""
     return cout % 16 == 0 and r % 4 == 0 and (cout // 16, r // 4) in SUPPORTED
 
 
@@ -31,7 +31,7 @@ def pack_conv3d(weight):
 
 
 def split_conv_supported(cin, cout, r):
-    """Shapes conv3d_k3_f16x2_impl dispatches (csrc/voxel_conv.hip; gldm_conv3d_k3_f16x2[_gn]: SPLIT_SHAPES with cin % 16 == 0,
+    """Shapes conv3d_k3_f16x2_impl dispatches (csrc/conv3d.hip; gldm_conv3d_k3_f16x2[_gn]: SPLIT_SHAPES with cin % 16 == 0,
     and the shipped encoder's first conv 3 -> 48 @ 24^3 with K = 81 packed into three 32-deep blocks)."""
     if (cin, cout, r) == (3, 48, 24):
         from .numerics import split_enabled
