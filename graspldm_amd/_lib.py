@@ -85,6 +85,8 @@ _SIGNATURES = {
     "gldm_sa_mlp_forward_f16x2_pre": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "gldm_ball_query_multi": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "gldm_group_max_concat": [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp],
+    "gldm_unet1d_supported": [_vp, _i],
+    "gldm_unet1d": [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
 }
 
 

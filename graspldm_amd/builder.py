@@ -8,11 +8,11 @@ from .diffusion import GaussianDiffusion1D
 from .grasp_classifier import PointsBasedGraspClassifier
 from .grasp_ldm import GraspLatentDDM
 from .grasp_vae import GraspCVAE
-from .resnets import ClassTimeConditionedResNet1D, ResNet1D, TimeConditionedResNet1D
+from .resnets import ClassTimeConditionedResNet1D, ResNet1D, TimeConditionedResNet1D, Unet1D
 
 DIFFUSION_MODELS = {"GaussianDiffusion1D": GaussianDiffusion1D, "TimeConditionedResNet1D": TimeConditionedResNet1D,
                     "ClassTimeConditionedResNet1D": ClassTimeConditionedResNet1D}
-STANDARD_MODULES = {"ResNet1D": ResNet1D}
+STANDARD_MODULES = {"ResNet1D": ResNet1D, "Unet1D": Unet1D}
 ALL_MODELS = {"GraspCVAE": GraspCVAE, "GraspLatentDDM": GraspLatentDDM, "PointsBasedGraspClassifier": PointsBasedGraspClassifier,
               **STANDARD_MODULES, **DIFFUSION_MODELS}
 

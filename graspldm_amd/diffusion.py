@@ -176,7 +176,7 @@ class GaussianDiffusion1D(nn.Module):
         model = self.model
         model._cond_rows_of(z_cond)
         eng = model.engine(device)
-        cemb = eng.cond_embed(z_cond.to(device))
+        cemb = eng.cond_embed(z_cond.to(device) if z_cond is not None else None)
         # class-conditioned denoiser: the label travels in kwargs (cls_cond or metas["mode_cls"]) to the model
         # call in the reference (gaussian_diffusion.py:271); here it becomes one [n, emb] operand of the launch
         semb = model.class_embedding(kwargs.get("cls_cond"), n=batch_size, metas=kwargs.get("metas")) \

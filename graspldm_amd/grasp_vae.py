@@ -8,16 +8,22 @@ import torch
 from torch import nn
 
 from .pc_encoders import PVCNN2Encoder, PVCNNEncoder
-from .resnets import ResNet1D
+from .resnets import ResNet1D, Unet1D
 
 
 def _get(cfg, key):
     return cfg[key] if isinstance(cfg, dict) else getattr(cfg, key)
 
 
+def _rows_of(cond):
+    """Rows of a conditioning latent: 0 for none (a Unet1D core without input conditioning), 1 for [n, Dc], R for [n, R, Dc]."""
+    return 0 if cond is None else (1 if cond.ndim == 2 else cond.shape[1])
+
+
 class ConditionalGraspPoseDecoder(nn.Module):
-    """grasp_vae.py:353-436: Linear(D->R) -> ResNet1D -> tmrp(6) / class_logits(1), one HIP launch."""
-    MODELS = {"ResNet1D": ResNet1D}
+    """grasp_vae.py:353-436: Linear(D->R) -> ResNet1D -> tmrp(6) / class_logits(1), one HIP launch.  With a Unet1D core:
+    in_layer, the fused Unet1D kernel, and the 7-row head as three launches (unet1d.UnetCoreEngine)."""
+    MODELS = {"Unet1D": Unet1D, "ResNet1D": ResNet1D}
 
     def __init__(self, config, in_features, feature_resolution, num_output_qualities=None):
         super().__init__()
@@ -39,6 +45,14 @@ class ConditionalGraspPoseDecoder(nn.Module):
     def _get_engine(self, device, rows):
         from ._cache import params_key, publish
         key = params_key(self.parameters(), device, rows)
+        if isinstance(self.net, Unet1D):
+            if self._engine is None or self._key != key:
+                from .unet1d import UnetCoreEngine
+                self.net.cond_rows = rows
+                sd = {k: v.detach().float().cpu() for k, v in self.state_dict().items()}
+                self._engine, self._key = UnetCoreEngine.decoder(self.net.engine(device), sd), key
+                publish(device)
+            return self._engine
         if self._engine is None or self._key != key:
             from .r1d import R1dEngine, pack_resnet1d
             sd = {k: v.detach().float().cpu() for k, v in self.state_dict().items()}
@@ -55,22 +69,26 @@ class ConditionalGraspPoseDecoder(nn.Module):
     def forward(self, z_h, cond=None, samples_per_cond=1):
         if not z_h.is_cuda:
             raise RuntimeError("z_h must be a CUDA tensor (graspldm_amd has no CPU path)")
-        eng = self._get_engine(z_h.device, 1 if cond.ndim == 2 else cond.shape[1])
+        eng = self._get_engine(z_h.device, _rows_of(cond))
         return eng.decode(z_h, eng.cond_embed(cond), samples_per_cond)
 
 
 class ConditionalGraspPoseEncoder(nn.Module):
     """grasp_vae.py:439-536: Linear(D->R) -> ResNet1D -> Linear(R->L).  On the fused path (GraspCVAE.encode) the
-    bottleneck's mu / logvar Linears ride on the same launch as the folded head (r1d_pack: encoder=)."""
+    bottleneck's mu / logvar Linears ride on the same launch as the folded head (r1d_pack: encoder=).  With a Unet1D
+    core the folded head is one launch behind the fused Unet1D kernel (unet1d.UnetCoreEngine)."""
+    MODELS = {"Unet1D": Unet1D, "ResNet1D": ResNet1D}
 
     def __init__(self, config, latent_size, feature_resolution=16):
         super().__init__()
+        assert _get(config, "type") in self.MODELS, (
+            f"Cannot build GraspPoseEncoder of model_type: {_get(config, 'type')} from supported models: {self.MODELS}")
         args = dict(_get(config, "args"))
         self.in_features = args.pop("in_features")
         self.out_features = latent_size
         self.feature_resolution = feature_resolution
         self.in_layer = nn.Linear(self.in_features, feature_resolution)
-        self.net = ResNet1D(dim=feature_resolution, **args)
+        self.net = self.MODELS[_get(config, "type")](dim=feature_resolution, **args)
         self.out_layer = nn.Linear(self.net.out_features, self.out_features)
         self._engine, self._key = None, None          # fused with a bottleneck
         self._engine_plain, self._key_plain = None, None  # out_layer only (forward() on its own)
@@ -78,6 +96,11 @@ class ConditionalGraspPoseEncoder(nn.Module):
     def _pack(self, device, rows, bottleneck):
         from .r1d import R1dEngine, pack_resnet1d
         sd = {k: v.detach().float().cpu() for k, v in self.state_dict().items()}
+        if isinstance(self.net, Unet1D):
+            from .unet1d import UnetCoreEngine
+            self.net.cond_rows = rows
+            bn = {k: v.detach().float().cpu() for k, v in bottleneck.state_dict().items()} if bottleneck is not None else None
+            return UnetCoreEngine.encoder(self.net.engine(device), sd, bn)
         lz = self.out_features
         if bottleneck is not None:
             bn = {k: v.detach().float().cpu() for k, v in bottleneck.state_dict().items()}
@@ -108,7 +131,7 @@ class ConditionalGraspPoseEncoder(nn.Module):
         """x [n,1,D], cond [n / samples_per_cond, R, Dc] -> [n,1,L] (grasp_vae.py:518-536)."""
         if not x.is_cuda:
             raise RuntimeError("x must be a CUDA tensor (graspldm_amd has no CPU path)")
-        eng = self._get_engine(x.device, 1 if cond.ndim == 2 else cond.shape[1])
+        eng = self._get_engine(x.device, _rows_of(cond))
         out, _, _ = eng.encode(x.reshape(x.shape[0], -1), eng.cond_embed(cond), samples_per_cond, want_z=False)
         return out.unsqueeze(-2)
 
@@ -219,7 +242,7 @@ class GraspCVAE(nn.Module):
             raise RuntimeError(f"{n} grasps do not split over {b} clouds")
         z_pc = self.encode_pc(xyz)
         ge = self.encoder.grasp_encoder
-        eng = ge._get_engine(xyz.device, 1 if z_pc.ndim == 2 else z_pc.shape[1], self.bottleneck)
+        eng = ge._get_engine(xyz.device, _rows_of(z_pc), self.bottleneck)
         mu, logvar, z = eng.encode(grasp, eng.cond_embed(z_pc), n // b, eps=eps, mix=mix, eps_times_std=eps_times_std,
                                    want_z=want_z)
         return mu, logvar, z, z_pc, n // b

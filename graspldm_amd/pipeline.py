@@ -7,14 +7,18 @@ from .synthetic import load_synthetic_weights
 
 
 def fpc_model_config(n_points=1024, scheduler="ddim", latent=4, pc_latent=64, pc_channels=3, encoder="PVCNNEncoder",
-                     encoder_scale=None, use_global_attention=False, use_local_attention=False):
+                     encoder_scale=None, use_global_attention=False, use_local_attention=False, vae_core="ResNet1D"):
     """configs/generation/fpc/fpc_1a_latentc3_z4_pc64_180k.py:25-153 as data.  encoder="PVCNN2Encoder": the same
     experiment conditioned by the SET-ABSTRACTION encoder family of the registry (pc_encoders.py:139-197 in its repaired
     form: PointNet++ set abstraction + PVConv + feature propagation, then the same head); encoder_scale =
     (scale_channels, scale_voxel_resolution), default the shipped (0.75, 0.75) / PVCNN2's own width (1, 1).
     use_global_attention: the encoder's attention block over all points (pc_encoders.py:65-69), off in the shipped config.
     use_local_attention (PVCNN2Encoder only): voxel attention inside the PVConv of the second set-abstraction stage
-    (pc_encoders.py:152-153, ext/pvcnn/utils.py:123); the key is absent from the config when the flag is off."""
+    (pc_encoders.py:152-153, ext/pvcnn/utils.py:123); the key is absent from the config when the flag is off.
+    vae_core="Unet1D": the pose decoder and the grasp encoder on the registry's other 1-D core (grasp_vae.py:356,440), with
+    dim_mults (1, 2, 4, 8) and no time conditioning; the denoiser is unchanged."""
+    if vae_core not in ("ResNet1D", "Unet1D"):
+        raise ValueError(f"vae_core must be ResNet1D or Unet1D, not {vae_core!r}")
     rn = dict(block_channels=(32, 64, 128, 256), input_conditioning_dims=pc_latent, resnet_block_groups=4, dropout=0.1)
     if use_local_attention and encoder != "PVCNN2Encoder":
         raise ValueError("use_local_attention is an argument of PVCNN2Encoder only")
@@ -31,11 +35,13 @@ def fpc_model_config(n_points=1024, scheduler="ddim", latent=4, pc_latent=64, pc
             **(dict(use_local_attention=True) if use_local_attention else {})))
     else:
         raise ValueError(f"encoder must be PVCNNEncoder or PVCNN2Encoder, not {encoder!r}")
+    core = rn if vae_core == "ResNet1D" else dict(dim_mults=(1, 2, 4, 8), input_conditioning_dims=pc_latent,
+                                                  is_time_conditioned=False, resnet_block_groups=4)
     vae = dict(model=dict(type="GraspCVAE", args=dict(
         grasp_latent_size=latent, pc_latent_size=pc_latent,
         pc_encoder_config=enc,
-        grasp_encoder_config=dict(type="ResNet1D", args=dict(in_features=7, **rn)),
-        decoder_config=dict(type="ResNet1D", args=dict(**rn)),
+        grasp_encoder_config=dict(type=vae_core, args=dict(in_features=7, **core)),
+        decoder_config=dict(type=vae_core, args=dict(**core)),
         loss_config=dict(reconstruction_loss=dict(type="GraspReconstructionLoss"), latent_loss=dict(type="VAELatentLoss")),
         num_output_qualities=0, intermediate_feature_resolution=16)))
     ddm = dict(model=dict(type="GraspLatentDDM", args=dict(

@@ -255,6 +255,157 @@ class ClassTimeConditionedResNet1D(TimeConditionedResNet1D):
                            sched_kind=SCHED_NONE, sample_emb=semb)
 
 
-__all__ = ["ResNet1D", "TimeConditionedResNet1D", "ClassTimeConditionedResNet1D", "ResnetBlock", "LinearAttention", "LayerNorm",
-           "WeightStandardizedConv2d", "RandomOrLearnedSinusoidalPosEmb"]
+class SinusoidalPosEmb(nn.Module):
+    """resnets.py:29-41 (no parameters; evaluated into the [T, E] table at pack time)."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.dim = dim
+
+
+class Attention(nn.Module):
+    """resnets.py:238-261: full softmax over positions; to_out is one Conv1d, no LayerNorm behind it."""
+
+    def __init__(self, dim, heads=4, dim_head=32):
+        super().__init__()
+        self.scale = dim_head ** -0.5
+        self.heads = heads
+        hidden = dim_head * heads
+        self.to_qkv = nn.Conv1d(dim, hidden * 3, 1, bias=False)
+        self.to_out = nn.Conv1d(hidden, dim, 1)
+
+
+class Unet1D(nn.Module):
+    """resnets.py:622-857: parameter holder in the reference's layout; forward is the fused kernel (csrc/unet1d.hip)."""
+
+    def __init__(self, dim: int, init_dim: int = None, out_channels: int = None, dim_mults: Sequence = (1, 2, 4, 8),
+                 channels: int = 1, input_conditioning_dims: int = None, is_self_conditioned: bool = False,
+                 is_time_conditioned: bool = True, resnet_block_groups: int = 8, learned_variance: bool = False,
+                 learned_sinusoidal_cond: bool = False, random_fourier_features: bool = False,
+                 learned_sinusoidal_dim: int = 16, dropout=None) -> None:
+        super().__init__()
+        if is_self_conditioned:
+            raise NotImplementedError("is_self_conditioned (resnets.py:677-678,801-803) is not on the generation hot path")
+        if learned_variance or (out_channels is not None and out_channels != 1):
+            raise NotImplementedError("learned_variance / out_channels != 1 (resnets.py:772-773): the kernel has one output channel")
+        if channels != 1:
+            raise NotImplementedError("channels must be 1 (resnets.py:678-681): the kernel reads one input row per sample")
+        if init_dim is not None and init_dim != dim:
+            raise NotImplementedError("init_dim must be None or equal to dim: final_res_block takes 2 * dim channels "
+                                      "(resnets.py:775,854), so anything else cannot run in the reference either")
+        if dim not in (16, 32):
+            raise NotImplementedError(f"dim must be 16 or 32 (widths are multiples of 16, at most 256), not {dim}")
+        dim_mults = tuple(dim_mults)
+        if not 2 <= len(dim_mults) <= 4:
+            raise NotImplementedError(f"2 to 4 dim_mults are supported, not {len(dim_mults)}")
+        dims = [dim] + [dim * m for m in dim_mults]
+        if any(w % 16 or not 16 <= w <= 256 for w in dims):
+            raise NotImplementedError(f"every width must be a multiple of 16 between 16 and 256, not {dims[1:]}")
+        if resnet_block_groups not in (4, 8):
+            raise NotImplementedError(f"resnet_block_groups must be 4 or 8, not {resnet_block_groups}")
+        self.channels = channels
+        self.in_features = self.out_features = dim
+        self.is_self_conditioned = False
+        self.dim_mults, self.groups = dim_mults, resnet_block_groups
+        self.init_conv = nn.Conv1d(channels, dim, 7, padding=3)
+        in_out = list(zip(dims[:-1], dims[1:]))
+        block_klass = partial(ResnetBlock, groups=resnet_block_groups)
+        self.emb_dim = emb_dim = dim * 4
+        self.dropout = nn.Dropout(p=dropout, inplace=True) if dropout is not None else None
+        self.random_or_learned_sinusoidal_cond = learned_sinusoidal_cond or random_fourier_features
+        if is_time_conditioned:
+            self.is_time_conditioned = True
+            if self.random_or_learned_sinusoidal_cond:
+                pos, fourier_dim = RandomOrLearnedSinusoidalPosEmb(learned_sinusoidal_dim, random_fourier_features), learned_sinusoidal_dim + 1
+            else:
+                pos, fourier_dim = SinusoidalPosEmb(dim), dim
+            self.time_mlp = nn.Sequential(pos, nn.Linear(fourier_dim, emb_dim), nn.GELU(), nn.Linear(emb_dim, emb_dim))
+        else:
+            self.is_time_conditioned = False
+            self.time_mlp = None
+        if input_conditioning_dims is not None:
+            self.is_input_conditioned = True
+            self.input_emb_layers = nn.Sequential(nn.Linear(input_conditioning_dims, emb_dim), nn.SiLU(),
+                                                  nn.Linear(emb_dim, emb_dim))
+        else:
+            self.is_input_conditioned = False
+            self.input_emb_layers = None
+        self.downs, self.ups = nn.ModuleList([]), nn.ModuleList([])
+        for ind, (dim_in, dim_out) in enumerate(in_out):
+            is_last = ind >= len(in_out) - 1
+            self.downs.append(nn.ModuleList([
+                block_klass(dim_in, dim_in, emb_dim=emb_dim),
+                block_klass(dim_in, dim_in, emb_dim=emb_dim),
+                Residual(PreNorm(dim_in, LinearAttention(dim_in))),
+                nn.Conv1d(dim_in, dim_out, 4, 2, 1) if not is_last else nn.Conv1d(dim_in, dim_out, 3, padding=1)]))
+        mid_dim = dims[-1]
+        self.mid_block1 = block_klass(mid_dim, mid_dim, emb_dim=emb_dim)
+        self.mid_attn = Residual(PreNorm(mid_dim, Attention(mid_dim)))
+        self.mid_block2 = block_klass(mid_dim, mid_dim, emb_dim=emb_dim)
+        for ind, (dim_in, dim_out) in enumerate(reversed(in_out)):
+            is_last = ind == len(in_out) - 1
+            self.ups.append(nn.ModuleList([
+                block_klass(dim_out + dim_in, dim_out, emb_dim=emb_dim),
+                block_klass(dim_out + dim_in, dim_out, emb_dim=emb_dim),
+                Residual(PreNorm(dim_out, LinearAttention(dim_out))),
+                nn.Sequential(nn.Upsample(scale_factor=2, mode="nearest"), nn.Conv1d(dim_out, dim_in, 3, padding=1))
+                if not is_last else nn.Conv1d(dim_out, dim_in, 3, padding=1)]))
+        self.out_channels = 1
+        self.final_res_block = block_klass(dim * 2, dim, emb_dim=emb_dim)
+        self.final_conv = nn.Conv1d(dim, self.out_channels, 1)
+        self._engine = None
+        self._engine_key = None
+        self.cond_rows = 1 if self.is_input_conditioned else 0
+        self.max_timesteps = 1000
+
+    def engine(self, device, **unused):
+        from ._cache import params_key, publish
+        from .unet1d import UnetEngine
+        key = params_key(self.parameters(), device, self.max_timesteps, self.cond_rows)
+        if self._engine is None or self._engine_key != key:
+            sd = {k: v.detach().float().cpu() for k, v in self.state_dict().items()}
+            self._engine = UnetEngine(sd, self.groups, self.cond_rows, self.is_time_conditioned,
+                                      self.max_timesteps if self.is_time_conditioned else None, device)
+            self._engine_key = key
+            publish(device)
+        return self._engine
+
+    def _cond_rows_of(self, z_cond):
+        if z_cond is None:
+            if self.is_input_conditioned:
+                raise RuntimeError("this Unet1D is input conditioned: z_cond is required (resnets.py:816-817)")
+            rows = 0
+        else:
+            if not self.is_input_conditioned:
+                raise RuntimeError("this Unet1D was built without input_conditioning_dims: it takes no z_cond")
+            rows = 1 if z_cond.ndim == 2 else z_cond.shape[1]
+            if z_cond.ndim == 3 and self.is_time_conditioned:
+                raise NotImplementedError("a 3-D z_cond with time conditioning: the reference adds time_emb [n, E] to input_emb "
+                                          "[n, R, E] untiled (resnets.py:816-822), a broadcast error unless n == R")
+            if rows > 4:
+                raise NotImplementedError(f"z_cond with at most 4 rows is supported, not {rows}")
+        if self.cond_rows != rows:
+            self.cond_rows = rows
+            self._engine = None
+        return rows
+
+    @torch.no_grad()
+    def forward(self, x, *, time=None, z_cond=None, x_self_cond=None, **kwargs):
+        if not x.is_cuda:
+            raise RuntimeError("x must be a CUDA tensor (graspldm_amd has no CPU path)")
+        sample_t = None
+        if self.is_time_conditioned:
+            if time is None:
+                raise TypeError("a time-conditioned Unet1D needs `time` (resnets.py:809-813: time_mlp(None) fails)")
+            tmax = int(time.max())
+            if tmax >= self.max_timesteps:
+                self.max_timesteps = tmax + 1
+            sample_t = time.to(device=x.device, dtype=torch.int32).contiguous()
+        self._cond_rows_of(z_cond)
+        eng = self.engine(x.device)
+        return eng.denoise(x, eng.cond_embed(z_cond), 1, sample_t=sample_t, sched_kind=SCHED_NONE)
+
+
+__all__ = ["ResNet1D", "TimeConditionedResNet1D", "ClassTimeConditionedResNet1D", "Unet1D", "ResnetBlock", "LinearAttention",
+           "Attention", "LayerNorm", "WeightStandardizedConv2d", "RandomOrLearnedSinusoidalPosEmb", "SinusoidalPosEmb"]
 _ = math

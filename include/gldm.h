@@ -679,6 +679,61 @@ int gldm_cls_head(const float *x /*[b,c,n]*/, const void *w1, const float *b1 /*
                   const float *l /*[n]*/, float c0, int b, int c, int rows, int n, int exact_f32, void *workspace,
                   long long workspace_bytes, float *logit /*[b]*/, float *prob /*[b]*/, gldm_stream_t stream);
 
+/* ---- Unet1D (additive; ref: grasp_ldm/models/modules/resnets.py:622-857) ------------------------------------------------
+ * One kernel carries a tile of `tile_samples` samples through the whole U-net and through every sampler step; the skip
+ * stack, the stem's output and the residual stream stay in LDS (csrc/unet1d.hip).  The packed buffer holds the weights and,
+ * at `prog_off`, the network as a PROGRAM of n_ops ops of 16 int32 each (graspldm_amd/unet1d_pack.py writes and
+ * bounds-checks it; LDS offsets in floats, weight offsets in floats from the buffer's start, -1 = absent):
+ *   CONV  {1, src0, c0, pitch_in, src1, c1, dst, pitch_out, M, mode, taps, Lin, Lout, w, bias, add}
+ *         dst[M][col] = W im2col(src0 | src1) + bias + add.  mode 0: taps centred (k = 1 / 3, resnets.py:130,191,748,767);
+ *         1: k = 4, stride 2, pad 1 (Downsample, :75-76); 2: nearest x2 then k = 3, pad 1 (Upsample, :68-72).  A second
+ *         source is the popped skip of an up block (:843-847) or `r` (:854): the concatenation is never built.  W is
+ *         [M/16][K/32][hi|lo][64][8 f16] (split-f16, the layout above) or, with exact_f32, [M/16][K/32][64][8 f32], K running
+ *         over [source][tap][channels padded to 32 with zero columns].  Also computes every ResnetBlock's scale/shift rows
+ *         (:193-202) from the tile's summed SiLU(embedding) columns (Lin = Lout = 1).
+ *   GN    {2, buf, C, pitch, L, gamma, beta, use_scale_shift, add, out, groups}   Block.norm + scale/shift + SiLU (:160-177)
+ *   ATT   {3, x, C, pitch, L, out, ln_buf, y_buf, ln_g, qkv_w, out_w, out_b, ln2_g}  Residual(PreNorm(LinearAttention))
+ *         (:211-235), or with ln2_g = -1 Residual(PreNorm(Attention)) (:238-261); qkv_w rows in head-major order
+ *         [head][q|k|v][32], out_w one [C x 32] matrix per head
+ *   FINAL {4, x, C, pitch, w, b}  final_conv (:776,857)        STEM {5, dst, C, pitch, w, b}  init_conv (:681,805) */
+#define GLDM_UNET1D_MAX_LEVELS 4
+typedef struct gldm_unet1d_desc {
+  int32_t dim, n_levels;
+  int32_t widths[GLDM_UNET1D_MAX_LEVELS + 1]; /* init_dim, then dim * dim_mults                                 */
+  int32_t groups, emb_dim;
+  int32_t cond_rows;    /* R of z_cond [n, R, Dc]; 1 for [n, Dc]; 0 without input conditioning                  */
+  int32_t time_cond;    /* is_time_conditioned (then cond_rows <= 1: :816-822 adds the two embeddings untiled)  */
+  int32_t has_emb;      /* time_cond || cond_rows > 0: the ResnetBlocks apply scale/shift                       */
+  int32_t exact_f32;    /* packed under numerics.f32_only(): f32 fragments, v_mfma_f32_16x16x4_f32              */
+  int32_t seq_len;      /* L the program's LDS map was laid out for                                             */
+  int32_t tile_samples; /* samples per workgroup, sized on the host from the LDS the net needs                  */
+  int32_t lds_floats;   /* dynamic LDS of a workgroup                                                           */
+  int32_t prog_off, n_ops;
+  int32_t o_lat, o_eps; /* [tile_samples][L] current latent row / network output                                */
+  int32_t o_emb;        /* [emb_dim][18] summed SiLU(embedding) per sample column                               */
+  int32_t o_ss;         /* [2 C][tile_samples] scale (+1, summed over R) and shift rows of the running block    */
+  int32_t o_qkv, o_o, o_a; /* attention: one head's q|k|v rows [96][pitch], its output [32][pitch], A [S][L][L]  */
+  int32_t n_floats;     /* length of the packed buffer                                                          */
+} gldm_unet1d_desc;
+
+/* 0 if gldm_unet1d runs this architecture at this length, GLDM_ERR_UNSUPPORTED otherwise (GLDM_ERR_INVALID_ARG for a null
+ * descriptor); decided from the header fields alone, before any HIP call.  dim in {16, 32}; 2..4 levels; widths
+ * multiples of 16, at most 256; groups 4 or 8; emb_dim = 4 dim; cond_rows <= 4 (<= 1 with time conditioning); 2 <= L <= 16
+ * with L % 2^(levels-1) == 0 (the reference fails at the first skip concat otherwise, :843). */
+int gldm_unet1d_supported(const gldm_unet1d_desc *desc, int seq_len);
+
+/* ref: resnets.py:779-857 (Unet1D.forward) and gaussian_diffusion.py:232-277 (the sample loop), fused like gldm_denoise:
+ * ONE launch runs all n_steps for every row.  sched_kind NONE with n_steps = 1 returns the module's output (sample_t
+ * [n] then gives a per-sample timestep); DDIM / DDPM read the coefficient rows documented at GLDM_SCHED_COEF_STRIDE;
+ * step_noise [n_steps, n, L] is read by DDPM steps with coef[7] != 0.  temb [T, emb_dim] is the host-evaluated time_mlp
+ * table (:710-715), cemb [n_cond, R, emb_dim] = input_emb_layers(z_cond) (:724-728), row i conditioned on
+ * cemb[i / samples_per_cond]; either is NULL when the net has no such conditioning.  No workspace. */
+int gldm_unet1d(const gldm_unet1d_desc *desc, const float *weights, const float *temb, const float *cemb,
+                int samples_per_cond, const float *x_in /*[n,1,L]*/, int n_samples, int seq_len,
+                const int32_t *timesteps /*[n_steps]*/, const int32_t *sample_t, int n_steps, int sched_kind,
+                int clip_sample, const float *sched_coef /*[n_steps,8]*/, const float *step_noise,
+                float *x_out /*[n,1,L]*/, gldm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
