@@ -86,6 +86,9 @@ _SIGNATURES = {
     "gldm_ball_query_multi": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "gldm_group_max_concat": [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp],
     "gldm_unet1d_supported": [_vp, _i],
+    "gldm_grasp_clearance_chunk": [],
+    "gldm_grasp_clearance": [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp],
+    "gldm_select_grasps": [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
     "gldm_unet1d": [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
 }
 

@@ -1,0 +1,177 @@
+"""Geometric filtering and selection of grasp poses (csrc/grasp_select.hip).
+
+  grasp_clearance   gldm_grasp_clearance: how far the open gripper's segments stay from a WHOLE scene cloud (table and
+                    clutter included, 10^5 .. 10^6 points) and how many scene points lie inside the finger-sweep tubes,
+                    per pose.  The geometry is the reference's marker geometry (grasp_ldm/utils/gripper.py:26-47, :80-128),
+                    which the reference only draws.
+  select_grasps     gldm_select_grasps: the best k of a cloud's candidates, or k diverse ones (greedy farthest pose under
+                    the control-point distance of grasp_ldm/losses/loss.py:77-127), one workgroup per cloud.
+  GraspSelection    what a caller asks of `_InferenceBase.select_grasps` (inference.py).
+"""
+import ctypes
+import math
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+
+from . import gripper
+from ._lib import GldmError
+from .dense import _need_cuda
+
+# the envelope of the two entries (csrc/grasp_select.hip; GLDM_ERR_UNSUPPORTED outside it)
+MAX_SCENE_POINTS = 1 << 24
+MAX_SEGMENTS = 8
+MAX_CANDIDATES = 2048
+MAX_CONTROL_POINTS = 64
+CHUNK = 256   # scene points staged per step (gldm_grasp_clearance_chunk)
+SCORE_BY = ("confidence", "success", "product")
+
+
+def clearance_supported(ns, sb, ss):
+    """The shape limits of gldm_grasp_clearance: ns scene points per cloud, sb body and ss sweep segments."""
+    return 1 <= ns <= MAX_SCENE_POINTS and 1 <= sb <= MAX_SEGMENTS and 0 <= ss <= MAX_SEGMENTS
+
+
+def select_supported(g, k, np_):
+    """The shape limits of gldm_select_grasps: g candidates per cloud, k picks, np_ control points."""
+    return 1 <= k <= g <= MAX_CANDIDATES and 1 <= np_ <= MAX_CONTROL_POINTS
+
+
+def _check_finite(named):
+    """One device reduction and one read-back for all tensors: GldmError naming the first that holds a non-finite value."""
+    flags = torch.stack([torch.isfinite(t).all() for _, t in named]).cpu()
+    for (name, _), ok in zip(named, flags.tolist()):
+        if not ok:
+            raise GldmError(f"{name} hold non-finite values")
+
+
+def _host_floats(x, name, cols):
+    """A small tensor / nested sequence -> (ctypes float array, rows); the segment and control-point arguments of the two
+    entries are host arrays (they travel as kernel arguments)."""
+    t = torch.as_tensor(x, dtype=torch.float32).detach().cpu().reshape(-1)
+    if t.numel() % cols:
+        raise RuntimeError(f"{name} must be [n,{cols // 3},3]" if cols == 6 else f"{name} must be [n,3]")
+    if not bool(torch.isfinite(t).all()):
+        raise GldmError(f"{name} hold non-finite values")
+    return (ctypes.c_float * max(1, t.numel()))(*t.tolist()), t.numel() // cols
+
+
+def _poses(H, name="H"):
+    _need_cuda(H, name)
+    if H.ndim == 3:
+        H = H.unsqueeze(0)
+    if H.ndim != 4 or H.shape[-2:] != (4, 4) or H.shape[0] < 1 or H.shape[1] < 1:
+        raise RuntimeError(f"{name} must be [B,G,4,4] (or [G,4,4] for one cloud), not {tuple(H.shape)}")
+    return H.contiguous().float()
+
+
+def grasp_clearance(scene, H, *, body_segments=None, sweep_segments=None, sweep_radius=gripper.SWEEP_RADIUS,
+                    max_clearance=0.05):
+    """scene [B, Ns, 3] (or [Ns, 3]) in the frame of the poses H [B, G, 4, 4] (or [G, 4, 4]) -> (clearance [B, G] f32,
+    contacts [B, G] int32).  clearance = min(max_clearance, distance of the nearest scene point to the nearest body segment)
+    with the point taken into the gripper frame, q = R^T (p - t); contacts = scene points within sweep_radius of a sweep
+    segment.  body_segments [Sb, 2, 3] default to gripper.OPEN_SEGMENTS, sweep_segments [Ss, 2, 3] to gripper.SWEEP_SEGMENTS
+    (an empty list: no contact test).  max_clearance is what makes the broad phase possible: a point farther than the
+    gripper's bounding sphere plus max_clearance is skipped, so it also bounds what a caller can ask of the result."""
+    from . import _lib as L
+    _need_cuda(scene, "scene")
+    H = _poses(H)
+    if scene.ndim == 2:
+        scene = scene.unsqueeze(0)
+    if scene.ndim != 3 or scene.shape[-1] != 3 or scene.shape[0] != H.shape[0]:
+        raise RuntimeError(f"scene must be [B,Ns,3] with B = {H.shape[0]} clouds (or [Ns,3] for one), not {tuple(scene.shape)}")
+    if scene.device != H.device:
+        raise RuntimeError("scene and H must live on the same device")
+    body, sb = _host_floats(gripper.OPEN_SEGMENTS if body_segments is None else body_segments, "body_segments", 6)
+    sweep, ss = _host_floats(gripper.SWEEP_SEGMENTS if sweep_segments is None else sweep_segments, "sweep_segments", 6)
+    b, g = H.shape[:2]
+    ns = scene.shape[1]
+    if not clearance_supported(ns, sb, ss):
+        raise NotImplementedError(f"gldm_grasp_clearance takes 1..{MAX_SCENE_POINTS} scene points per cloud, 1..{MAX_SEGMENTS} "
+                                  f"body and 0..{MAX_SEGMENTS} sweep segments, not Ns={ns}, Sb={sb}, Ss={ss}")
+    if not (math.isfinite(max_clearance) and max_clearance > 0) or not (math.isfinite(sweep_radius) and sweep_radius >= 0):
+        raise ValueError("max_clearance must be > 0 and sweep_radius >= 0")
+    scene = scene.contiguous().float()
+    _check_finite((("the scene points", scene), ("the grasp poses", H)))
+    clearance = torch.empty(b, g, dtype=torch.float32, device=H.device)
+    contacts = torch.empty(b, g, dtype=torch.int32, device=H.device)
+    with torch.cuda.device(H.device):
+        L.call("gldm_grasp_clearance", L.ptr(scene), L.ptr(H), b, g, ns, body, sb, sweep if ss else None, ss,
+               ctypes.c_float(sweep_radius), ctypes.c_float(max_clearance), L.ptr(clearance), L.ptr(contacts),
+               L.current_stream(H.device))
+    return clearance, contacts
+
+
+def select_grasps(H, score, keep=None, k=None, diverse=False, control_points=None, min_separation=0.0):
+    """Which k of each cloud's candidates to hand on: H [B, G, 4, 4] (or [G, 4, 4]), score [B, G], keep [B, G] bool or None
+    -> (index [B, k] int32, -1 behind the last pick; count [B] int32; gap [B, k] f32).
+    diverse=False: the kept candidates by falling score (lowest index first on a tie); gap is 0.
+    diverse=True: the best-scored kept candidate first, then repeatedly the one whose control points lie farthest (mean
+    squared distance, the reference's pose metric) from every pick so far; stops early once that distance falls below
+    min_separation^2.  gap = RMS control-point distance (metres) of a pick to the nearest earlier one, +inf for the first.
+    k defaults to G; control_points [Np, 3] to gripper.control_points(16)."""
+    from . import _lib as L
+    H = _poses(H)
+    b, g = H.shape[:2]
+    _need_cuda(score, "score")
+    score = score.reshape(b, g).contiguous().float()
+    k = g if k is None else int(k)
+    ctrl, np_ = _host_floats(gripper.control_points(16) if control_points is None else control_points, "control_points", 3)
+    if not select_supported(g, k, np_):
+        raise NotImplementedError(f"gldm_select_grasps takes 1 <= k <= G <= {MAX_CANDIDATES} candidates per cloud and "
+                                  f"1..{MAX_CONTROL_POINTS} control points, not k={k}, G={g}, Np={np_}")
+    if not (math.isfinite(min_separation) and min_separation >= 0):
+        raise ValueError("min_separation must be >= 0")
+    if keep is not None:
+        _need_cuda(keep, "keep")
+        keep = keep.reshape(b, g).to(torch.uint8).contiguous()
+    _check_finite((("the grasp poses", H), ("the scores", score)))
+    index = torch.empty(b, k, dtype=torch.int32, device=H.device)
+    count = torch.empty(b, dtype=torch.int32, device=H.device)
+    gap = torch.empty(b, k, dtype=torch.float32, device=H.device)
+    with torch.cuda.device(H.device):
+        L.call("gldm_select_grasps", L.ptr(H), L.ptr(score), L.ptr(keep), b, g, ctrl, np_, k, int(bool(diverse)),
+               ctypes.c_float(min_separation), L.ptr(index), L.ptr(count), L.ptr(gap), L.current_stream(H.device))
+    return index, count, gap
+
+
+@dataclass(frozen=True)
+class GraspSelection:
+    """What to keep of a result dict (`_InferenceBase.select_grasps`).  Filters, cheapest first: min_confidence on the
+    decoder's confidence; collision_free (clearance of the open gripper to the scene > body_radius) and min_contacts (scene
+    points between the fingers) from one clearance launch; min_success on the classifier's probability, scored for the
+    survivors only.  Then top_k (None: every survivor) by `score_by`, or `diverse` ones at least min_separation apart."""
+    min_confidence: Optional[float] = None
+    min_success: Optional[float] = None
+    collision_free: bool = False
+    body_radius: float = gripper.BODY_RADIUS
+    min_contacts: int = 0
+    top_k: Optional[int] = None
+    diverse: bool = False
+    min_separation: float = 0.0
+    score_by: str = "confidence"
+
+    def __post_init__(self):
+        for name in ("min_confidence", "min_success"):
+            v = getattr(self, name)
+            if v is not None and not (isinstance(v, (int, float)) and 0.0 <= v <= 1.0):
+                raise ValueError(f"{name} must lie in [0, 1] (or be None), not {v!r}")
+        if not (isinstance(self.body_radius, (int, float)) and math.isfinite(self.body_radius) and self.body_radius >= 0):
+            raise ValueError(f"body_radius must be >= 0, not {self.body_radius!r}")
+        if not (isinstance(self.min_contacts, int) and not isinstance(self.min_contacts, bool) and self.min_contacts >= 0):
+            raise ValueError(f"min_contacts must be an integer >= 0, not {self.min_contacts!r}")
+        if self.top_k is not None and not (isinstance(self.top_k, int) and not isinstance(self.top_k, bool) and self.top_k >= 1):
+            raise ValueError(f"top_k must be an integer >= 1 (or None), not {self.top_k!r}")
+        if not (isinstance(self.min_separation, (int, float)) and math.isfinite(self.min_separation) and self.min_separation >= 0):
+            raise ValueError(f"min_separation must be >= 0, not {self.min_separation!r}")
+        if self.score_by not in SCORE_BY:
+            raise ValueError(f"score_by must be one of {SCORE_BY}, not {self.score_by!r}")
+
+    @property
+    def needs_clearance(self):
+        return bool(self.collision_free) or self.min_contacts > 0
+
+    @property
+    def needs_success(self):
+        return self.min_success is not None or self.score_by in ("success", "product")

@@ -15,6 +15,14 @@ BOTTOM_CENTER = (0.0, 0.0, 1.12169998e-01)
 # left finger, right finger, wrist, palm
 OPEN_SEGMENTS = ((CENTER_LEFT, BOTTOM_LEFT), (CENTER_RIGHT, BOTTOM_RIGHT), (TOP, CENTER), (CENTER_RIGHT, CENTER_LEFT))
 
+# the "finger sweep" segments between the finger tips (gripper.py:33-47, COLLISION_SEGMENTS): what lies within
+# SWEEP_RADIUS of them is between the fingers (create_grasp_collision_marker, :80-103: tubes of radius 0.006 m "for checking
+# collisions in the grasp area"; create_grasp_body_marker :105-128 wraps OPEN_SEGMENTS in the same tubes)
+SWEEP_SEGMENTS = (((4.1e-02, -7.27595772e-12, 1.08169998e-01), (-4.1e-02, -7.27595772e-12, 1.08169998e-01)),
+                  ((4.1e-02, -7.27595772e-12, 0.98169998e-01), (-4.1e-02, -7.27595772e-12, 0.98169998e-01)))
+SWEEP_RADIUS = 0.006
+BODY_RADIUS = 0.006
+
 DEFAULT_POINTS = 64   # 1024 cloud points + 64 = 1088 = 34 x 32: the merged scene stays on the 32-point-tile launches
 
 

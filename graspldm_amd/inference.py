@@ -50,7 +50,7 @@ class _InferenceBase:
         self.classifier = None
         self.gripper_points = None
 
-    def _results(self, pc, metas, tmrp, cls_logit, num_pcs, num_grasps, all_steps=()):
+    def _results(self, pc, metas, tmrp, cls_logit, num_pcs, num_grasps, all_steps=(), score=True):
         # before anything leaves the device: a lost hand-off inside the fused sampling launch raises here
         # (status, not silent garbage: the reference exits the process on a CUDA error, cuda_utils.cuh:28-37)
         for m in self.model.modules():
@@ -82,8 +82,106 @@ class _InferenceBase:
         out = dict(grasps=H.view(num_pcs, num_grasps, 4, 4), grasp_tmrp=un.view(num_pcs, num_grasps, 6),
                    confidence=conf.view(num_pcs, num_grasps, 1), qualities=None, pc=unnormalize_pc(pc, metas),
                    all_steps_grasps=steps_H)
-        if self.classifier is not None:   # additive: the key exists only with a classifier set
+        if self.classifier is not None and score:   # additive: the key exists only with a classifier set
             out["success"] = self.score_grasps(pc, metas, out["grasps"]).unsqueeze(-1)
+        return out
+
+    def _finish(self, out, pc, metas, selection, scene_pc):
+        """The tail of every generation entry: with a selection the classifier has not run yet (select_grasps scores the
+        poses that the cheap filters leave, or the selected ones)."""
+        if selection is None:
+            return out
+        return self.select_grasps(out, selection, scene_pc=scene_pc, pc=pc, metas=metas)
+
+    @torch.no_grad()
+    def select_grasps(self, results, selection, scene_pc=None, pc=None, metas=None):
+        """Filter and select the poses of a result dict (graspldm_amd.grasp_select.GraspSelection) -> a NEW dict; `results`
+        is not modified.  scene_pc [B, Ns, 3] (or [Ns, 3]): the whole scene in the frame of results["pc"] -- table and
+        clutter included --, default results["pc"] itself.  pc / metas: the normalised cloud(s) and metas the results were
+        generated from; needed only where the classifier has to run (generate_grasps(..., selection=) passes them).
+        Cheap first: confidence mask -> one clearance launch (only if collision_free / min_contacts ask for it) -> the
+        classifier on the survivors (only if min_success / score_by need it) -> top-k or diverse launch -> with a classifier
+        attached and not yet run, the classifier on the k selected poses.
+        grasps, grasp_tmrp, confidence (success, latent_* when present) come back gathered to [B, K, ...], NaN in the slots
+        behind selected_count; added keys: selected_index [B, K] (-1 padded), selected_count [B], selected_gap [B, K],
+        clearance / contacts [B, G] (None when no filter asked for them)."""
+        from . import grasp_select as gs
+        if not isinstance(selection, gs.GraspSelection):
+            raise TypeError("selection must be a graspldm_amd.grasp_select.GraspSelection")
+        H = results["grasps"].to(self.device)
+        b, g = H.shape[:2]
+        conf = results["confidence"].to(self.device).reshape(b, g)
+        keep = torch.ones(b, g, dtype=torch.bool, device=self.device)
+        if selection.min_confidence is not None:
+            keep &= conf >= selection.min_confidence
+        clearance = contacts = None
+        if selection.needs_clearance:
+            scene = results["pc"] if scene_pc is None else scene_pc
+            scene = (scene.unsqueeze(0) if scene.ndim == 2 else scene).to(self.device)
+            if scene.shape[0] == 1 and b > 1:
+                scene = scene.expand(b, -1, -1)
+            clearance, contacts = gs.grasp_clearance(scene, H, max_clearance=max(0.05, 2.0 * selection.body_radius))
+            if selection.collision_free:
+                keep &= clearance > selection.body_radius
+            if selection.min_contacts > 0:
+                keep &= contacts >= selection.min_contacts
+        success = results.get("success")
+        success = None if success is None else success.to(self.device).reshape(b, g)
+
+        def score(Hsel):   # [B, n, 4, 4] -> [B, n]
+            if self.classifier is None:
+                raise RuntimeError("the selection needs success probabilities (min_success / score_by) but no classifier is "
+                                   "attached: call set_classifier(model) first")
+            if pc is None or metas is None:
+                raise RuntimeError("scoring needs the normalised cloud and its metas: pass pc= and metas= (generate_grasps("
+                                   "..., selection=) does)")
+            return self.score_grasps(pc, metas, Hsel)
+
+        def pad_gather(index, count, n):   # poses at index[:, :n], the slots behind count filled with the cloud's first one
+            idx = index[:, :n].long()
+            first = idx[:, :1].clamp(min=0)
+            valid = torch.arange(n, device=self.device)[None, :] < count[:, None]
+            idx = torch.where(valid, idx, first.expand(-1, n))
+            return H.gather(1, idx.view(b, n, 1, 1).expand(-1, -1, 4, 4)), idx, valid
+
+        if selection.needs_success and success is None:
+            # compact the survivors (top-k mode: kept candidates in front), score them, scatter back; the rest stay NaN
+            index, count, _ = gs.select_grasps(H, conf, keep=keep, k=g)
+            success = torch.full((b, g), float("nan"), device=self.device)
+            n = int(count.max())
+            if n > 0:
+                Hs, idx, valid = pad_gather(index, count, n)
+                s = score(Hs).reshape(b, n)
+                rows = torch.arange(b, device=self.device)[:, None].expand(-1, n)
+                success[rows[valid], idx[valid]] = s[valid]
+        if selection.min_success is not None:
+            keep &= success >= selection.min_success   # NaN (unscored) compares false
+        by = {"confidence": conf, "success": success, "product": None if success is None else conf * success}[selection.score_by]
+        by = torch.where(keep, by, torch.zeros_like(conf))   # dropped poses may carry NaN
+        k = g if selection.top_k is None else min(selection.top_k, g)
+        index, count, gap = gs.select_grasps(H, by, keep=keep, k=k, diverse=selection.diverse,
+                                             min_separation=selection.min_separation)
+        valid = torch.arange(k, device=self.device)[None, :] < count[:, None]
+        idx = index.long().clamp(min=0)
+        out = dict(results)
+        per_pose = {key: out[key] for key in ("grasps", "grasp_tmrp", "confidence", "latent_mu", "latent_logvar")
+                    if out.get(key) is not None}
+        if success is not None:
+            per_pose["success"] = success.unsqueeze(-1)
+        for key, t in per_pose.items():
+            t = t.to(self.device)
+            tail = t.shape[2:]
+            ix = idx.view(b, k, *([1] * len(tail))).expand(-1, -1, *tail)
+            vm = valid.view(b, k, *([1] * len(tail)))
+            out[key] = torch.where(vm, t.gather(1, ix), torch.full((), float("nan"), dtype=t.dtype, device=self.device))
+        if success is None and self.classifier is not None:   # the classifier has not run: the k selected poses only
+            n = int(count.max())
+            sel = torch.full((b, k), float("nan"), device=self.device)
+            if n > 0:
+                Hs, _, v = pad_gather(index, count, n)
+                sel[:, :n] = torch.where(v, score(Hs).reshape(b, n), sel[:, :n])
+            out["success"] = sel.unsqueeze(-1)
+        out.update(selected_index=index, selected_count=count, selected_gap=gap, clearance=clearance, contacts=contacts)
         return out
 
     def set_classifier(self, model, gripper_points=None):
@@ -165,12 +263,16 @@ class _InferenceBase:
         return self.normalize_input(pc)
 
     def infer_on_pointcloud(self, pc, num_grasps=10, return_intermediate=False, num_points=None,
-                            use_farthest_point=True):
+                            use_farthest_point=True, selection=None, scene_pc=None):
         """tools/inference.py:658-666 (= generate_on_pointcloud, grasp_ldm/inference/inference_base.py:161-179).
         `num_points` (additive): first bring every cloud to the encoder's point count
-        (PointCloudHelpers.regularize_pc_point_count; farthest-point selection by default)."""
+        (PointCloudHelpers.regularize_pc_point_count; farthest-point selection by default).  `selection` / `scene_pc`
+        (additive): filter and select the poses (select_grasps); scene_pc is in the frame of `pc`."""
         pcn, metas = self.prepare_pointcloud(pc, num_points, use_farthest_point)
-        return self.generate_grasps(pcn, metas, num_grasps=num_grasps, return_intermediate=return_intermediate)
+        if selection is None:
+            return self.generate_grasps(pcn, metas, num_grasps=num_grasps, return_intermediate=return_intermediate)
+        return self.generate_grasps(pcn, metas, num_grasps=num_grasps, return_intermediate=return_intermediate,
+                                    selection=selection, scene_pc=scene_pc)
 
     generate_on_pointcloud = infer_on_pointcloud
 
@@ -228,7 +330,8 @@ class InferenceLDM(_InferenceBase):
             warnings.warn("ACRONYM dataset loading is out of scope; use generate_grasps(pc, metas)")
 
     @torch.no_grad()
-    def generate_grasps(self, pc, metas, num_grasps=10, return_intermediate=False, x_T=None, **kwargs):
+    def generate_grasps(self, pc, metas, num_grasps=10, return_intermediate=False, x_T=None, selection=None, scene_pc=None,
+                        **kwargs):
         batch = (pc.unsqueeze(0) if pc.ndim == 2 else pc).to(self.device)
         extra_sampler = {}
         if self.fast_sampler == "DPMPP":  # tools/inference.py:607-609
@@ -252,10 +355,11 @@ class InferenceLDM(_InferenceBase):
             extra["metas"] = {k: (v.to(self.device) if isinstance(v, torch.Tensor) else v) for k, v in metas.items()}
         (tmrp, logit), steps = self.model.generate_grasps(batch, num_grasps=num_grasps,
                                                           return_intermediate=return_intermediate, x_T=x_T, **extra)
-        return self._results(batch, metas, tmrp, logit, batch.shape[0], num_grasps, all_steps=steps)
+        out = self._results(batch, metas, tmrp, logit, batch.shape[0], num_grasps, all_steps=steps, score=selection is None)
+        return self._finish(out, batch, metas, selection, scene_pc)
 
     @torch.no_grad()
-    def refine_grasps(self, pc, metas, H, strength=0.3, noise=None, **kwargs):
+    def refine_grasps(self, pc, metas, H, strength=0.3, noise=None, selection=None, scene_pc=None, **kwargs):
         """Reverse diffusion started from given grasps H [B,G,4,4] (cloud frame, un-normalised) instead of from noise
         (GraspLatentDDM.refine_grasps).  Same result dict as generate_grasps, plus latent_mu / latent_logvar [B,G,L]."""
         batch = (pc.unsqueeze(0) if pc.ndim == 2 else pc).to(self.device)
@@ -269,9 +373,9 @@ class InferenceLDM(_InferenceBase):
         if hasattr(self.model.diffusion_model.model, "class_embedding"):
             extra["metas"] = {k: (v.to(self.device) if isinstance(v, torch.Tensor) else v) for k, v in metas.items()}
         (tmrp, logit), lat = self.model._refine(batch, h, strength, noise=noise, **extra)
-        out = self._results(batch, metas, tmrp, logit, batch.shape[0], g)
+        out = self._results(batch, metas, tmrp, logit, batch.shape[0], g, score=selection is None)
         out["latent_mu"], out["latent_logvar"] = lat["mu"].view(batch.shape[0], g, -1), lat["logvar"].view(batch.shape[0], g, -1)
-        return out
+        return self._finish(out, batch, metas, selection, scene_pc)
 
 
 class InferenceVAE(_InferenceBase):
@@ -289,15 +393,15 @@ class InferenceVAE(_InferenceBase):
             self.model = m.to(self.device).eval()
 
     @torch.no_grad()
-    def generate_grasps(self, pc, metas, num_grasps=10, z_h=None, **kwargs):
+    def generate_grasps(self, pc, metas, num_grasps=10, z_h=None, selection=None, scene_pc=None, **kwargs):
         batch = (pc.unsqueeze(0) if pc.ndim == 2 else pc).to(self.device)
         tmrp, logit = self.model.generate_grasps(batch, num_grasps, z_h=z_h)
-        out = self._results(batch, metas, tmrp, logit, batch.shape[0], num_grasps)
+        out = self._results(batch, metas, tmrp, logit, batch.shape[0], num_grasps, score=selection is None)
         out.pop("all_steps_grasps")
-        return out
+        return self._finish(out, batch, metas, selection, scene_pc)
 
     @torch.no_grad()
-    def reconstruct_grasps(self, pc, metas, H, eps=None, **kwargs):
+    def reconstruct_grasps(self, pc, metas, H, eps=None, selection=None, scene_pc=None, **kwargs):
         """Given grasps H [B,G,4,4] (cloud frame, un-normalised) through the VAE: normalise -> encode -> decode
         (GraspCVAE.forward(compute_loss=False)).  eps [B*G, L]: the normals of the reparameterisation; None decodes the
         mean (z = mu).  Same result dict as generate_grasps, plus latent_mu / latent_logvar [B,G,L]."""
@@ -306,7 +410,7 @@ class InferenceVAE(_InferenceBase):
         vae = getattr(self.model, "vae_model", None) or self.model
         mu, logvar, z, z_pc, g = vae._encode(batch, h, eps=None if eps is None else eps.to(self.device))
         tmrp, logit = vae.decoder(z, z_pc, samples_per_cond=g)
-        out = self._results(batch, metas, tmrp, logit, batch.shape[0], g)
+        out = self._results(batch, metas, tmrp, logit, batch.shape[0], g, score=selection is None)
         out.pop("all_steps_grasps")
         out["latent_mu"], out["latent_logvar"] = mu.view(batch.shape[0], g, -1), logvar.view(batch.shape[0], g, -1)
-        return out
+        return self._finish(out, batch, metas, selection, scene_pc)

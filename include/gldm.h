@@ -679,6 +679,47 @@ int gldm_cls_head(const float *x /*[b,c,n]*/, const void *w1, const float *b1 /*
                   const float *l /*[n]*/, float c0, int b, int c, int rows, int n, int exact_f32, void *workspace,
                   long long workspace_bytes, float *logit /*[b]*/, float *prob /*[b]*/, gldm_stream_t stream);
 
+/* ------------------------------------------------ grasp selection (additive, ABI 14; csrc/grasp_select.hip) */
+
+/* Gripper clearance and finger-sweep contacts of every pose against a whole scene cloud.  The geometry is the
+ * reference's (grasp_ldm/utils/gripper.py:26-47: the four segments of the open gripper and the two "finger sweep"
+ * segments between the finger tips; :80-128 wraps both in tubes "for checking collisions in the grasp area"); the
+ * reference only draws them.  scene [b,ns,3] f32 in the frame of the poses; H [b*g,4,4] row-major, row c*g + i belongs
+ * to cloud c.  `body` [sb,2,3] and `sweep` [ss,2,3] are HOST arrays of segments (a, b) in the gripper frame (as radius
+ * and u of gldm_ball_query_multi: they travel as kernel arguments).  For a pose (R, t) a scene point p becomes
+ * q = R^T (p - t); its distance to a segment is |q - a - u (b - a)|, u = clamp((q - a).(b - a) / |b - a|^2, 0, 1).
+ *   clearance[c*g + i] = min(cap, min over points and body segments of that distance)
+ *   contacts[c*g + i]  = points whose smallest SQUARED distance to a sweep segment is <= r_sweep^2 (0 when ss = 0)
+ * A point farther than rho + max(cap, r_sweep) (plus a margin) from the centre of the gripper's bounding sphere of radius
+ * rho changes neither output and is skipped, a staged chunk of gldm_grasp_clearance_chunk() points at a time.  Both
+ * reductions are exact (min of non-negative floats through their integer views, integer sum; device atomics behind an
+ * initialising launch): bitwise repeatable, independent of b, of a pose's position and of how the scene is split.  No FMA
+ * contraction.  Inputs must be finite (the caller checks).
+ * Envelope, checked before any pointer or the device is touched: 1 <= ns <= 2^24, 1 <= sb <= 8, 0 <= ss <= 8 or
+ * GLDM_ERR_UNSUPPORTED; b, g >= 1, cap > 0, r_sweep >= 0, no null pointer or GLDM_ERR_INVALID_ARG. */
+int gldm_grasp_clearance_chunk(void);
+int gldm_grasp_clearance(const float *scene /*[b,ns,3]*/, const float *H /*[b*g,4,4]*/, int b, int g, int ns,
+                         const float *body /*host [sb,2,3]*/, int sb, const float *sweep /*host [ss,2,3] or NULL*/, int ss,
+                         float r_sweep, float cap, float *clearance /*[b*g]*/, int32_t *contacts /*[b*g]*/,
+                         gldm_stream_t stream);
+
+/* Which k of a cloud's g candidate poses to keep: one workgroup per cloud, the rounds run inside the launch.
+ * score [b*g] f32 (finite); keep [b*g] uint8 or NULL (all); ctrl [np,3]: HOST array of gripper control points.
+ * mode 0 (top-k): the kept candidates in the order (score falling, index rising); gap is written 0.
+ * mode 1 (diverse): greedy farthest-pose selection under the reference's control-point distance
+ *   D(i, j) = (1/np) sum_k |H_i c_k - H_j c_k|^2      (grasp_ldm/losses/loss.py:77-127)
+ * evaluated in closed form around the control points' centroid cb:
+ *   D = |dt + dR cb|^2 + tr(dR Me dR^T),  dt, dR = differences of the two poses, Me = (1/np) sum (c - cb)(c - cb)^T.
+ * First pick: highest score, lowest index on a tie.  m_j = min over the picks so far of D(pick, j); every later pick
+ * maximises m_j, lowest index on a tie.  Picking stops after k picks, when no candidate is left, or when the best
+ * m_j < min_separation^2.  gap = sqrt(m) of a pick when it was taken (RMS control-point distance to the nearest earlier
+ * pick, metres); +inf for the first pick.
+ * index [b,k]: -1 behind the last pick; count [b]; gap [b,k]: 0 behind the last pick.  Every slot is written.
+ * Envelope: 1 <= k <= g <= 2048, 1 <= np <= 64 or GLDM_ERR_UNSUPPORTED (checked first, as above). */
+int gldm_select_grasps(const float *H /*[b*g,4,4]*/, const float *score /*[b*g]*/, const uint8_t *keep /*[b*g] or NULL*/,
+                       int b, int g, const float *ctrl /*host [np,3]*/, int np, int k, int mode, float min_separation,
+                       int32_t *index /*[b,k]*/, int32_t *count /*[b]*/, float *gap /*[b,k]*/, gldm_stream_t stream);
+
 /* ---- Unet1D (additive; ref: grasp_ldm/models/modules/resnets.py:622-857) ------------------------------------------------
  * One kernel carries a tile of `tile_samples` samples through the whole U-net and through every sampler step; the skip
  * stack, the stem's output and the residual stream stay in LDS (csrc/unet1d.hip).  The packed buffer holds the weights and,

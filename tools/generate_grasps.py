@@ -11,7 +11,12 @@ no network here for either), --out FILE.npz, --classifier_config FILE [--classif
 generated grasp with a PointsBasedGraspClassifier: the results and the written file gain `success`), --refine_from FILE [--refine_strength S] (start from given grasps instead of
 from noise: with --mode VAE the file's grasps are reconstructed through the VAE, with --mode LDM they are encoded, diffused
 forward to `S` of the schedule and denoised again; FILE is .npy / .npz key `grasps`, [G,4,4] or [B,G,4,4] -- one set per
-sample / cloud file in order --, un-normalised, in the cloud's frame; --num_grasps is taken from the file then).  `--inference_steps` is honoured (the reference
+sample / cloud file in order --, un-normalised, in the cloud's frame; --num_grasps is taken from the file then),
+--collision_free / --min_contacts N [--scene_file FILE] / --min_confidence X / --min_success X / --top_k K / --diverse
+[--min_separation M] (geometric filtering and selection of the generated poses, graspldm_amd/grasp_select.py: the gripper
+must clear the scene, N scene points must lie between the fingers, thresholds on confidence and on the classifier's
+success, the best K or K diverse ones; --out gains selected_index, selected_count, selected_gap, clearance, contacts;
+without any of these flags nothing changes).  `--inference_steps` is honoured (the reference
 silently ignores it: it passes use_fast_sampler=False, tools/generate_grasps.py:69-79).
 """
 import argparse
@@ -63,8 +68,59 @@ def parse_args(argv=None):
                    help="the classifier's checkpoint (optional with --synthetic: the synthetic weight recipe is used)")
     p.add_argument("--sort_by_success", action="store_true",
                    help="with --classifier_config: order each cloud's grasps by falling success probability in --out")
+    p.add_argument("--scene_file", type=str, action="append", default=None, metavar="FILE",
+                   help="the whole scene (table, clutter) for --collision_free / --min_contacts, read like --pc_file and in the "
+                        "frame of the --pc_file cloud: one file, or one per cloud (default: the cloud itself)")
+    p.add_argument("--collision_free", action="store_true",
+                   help="keep only poses whose open gripper stays clear of every scene point")
+    p.add_argument("--min_contacts", type=int, default=0, metavar="N",
+                   help="keep only poses with at least N scene points between the fingers")
+    p.add_argument("--min_confidence", type=float, default=None, metavar="X", help="keep only poses with confidence >= X")
+    p.add_argument("--min_success", type=float, default=None, metavar="X",
+                   help="with --classifier_config: keep only poses with success probability >= X (only the poses that "
+                        "pass the cheaper filters are scored)")
+    p.add_argument("--top_k", type=int, default=None, metavar="K", help="return the best K surviving poses of each cloud")
+    p.add_argument("--diverse", action="store_true",
+                   help="with --top_k: K poses spread over the survivors (greedy farthest pose) instead of the K best")
+    p.add_argument("--min_separation", type=float, default=0.0, metavar="M",
+                   help="with --diverse: stop once no survivor is at least M metres (RMS control-point distance) from every pick")
     p.add_argument("--out", type=str, default=None, help="write results of all samples to this .npz")
     return p.parse_args(argv)
+
+
+def build_selection(args):
+    """The GraspSelection of the selection flags, or None when none of them is set (nothing changes then)."""
+    asked = (args.collision_free or args.min_contacts or args.min_confidence is not None or args.min_success is not None
+             or args.top_k is not None or args.diverse or args.min_separation or args.scene_file)
+    if not asked:
+        return None
+    if args.min_success is not None and not args.classifier_config:
+        raise SystemExit("--min_success needs --classifier_config")
+    if args.top_k is not None and args.top_k < 1:
+        raise SystemExit("--top_k must be at least 1")
+    if args.scene_file and not (args.collision_free or args.min_contacts):
+        raise SystemExit("--scene_file is read by --collision_free / --min_contacts only")
+    if args.scene_file and len(args.scene_file) not in (1, len(args.pc_file) if args.pc_file else args.num_samples):
+        raise SystemExit("--scene_file: one file, or one per cloud")
+    from graspldm_amd.grasp_select import GraspSelection
+    try:
+        return GraspSelection(min_confidence=args.min_confidence, min_success=args.min_success,
+                              collision_free=args.collision_free, min_contacts=args.min_contacts, top_k=args.top_k,
+                              diverse=args.diverse, min_separation=args.min_separation,
+                              score_by="success" if args.min_success is not None else "confidence")
+    except ValueError as e:
+        raise SystemExit(str(e))
+
+
+def selection_kwargs(args, selection, i):
+    """selection= / scene_pc= of the i-th cloud ({} without selection flags: the calls stay what they were)."""
+    if selection is None:
+        return {}
+    scene = None
+    if args.scene_file:
+        from graspldm_amd.pointcloud import read_cloud_file
+        scene = torch.from_numpy(read_cloud_file(args.scene_file[i if len(args.scene_file) > 1 else 0]))
+    return dict(selection=selection, scene_pc=scene)
 
 
 def setup_model(args):
@@ -141,18 +197,20 @@ def read_grasp_file(path):
     return torch.from_numpy(H)
 
 
-def run_one(args, model, pcn, metas, start, i):
+def run_one(args, model, pcn, metas, start, i, sel=None):
     """One cloud: generation, or reconstruction / refinement of the i-th grasp set of --refine_from."""
+    sel = sel or {}
     if start is None:
-        return model.generate_grasps(pcn, metas, num_grasps=args.num_grasps)
+        return model.generate_grasps(pcn, metas, num_grasps=args.num_grasps, **sel)
     H = start[i if start.shape[0] > 1 else 0].unsqueeze(0)
     if args.mode == "LDM":
-        return model.refine_grasps(pcn, metas, H, strength=args.refine_strength)
-    return model.reconstruct_grasps(pcn, metas, H)
+        return model.refine_grasps(pcn, metas, H, strength=args.refine_strength, **sel)
+    return model.reconstruct_grasps(pcn, metas, H, **sel)
 
 
 def main(argv=None):
     args = parse_args(argv)
+    selection = build_selection(args)
     start = None
     if args.refine_from:
         if not 0.0 <= args.refine_strength <= 1.0:
@@ -179,10 +237,11 @@ def main(argv=None):
             pc = torch.from_numpy(read_cloud_file(path))
             if start is None:
                 res = model.infer_on_pointcloud(pc, num_grasps=args.num_grasps, num_points=n_pts,
-                                                use_farthest_point=not args.random_resample)
+                                                use_farthest_point=not args.random_resample,
+                                                **selection_kwargs(args, selection, len(results)))
             else:
                 pcn, metas = model.prepare_pointcloud(pc, num_points=n_pts, use_farthest_point=not args.random_resample)
-                res = run_one(args, model, pcn, metas, start, len(results))
+                res = run_one(args, model, pcn, metas, start, len(results), selection_kwargs(args, selection, len(results)))
             conf = res["confidence"].flatten()
             print(f"{path}: {pc.shape[0]} points -> {n_pts}; grasps {tuple(res['grasps'].shape)}  "
                   f"confidence mean {conf.mean().item():.3f}  best {conf.max().item():.3f}")
@@ -196,7 +255,7 @@ def main(argv=None):
         else:
             raise SystemExit("ACRONYM dataset loading is out of scope: pass the object's cloud with --pc_file FILE "
                              "(.npy / .ply / ...), or run on synthetic clouds with --synthetic N")
-        res = run_one(args, model, pc, metas, start, i)
+        res = run_one(args, model, pc, metas, start, i, selection_kwargs(args, selection, i))
         conf = res["confidence"].flatten()
         print(f"sample {i}: cloud #{idx}  grasps {tuple(res['grasps'].shape)}  "
               f"confidence mean {conf.mean().item():.3f}  best {conf.max().item():.3f}")
@@ -223,8 +282,10 @@ def finish(args, results):
                     idx = order.view(*order.shape, *([1] * (r[k].ndim - 2))).expand_as(r[k])
                     r[k] = torch.gather(r[k], 1, idx)
     if args.out:
-        extra = {k: torch.cat([r[k] for r in results]).cpu().numpy() for k in ("latent_mu", "latent_logvar", "success")
-                 if all(k in r for r in results)}
+        extra = {k: torch.cat([r[k] for r in results]).cpu().numpy()
+                 for k in ("latent_mu", "latent_logvar", "success", "selected_index", "selected_count", "selected_gap",
+                           "clearance", "contacts")
+                 if all(r.get(k) is not None for r in results)}
         np.savez_compressed(args.out, grasps=torch.cat([r["grasps"] for r in results]).cpu().numpy(),
                             grasp_tmrp=torch.cat([r["grasp_tmrp"] for r in results]).cpu().numpy(),
                             confidence=torch.cat([r["confidence"] for r in results]).cpu().numpy(), **extra)
