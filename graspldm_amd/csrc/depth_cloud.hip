@@ -1,0 +1,220 @@
+// depth_cloud.hip -- depth frames to ordered point clouds on gfx950 (gldm_depth_to_cloud, include/gldm.h).
+//
+// ref: grasp_ldm/utils/camera.py:176-215 (Camera.depth_to_pointcloud_torch): the pinhole deprojection in front of
+// regularize_pc_point_count and normalize_input.  Compiled with -ffp-contract=off (csrc/Makefile, SRCS_STRICT): the keep
+// predicates and every product, quotient and sum round once per written operation, which is what the reference's torch
+// expression computes on f32 tensors with its f64 intrinsics cast to f32.
+//
+// Layout: a frame's H*W pixels are cut into tiles of kTile = kBlock * kPerThread consecutive pixels, one workgroup per
+// (tile, frame).  Thread t of a tile looks at pixels base + q * kBlock + t, q = 0 .. kPerThread - 1 (coalesced loads), so
+// ascending pixel order is (q, wave, lane) order.
+//
+// Ordered compaction without any workgroup waiting for another: two launches.
+//   pass 1  every tile counts its kept pixels -> tile_count[f][tile]                      (caller workspace)
+//   pass 2  every tile sums the counts of the tiles in front of it in its frame (at most 8191 ints, one strided read +
+//           one workgroup reduction), predicates again, and writes its points at that offset; inside the tile the slot
+//           of a pixel is the exclusive prefix over the (q, wave) ballot counts plus the popcount of the lower lanes.
+//           The last tile of a frame writes count[f].
+// Both passes call the same inlined `deproject` on the same loaded values, so they cannot disagree about a pixel.
+#include <hip/hip_runtime.h>
+#include <float.h>
+#include <stdint.h>
+
+#include "gldm.h"
+
+#define GLDM_API extern "C" __attribute__((visibility("default")))
+
+namespace {
+
+constexpr int kWave = 64;
+constexpr int kBlock = 256;
+constexpr int kWaves = kBlock / kWave;
+constexpr int kPerThread = 8;
+constexpr int kTile = kBlock * kPerThread;   // 2048 pixels
+constexpr int kMaxPixels = 1 << 24;
+constexpr int kMaxFrames = 65535;            // grid.y
+
+inline int launch_status() { return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH; }
+inline hipStream_t as_stream(gldm_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
+
+struct DepthParams {
+  float fx, fy, cx, cy, z_min, z_max, depth_scale;
+  float xf[12];          // cam_to_world, 3 x 4 row major
+  float lo[3], hi[3];    // box in the output frame
+  int has_xf, has_box;
+  int w, hw;
+};
+
+__device__ __forceinline__ float load_depth(const float *d, size_t i, float) { return d[i]; }
+__device__ __forceinline__ float load_depth(const uint16_t *d, size_t i, float scale) { return (float)d[i] * scale; }
+
+// The one predicate + point of a pixel; `d` and `m` are the loaded depth (metres) and mask byte (1 without a mask).
+__device__ __forceinline__ bool deproject(const DepthParams &P, int pix, float d, unsigned m, float &ox, float &oy, float &oz) {
+  if (!(d > P.z_min && d <= P.z_max) || m == 0u) return false;
+  const int v = pix / P.w, u = pix - v * P.w;
+  const float x = __fdiv_rn(((float)u - P.cx) * d, P.fx);
+  const float y = __fdiv_rn(((float)v - P.cy) * d, P.fy);
+  const float z = d;
+  if (!P.has_xf) {
+    ox = x; oy = y; oz = z;
+  } else {
+    ox = ((P.xf[0] * x + P.xf[1] * y) + P.xf[2] * z) + P.xf[3];
+    oy = ((P.xf[4] * x + P.xf[5] * y) + P.xf[6] * z) + P.xf[7];
+    oz = ((P.xf[8] * x + P.xf[9] * y) + P.xf[10] * z) + P.xf[11];
+  }
+  if (P.has_box) {
+    if (!(ox >= P.lo[0] && ox <= P.hi[0] && oy >= P.lo[1] && oy <= P.hi[1] && oz >= P.lo[2] && oz <= P.hi[2])) return false;
+  }
+  return true;
+}
+
+// Sum of v over the workgroup, in every thread (s_red: kWaves ints).
+__device__ __forceinline__ int block_sum(int v, int *s_red) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, kWave);
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int t = 0;
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) t += s_red[w];
+  return t;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void depth_count_kernel(const T *__restrict__ depth, const uint8_t *__restrict__ mask,
+                                                             DepthParams P, int tiles, int32_t *__restrict__ tile_count) {
+  __shared__ int s_red[kWaves];
+  const int tile = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
+  const size_t fbase = (size_t)f * P.hw;
+  int kept = 0;
+#pragma unroll
+  for (int q = 0; q < kPerThread; ++q) {
+    const int pix = tile * kTile + q * kBlock + tid;
+    if (pix < P.hw) {
+      const float d = load_depth(depth, fbase + pix, P.depth_scale);
+      const unsigned m = mask ? mask[fbase + pix] : 1u;
+      float x, y, z;
+      kept += deproject(P, pix, d, m, x, y, z) ? 1 : 0;
+    }
+  }
+  const int total = block_sum(kept, s_red);
+  if (tid == 0) tile_count[(size_t)f * tiles + tile] = total;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void depth_write_kernel(const T *__restrict__ depth, const uint8_t *__restrict__ mask,
+                                                             DepthParams P, int tiles, const int32_t *__restrict__ tile_count,
+                                                             float *__restrict__ points, int32_t *__restrict__ count,
+                                                             int32_t *__restrict__ pixel) {
+  __shared__ int s_red[kWaves];
+  __shared__ int s_cnt[kPerThread * kWaves + 1];
+  const int tile = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const size_t fbase = (size_t)f * P.hw;
+  // offset of this tile: the counts of the tiles in front of it in this frame
+  int front = 0;
+  for (int t = tid; t < tile; t += kBlock) front += tile_count[(size_t)f * tiles + t];
+  const int offset = block_sum(front, s_red);
+  float x[kPerThread], y[kPerThread], z[kPerThread];
+  unsigned keepbits = 0u;
+  int below[kPerThread];
+#pragma unroll
+  for (int q = 0; q < kPerThread; ++q) {
+    const int pix = tile * kTile + q * kBlock + tid;
+    bool k = false;
+    x[q] = y[q] = z[q] = 0.f;
+    if (pix < P.hw) {
+      const float d = load_depth(depth, fbase + pix, P.depth_scale);
+      const unsigned m = mask ? mask[fbase + pix] : 1u;
+      k = deproject(P, pix, d, m, x[q], y[q], z[q]);
+    }
+    const unsigned long long bal = __ballot(k);
+    below[q] = __popcll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0) s_cnt[q * kWaves + wave] = __popcll(bal);
+    keepbits |= k ? (1u << q) : 0u;
+  }
+  __syncthreads();
+  if (tid == 0) {   // exclusive prefix over the 32 (q, wave) counts, in place; the total behind them
+    int run = 0;
+    for (int i = 0; i < kPerThread * kWaves; ++i) {
+      const int c = s_cnt[i];
+      s_cnt[i] = run;
+      run += c;
+    }
+    s_cnt[kPerThread * kWaves] = run;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < kPerThread; ++q) {
+    if (keepbits & (1u << q)) {
+      const size_t row = fbase + (size_t)(offset + s_cnt[q * kWaves + wave] + below[q]);   // < fbase + hw: at most hw pixels are kept
+      points[3 * row] = x[q];
+      points[3 * row + 1] = y[q];
+      points[3 * row + 2] = z[q];
+      if (pixel) pixel[row] = tile * kTile + q * kBlock + tid;
+    }
+  }
+  if (tile == tiles - 1 && tid == 0) count[f] = offset + s_cnt[kPerThread * kWaves];
+}
+
+template <typename T>
+int run(const T *depth, const uint8_t *mask, const DepthParams &P, int frames, int tiles, int32_t *ws, float *points,
+        int32_t *count, int32_t *pixel, hipStream_t s) {
+  hipLaunchKernelGGL((depth_count_kernel<T>), dim3(tiles, frames), dim3(kBlock), 0, s, depth, mask, P, tiles, ws);
+  int st = launch_status();
+  if (st != GLDM_OK) return st;
+  hipLaunchKernelGGL((depth_write_kernel<T>), dim3(tiles, frames), dim3(kBlock), 0, s, depth, mask, P, tiles, ws, points,
+                     count, pixel);
+  return launch_status();
+}
+
+// 0, or the status of a shape outside the envelope
+int check_shape(int frames, int h, int w) {
+  if (frames < 1 || h < 1 || w < 1) return GLDM_ERR_INVALID_ARG;
+  if ((long long)h * w > kMaxPixels || frames > kMaxFrames) return GLDM_ERR_UNSUPPORTED;
+  return GLDM_OK;
+}
+
+}  // namespace
+
+GLDM_API int gldm_depth_to_cloud_tile_pixels(void) { return kTile; }
+
+GLDM_API long long gldm_depth_to_cloud_workspace_bytes(int frames, int h, int w) {
+  const int st = check_shape(frames, h, w);
+  if (st != GLDM_OK) return st;
+  const long long tiles = ((long long)h * w + kTile - 1) / kTile;
+  return (long long)frames * tiles * (long long)sizeof(int32_t);
+}
+
+GLDM_API int gldm_depth_to_cloud(const void *depth, int depth_is_u16, float depth_scale, const uint8_t *mask, int frames,
+                                 int h, int w, float fx, float fy, float cx, float cy, float z_min, float z_max,
+                                 const float *cam_to_world, const float *box_lo, const float *box_hi, void *workspace,
+                                 long long workspace_bytes, float *points, int32_t *count, int32_t *pixel,
+                                 gldm_stream_t stream) {
+  // the envelope first: nothing below touches a pointer or the device before it holds
+  const int st = check_shape(frames, h, w);
+  if (st != GLDM_OK) return st;
+  if (!(fx != 0.f) || !(fy != 0.f) || !(z_min < z_max) || fx != fx || fy != fy || cx != cx || cy != cy)
+    return GLDM_ERR_INVALID_ARG;
+  if (!depth || !workspace || !points || !count || (box_lo == nullptr) != (box_hi == nullptr)) return GLDM_ERR_INVALID_ARG;
+  if (depth_is_u16 != 0 && depth_is_u16 != 1) return GLDM_ERR_INVALID_ARG;
+  if (workspace_bytes < gldm_depth_to_cloud_workspace_bytes(frames, h, w)) return GLDM_ERR_WORKSPACE;
+  DepthParams P;
+  P.fx = fx; P.fy = fy; P.cx = cx; P.cy = cy; P.z_min = z_min; P.z_max = z_max;
+  P.depth_scale = depth_is_u16 ? depth_scale : 1.f;
+  P.has_xf = cam_to_world != nullptr;
+  P.has_box = box_lo != nullptr;
+  for (int i = 0; i < 12; ++i) P.xf[i] = cam_to_world ? cam_to_world[i] : 0.f;
+  for (int i = 0; i < 3; ++i) {
+    P.lo[i] = box_lo ? box_lo[i] : 0.f;
+    P.hi[i] = box_hi ? box_hi[i] : 0.f;
+  }
+  P.w = w;
+  P.hw = h * w;
+  const int tiles = (P.hw + kTile - 1) / kTile;
+  int32_t *ws = static_cast<int32_t *>(workspace);
+  hipStream_t s = as_stream(stream);
+  if (depth_is_u16)
+    return run(static_cast<const uint16_t *>(depth), mask, P, frames, tiles, ws, points, count, pixel, s);
+  return run(static_cast<const float *>(depth), mask, P, frames, tiles, ws, points, count, pixel, s);
+}

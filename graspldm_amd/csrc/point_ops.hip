@@ -9,6 +9,7 @@
 //    order" semantics exactly;
 //  * FPS keeps coordinates and running distances in registers/LDS for all M
 //    rounds, one barrier per round, 64-bit (distance, tie-key) wave arg-max;
+//    clouds beyond 8192 points: one launch per round over slices of the cloud;
 //  * the voxel scatter-mean is deterministic: points are bitonic-sorted by
 //    (voxel, index) in LDS and each voxel is summed in ascending point index;
 //  * distance / interpolation arithmetic is compiled with -ffp-contract=off so
@@ -286,6 +287,82 @@ __global__ __launch_bounds__(64) void fps_wave_kernel(const float *__restrict__ 
     const unsigned lmax = wave_max_u32(hi == hmax ? lo : 0u);
     old = (int)((~lmax) & 0x3FFFFFu);
     if (lane == 0) out[j] = old;
+  }
+}
+
+// Rule-1 selection on clouds beyond one workgroup's registers (8192 < n <= 2^22): a cloud is cut into `slices` runs of
+// `slice` consecutive points, one workgroup each, and a round is ONE LAUNCH over (slices, b) -- the grid-wide decision of a
+// round happens at the launch boundary, no workgroup ever waits for another.  Launch r:
+//   1. every workgroup reduces the partial keys that launch r-1 left (one per slice, at most kFpsLargeMaxSlices; exact:
+//      the same 64-bit key as above, max distance bits then lowest index) to pick r (r = 0: index 0) -- redundantly, which
+//      costs a few hundred L2 reads and saves a launch; slice 0 writes out[r];
+//   2. unless r is the last round, it updates its slice's running minima (global workspace, start 1e7 taken as a constant in
+//      launch 0, so the workspace needs no initialisation) with the distance to pick r and leaves its own partial key in the
+//      other half of the double-buffered partials.
+// Slice i is workgroup i in every round, so a slice's points and minima are re-read by the same XCD's L2 each round.
+// `counts` (optional): the live rows of each cloud (row stride n); rows past it are never read; a cloud with
+// counts[b] <= m gets 0 .. counts[b]-1 then -1 (the reference's nclusters >= N -> arange case).
+constexpr int kFpsLargeBlock = 256;
+constexpr int kFpsLargeMinSlice = 1024;
+constexpr int kFpsLargeMaxSlices = 512;
+constexpr int kFpsLargeMaxN = 1 << 22;   // the index field of the key
+constexpr int kFpsLargeMaxM = 8192;
+
+__global__ __launch_bounds__(kFpsLargeBlock) void fps_large_round_kernel(const float *__restrict__ points, int n, int m,
+                                                                         int slice, const int32_t *__restrict__ counts,
+                                                                         float *__restrict__ mind,
+                                                                         unsigned long long *__restrict__ partials, int r,
+                                                                         int32_t *__restrict__ out) {
+  __shared__ unsigned long long s_part[kFpsLargeBlock / kWave];
+  const int s = blockIdx.x, slices = gridDim.x, b = blockIdx.y, tid = threadIdx.x;
+  int cnt = counts ? counts[b] : n;
+  cnt = cnt < 0 ? 0 : (cnt > n ? n : cnt);
+  out += (size_t)b * m;
+  if (cnt <= m) {
+    if (s == 0 && tid == 0) out[r] = r < cnt ? r : -1;
+    return;
+  }
+  points += (size_t)b * 3 * n;
+  mind += (size_t)b * n;
+  const unsigned long long *prev = partials + ((size_t)((r + 1) & 1) * gridDim.y + b) * slices;
+  unsigned long long *mine = partials + ((size_t)(r & 1) * gridDim.y + b) * slices;
+  int pick = 0;
+  if (r > 0) {
+    unsigned long long v = 0ull;
+    for (int i = tid; i < slices; i += kFpsLargeBlock) {
+      const unsigned long long o = prev[i];
+      v = o > v ? o : v;
+    }
+    v = wave_max_u64(v);
+    if ((tid & 63) == 0) s_part[tid >> 6] = v;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < kFpsLargeBlock / kWave; ++w) v = s_part[w] > v ? s_part[w] : v;
+    pick = (int)((~(unsigned int)v) & 0x3FFFFFu);   // < cnt: only live rows ever left a non-zero key
+    __syncthreads();
+  }
+  if (s == 0 && tid == 0) out[r] = pick;
+  if (r == m - 1) return;
+  const float x1 = points[3 * (size_t)pick], y1 = points[3 * (size_t)pick + 1], z1 = points[3 * (size_t)pick + 2];
+  const int k0 = s * slice;
+  const int k1 = (k0 + slice < cnt) ? k0 + slice : cnt;   // k0 >= cnt: an empty slice, key 0 (below every real key)
+  unsigned long long best = 0ull;
+  for (int k = k0 + tid; k < k1; k += kFpsLargeBlock) {
+    const float x = points[3 * (size_t)k], y = points[3 * (size_t)k + 1], z = points[3 * (size_t)k + 2];
+    const float d = __fsqrt_rn((x - x1) * (x - x1) + (y - y1) * (y - y1) + (z - z1) * (z - z1));
+    const float old = r == 0 ? 1e7f : mind[k];
+    const float d2 = d < old ? d : old;
+    mind[k] = d2;
+    const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | ~(unsigned int)k;
+    best = key > best ? key : best;
+  }
+  best = wave_max_u64(best);
+  if ((tid & 63) == 0) s_part[tid >> 6] = best;
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int w = 1; w < kFpsLargeBlock / kWave; ++w) best = s_part[w] > best ? s_part[w] : best;
+    mine[s] = best;
   }
 }
 
@@ -958,6 +1035,55 @@ GLDM_API int gldm_farthest_points_euclid(const float *points, int b, int n, int 
   if (m == 0) return GLDM_OK;
   if (n > 1024 * kFpsMaxPerThread) return GLDM_ERR_UNSUPPORTED;
   return dispatch_fps<1>(points, b, n, m, out_idx, as_stream(stream));
+}
+
+namespace {
+// 0, or the status of a shape outside the envelope of the large selection
+int fps_large_check(int b, int n, int m) {
+  if (b <= 0 || n <= 0 || m < 0) return GLDM_ERR_INVALID_ARG;
+  if (n <= 1024 * kFpsMaxPerThread || n > kFpsLargeMaxN || m > kFpsLargeMaxM || b > 65535) return GLDM_ERR_UNSUPPORTED;
+  return GLDM_OK;
+}
+int fps_large_slice(int n) {
+  int slice = kFpsLargeMinSlice;
+  while (ceil_div(n, slice) > kFpsLargeMaxSlices) slice *= 2;
+  return slice;
+}
+long long fps_large_minima_bytes(int b, int n) { return (((long long)b * n * 4) + 7) / 8 * 8; }
+}  // namespace
+
+GLDM_API int gldm_farthest_points_euclid_large_slice(int n) {
+  if (n <= 1024 * kFpsMaxPerThread || n > kFpsLargeMaxN) return GLDM_ERR_UNSUPPORTED;
+  return fps_large_slice(n);
+}
+
+GLDM_API long long gldm_farthest_points_euclid_large_workspace_bytes(int b, int n) {
+  const int st = fps_large_check(b, n, 1);
+  if (st != GLDM_OK) return st;
+  return fps_large_minima_bytes(b, n) + 2ll * b * ceil_div(n, fps_large_slice(n)) * (long long)sizeof(unsigned long long);
+}
+
+GLDM_API int gldm_farthest_points_euclid_large(const float *points, const int32_t *counts, int b, int n, int m,
+                                               void *workspace, long long workspace_bytes, int32_t *out_idx,
+                                               gldm_stream_t stream) {
+  const int st = fps_large_check(b, n, m);   // the envelope before any pointer
+  if (st != GLDM_OK) return st;
+  if (m > n) return GLDM_ERR_INVALID_ARG;
+  if (!points || !out_idx || !workspace || (reinterpret_cast<uintptr_t>(workspace) & 7u)) return GLDM_ERR_INVALID_ARG;
+  if (m == 0) return GLDM_OK;
+  if (workspace_bytes < gldm_farthest_points_euclid_large_workspace_bytes(b, n)) return GLDM_ERR_WORKSPACE;
+  const int slice = fps_large_slice(n), slices = ceil_div(n, slice);
+  float *mind = static_cast<float *>(workspace);
+  unsigned long long *partials =
+      reinterpret_cast<unsigned long long *>(static_cast<char *>(workspace) + fps_large_minima_bytes(b, n));
+  hipStream_t s = as_stream(stream);
+  for (int r = 0; r < m; ++r) {   // one launch per round, enqueued back to back; no synchronisation here
+    hipLaunchKernelGGL(fps_large_round_kernel, dim3(slices, b), dim3(kFpsLargeBlock), 0, s, points, n, m, slice, counts,
+                       mind, partials, r, out_idx);
+    const int ls = launch_status();
+    if (ls != GLDM_OK) return ls;
+  }
+  return GLDM_OK;
 }
 
 GLDM_API int gldm_normalize_cloud(const float *pc, int b, int n, float shift_x, float shift_y, float shift_z,

@@ -276,6 +276,53 @@ class _InferenceBase:
 
     generate_on_pointcloud = infer_on_pointcloud
 
+    def infer_on_depth(self, depth, camera, mask=None, num_grasps=10, num_points=None, use_farthest_point=True,
+                       z_range=None, depth_scale=None, cam_to_world=None, crop_box=None, selection=None, scene_pc=None,
+                       return_intermediate=False):
+        """From a depth frame to grasps without leaving the GPU (additive; the reference stops at
+        Camera.depth_to_pointcloud_torch, grasp_ldm/utils/camera.py:176-215, and leaves the rest to the caller).
+        depth [H, W] or [F, H, W] (CUDA; float32 metres or raw 16-bit units with depth_scale), camera: a
+        graspldm_amd.camera.Camera.  Object cloud of every frame = the deprojection under `mask` / `crop_box` inside
+        `z_range` (pointcloud.depth_to_cloud), then prepare_pointcloud (num_points, farthest-point selection by default),
+        then generate_grasps: exactly infer_on_pointcloud on that cloud.  When `selection` asks for collision_free or
+        min_contacts and no scene_pc is given, the scene is the same frame without mask and crop, inside z_range.
+        Poses are in the camera frame, or in the world frame with cam_to_world (3 x 4 / 4 x 4).  A frame whose object
+        cloud is empty raises ValueError before anything is generated.  F frames -> results of batch F."""
+        from .pointcloud import PointCloudHelpers, depth_to_cloud
+        depth = depth.to(self.device) if isinstance(depth, torch.Tensor) else depth
+        mask = mask.to(self.device) if isinstance(mask, torch.Tensor) else mask
+        kw = dict(z_range=z_range, depth_scale=depth_scale, cam_to_world=cam_to_world)
+        clouds = depth_to_cloud(depth, camera, mask=mask, crop_box=crop_box, **kw)
+        single = depth.ndim == 2
+        clouds = [clouds] if single else clouds
+        for f, c in enumerate(clouds):
+            if c.shape[0] == 0:
+                raise ValueError(f"frame {f}: the object cloud is empty (no pixel passes the mask, the depth window "
+                                 "and the crop box)")
+        if selection is not None and scene_pc is None and selection.needs_clearance:
+            scenes = depth_to_cloud(depth, camera, **kw)
+            if single:
+                scene_pc = scenes
+            elif len({s.shape[0] for s in scenes}) == 1:
+                scene_pc = torch.stack(scenes)
+            else:
+                raise ValueError("the frames' scene clouds differ in size and cannot form one batch: pass scene_pc "
+                                 "[F, Ns, 3], or call infer_on_depth frame by frame")
+        extra = {} if selection is None else dict(selection=selection, scene_pc=scene_pc)
+        if single:
+            return self.infer_on_pointcloud(clouds[0], num_grasps=num_grasps, return_intermediate=return_intermediate,
+                                            num_points=num_points, use_farthest_point=use_farthest_point, **extra)
+        if num_points is None:
+            if len({c.shape[0] for c in clouds}) != 1:
+                raise ValueError("the frames' object clouds differ in size: pass num_points")
+            batch = torch.stack(clouds)
+        else:
+            batch = torch.stack([c if c.shape[0] == num_points else
+                                 PointCloudHelpers.regularize_pc_point_count(c, num_points, use_farthest_point)
+                                 for c in clouds])
+        pcn, metas = self.normalize_input(batch)
+        return self.generate_grasps(pcn, metas, num_grasps=num_grasps, return_intermediate=return_intermediate, **extra)
+
     def generate_class_conditioned_grasps(self, pc, num_grasps=10, metas=None, data_idx=None, class_label=0, **kwargs):
         """tools/inference.py:330-364: the label, repeated per grasp, travels in metas["mode_cls"] to the
         class-conditioned denoiser (ClassTimeConditionedResNet1D).  One cloud, like the reference."""

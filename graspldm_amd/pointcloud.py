@@ -7,7 +7,13 @@ regularize_pc_point_count :124-158, farthest_points :160-217) and `normalize_inp
 centring/scaling) runs in libgldm_hip.so; the RANDOM index draws stay on the host and use exactly
 the generator calls the reference makes (np.random.choice / torch.randperm), so a seeded run picks
 the same points.  CPU tensors are rejected like everywhere else in this package.
+
+In front of that, from a depth camera: `depth_to_cloud` deprojects depth frames on the GPU
+(gldm_depth_to_cloud; Camera.depth_to_pointcloud_torch, grasp_ldm/utils/camera.py:176-215), `read_depth_file` reads them
+from disk, and clouds of more than 8192 points take gldm_farthest_points_euclid_large.
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -50,8 +56,37 @@ def farthest_point_indices(pc, nclusters):
     if nclusters >= n:
         return torch.arange(n, dtype=torch.int32, device=pcb.device).unsqueeze(0).repeat(b, 1)
     idx = torch.empty((b, int(nclusters)), dtype=torch.int32, device=pcb.device)
+    if n > FPS_SMALL_MAX:
+        return farthest_point_indices_large(pcb, int(nclusters), out=idx)
     with torch.cuda.device(pcb.device):
         L.call("gldm_farthest_points_euclid", L.ptr(pcb), b, n, int(nclusters), L.ptr(idx), L.current_stream(pcb.device))
+    return idx
+
+
+FPS_SMALL_MAX = 8192   # gldm_farthest_points_euclid's ceiling; larger clouds take gldm_farthest_points_euclid_large
+
+
+def farthest_point_indices_large(pc, nclusters, counts=None, out=None):
+    """gldm_farthest_points_euclid_large on pc [B,N,3] with 8192 < N <= 2^22: the same indices as
+    farthest_point_indices, one launch per round over many workgroups.  counts (int32 [B] on the device, optional): the
+    live rows of each cloud -- rows past them are never read, and a cloud with counts[b] <= nclusters gets
+    0 .. counts[b]-1 followed by -1.  -> int32 [B, nclusters]."""
+    pcb = _as_batch(pc)
+    b, n, _ = pcb.shape
+    m = int(nclusters)
+    h = L.lib()
+    nbytes = h.gldm_farthest_points_euclid_large_workspace_bytes(b, n)
+    if nbytes < 0:
+        raise L.GldmError(f"gldm_farthest_points_euclid_large: {h.gldm_status_string(int(nbytes)).decode()} "
+                          f"(b = {b}, n = {n}; 8192 < n <= 2^22)")
+    if counts is not None:
+        _need_cuda(counts, "counts")
+        counts = counts.to(device=pcb.device, dtype=torch.int32).reshape(b).contiguous()
+    idx = torch.empty((b, m), dtype=torch.int32, device=pcb.device) if out is None else out
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=pcb.device)
+    with torch.cuda.device(pcb.device):
+        L.call("gldm_farthest_points_euclid_large", L.ptr(pcb), L.ptr(counts), b, n, m, L.ptr(ws), nbytes, L.ptr(idx),
+               L.current_stream(pcb.device))
     return idx
 
 
@@ -140,6 +175,137 @@ def normalize_input(pc, pc_shift=PC_SHIFT, pc_scale=PC_SCALE, mrp_scale=MRP_SCAL
     metas = dict(pc_mean=pc_mean if pc.ndim == 3 else pc_mean[0], pc_std=sc.to(dev).unsqueeze(0),
                  grasp_mean=gm, grasp_std=gstd, dataset_normalized=True, use_dataset_statistics=False)
     return (out if pc.ndim == 3 else out[0]), metas
+
+
+FLT_MAX = 3.4028234663852886e38
+
+
+def depth_tile_pixels():
+    """Pixels per tile (= per workgroup) of gldm_depth_to_cloud."""
+    return int(L.lib().gldm_depth_to_cloud_tile_pixels())
+
+
+def _host_floats(v, n, name):
+    a = np.ascontiguousarray(np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, dtype=np.float32).reshape(-1))
+    if a.size != n:
+        raise ValueError(f"{name} must hold {n} numbers, not {a.size}")
+    return a
+
+
+def depth_to_cloud(depth, camera, mask=None, z_range=None, depth_scale=None, cam_to_world=None, crop_box=None,
+                   return_pixels=False):
+    """Depth frame(s) -> cloud(s), one HIP entry (gldm_depth_to_cloud): the deprojection of
+    Camera.depth_to_pointcloud_torch (grasp_ldm/utils/camera.py:176-215) with a mask, a depth window, a rigid transform
+    and a crop box folded in.
+      depth         CUDA [H, W] or [F, H, W]: float32 metres, or raw sensor units as torch.uint16 (or int16 holding the
+                    same bits) together with depth_scale (metres per unit, e.g. 0.001)
+      camera        graspldm_amd.camera.Camera (fx, fy, cx, cy; its width / height must match)
+      mask          CUDA bool / uint8 of depth's shape, nonzero = keep
+      z_range       (z_min, z_max): kept iff z_min < d <= z_max; default (0, FLT_MAX): NaN, inf, zero and negative
+                    depth are dropped
+      cam_to_world  3 x 4 or 4 x 4 (host or device; read on the host): points come out as R p + t
+      crop_box      ((x0, y0, z0), (x1, y1, z1)) in the output frame, faces included
+    Kept pixels come in ascending pixel index v * W + u (the order of torch.where(depth > 0)).
+    -> [n, 3] for an [H, W] input, a list of F clouds [n_f, 3] for [F, H, W] (views of one buffer, cut after ONE
+    read-back of the counts); with return_pixels also the int32 source pixel indices in the same form."""
+    _need_cuda(depth, "depth")
+    if depth.ndim not in (2, 3):
+        raise ValueError(f"depth must be [H, W] or [F, H, W], not {tuple(depth.shape)}")
+    single = depth.ndim == 2
+    d = (depth.unsqueeze(0) if single else depth).contiguous()
+    f, h, w = d.shape
+    if (h, w) != (camera.height, camera.width):
+        raise ValueError(f"depth frames are {h} x {w}, the camera model is {camera.height} x {camera.width}")
+    raw_types = tuple(t for t in (getattr(torch, "uint16", None), torch.int16) if t is not None)
+    is_u16 = d.dtype in raw_types
+    if is_u16:
+        if depth_scale is None:
+            raise ValueError("raw 16-bit depth needs depth_scale (metres per unit)")
+    elif d.dtype == torch.float32:
+        if depth_scale is not None:
+            raise ValueError("depth_scale goes with raw 16-bit depth; float32 depth is in metres")
+    else:
+        raise ValueError(f"depth must be float32 (metres) or 16-bit raw units, not {d.dtype}")
+    dev = d.device
+    m8 = None
+    if mask is not None:
+        _need_cuda(mask, "mask")
+        m8 = (mask.unsqueeze(0) if mask.ndim == 2 else mask)
+        if tuple(m8.shape) != (f, h, w):
+            raise ValueError(f"mask {tuple(mask.shape)} does not match depth {tuple(depth.shape)}")
+        m8 = (m8 if m8.dtype == torch.uint8 else (m8 != 0).to(torch.uint8)).to(dev).contiguous()
+    z_min, z_max = (0.0, FLT_MAX) if z_range is None else (float(z_range[0]), float(z_range[1]))
+    xf = lo = hi = None
+    if cam_to_world is not None:
+        t = np.asarray(cam_to_world.detach().cpu() if isinstance(cam_to_world, torch.Tensor) else cam_to_world, dtype=np.float32)
+        if t.shape not in ((3, 4), (4, 4)):
+            raise ValueError(f"cam_to_world must be 3 x 4 or 4 x 4, not {t.shape}")
+        xf = np.ascontiguousarray(t[:3].reshape(-1))
+    if crop_box is not None:
+        lo, hi = _host_floats(crop_box[0], 3, "crop_box[0]"), _host_floats(crop_box[1], 3, "crop_box[1]")
+    fx, fy, cx, cy = camera.intrinsics
+    lib = L.lib()
+    nbytes = lib.gldm_depth_to_cloud_workspace_bytes(f, h, w)
+    if nbytes < 0:
+        raise L.GldmError(f"gldm_depth_to_cloud: {lib.gldm_status_string(int(nbytes)).decode()} (frames {f}, {h} x {w}; "
+                          "1 <= H*W <= 2^24)")
+    ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+    points = torch.empty((f, h * w, 3), dtype=torch.float32, device=dev)
+    count = torch.empty(f, dtype=torch.int32, device=dev)
+    pixel = torch.empty((f, h * w), dtype=torch.int32, device=dev) if return_pixels else None
+    hp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+    with torch.cuda.device(dev):
+        L.call("gldm_depth_to_cloud", L.ptr(d), int(is_u16), float(depth_scale or 1.0), L.ptr(m8), f, h, w, fx, fy, cx, cy,
+               z_min, z_max, hp(xf), hp(lo), hp(hi), L.ptr(ws), nbytes, L.ptr(points), L.ptr(count), L.ptr(pixel),
+               L.current_stream(dev))
+    counts = count.tolist()   # the one read-back
+    clouds = [points[i, :c] for i, c in enumerate(counts)]
+    if not return_pixels:
+        return clouds[0] if single else clouds
+    pixels = [pixel[i, :c] for i, c in enumerate(counts)]
+    return (clouds[0], pixels[0]) if single else (clouds, pixels)
+
+
+def read_depth_file(path):
+    """A depth image from disk -> numpy [H, W]: float32 (metres) or uint16 (raw units: pass depth_scale on).  `.npy`,
+    `.npz` (key depth, else arr_0) and 16-bit `.png` (only where PIL is installed)."""
+    ext = path.rsplit(".", 1)[-1].lower() if "." in path else ""
+    if ext == "npy":
+        a = np.load(path)
+    elif ext == "npz":
+        with np.load(path) as z:
+            key = next((k for k in ("depth", "arr_0") if k in z.files), None)
+            if key is None:
+                raise ValueError(f"{path}: none of the arrays depth / arr_0 found (has {z.files})")
+            a = z[key]
+    elif ext == "png":
+        try:
+            from PIL import Image
+        except ImportError as e:
+            raise RuntimeError(f"{path}: reading .png depth needs PIL (Pillow), which is not installed; convert the "
+                               "image to .npy / .npz") from e
+        a = np.asarray(Image.open(path))
+        if a.dtype != np.uint16:
+            raise ValueError(f"{path}: expected a 16-bit single-channel depth image, got {a.dtype} {a.shape}")
+    else:
+        raise ValueError(f"{path}: unknown depth format (.npy .npz .png)")
+    a = np.asarray(a)
+    if a.ndim != 2 or a.size == 0:
+        raise ValueError(f"{path}: expected an [H, W] depth image, got {a.shape}")
+    if a.dtype == np.uint16:
+        return np.ascontiguousarray(a)
+    if a.dtype.kind not in "fiu":
+        raise ValueError(f"{path}: depth must be numeric, got {a.dtype}")
+    return np.ascontiguousarray(a.astype(np.float32))
+
+
+def depth_to_tensor(a, device):
+    """read_depth_file's array on the device: float32, or the uint16 bits (as int16 where torch has no uint16)."""
+    if a.dtype == np.uint16:
+        if hasattr(torch, "uint16"):
+            return torch.from_numpy(a).to(device)
+        return torch.from_numpy(a.view(np.int16)).to(device)
+    return torch.from_numpy(a).to(device)
 
 
 def read_cloud_file(path):

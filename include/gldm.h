@@ -108,6 +108,49 @@ int gldm_voxel_coords(const float *coords /*[b,3,n]*/, int b, int n, int r, int 
 int gldm_farthest_points_euclid(const float *points /*[b,n,3]*/, int b, int n, int m,
                                 int32_t *out_idx /*[b,m]*/, gldm_stream_t stream);
 
+/* The same selection for clouds beyond one workgroup: 8192 < n <= 2^22 rows per cloud, 1 <= m <= min(n, 8192)
+ * (GLDM_ERR_UNSUPPORTED outside, checked before any pointer; m = 0 is a no-op).  ref: pointcloud_helpers.py:162-223, the
+ * contract of gldm_farthest_points_euclid word for word: start at index 0, sqrt((dx^2 + dy^2) + dz^2) in f32, running
+ * minimum from 1e7, pick = largest distance, lowest index on ties; bit-identical indices.
+ * counts [b] (device, may be NULL = every cloud has n rows): the live rows of each cloud, all with row stride n, so the
+ * frames of one gldm_depth_to_cloud call go through one call; no row past counts[b] is read.  A cloud with counts[b] <= m
+ * gets 0 .. counts[b]-1 followed by -1 (the reference's nclusters >= N -> arange, :185-191).
+ * workspace: gldm_farthest_points_euclid_large_workspace_bytes(b, n) bytes, 8-byte aligned, uninitialised, private to the
+ * stream until the work has finished (running minima [b, n] f32 + two sets of one 64-bit key per slice); smaller:
+ * GLDM_ERR_WORKSPACE.  The bytes query returns a negative GLDM_ERR_* status for a shape outside the envelope.
+ * One launch per round over (slices, b), enqueued back to back; returns without synchronising.
+ * gldm_farthest_points_euclid_large_slice(n): the rows per slice (= per workgroup) at this n. */
+long long gldm_farthest_points_euclid_large_workspace_bytes(int b, int n);
+int gldm_farthest_points_euclid_large_slice(int n);
+int gldm_farthest_points_euclid_large(const float *points /*[b,n,3]*/, const int32_t *counts /*[b] or NULL*/, int b, int n,
+                                      int m, void *workspace, long long workspace_bytes, int32_t *out_idx /*[b,m]*/,
+                                      gldm_stream_t stream);
+
+/* ref: grasp_ldm/utils/camera.py:176-215 (Camera.depth_to_pointcloud_torch): depth frames -> ordered clouds.
+ * depth [frames,h,w]: f32 metres (depth_is_u16 = 0) or u16 raw units (1; d = f32(raw) * depth_scale).  mask [frames,h,w]
+ * u8 or NULL, nonzero = keep.  A pixel (u, v) is kept iff d > z_min && d <= z_max (NaN never passes; z_max = FLT_MAX drops
+ * inf), the mask is nonzero, and, with a box, lo <= p' <= hi on all three axes.  Each step rounds once in f32 (no
+ * contraction, IEEE division):  x = ((f32(u) - cx) * d) / fx,  y = ((f32(v) - cy) * d) / fy,  z = d;  with cam_to_world
+ * (host, 3 x 4 row major, or NULL)  p'_i = ((R_i0*x + R_i1*y) + R_i2*z) + t_i.  box_lo / box_hi (host [3], both or
+ * neither) are in the output frame.
+ * Kept pixels of a frame come out in ascending pixel index v*w + u (the row-major order of torch.where(depth > 0)):
+ * points [frames, h*w, 3] rows 0 .. count[f]-1, rows past count[f] are not written; count [frames] int32; pixel
+ * [frames, h*w] int32 (the source pixel of every row) or NULL.
+ * Envelope, checked before any pointer or the device is touched: frames >= 1, 1 <= h*w <= 2^24, frames <= 65535
+ * (GLDM_ERR_UNSUPPORTED beyond), fx, fy != 0, z_min < z_max (GLDM_ERR_INVALID_ARG).
+ * workspace: gldm_depth_to_cloud_workspace_bytes(frames, h, w) bytes (one int32 per tile; a negative GLDM_ERR_* status for a
+ * shape outside the envelope), uninitialised, private to the stream until the work has finished.  Two launches, no
+ * workgroup waits for another.  gldm_depth_to_cloud_tile_pixels(): the pixels per tile (= per workgroup). */
+long long gldm_depth_to_cloud_workspace_bytes(int frames, int h, int w);
+int gldm_depth_to_cloud_tile_pixels(void);
+int gldm_depth_to_cloud(const void *depth /*[frames,h,w] f32 or u16*/, int depth_is_u16, float depth_scale,
+                        const uint8_t *mask /*[frames,h,w] or NULL*/, int frames, int h, int w,
+                        float fx, float fy, float cx, float cy, float z_min, float z_max,
+                        const float *cam_to_world /*host [12] or NULL*/, const float *box_lo /*host [3] or NULL*/,
+                        const float *box_hi /*host [3] or NULL*/, void *workspace, long long workspace_bytes,
+                        float *points /*[frames,h*w,3]*/, int32_t *count /*[frames]*/, int32_t *pixel /*[frames,h*w] or NULL*/,
+                        gldm_stream_t stream);
+
 /* ref: tools/inference.py:570-591 (InferenceLDM.normalize_input) and
  * grasp_ldm/inference/inference_base.py:181-212: pc_out = ((pc - mean_points(pc)) - shift) / scale
  * per axis (shift = _INPUT_PC_SHIFT, scale = _INPUT_PC_SCALE of set_normalization_params :103-130),

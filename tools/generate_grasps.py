@@ -16,7 +16,10 @@ sample / cloud file in order --, un-normalised, in the cloud's frame; --num_gras
 [--min_separation M] (geometric filtering and selection of the generated poses, graspldm_amd/grasp_select.py: the gripper
 must clear the scene, N scene points must lie between the fingers, thresholds on confidence and on the classifier's
 success, the best K or K diverse ones; --out gains selected_index, selected_count, selected_gap, clearance, contacts;
-without any of these flags nothing changes).  `--inference_steps` is honoured (the reference
+without any of these flags nothing changes), --depth_file FILE --camera_json FILE [--mask_file FILE] [--depth_scale S]
+[--z_range MIN MAX] [--crop_box x0 y0 z0 x1 y1 z1] (generate on a depth frame: deprojected on the GPU, the masked / cropped
+pixels are the object, and for --collision_free / --min_contacts without --scene_file the whole frame is the scene;
+exclusive with --pc_file and --synthetic).  `--inference_steps` is honoured (the reference
 silently ignores it: it passes use_fast_sampler=False, tools/generate_grasps.py:69-79).
 """
 import argparse
@@ -84,8 +87,71 @@ def parse_args(argv=None):
                    help="with --top_k: K poses spread over the survivors (greedy farthest pose) instead of the K best")
     p.add_argument("--min_separation", type=float, default=0.0, metavar="M",
                    help="with --diverse: stop once no survivor is at least M metres (RMS control-point distance) from every pick")
+    p.add_argument("--depth_file", type=str, default=None, metavar="FILE",
+                   help="generate on a depth frame ([H,W]; .npy / .npz float metres or uint16 raw units, 16-bit .png where "
+                        "PIL is installed): deprojected on the GPU with --camera_json, then as --pc_file")
+    p.add_argument("--camera_json", type=str, default=None, metavar="FILE",
+                   help="camera model of --depth_file (keys cameraMatrix, width, height, ...)")
+    p.add_argument("--mask_file", type=str, default=None, metavar="FILE",
+                   help="with --depth_file: object mask [H,W] (.npy / .npz key mask or arr_0), nonzero = object pixel")
+    p.add_argument("--depth_scale", type=float, default=None, metavar="S",
+                   help="with --depth_file of raw 16-bit units: metres per unit (e.g. 0.001)")
+    p.add_argument("--z_range", type=float, nargs=2, default=None, metavar=("MIN", "MAX"),
+                   help="with --depth_file: keep MIN < depth <= MAX metres (default: every finite depth > 0)")
+    p.add_argument("--crop_box", type=float, nargs=6, default=None, metavar=("x0", "y0", "z0", "x1", "y1", "z1"),
+                   help="with --depth_file: keep object points inside this box (camera frame, metres)")
     p.add_argument("--out", type=str, default=None, help="write results of all samples to this .npz")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    check_depth_flags(args)
+    return args
+
+
+def check_depth_flags(args):
+    """--depth_file excludes --pc_file / --synthetic and needs --camera_json; its companions need it."""
+    if args.depth_file:
+        if args.pc_file or args.synthetic:
+            raise SystemExit("--depth_file, --pc_file and --synthetic exclude each other")
+        if not args.camera_json:
+            raise SystemExit("--depth_file needs --camera_json")
+        if args.refine_from:
+            raise SystemExit("--refine_from runs on --pc_file / --synthetic clouds")
+        if args.scene_file and len(args.scene_file) != 1:
+            raise SystemExit("--scene_file: one file for the one --depth_file frame")
+        return
+    for flag in ("camera_json", "mask_file", "depth_scale", "z_range", "crop_box"):
+        if getattr(args, flag) is not None:
+            raise SystemExit(f"--{flag} goes with --depth_file")
+
+
+def read_mask_file(path):
+    a = np.load(path)
+    if hasattr(a, "files"):
+        key = next((k for k in ("mask", "arr_0") if k in a.files), None)
+        if key is None:
+            raise SystemExit(f"{path}: none of the arrays mask / arr_0 found (has {list(a.files)})")
+        a = a[key]
+    a = np.asarray(a)
+    if a.ndim != 2:
+        raise SystemExit(f"{path}: the mask must be [H, W], found {a.shape}")
+    return torch.from_numpy(np.ascontiguousarray((a != 0).astype(np.uint8)))
+
+
+def run_depth(args, model, selection):
+    """--depth_file: one frame through infer_on_depth."""
+    from graspldm_amd.camera import Camera
+    from graspldm_amd.pointcloud import depth_to_tensor, read_depth_file
+    cam = Camera(args.camera_json)
+    depth = depth_to_tensor(read_depth_file(args.depth_file), args.device)
+    mask = read_mask_file(args.mask_file).to(args.device) if args.mask_file else None
+    n_pts = args.num_points or encoder_points(model.model)
+    box = None if args.crop_box is None else (args.crop_box[:3], args.crop_box[3:])
+    res = model.infer_on_depth(depth, cam, mask=mask, num_grasps=args.num_grasps, num_points=n_pts,
+                               use_farthest_point=not args.random_resample, z_range=args.z_range,
+                               depth_scale=args.depth_scale, crop_box=box, **selection_kwargs(args, selection, 0))
+    conf = res["confidence"].flatten()
+    print(f"{args.depth_file}: {tuple(depth.shape)} depth -> {n_pts} points; grasps {tuple(res['grasps'].shape)}  "
+          f"confidence mean {conf.mean().item():.3f}  best {conf.max().item():.3f}")
+    return [res]
 
 
 def build_selection(args):
@@ -230,6 +296,8 @@ def main(argv=None):
     model = setup_classifier(args, setup_model(args))
     from graspldm_amd.synthetic import normalize_cloud, synthetic_cloud
     results = []
+    if args.depth_file:
+        return finish(args, run_depth(args, model, selection))
     if args.pc_file:
         from graspldm_amd.pointcloud import read_cloud_file
         n_pts = args.num_points or encoder_points(model.model)
