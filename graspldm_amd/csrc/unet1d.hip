@@ -261,26 +261,8 @@ __device__ __forceinline__ void u_attention(float *lds, const float *__restrict_
   }
 }
 
-// x_{t-1} from (x_t, eps): the arithmetic of gldm_denoise's step (csrc/resnet1d.hip), one rounding per written operation
-#pragma clang fp contract(off)
-__device__ __forceinline__ float u_sched_update(int kind, int clip, const float *cf, float x, float eps, float noise) {
-  float x0 = (x - cf[0] * eps) / cf[1];
-  if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-  if (kind == GLDM_SCHED_DDIM) {
-    const float a = cf[2] * x0;
-    const float b = cf[3] * eps;
-    return a + b;
-  }
-  const float a = cf[4] * x0;
-  const float b = cf[5] * x;
-  float prev = a + b;
-  if (cf[7] != 0.f) {
-    const float nz = cf[6] * noise;
-    prev = prev + nz;
-  }
-  return prev;
-}
-#pragma clang fp contract(fast)
+// x_{t-1} from (x_t, eps): scheduler_update, the arithmetic of gldm_denoise's step
+#include "diffusion_step.h"
 
 template <bool F32>
 __global__ __launch_bounds__(kUThreads) void unet1d_kernel(const UArgs a) {
@@ -357,7 +339,7 @@ __global__ __launch_bounds__(kUThreads) void unet1d_kernel(const UArgs a) {
         float nz = 0.f;
         if (a.kind == GLDM_SCHED_DDPM && cf[7] != 0.f && a.noise && gi < a.n)
           nz = a.noise[((size_t)step * a.n + gi) * L + i % L];
-        lds[d.o_lat + i] = u_sched_update(a.kind, a.clip, cf, lds[d.o_lat + i], lds[d.o_eps + i], nz);
+        lds[d.o_lat + i] = scheduler_update(a.kind, a.clip, cf, lds[d.o_lat + i], lds[d.o_eps + i], nz);
       }
       __syncthreads();
     }

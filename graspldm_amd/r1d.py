@@ -41,7 +41,7 @@ class R1dEngine:
         """Sum of the hand-off error words of every workspace (0 unless a bounded wait expired); synchronises."""
         return int(sum(int(ws[12:16].view(torch.int32).item()) for ws in self._ws.values()))
 
-    # A step-segment hand-off whose bounded wait expires (csrc/resnet1d.hip: chain_take) poisons its tile with NaN
+    # A step-segment hand-off whose bounded wait expires (csrc/r1d_chain.h: chain_take) poisons its tile with NaN
     # and sets the workspace's error word.  The word is copied to pinned host memory behind every multi-step launch
     # (4 bytes, asynchronous, same stream) and looked at without a host sync at the next launch on that workspace,
     # and with one in check(), which the inference harness calls before results leave the device.

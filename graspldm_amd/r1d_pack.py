@@ -229,7 +229,7 @@ def pack_resnet1d(sd, p, groups, seq_len, cond_rows=3, num_steps=None, decoder=N
         for pr in range(2):
             rows = torch.cat([wqkv[o + 64 * pr:o + 64 * pr + 64] for o in (0, hid, 2 * hid)])
             lv.qkv_w[pr] = buf.add(mfma_a_fragments(rows))
-        # PreNorm LayerNorm folded into to_qkv (csrc/resnet1d.hip: qkv_ln_pm / qkv4_pm), to_qkv's own row order:
+        # PreNorm LayerNorm folded into to_qkv (csrc/r1d_wide.h: qkv_att_pm / qkv_att16_pm), to_qkv's own row order:
         # W LN(x) = rstd (W' x - mean s),  W' = W diag(g), s = W' 1; products and sums in f64, rounded once
         wn = (wqkv.double() * sd[q + "2.fn.norm.g"].double().reshape(1, -1)).float()
         lv.qkvn_w = buf.add(mfma_a_fragments(wn))

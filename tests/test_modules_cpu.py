@@ -173,7 +173,7 @@ def test_decoder_workspace_holds_the_scale_shift_table():
 
 def test_folded_prenorm_qkv_block_of_the_descriptor(fpc_state_dict):
     """ABI 4: per level, to_qkv with the PreNorm LayerNorm gain folded in (W' = W diag(g), to_qkv's own row order,
-    MFMA fragment order) and its row sums s = W' 1, so that W LN(x) = rstd (W' x - mean s) (csrc/resnet1d.hip:
+    MFMA fragment order) and its row sums s = W' 1, so that W LN(x) = rstd (W' x - mean s) (csrc/r1d_wide.h:
     qkv_att_pm).  Checked entry by entry against the state dict, and the identity itself against torch's LayerNorm form
     (resnets.py:104-124)."""
     from graspldm_amd.r1d_pack import pack_resnet1d

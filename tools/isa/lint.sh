@@ -10,7 +10,7 @@ dis() {  # source file -> listing
   /opt/rocm/lib/llvm/bin/clang-offload-bundler --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --input=$tmp/x.co --output=$tmp/x.elf --unbundle
   /opt/rocm/lib/llvm/bin/llvm-objdump -d --no-show-raw-insn $tmp/x.elf > $2
 }
-dis graspldm_amd/csrc/resnet1d.hip $tmp/r1d.s
+dis graspldm_amd/csrc/resnet1d.hip $tmp/r1d.s   # r1d_kernel: the source includes every header of the family (r1d_*.h, quad*_narrow.h)
 dis graspldm_amd/csrc/sa_mlp.hip $tmp/sa.s
 dis graspldm_amd/csrc/pointwise_mlp.hip $tmp/pw.s
 dis graspldm_amd/csrc/conv3d.hip $tmp/c3.s
@@ -22,7 +22,7 @@ lst() {  # kernel -> the listing that holds it
   case $1 in r1d_*) echo $tmp/r1d.s;; sa_*) echo $tmp/sa.s;; pointwise_mlp*) echo $tmp/pw.s;; pointwise_*|linear_*|bias_*) echo $tmp/ps.s;; conv3d_*) echo $tmp/c3.s;; gn_*|groupnorm_*|se_*|devoxelize_*) echo $tmp/vn.s;; attn_*) echo $tmp/pa.s;; cls_*) echo $tmp/gc.s;; esac
 }
 for k in r1d_kernelILi64ELi4 r1d_kernelILi32ELi16 pointwise_mlp_sp_kernel attn_gemm_kernelILb0ELb0 attn_gemm_kernelILb0ELb1 cls_head_kernelILb0 cls_head_kernelILb1; do python3 tools/isa/sunk_prefetch_scan.py $(lst $k) $k; python3 tools/isa/branch_density.py $(lst $k) $k; done
-# hand-written DPP blocks (quad_narrow.h, mfma_core.h): no VALU write closer than 2 wait states in front of a DPP read
+# hand-written DPP blocks (quad_narrow.h, quad16_narrow.h, mfma_core.h): no VALU write closer than 2 wait states in front of a DPP read
 # of the same register -- nothing checks that inside an asm statement; fails the lint on any hit
 rc=0
 for k in r1d_kernelILi64ELi4 r1d_kernelILi64ELi16 r1d_kernelILi32ELi4 r1d_kernelILi32ELi16 sa_mlp3_kernel sa_mlp2_kernel pointwise_mlp_sp_kernel attn_gemm_kernelILb0ELb0 attn_gemm_kernelILb0ELb1 attn_gemm_kernelILb1ELb0 cls_head_kernelILb0 cls_head_kernelILb1; do
