@@ -96,6 +96,11 @@ _SIGNATURES = {
     "gldm_depth_to_cloud_tile_pixels": [],
     "gldm_depth_to_cloud": [_vp, _i, _f, _vp, _i, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp],
     "gldm_unet1d": [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "gldm_depth_to_objects_workspace_bytes": [_i, _i, _i, _i],   # returns long long (restype set in lib())
+    "gldm_depth_to_objects": [_vp, _i, _f, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _ll, _vp, _vp,
+                              _vp, _vp, _vp],
+    "gldm_farthest_points_euclid_ragged_workspace_bytes": [_i, _i],   # returns long long (restype set in lib())
+    "gldm_farthest_points_euclid_ragged": [_vp, _vp, _vp, _i, _i, _i, _vp, _ll, _vp, _vp],
 }
 
 
@@ -150,6 +155,8 @@ def lib():
     h.gldm_cls_head_workspace_bytes.restype = ctypes.c_longlong
     h.gldm_farthest_points_euclid_large_workspace_bytes.restype = ctypes.c_longlong
     h.gldm_depth_to_cloud_workspace_bytes.restype = ctypes.c_longlong
+    h.gldm_depth_to_objects_workspace_bytes.restype = ctypes.c_longlong
+    h.gldm_farthest_points_euclid_ragged_workspace_bytes.restype = ctypes.c_longlong
     h.gldm_squeeze_parts.argtypes = []
     h.gldm_squeeze_parts.restype = _i
     _lib = h

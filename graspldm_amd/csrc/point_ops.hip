@@ -366,6 +366,140 @@ __global__ __launch_bounds__(kFpsLargeBlock) void fps_large_round_kernel(const f
   }
 }
 
+// Rule-1 selection over clouds of DIFFERENT sizes packed in one [rows, 3] array (gldm_farthest_points_euclid_ragged): cloud b
+// is rows start[b] .. start[b] + min(count[b], n_max).  Two forms, the keys and the arithmetic of the kernels above, so
+// every cloud gets the picks it would get alone:
+//   fps_ragged_block_kernel  one workgroup per cloud for counts <= 8192 (fps_kernel<1024, 8, 1> with the live row count read
+//                            per cloud, LDS sized for min(n_max, 8192) rows); also writes the 0 .. count-1, -1 rows of the
+//                            clouds with count <= m.  Workgroups of larger clouds leave at once.
+//   fps_ragged_round_kernel  fps_large_round_kernel over (slices(n_max), b) for counts > 8192 (> m, always), rows read at
+//                            start[b]; minima [b, n_max]; workgroups of smaller clouds and of slices past the count leave
+//                            at once, and the partials of those slices are never read.
+constexpr int kFpsRaggedThreads = 1024;
+constexpr int kFpsBlockMaxN = kFpsRaggedThreads * kFpsMaxPerThread;   // 8192
+
+__device__ __forceinline__ int ragged_count(const int32_t *__restrict__ count, int b, int n_max) {
+  const int c = count[b];
+  return c < 0 ? 0 : (c > n_max ? n_max : c);
+}
+
+__global__ __launch_bounds__(kFpsRaggedThreads) void fps_ragged_block_kernel(const float *__restrict__ points,
+                                                                             const int32_t *__restrict__ start,
+                                                                             const int32_t *__restrict__ count, int n_max,
+                                                                             int m, int32_t *__restrict__ out) {
+  extern __shared__ float s_xyz[];  // [3][n], n <= min(n_max, 8192)
+  constexpr int kThreads = kFpsRaggedThreads, kPerThread = kFpsMaxPerThread, kWaves = kThreads / kWave;
+  __shared__ unsigned long long s_part[2][kWaves];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int n = ragged_count(count, b, n_max);
+  if (n > kFpsBlockMaxN) return;   // the round launches serve it
+  out += (size_t)b * m;
+  if (n <= m) {
+    for (int j = tid; j < m; j += kThreads) out[j] = j < n ? j : -1;
+    return;
+  }
+  const float *coords = points + 3 * (size_t)start[b];
+  for (int i = tid; i < 3 * n; i += kThreads) s_xyz[(i % 3) * n + i / 3] = coords[i];
+  float x[kPerThread], y[kPerThread], z[kPerThread], dist[kPerThread];
+#pragma unroll
+  for (int q = 0; q < kPerThread; ++q) {
+    const int k = tid + q * kThreads;
+    const bool ok = k < n;
+    x[q] = ok ? coords[3 * k] : 0.f;
+    y[q] = ok ? coords[3 * k + 1] : 0.f;
+    z[q] = ok ? coords[3 * k + 2] : 0.f;
+    dist[q] = 1e7f;
+  }
+  if (tid == 0) out[0] = 0;
+  __syncthreads();
+  int old = 0;
+  const int wave = tid >> 6, lane = tid & 63;
+  for (int j = 1; j < m; ++j) {
+    const float x1 = s_xyz[old], y1 = s_xyz[old + n], z1 = s_xyz[old + 2 * n];
+    unsigned long long best = 0ull;  // below every real key (low word of a real key is never 0)
+#pragma unroll
+    for (int q = 0; q < kPerThread; ++q) {
+      const int k = tid + q * kThreads;
+      if (k < n) {
+        const float d = __fsqrt_rn((x[q] - x1) * (x[q] - x1) + (y[q] - y1) * (y[q] - y1) + (z[q] - z1) * (z[q] - z1));
+        const float d2 = d < dist[q] ? d : dist[q];
+        dist[q] = d2;
+        const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | ~(unsigned int)k;
+        best = key > best ? key : best;
+      }
+    }
+    best = wave_max_u64(best);
+    if (lane == 0) s_part[j & 1][wave] = best;
+    __syncthreads();
+    unsigned long long v = lane < kWaves ? s_part[j & 1][lane] : 0ull;
+#pragma unroll
+    for (int off = kWaves / 2; off >= 1; off >>= 1) {
+      const unsigned long long o = __shfl_xor(v, off, kWave);
+      v = o > v ? o : v;
+    }
+    best = __shfl(v, 0, kWave);
+    old = (int)((~(unsigned int)best) & 0x3FFFFFu);
+    if (tid == 0) out[j] = old;
+  }
+}
+
+__global__ __launch_bounds__(kFpsLargeBlock) void fps_ragged_round_kernel(const float *__restrict__ points,
+                                                                          const int32_t *__restrict__ start,
+                                                                          const int32_t *__restrict__ count, int n_max, int m,
+                                                                          int slice, float *__restrict__ mind,
+                                                                          unsigned long long *__restrict__ partials, int r,
+                                                                          int32_t *__restrict__ out) {
+  __shared__ unsigned long long s_part[kFpsLargeBlock / kWave];
+  const int s = blockIdx.x, slices = gridDim.x, b = blockIdx.y, tid = threadIdx.x;
+  const int cnt = ragged_count(count, b, n_max);
+  if (cnt <= kFpsBlockMaxN) return;   // the one-workgroup form served it
+  const int live = (cnt + slice - 1) / slice;   // slices that hold rows
+  if (s >= live) return;
+  out += (size_t)b * m;
+  points += 3 * (size_t)start[b];
+  mind += (size_t)b * n_max;
+  const unsigned long long *prev = partials + ((size_t)((r + 1) & 1) * gridDim.y + b) * slices;
+  unsigned long long *mine = partials + ((size_t)(r & 1) * gridDim.y + b) * slices;
+  int pick = 0;
+  if (r > 0) {
+    unsigned long long v = 0ull;
+    for (int i = tid; i < live; i += kFpsLargeBlock) {
+      const unsigned long long o = prev[i];
+      v = o > v ? o : v;
+    }
+    v = wave_max_u64(v);
+    if ((tid & 63) == 0) s_part[tid >> 6] = v;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < kFpsLargeBlock / kWave; ++w) v = s_part[w] > v ? s_part[w] : v;
+    pick = (int)((~(unsigned int)v) & 0x3FFFFFu);   // < cnt: every live slice left the key of a live row
+    __syncthreads();
+  }
+  if (s == 0 && tid == 0) out[r] = pick;
+  if (r == m - 1) return;
+  const float x1 = points[3 * (size_t)pick], y1 = points[3 * (size_t)pick + 1], z1 = points[3 * (size_t)pick + 2];
+  const int k0 = s * slice;   // < cnt
+  const int k1 = (k0 + slice < cnt) ? k0 + slice : cnt;
+  unsigned long long best = 0ull;
+  for (int k = k0 + tid; k < k1; k += kFpsLargeBlock) {
+    const float x = points[3 * (size_t)k], y = points[3 * (size_t)k + 1], z = points[3 * (size_t)k + 2];
+    const float d = __fsqrt_rn((x - x1) * (x - x1) + (y - y1) * (y - y1) + (z - z1) * (z - z1));
+    const float old = r == 0 ? 1e7f : mind[k];
+    const float d2 = d < old ? d : old;
+    mind[k] = d2;
+    const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | ~(unsigned int)k;
+    best = key > best ? key : best;
+  }
+  best = wave_max_u64(best);
+  if ((tid & 63) == 0) s_part[tid >> 6] = best;
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int w = 1; w < kFpsLargeBlock / kWave; ++w) best = s_part[w] > best ? s_part[w] : best;
+    mine[s] = best;
+  }
+}
+
 // -------------------------------------------------- 3-NN + interpolation --
 __global__ __launch_bounds__(256) void three_nn_kernel(const float *__restrict__ points,
                                                        const float *__restrict__ centers, int n, int m,
@@ -1081,6 +1215,52 @@ GLDM_API int gldm_farthest_points_euclid_large(const float *points, const int32_
     hipLaunchKernelGGL(fps_large_round_kernel, dim3(slices, b), dim3(kFpsLargeBlock), 0, s, points, n, m, slice, counts,
                        mind, partials, r, out_idx);
     const int ls = launch_status();
+    if (ls != GLDM_OK) return ls;
+  }
+  return GLDM_OK;
+}
+
+namespace {
+// 0, or the status of a shape outside the envelope of the ragged selection
+int fps_ragged_check(int b, int n_max, int m) {
+  if (b <= 0 || n_max <= 0 || m < 0) return GLDM_ERR_INVALID_ARG;
+  if (n_max > kFpsLargeMaxN || m > kFpsLargeMaxM || b > 65535) return GLDM_ERR_UNSUPPORTED;
+  return GLDM_OK;
+}
+}  // namespace
+
+GLDM_API long long gldm_farthest_points_euclid_ragged_workspace_bytes(int b, int n_max) {
+  const int st = fps_ragged_check(b, n_max, 1);
+  if (st != GLDM_OK) return st;
+  if (n_max <= kFpsBlockMaxN) return 0;
+  return fps_large_minima_bytes(b, n_max) +
+         2ll * b * ceil_div(n_max, fps_large_slice(n_max)) * (long long)sizeof(unsigned long long);
+}
+
+GLDM_API int gldm_farthest_points_euclid_ragged(const float *points, const int32_t *start, const int32_t *count, int b,
+                                                int n_max, int m, void *workspace, long long workspace_bytes,
+                                                int32_t *out_idx, gldm_stream_t stream) {
+  const int st = fps_ragged_check(b, n_max, m);   // the envelope before any pointer
+  if (st != GLDM_OK) return st;
+  const bool large = n_max > kFpsBlockMaxN;
+  if (!points || !start || !count || !out_idx) return GLDM_ERR_INVALID_ARG;
+  if (large && (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 7u))) return GLDM_ERR_INVALID_ARG;
+  if (m == 0) return GLDM_OK;
+  if (large && workspace_bytes < gldm_farthest_points_euclid_ragged_workspace_bytes(b, n_max)) return GLDM_ERR_WORKSPACE;
+  hipStream_t s = as_stream(stream);
+  const int lds_rows = large ? kFpsBlockMaxN : n_max;
+  hipLaunchKernelGGL(fps_ragged_block_kernel, dim3(b), dim3(kFpsRaggedThreads), (size_t)3 * lds_rows * sizeof(float), s,
+                     points, start, count, n_max, m, out_idx);
+  int ls = launch_status();
+  if (ls != GLDM_OK || !large) return ls;
+  const int slice = fps_large_slice(n_max), slices = ceil_div(n_max, slice);
+  float *mind = static_cast<float *>(workspace);
+  unsigned long long *partials =
+      reinterpret_cast<unsigned long long *>(static_cast<char *>(workspace) + fps_large_minima_bytes(b, n_max));
+  for (int r = 0; r < m; ++r) {   // one launch per round, enqueued back to back; no synchronisation here
+    hipLaunchKernelGGL(fps_ragged_round_kernel, dim3(slices, b), dim3(kFpsLargeBlock), 0, s, points, start, count, n_max, m,
+                       slice, mind, partials, r, out_idx);
+    ls = launch_status();
     if (ls != GLDM_OK) return ls;
   }
   return GLDM_OK;

@@ -323,6 +323,69 @@ class _InferenceBase:
         pcn, metas = self.normalize_input(batch)
         return self.generate_grasps(pcn, metas, num_grasps=num_grasps, return_intermediate=return_intermediate, **extra)
 
+    def infer_on_scene(self, depth, camera, labels, num_grasps=10, num_points=None, num_labels=None, min_object_points=32,
+                       use_farthest_point=True, mask=None, z_range=None, depth_scale=None, cam_to_world=None, crop_box=None,
+                       selection=None, scene_pc=None):
+        """One depth frame [H, W] with an instance-label image -> the grasps of every object, as ONE batch (additive,
+        DESIGN.md 4.11).  labels: integer tensor of depth's shape, object k = label k (1 .. num_labels, at most 64; default
+        labels.max()); the other arguments as infer_on_depth.  Objects with fewer than min_object_points points are skipped;
+        the kept ones (ascending label) go through pointcloud.regularize_objects (num_points; None only if they all have
+        the same size), normalize_input and generate_grasps: exactly generate_grasps on the stacked clouds.  When
+        `selection` asks for collision_free or min_contacts and no scene_pc is given, the scene is the same frame without
+        labels, mask and crop, inside z_range, as one [1, Ns, 3] cloud for every object.
+        Added keys: object_label [B] and object_points [B] (label and raw point count of every row of the batch),
+        scene_rank [n, 2] int64: (object row, slot) of every pose that is not NaN, by falling score (selection.score_by;
+        confidence without a selection), ties to the lower object, then the lower slot."""
+        from .pointcloud import _depth_to_objects_packed, depth_to_cloud, regularize_objects
+        depth = depth.to(self.device) if isinstance(depth, torch.Tensor) else depth
+        labels = labels.to(self.device) if isinstance(labels, torch.Tensor) else labels
+        mask = mask.to(self.device) if isinstance(mask, torch.Tensor) else mask
+        if not isinstance(depth, torch.Tensor) or depth.ndim != 2:
+            raise ValueError("infer_on_scene takes one frame [H, W]")
+        kw = dict(z_range=z_range, depth_scale=depth_scale, cam_to_world=cam_to_world)
+        points, _, starts, counts = _depth_to_objects_packed(depth, camera, labels, num_labels=num_labels, mask=mask,
+                                                             crop_box=crop_box, **kw)
+        packed, starts, counts = points[0], starts[0], counts[0]
+        kept = [k for k, c in enumerate(counts) if c >= max(int(min_object_points), 1)]
+        if not kept:
+            raise ValueError(f"no object has at least {min_object_points} points (labels 1 .. {len(counts)} hold "
+                             f"{counts} after the mask, the depth window and the crop box)")
+        ks, kc = [starts[k] for k in kept], [counts[k] for k in kept]
+        if num_points is None:
+            if len(set(kc)) != 1:
+                raise ValueError("the objects' clouds differ in size: pass num_points")
+            batch = torch.stack([packed[s:s + c] for s, c in zip(ks, kc)])
+        else:
+            batch = regularize_objects(packed, ks, kc, num_points, use_farthest_point)
+        if selection is not None and scene_pc is None and selection.needs_clearance:
+            scene_pc = depth_to_cloud(depth, camera, **kw).unsqueeze(0)
+        extra = {} if selection is None else dict(selection=selection, scene_pc=scene_pc)
+        pcn, metas = self.normalize_input(batch)
+        out = self.generate_grasps(pcn, metas, num_grasps=num_grasps, **extra)
+        out["object_label"] = torch.tensor([k + 1 for k in kept], dtype=torch.int64, device=self.device)
+        out["object_points"] = torch.tensor(kc, dtype=torch.int64, device=self.device)
+        out["scene_rank"] = self._scene_rank(out, selection)
+        return out
+
+    @staticmethod
+    def _scene_rank(out, selection):
+        """(object row, slot) [n, 2] of the poses of a result dict that are not NaN, by falling score; ties keep the
+        row-major order."""
+        H = out["grasps"]
+        b, g = H.shape[:2]
+        conf = out["confidence"].reshape(b, g)
+        by = "confidence" if selection is None else selection.score_by
+        if by != "confidence":
+            success = out["success"].reshape(b, g)
+            score = success if by == "success" else conf * success
+        else:
+            score = conf
+        valid = ~torch.isnan(H.reshape(b, g, 16)).any(dim=2)
+        flat = torch.nonzero(valid.reshape(-1)).reshape(-1)
+        s = torch.nan_to_num(score.reshape(-1)[flat], nan=float("-inf"))
+        order = flat[torch.sort(s, descending=True, stable=True).indices]
+        return torch.stack([order // g, order % g], dim=1)
+
     def generate_class_conditioned_grasps(self, pc, num_grasps=10, metas=None, data_idx=None, class_label=0, **kwargs):
         """tools/inference.py:330-364: the label, repeated per grasp, travels in metas["mode_cls"] to the
         class-conditioned denoiser (ClassTimeConditionedResNet1D).  One cloud, like the reference."""

@@ -10,7 +10,10 @@ the same points.  CPU tensors are rejected like everywhere else in this package.
 
 In front of that, from a depth camera: `depth_to_cloud` deprojects depth frames on the GPU
 (gldm_depth_to_cloud; Camera.depth_to_pointcloud_torch, grasp_ldm/utils/camera.py:176-215), `read_depth_file` reads them
-from disk, and clouds of more than 8192 points take gldm_farthest_points_euclid_large.
+from disk, and clouds of more than 8192 points take gldm_farthest_points_euclid_large.  With an instance-label image
+ `depth_to_objects` cuts the frame into every object's cloud in one pass (gldm_depth_to_objects) and
+`regularize_objects` brings clouds of different sizes to one point count with one ragged selection
+(gldm_farthest_points_euclid_ragged) and one gather.
 """
 import ctypes
 
@@ -216,33 +219,8 @@ def depth_to_cloud(depth, camera, mask=None, z_range=None, depth_scale=None, cam
     f, h, w = d.shape
     if (h, w) != (camera.height, camera.width):
         raise ValueError(f"depth frames are {h} x {w}, the camera model is {camera.height} x {camera.width}")
-    raw_types = tuple(t for t in (getattr(torch, "uint16", None), torch.int16) if t is not None)
-    is_u16 = d.dtype in raw_types
-    if is_u16:
-        if depth_scale is None:
-            raise ValueError("raw 16-bit depth needs depth_scale (metres per unit)")
-    elif d.dtype == torch.float32:
-        if depth_scale is not None:
-            raise ValueError("depth_scale goes with raw 16-bit depth; float32 depth is in metres")
-    else:
-        raise ValueError(f"depth must be float32 (metres) or 16-bit raw units, not {d.dtype}")
+    is_u16, m8, z_min, z_max, xf, lo, hi = _depth_options(d, depth, mask, z_range, depth_scale, cam_to_world, crop_box)
     dev = d.device
-    m8 = None
-    if mask is not None:
-        _need_cuda(mask, "mask")
-        m8 = (mask.unsqueeze(0) if mask.ndim == 2 else mask)
-        if tuple(m8.shape) != (f, h, w):
-            raise ValueError(f"mask {tuple(mask.shape)} does not match depth {tuple(depth.shape)}")
-        m8 = (m8 if m8.dtype == torch.uint8 else (m8 != 0).to(torch.uint8)).to(dev).contiguous()
-    z_min, z_max = (0.0, FLT_MAX) if z_range is None else (float(z_range[0]), float(z_range[1]))
-    xf = lo = hi = None
-    if cam_to_world is not None:
-        t = np.asarray(cam_to_world.detach().cpu() if isinstance(cam_to_world, torch.Tensor) else cam_to_world, dtype=np.float32)
-        if t.shape not in ((3, 4), (4, 4)):
-            raise ValueError(f"cam_to_world must be 3 x 4 or 4 x 4, not {t.shape}")
-        xf = np.ascontiguousarray(t[:3].reshape(-1))
-    if crop_box is not None:
-        lo, hi = _host_floats(crop_box[0], 3, "crop_box[0]"), _host_floats(crop_box[1], 3, "crop_box[1]")
     fx, fy, cx, cy = camera.intrinsics
     lib = L.lib()
     nbytes = lib.gldm_depth_to_cloud_workspace_bytes(f, h, w)
@@ -264,6 +242,180 @@ def depth_to_cloud(depth, camera, mask=None, z_range=None, depth_scale=None, cam
         return clouds[0] if single else clouds
     pixels = [pixel[i, :c] for i, c in enumerate(counts)]
     return (clouds[0], pixels[0]) if single else (clouds, pixels)
+
+
+MAX_LABELS = 64   # gldm_depth_to_objects' ceiling on num_labels
+
+
+def depth_to_objects(depth, camera, labels, num_labels=None, mask=None, z_range=None, depth_scale=None, cam_to_world=None,
+                     crop_box=None, return_pixels=False):
+    """Depth frame(s) + instance labels -> every object's cloud, one HIP entry (gldm_depth_to_objects).
+    Arguments as depth_to_cloud, plus
+      labels      CUDA integer tensor of depth's shape: pixel of object k = label k (1 .. num_labels); labels <= 0 or
+                  > num_labels are background
+      num_labels  K (1 .. 64); default int(labels.max()) (one more read-back), at least 1
+    The cloud of object k is bit-identical to depth_to_cloud(depth, camera, mask=(labels == k) & mask, ...).
+    -> a list of K clouds [count_k, 3] (empty ones included) for an [H, W] input, a list of F such lists for [F, H, W]:
+    views of one buffer, cut after ONE read-back of start / count; with return_pixels also the int32 source pixel indices
+    in the same form."""
+    points, pixel, starts, counts = _depth_to_objects_packed(depth, camera, labels, num_labels, mask, z_range, depth_scale,
+                                                             cam_to_world, crop_box, return_pixels)
+    single = depth.ndim == 2
+    clouds = [[points[i, s:s + c] for s, c in zip(st, ct)] for i, (st, ct) in enumerate(zip(starts, counts))]
+    if not return_pixels:
+        return clouds[0] if single else clouds
+    pixels = [[pixel[i, s:s + c] for s, c in zip(st, ct)] for i, (st, ct) in enumerate(zip(starts, counts))]
+    return (clouds[0], pixels[0]) if single else (clouds, pixels)
+
+
+def _depth_to_objects_packed(depth, camera, labels, num_labels=None, mask=None, z_range=None, depth_scale=None,
+                             cam_to_world=None, crop_box=None, return_pixels=False):
+    """depth_to_objects before the cut: (points [F, H*W, 3], pixel [F, H*W] or None, start, count); start / count are host
+    lists [F][K] from the one read-back, start relative to the frame's row 0."""
+    _need_cuda(depth, "depth")
+    _need_cuda(labels, "labels")
+    if depth.ndim not in (2, 3):
+        raise ValueError(f"depth must be [H, W] or [F, H, W], not {tuple(depth.shape)}")
+    if tuple(labels.shape) != tuple(depth.shape):
+        raise ValueError(f"labels {tuple(labels.shape)} do not match depth {tuple(depth.shape)}")
+    if labels.dtype.is_floating_point or labels.dtype == torch.bool:
+        raise ValueError(f"labels must be an integer tensor, not {labels.dtype}")
+    single = depth.ndim == 2
+    d = (depth.unsqueeze(0) if single else depth).contiguous()
+    f, h, w = d.shape
+    if (h, w) != (camera.height, camera.width):
+        raise ValueError(f"depth frames are {h} x {w}, the camera model is {camera.height} x {camera.width}")
+    is_u16, m8, z_min, z_max, xf, lo, hi = _depth_options(d, depth, mask, z_range, depth_scale, cam_to_world, crop_box)
+    dev = d.device
+    lab = labels.reshape(f, h, w).to(device=dev, dtype=torch.int32).contiguous()
+    k = max(int(lab.max()), 1) if num_labels is None else int(num_labels)
+    if k > MAX_LABELS:
+        raise NotImplementedError(f"num_labels = {k}: gldm_depth_to_objects takes at most {MAX_LABELS} labels per call")
+    if k < 1:
+        raise ValueError(f"num_labels must be at least 1, not {k}")
+    fx, fy, cx, cy = camera.intrinsics
+    lib = L.lib()
+    nbytes = lib.gldm_depth_to_objects_workspace_bytes(f, h, w, k)
+    if nbytes < 0:
+        raise L.GldmError(f"gldm_depth_to_objects: {lib.gldm_status_string(int(nbytes)).decode()} (frames {f}, {h} x {w}, "
+                          f"{k} labels; 1 <= H*W <= 2^24)")
+    ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+    points = torch.empty((f, h * w, 3), dtype=torch.float32, device=dev)
+    sc = torch.empty((2, f, k), dtype=torch.int32, device=dev)   # start, count: one buffer, one read-back
+    pixel = torch.empty((f, h * w), dtype=torch.int32, device=dev) if return_pixels else None
+    hp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+    with torch.cuda.device(dev):
+        L.call("gldm_depth_to_objects", L.ptr(d), int(is_u16), float(depth_scale or 1.0), L.ptr(m8), L.ptr(lab), k, f, h, w,
+               fx, fy, cx, cy, z_min, z_max, hp(xf), hp(lo), hp(hi), L.ptr(ws), nbytes, L.ptr(points), L.ptr(sc[0]),
+               L.ptr(sc[1]), L.ptr(pixel), L.current_stream(dev))
+    starts, counts = sc.tolist()   # the one read-back
+    return points, pixel, starts, counts
+
+
+def _depth_options(d, depth, mask, z_range, depth_scale, cam_to_world, crop_box):
+    """The checks and host-side conversions depth_to_cloud makes on its optional arguments, for frames d [F,H,W]:
+    -> (is_u16, mask u8 or None, z_min, z_max, xf, lo, hi)."""
+    f, h, w = d.shape
+    raw_types = tuple(t for t in (getattr(torch, "uint16", None), torch.int16) if t is not None)
+    is_u16 = d.dtype in raw_types
+    if is_u16:
+        if depth_scale is None:
+            raise ValueError("raw 16-bit depth needs depth_scale (metres per unit)")
+    elif d.dtype == torch.float32:
+        if depth_scale is not None:
+            raise ValueError("depth_scale goes with raw 16-bit depth; float32 depth is in metres")
+    else:
+        raise ValueError(f"depth must be float32 (metres) or 16-bit raw units, not {d.dtype}")
+    m8 = None
+    if mask is not None:
+        _need_cuda(mask, "mask")
+        m8 = (mask.unsqueeze(0) if mask.ndim == 2 else mask)
+        if tuple(m8.shape) != (f, h, w):
+            raise ValueError(f"mask {tuple(mask.shape)} does not match depth {tuple(depth.shape)}")
+        m8 = (m8 if m8.dtype == torch.uint8 else (m8 != 0).to(torch.uint8)).to(d.device).contiguous()
+    z_min, z_max = (0.0, FLT_MAX) if z_range is None else (float(z_range[0]), float(z_range[1]))
+    xf = lo = hi = None
+    if cam_to_world is not None:
+        t = np.asarray(cam_to_world.detach().cpu() if isinstance(cam_to_world, torch.Tensor) else cam_to_world, dtype=np.float32)
+        if t.shape not in ((3, 4), (4, 4)):
+            raise ValueError(f"cam_to_world must be 3 x 4 or 4 x 4, not {t.shape}")
+        xf = np.ascontiguousarray(t[:3].reshape(-1))
+    if crop_box is not None:
+        lo, hi = _host_floats(crop_box[0], 3, "crop_box[0]"), _host_floats(crop_box[1], 3, "crop_box[1]")
+    return is_u16, m8, z_min, z_max, xf, lo, hi
+
+
+def farthest_point_indices_ragged(packed, start, count, n_max, nclusters):
+    """gldm_farthest_points_euclid_ragged: farthest-point selection over B clouds of different sizes packed in
+    `packed` [rows, 3]; start / count: int32 [B] on the device, n_max: a host upper bound of the counts.  -> int32
+    [B, nclusters], relative to each cloud's start: what farthest_point_indices returns for that cloud alone; a cloud with
+    count <= nclusters gets 0 .. count-1 followed by -1."""
+    _need_cuda(packed, "packed")
+    if packed.ndim != 2 or packed.shape[1] != 3:
+        raise ValueError(f"packed must be [rows, 3], not {tuple(packed.shape)}")
+    pts = packed.contiguous().float()
+    dev = pts.device
+    start = start.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    count = count.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    b, m, n_max = start.shape[0], int(nclusters), int(n_max)
+    if count.shape[0] != b:
+        raise ValueError(f"start holds {b} clouds, count {count.shape[0]}")
+    h = L.lib()
+    nbytes = h.gldm_farthest_points_euclid_ragged_workspace_bytes(b, n_max)
+    if nbytes < 0:
+        raise L.GldmError(f"gldm_farthest_points_euclid_ragged: {h.gldm_status_string(int(nbytes)).decode()} "
+                          f"(b = {b}, n_max = {n_max}; 1 <= n_max <= 2^22)")
+    idx = torch.empty((b, m), dtype=torch.int32, device=dev)
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev) if nbytes else None
+    with torch.cuda.device(dev):
+        L.call("gldm_farthest_points_euclid_ragged", L.ptr(pts), L.ptr(start), L.ptr(count), b, n_max, m, L.ptr(ws), nbytes,
+               L.ptr(idx), L.current_stream(dev))
+    return idx
+
+
+def regularize_objects(packed, start, count, num_points, use_farthest_point=True, rng=None):
+    """B clouds of different sizes -> [B, num_points, 3]: row i equals
+    PointCloudHelpers.regularize_pc_point_count(packed[start[i]:start[i] + count[i]], num_points, use_farthest_point, rng),
+    called in ascending i (the order of the draws of rng / np.random).  packed [rows, 3] on the device; start / count:
+    host sequences of ints.  Clouds above num_points with use_farthest_point go through ONE ragged selection
+    (gldm_farthest_points_euclid_ragged); the others get the host-drawn indices of that function; then one
+    gldm_gather_points over the packed rows."""
+    _need_cuda(packed, "packed")
+    if packed.ndim != 2 or packed.shape[1] != 3:
+        raise ValueError(f"packed must be [rows, 3], not {tuple(packed.shape)}")
+    start, count = [int(s) for s in start], [int(c) for c in count]
+    if len(start) != len(count) or not start:
+        raise ValueError(f"start holds {len(start)} clouds, count {len(count)}; at least one is needed")
+    num_points = int(num_points)
+    for i, (s, c) in enumerate(zip(start, count)):
+        if c <= 0:
+            raise ValueError(f"cloud {i} is empty")
+        if s < 0 or s + c > packed.shape[0]:
+            raise ValueError(f"cloud {i}: rows {s} .. {s + c} leave packed [{packed.shape[0]}, 3]")
+    rng = np.random if rng is None else rng
+    pts = packed.contiguous().float()
+    dev = pts.device
+    b = len(start)
+    idx = torch.zeros((b, num_points), dtype=torch.int64)
+    far = []
+    for i, n in enumerate(count):   # the draws, in the order the per-cloud function makes them
+        if n > num_points:
+            if use_farthest_point:
+                far.append(i)
+            else:
+                idx[i] = torch.from_numpy(np.asarray(rng.choice(range(n), size=num_points, replace=False)))
+        elif n < num_points:
+            extra = torch.from_numpy(np.asarray(rng.choice(range(n), size=num_points - n)))
+            idx[i] = torch.cat([torch.arange(n), extra.long()])
+        else:
+            idx[i] = torch.arange(n)
+    rows = (idx + torch.tensor(start, dtype=torch.int64).unsqueeze(1)).to(device=dev, dtype=torch.int32)
+    if far:
+        fs = torch.tensor([start[i] for i in far], dtype=torch.int32, device=dev)
+        fc = torch.tensor([count[i] for i in far], dtype=torch.int32, device=dev)
+        sel = farthest_point_indices_ragged(pts, fs, fc, max(count[i] for i in far), num_points)
+        rows[torch.tensor(far, device=dev)] = sel + fs.unsqueeze(1)
+    return gather_points(pts.unsqueeze(0), rows.reshape(1, -1)).reshape(b, num_points, 3)
 
 
 def read_depth_file(path):

@@ -126,6 +126,22 @@ int gldm_farthest_points_euclid_large(const float *points /*[b,n,3]*/, const int
                                       int m, void *workspace, long long workspace_bytes, int32_t *out_idx /*[b,m]*/,
                                       gldm_stream_t stream);
 
+/* The same selection over clouds of different sizes in one call: cloud i is rows start[i] .. start[i] + min(count[i], n_max)
+ * of points [rows,3] (start / count: device int32 [b]; n_max: a host upper bound of the counts, counts above it are
+ * clamped).  The rule of gldm_farthest_points_euclid word for word (start at the cloud's row 0, sqrt((dx^2 + dy^2) + dz^2)
+ * in f32, minima from 1e7, largest distance, lowest index on ties, the same 64-bit key), so out_idx [b,m] holds, relative to
+ * the cloud's start, exactly the indices the two entries above return for that cloud alone.  A cloud with count <= m gets
+ * 0 .. count-1 followed by -1, count <= 0 all -1.  No row outside a cloud's range is read.
+ * Envelope, checked before any pointer: 1 <= b <= 65535, 1 <= n_max <= 2^22, 0 <= m <= 8192 (GLDM_ERR_UNSUPPORTED beyond;
+ * m = 0 is a no-op).  One launch serves every cloud of at most 8192 rows (one workgroup each); with n_max > 8192, m further
+ * launches, one per round over (slices(n_max), b), serve the larger ones.  Returns without synchronising.
+ * workspace: gldm_farthest_points_euclid_ragged_workspace_bytes(b, n_max) bytes, 8-byte aligned, uninitialised, private to
+ * the stream until the work has finished; 0 for n_max <= 8192, and workspace may then be NULL. */
+long long gldm_farthest_points_euclid_ragged_workspace_bytes(int b, int n_max);
+int gldm_farthest_points_euclid_ragged(const float *points /*[rows,3]*/, const int32_t *start /*[b]*/,
+                                       const int32_t *count /*[b]*/, int b, int n_max, int m, void *workspace,
+                                       long long workspace_bytes, int32_t *out_idx /*[b,m]*/, gldm_stream_t stream);
+
 /* ref: grasp_ldm/utils/camera.py:176-215 (Camera.depth_to_pointcloud_torch): depth frames -> ordered clouds.
  * depth [frames,h,w]: f32 metres (depth_is_u16 = 0) or u16 raw units (1; d = f32(raw) * depth_scale).  mask [frames,h,w]
  * u8 or NULL, nonzero = keep.  A pixel (u, v) is kept iff d > z_min && d <= z_max (NaN never passes; z_max = FLT_MAX drops
@@ -150,6 +166,30 @@ int gldm_depth_to_cloud(const void *depth /*[frames,h,w] f32 or u16*/, int depth
                         const float *box_hi /*host [3] or NULL*/, void *workspace, long long workspace_bytes,
                         float *points /*[frames,h*w,3]*/, int32_t *count /*[frames]*/, int32_t *pixel /*[frames,h*w] or NULL*/,
                         gldm_stream_t stream);
+
+/* Labelled frames: every object's ordered cloud in one pass (additive; the reference has no counterpart).  Everything of
+ * gldm_depth_to_cloud plus labels [frames,h,w] int32 and num_labels K: a pixel belongs to object k (1 .. K) iff its label
+ * is k and gldm_depth_to_cloud's predicate keeps it; labels <= 0 or > K are background.
+ * points [frames, h*w, 3]: inside a frame the objects lie one after another in ascending label, inside an object the
+ * pixels in ascending pixel index; start / count [frames, K] int32: object (f, k+1) is rows start[f][k] .. + count[f][k] of
+ * frame f (start relative to the frame's row 0; an absent label has count 0); pixel [frames, h*w] int32 or NULL.  Rows past
+ * a frame's total are not written.  The rows, count and pixels of object (f, k) are bit-identical to what
+ * gldm_depth_to_cloud writes for frame f with mask = (labels == k) & mask (the same inlined arithmetic).
+ * Envelope, checked before any pointer or the device is touched: gldm_depth_to_cloud's, and 1 <= K (GLDM_ERR_INVALID_ARG)
+ * <= 64 (GLDM_ERR_UNSUPPORTED).
+ * workspace: gldm_depth_to_objects_workspace_bytes(frames, h, w, K) bytes (one int32 per (label, tile); a negative
+ * GLDM_ERR_* status outside the envelope), uninitialised, private to the stream until the work has finished.  Three
+ * launches (per-tile per-label counts, a scan over the tiles of every (frame, label), the write pass); no workgroup waits
+ * for another. */
+long long gldm_depth_to_objects_workspace_bytes(int frames, int h, int w, int num_labels);
+int gldm_depth_to_objects(const void *depth /*[frames,h,w] f32 or u16*/, int depth_is_u16, float depth_scale,
+                          const uint8_t *mask /*[frames,h,w] or NULL*/, const int32_t *labels /*[frames,h,w]*/,
+                          int num_labels, int frames, int h, int w, float fx, float fy, float cx, float cy, float z_min,
+                          float z_max, const float *cam_to_world /*host [12] or NULL*/,
+                          const float *box_lo /*host [3] or NULL*/, const float *box_hi /*host [3] or NULL*/,
+                          void *workspace, long long workspace_bytes, float *points /*[frames,h*w,3]*/,
+                          int32_t *start /*[frames,K]*/, int32_t *count /*[frames,K]*/,
+                          int32_t *pixel /*[frames,h*w] or NULL*/, gldm_stream_t stream);
 
 /* ref: tools/inference.py:570-591 (InferenceLDM.normalize_input) and
  * grasp_ldm/inference/inference_base.py:181-212: pc_out = ((pc - mean_points(pc)) - shift) / scale

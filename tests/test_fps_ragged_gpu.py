@@ -1,0 +1,132 @@
+"""GPU: gldm_farthest_points_euclid_ragged (csrc/point_ops.hip) -- one call over clouds of different sizes -- against
+oracle.front_end.farthest_points per cloud and against the existing entries per cloud (gldm_farthest_points_euclid up to
+8192 rows, gldm_farthest_points_euclid_large beyond); and pointcloud.regularize_objects against the per-cloud
+PointCloudHelpers.regularize_pc_point_count.  Indices are integers: everything is exact."""
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+
+def _cloud(n, seed):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.rand(n, 3, generator=g) - 0.5) * torch.tensor([0.3, 0.2, 0.1])
+
+
+def _pack(clouds, first=3, gaps=(5, 1, 7)):
+    """Clouds at odd starts in one [rows, 3] array, the rows between them filled with NaN and 1e30 alternately."""
+    rows, start = [torch.full((first, 3), float("nan"))], []
+    at = first
+    for i, c in enumerate(clouds):
+        start.append(at)
+        rows.append(c)
+        gap = gaps[i % len(gaps)]
+        filler = torch.full((gap, 3), float("nan"))
+        filler[1::2] = 1e30
+        rows.append(filler)
+        at += c.shape[0] + gap
+    return torch.cat(rows).contiguous(), start
+
+
+def _ragged(packed, start, count, n_max, m):
+    from graspldm_amd.pointcloud import farthest_point_indices_ragged
+    out = farthest_point_indices_ragged(packed.cuda(), torch.tensor(start, dtype=torch.int32).cuda(),
+                                        torch.tensor(count, dtype=torch.int32).cuda(), n_max, m)
+    assert out.dtype == torch.int32 and tuple(out.shape) == (len(start), m)
+    return out.cpu()
+
+
+def _expect(cloud, m):
+    """[m] int32: the oracle's picks, -1 behind a cloud of at most m rows; checked against the existing entry too."""
+    from oracle import front_end as F
+    from graspldm_amd.pointcloud import farthest_point_indices
+    n = cloud.shape[0]
+    exp = torch.full((m,), -1, dtype=torch.int32)
+    if n == 0:
+        return exp
+    picks = torch.from_numpy(F.farthest_points(cloud.numpy(), m))
+    exp[:picks.shape[0]] = picks
+    if n > m:   # the existing entries, this cloud alone
+        assert torch.equal(farthest_point_indices(cloud.cuda(), m)[0].cpu(), exp)
+    return exp
+
+
+def _check(clouds, m, n_max=None, counts=None):
+    packed, start = _pack(clouds)
+    counts = [c.shape[0] for c in clouds] if counts is None else counts
+    n_max = max(counts) if n_max is None else n_max
+    got = _ragged(packed, start, counts, n_max, m)
+    for i, c in enumerate(clouds):
+        live = c[:max(0, min(counts[i], n_max))]
+        assert torch.equal(got[i], _expect(live, m)), (i, live.shape[0])
+    return got
+
+
+def test_small_clouds_of_every_size_in_one_call():
+    sizes = [1, 5, 64, 65, 1024, 1025, 8192]
+    got = _check([_cloud(n, seed=n) for n in sizes], m=64)
+    assert got[0].tolist() == [0] + [-1] * 63 and got[2].tolist() == list(range(64))   # count <= m: arange, then -1
+    assert int(got[3].min()) >= 0 and got[3, 0] == 0
+
+
+def test_large_and_small_clouds_in_one_call():
+    sizes = [8193, 300, 20011]
+    got = _check([_cloud(n, seed=n) for n in sizes], m=64)
+    assert len(set(got[2].tolist())) == 64 and int(got[2].max()) > 8192
+
+
+def test_n_max_above_every_count_and_below_some():
+    clouds = [_cloud(n, seed=n + 1) for n in (700, 9000, 40)]
+    _check(clouds, m=32, n_max=12345)
+    _check(clouds[:1] + clouds[2:], m=32, n_max=8192)
+    # a count above n_max is clamped: the cloud is its first n_max rows
+    _check(clouds, m=32, n_max=8500)
+    _check(clouds, m=32, n_max=500)
+
+
+def test_ties_on_a_lattice_and_on_coinciding_halves():
+    g = torch.Generator().manual_seed(2)
+    lattice = torch.stack(torch.meshgrid(torch.arange(12.0), torch.arange(11.0), torch.arange(9.0), indexing="ij"), -1)
+    lattice = lattice.reshape(-1, 3)[torch.randperm(12 * 11 * 9, generator=g)]              # 1188 rows, integer distances
+    half = _cloud(4500, seed=8)
+    big_lattice = torch.stack(torch.meshgrid(torch.arange(25.0), torch.arange(24.0), torch.arange(15.0), indexing="ij"), -1)
+    big_lattice = big_lattice.reshape(-1, 3)[torch.randperm(25 * 24 * 15, generator=g)]   # 9000 rows
+    _check([lattice, torch.cat([half[:600], half[:600]]), torch.cat([half, half]), big_lattice], m=48)
+
+
+def test_counts_at_most_m_and_zero():
+    clouds = [_cloud(n, seed=n + 3) for n in (10, 64, 63, 200)]
+    got = _check(clouds, m=64, counts=[10, 64, 0, -4], n_max=64)
+    assert got[0].tolist() == list(range(10)) + [-1] * 54 and got[1].tolist() == list(range(64))
+    assert got[2].tolist() == [-1] * 64 and got[3].tolist() == [-1] * 64
+    # the same beside a cloud that takes the round launches
+    got = _check([_cloud(10, 1), _cloud(8200, 2), _cloud(30, 3)], m=16, counts=[10, 8200, 0])
+    assert got[0].tolist() == list(range(10)) + [-1] * 6 and got[2].tolist() == [-1] * 16
+
+
+def test_two_calls_are_equal():
+    clouds = [_cloud(n, seed=n) for n in (3000, 8300)]
+    packed, start = _pack(clouds)
+    a = _ragged(packed, start, [3000, 8300], 8300, 40)
+    b = _ragged(packed, start, [3000, 8300], 8300, 40)
+    assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("use_fps", [True, False])
+def test_regularize_objects_equals_the_per_cloud_function(use_fps):
+    from graspldm_amd.pointcloud import PointCloudHelpers, regularize_objects
+    sizes = [2000, 300, 9001, 512, 513]   # above, below (resampled), round launches, equal, one above
+    clouds = [_cloud(n, seed=n + 5) for n in sizes]
+    packed, start = _pack(clouds)
+    finite = torch.nan_to_num(packed, nan=7.0)   # the gaps stay distinguishable, and a gathered gap row would show
+    np.random.seed(3)
+    exp = torch.stack([PointCloudHelpers.regularize_pc_point_count(c.cuda(), 512, use_fps) for c in clouds])
+    np.random.seed(3)
+    got = regularize_objects(finite.cuda(), start, sizes, 512, use_farthest_point=use_fps)
+    assert tuple(got.shape) == (5, 512, 3) and torch.equal(got, exp)
+    rng_a, rng_b = np.random.RandomState(9), np.random.RandomState(9)
+    exp = torch.stack([PointCloudHelpers.regularize_pc_point_count(c.cuda(), 512, use_fps, rng_a) for c in clouds])
+    assert torch.equal(regularize_objects(finite.cuda(), start, sizes, 512, use_fps, rng_b), exp)
+    with pytest.raises(ValueError, match="cloud 1 is empty"):
+        regularize_objects(finite.cuda(), start, [5, 0, 5, 5, 5], 512)

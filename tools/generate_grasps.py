@@ -19,7 +19,9 @@ success, the best K or K diverse ones; --out gains selected_index, selected_coun
 without any of these flags nothing changes), --depth_file FILE --camera_json FILE [--mask_file FILE] [--depth_scale S]
 [--z_range MIN MAX] [--crop_box x0 y0 z0 x1 y1 z1] (generate on a depth frame: deprojected on the GPU, the masked / cropped
 pixels are the object, and for --collision_free / --min_contacts without --scene_file the whole frame is the scene;
-exclusive with --pc_file and --synthetic).  `--inference_steps` is honoured (the reference
+exclusive with --pc_file and --synthetic), --labels_file FILE [--min_object_points N] (with --depth_file: an instance-label
+image, object k = label k; every object with at least N points gets its grasps in one batch, infer_on_scene; --out gains
+object_label, object_points, scene_rank).  `--inference_steps` is honoured (the reference
 silently ignores it: it passes use_fast_sampler=False, tools/generate_grasps.py:69-79).
 """
 import argparse
@@ -94,6 +96,11 @@ def parse_args(argv=None):
                    help="camera model of --depth_file (keys cameraMatrix, width, height, ...)")
     p.add_argument("--mask_file", type=str, default=None, metavar="FILE",
                    help="with --depth_file: object mask [H,W] (.npy / .npz key mask or arr_0), nonzero = object pixel")
+    p.add_argument("--labels_file", type=str, default=None, metavar="FILE",
+                   help="with --depth_file: instance labels [H,W] (integer; .npy / .npz key labels or arr_0), object k = "
+                        "label k >= 1: grasps for every object of the frame in one batch")
+    p.add_argument("--min_object_points", type=int, default=None, metavar="N",
+                   help="with --labels_file: skip objects with fewer than N points (default 32)")
     p.add_argument("--depth_scale", type=float, default=None, metavar="S",
                    help="with --depth_file of raw 16-bit units: metres per unit (e.g. 0.001)")
     p.add_argument("--z_range", type=float, nargs=2, default=None, metavar=("MIN", "MAX"),
@@ -117,8 +124,10 @@ def check_depth_flags(args):
             raise SystemExit("--refine_from runs on --pc_file / --synthetic clouds")
         if args.scene_file and len(args.scene_file) != 1:
             raise SystemExit("--scene_file: one file for the one --depth_file frame")
+        if args.min_object_points is not None and not args.labels_file:
+            raise SystemExit("--min_object_points goes with --labels_file")
         return
-    for flag in ("camera_json", "mask_file", "depth_scale", "z_range", "crop_box"):
+    for flag in ("camera_json", "mask_file", "labels_file", "min_object_points", "depth_scale", "z_range", "crop_box"):
         if getattr(args, flag) is not None:
             raise SystemExit(f"--{flag} goes with --depth_file")
 
@@ -136,8 +145,21 @@ def read_mask_file(path):
     return torch.from_numpy(np.ascontiguousarray((a != 0).astype(np.uint8)))
 
 
+def read_labels_file(path):
+    a = np.load(path)
+    if hasattr(a, "files"):
+        key = next((k for k in ("labels", "arr_0") if k in a.files), None)
+        if key is None:
+            raise SystemExit(f"{path}: none of the arrays labels / arr_0 found (has {list(a.files)})")
+        a = a[key]
+    a = np.asarray(a)
+    if a.ndim != 2 or a.dtype.kind not in "iu":
+        raise SystemExit(f"{path}: the labels must be an integer [H, W] image, found {a.dtype} {a.shape}")
+    return torch.from_numpy(np.ascontiguousarray(a.astype(np.int32)))
+
+
 def run_depth(args, model, selection):
-    """--depth_file: one frame through infer_on_depth."""
+    """--depth_file: one frame through infer_on_depth, or with --labels_file through infer_on_scene."""
     from graspldm_amd.camera import Camera
     from graspldm_amd.pointcloud import depth_to_tensor, read_depth_file
     cam = Camera(args.camera_json)
@@ -145,6 +167,18 @@ def run_depth(args, model, selection):
     mask = read_mask_file(args.mask_file).to(args.device) if args.mask_file else None
     n_pts = args.num_points or encoder_points(model.model)
     box = None if args.crop_box is None else (args.crop_box[:3], args.crop_box[3:])
+    if args.labels_file:
+        labels = read_labels_file(args.labels_file).to(args.device)
+        res = model.infer_on_scene(depth, cam, labels, num_grasps=args.num_grasps, num_points=n_pts,
+                                   min_object_points=32 if args.min_object_points is None else args.min_object_points,
+                                   use_farthest_point=not args.random_resample, mask=mask, z_range=args.z_range,
+                                   depth_scale=args.depth_scale, crop_box=box, **selection_kwargs(args, selection, 0))
+        conf = res["confidence"].flatten()
+        conf = conf[~torch.isnan(conf)]
+        print(f"{args.depth_file}: {tuple(depth.shape)} depth, objects {res['object_label'].tolist()} with "
+              f"{res['object_points'].tolist()} points -> {n_pts} each; grasps {tuple(res['grasps'].shape)}  "
+              f"confidence mean {conf.mean().item():.3f}  best {conf.max().item():.3f}")
+        return [res]
     res = model.infer_on_depth(depth, cam, mask=mask, num_grasps=args.num_grasps, num_points=n_pts,
                                use_farthest_point=not args.random_resample, z_range=args.z_range,
                                depth_scale=args.depth_scale, crop_box=box, **selection_kwargs(args, selection, 0))
@@ -352,7 +386,7 @@ def finish(args, results):
     if args.out:
         extra = {k: torch.cat([r[k] for r in results]).cpu().numpy()
                  for k in ("latent_mu", "latent_logvar", "success", "selected_index", "selected_count", "selected_gap",
-                           "clearance", "contacts")
+                           "clearance", "contacts", "object_label", "object_points", "scene_rank")
                  if all(r.get(k) is not None for r in results)}
         np.savez_compressed(args.out, grasps=torch.cat([r["grasps"] for r in results]).cpu().numpy(),
                             grasp_tmrp=torch.cat([r["grasp_tmrp"] for r in results]).cpu().numpy(),
