@@ -101,6 +101,15 @@ _SIGNATURES = {
                               _vp, _vp, _vp],
     "gldm_farthest_points_euclid_ragged_workspace_bytes": [_i, _i],   # returns long long (restype set in lib())
     "gldm_farthest_points_euclid_ragged": [_vp, _vp, _vp, _i, _i, _i, _vp, _ll, _vp, _vp],
+    "gldm_plane_ransac_workspace_bytes": [_i, _i],   # returns long long (restype set in lib())
+    "gldm_plane_ransac_tile_points": [],
+    "gldm_plane_ransac": [_vp, _i, _vp, _i, _f, _f, _vp, _ll, _vp, _vp, _vp],
+    "gldm_plane_moments_workspace_bytes": [_i],   # returns long long (restype set in lib())
+    "gldm_plane_moments": [_vp, _i, _vp, _f, _vp, _ll, _vp, _vp],
+    "gldm_segment_tabletop_workspace_bytes": [_i, _i],   # returns long long (restype set in lib())
+    "gldm_segment_tile_shape": [ctypes.POINTER(_i), ctypes.POINTER(_i)],
+    "gldm_segment_tabletop": [_vp, _i, _f, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _i, _vp,
+                              _ll, _vp, _vp, _vp, _vp, _vp],
 }
 
 
@@ -157,6 +166,9 @@ def lib():
     h.gldm_depth_to_cloud_workspace_bytes.restype = ctypes.c_longlong
     h.gldm_depth_to_objects_workspace_bytes.restype = ctypes.c_longlong
     h.gldm_farthest_points_euclid_ragged_workspace_bytes.restype = ctypes.c_longlong
+    h.gldm_plane_ransac_workspace_bytes.restype = ctypes.c_longlong
+    h.gldm_plane_moments_workspace_bytes.restype = ctypes.c_longlong
+    h.gldm_segment_tabletop_workspace_bytes.restype = ctypes.c_longlong
     h.gldm_squeeze_parts.argtypes = []
     h.gldm_squeeze_parts.restype = _i
     _lib = h

@@ -367,6 +367,31 @@ class _InferenceBase:
         out["scene_rank"] = self._scene_rank(out, selection)
         return out
 
+    def infer_on_tabletop(self, depth, camera, num_grasps=10, num_points=None, segmentation=None, min_object_points=32,
+                          use_farthest_point=True, mask=None, z_range=None, depth_scale=None, cam_to_world=None,
+                          crop_box=None, selection=None, scene_pc=None):
+        """One depth frame [H, W] of objects standing on a table -> the grasps of every object, without a label image
+        (additive): pointcloud.segment_tabletop makes the labels on the GPU (a RANSAC table plane, then the
+        connected components above it), infer_on_scene does the rest with them.  segmentation: a dict of
+        segment_tabletop's own options (plane, height_range, link_dist, min_pixels, max_objects, tol, hypotheses, rng,
+        refit, min_cross2); the depth options go to both.  The result of infer_on_scene gains `labels` ([H, W] int32) and
+        `table_plane` (pointcloud.TablePlane).  No object found: ValueError."""
+        from .pointcloud import segment_tabletop
+        depth = depth.to(self.device) if isinstance(depth, torch.Tensor) else depth
+        mask = mask.to(self.device) if isinstance(mask, torch.Tensor) else mask
+        if not isinstance(depth, torch.Tensor) or depth.ndim != 2:
+            raise ValueError("infer_on_tabletop takes one frame [H, W]")
+        kw = dict(mask=mask, z_range=z_range, depth_scale=depth_scale, cam_to_world=cam_to_world, crop_box=crop_box)
+        labels, num, plane = segment_tabletop(depth, camera, **dict(segmentation or {}), **kw)
+        if num < 1:
+            raise ValueError("no object found on the table (no component of enough pixels inside the height range)")
+        out = self.infer_on_scene(depth, camera, labels, num_grasps=num_grasps, num_points=num_points, num_labels=num,
+                                  min_object_points=min_object_points, use_farthest_point=use_farthest_point,
+                                  selection=selection, scene_pc=scene_pc, **kw)
+        out["labels"] = labels
+        out["table_plane"] = plane
+        return out
+
     @staticmethod
     def _scene_rank(out, selection):
         """(object row, slot) [n, 2] of the poses of a result dict that are not NaN, by falling score; ties keep the

@@ -13,7 +13,9 @@ In front of that, from a depth camera: `depth_to_cloud` deproje
 from disk, and clouds of more than 8192 points take gldm_farthest_points_euclid_large.  With an instance-label image
  `depth_to_objects` cuts the frame into every object's cloud in one pass (gldm_depth_to_objects) and
 `regularize_objects` brings clouds of different sizes to one point count with one ragged selection
-(gldm_farthest_points_euclid_ragged) and one gather.
+(gldm_farthest_points_euclid_ragged) and one gather.  Without a label image `fit_table_plane` finds the
+table (gldm_plane_ransac, gldm_plane_moments) and `segment_tabletop` labels the objects standing on it
+(gldm_segment_tabletop).
 """
 import ctypes
 
@@ -532,3 +534,201 @@ def _read_ply_vertices(path):
         dt = np.dtype([(n, "<" + t) for n, t in props])
         v = np.frombuffer(f.read(dt.itemsize * n_vert), dtype=dt, count=n_vert)
         return np.stack([v["x"], v["y"], v["z"]], axis=1)
+
+
+# ------------------------------------------------------------------------------------------ tabletop segmentation --
+# a RANSAC table plane (gldm_plane_ransac, gldm_plane_moments) and the objects above it as connected
+# components of the depth image (gldm_segment_tabletop).  The draws and the 3 x 3 eigen-solve stay on the host.
+RANSAC_MAX_HYPOTHESES = 4096   # gldm_plane_ransac's ceiling on t
+
+
+class TablePlane:
+    """A plane n . p + offset = 0 (f32): `normal` numpy [3], `offset` float, `inliers` (points within tol of the winning
+    hypothesis) and `hypothesis` (its index among the draws).  The camera centre has positive height."""
+
+    def __init__(self, normal, offset, inliers=0, hypothesis=-1):
+        self.normal = np.asarray(normal, dtype=np.float32).reshape(3)
+        self.offset = float(np.float32(offset))
+        self.inliers = int(inliers)
+        self.hypothesis = int(hypothesis)
+
+    def as_array(self):
+        return np.ascontiguousarray(np.append(self.normal, np.float32(self.offset)).astype(np.float32))
+
+    def __repr__(self):
+        return f"TablePlane(normal={self.normal.tolist()}, offset={self.offset}, inliers={self.inliers}, hypothesis={self.hypothesis})"
+
+
+def segment_tile_shape():
+    """(tile width, tile height) in pixels of gldm_segment_tabletop's first launch."""
+    tw, th = ctypes.c_int(0), ctypes.c_int(0)
+    L.call("gldm_segment_tile_shape", ctypes.byref(tw), ctypes.byref(th))
+    return tw.value, th.value
+
+
+def plane_ransac(points, triples, tol, min_cross2=1e-8):
+    """gldm_plane_ransac: points CUDA [n, 3] f32, triples integer [T, 3] (host or device) -> (planes [T, 4] f32,
+    counts [T] int32) on the device; a degenerate hypothesis has plane 0 and count -1."""
+    _need_cuda(points, "points")
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be [n, 3], not {tuple(points.shape)}")
+    pts = points.contiguous().float()
+    dev = pts.device
+    tri = torch.as_tensor(triples).to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
+    n, t = pts.shape[0], tri.shape[0]
+    lib = L.lib()
+    nbytes = lib.gldm_plane_ransac_workspace_bytes(n, t)
+    if nbytes < 0:
+        raise L.GldmError(f"gldm_plane_ransac: {lib.gldm_status_string(int(nbytes)).decode()} (n = {n}, t = {t}; "
+                          f"1 <= n <= 2^24, 1 <= t <= {RANSAC_MAX_HYPOTHESES})")
+    ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+    planes = torch.empty((t, 4), dtype=torch.float32, device=dev)
+    counts = torch.empty(t, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.call("gldm_plane_ransac", L.ptr(pts), n, L.ptr(tri), t, float(tol), float(min_cross2), L.ptr(ws), nbytes,
+               L.ptr(planes), L.ptr(counts), L.current_stream(dev))
+    return planes, counts
+
+
+def plane_moments(points, plane, tol):
+    """gldm_plane_moments: points CUDA [n, 3], plane 4 host floats -> f64 [10] on the device: count, the three sums and the
+    six second moments of the points within tol of the plane."""
+    _need_cuda(points, "points")
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be [n, 3], not {tuple(points.shape)}")
+    pts = points.contiguous().float()
+    dev = pts.device
+    pl = _host_floats(plane, 4, "plane")
+    n = pts.shape[0]
+    lib = L.lib()
+    nbytes = lib.gldm_plane_moments_workspace_bytes(n)
+    if nbytes < 0:
+        raise L.GldmError(f"gldm_plane_moments: {lib.gldm_status_string(int(nbytes)).decode()} (n = {n}; 1 <= n <= 2^24)")
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    out = torch.empty(10, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        L.call("gldm_plane_moments", L.ptr(pts), n, pl.ctypes.data_as(ctypes.c_void_p), float(tol), L.ptr(ws), nbytes,
+               L.ptr(out), L.current_stream(dev))
+    return out
+
+
+def _camera_centre(cam_to_world):
+    if cam_to_world is None:
+        return np.zeros(3, dtype=np.float64)
+    t = np.asarray(cam_to_world.detach().cpu() if isinstance(cam_to_world, torch.Tensor) else cam_to_world, dtype=np.float32)
+    return t[:3, 3].astype(np.float64)
+
+
+def orient_plane(normal, offset, centre):
+    """(normal, offset) f32 with the sign that gives `centre` positive height; a centre on the plane: the first non-zero
+    component of the normal positive."""
+    n = np.asarray(normal, dtype=np.float32)
+    o = np.float32(offset)
+    hgt = float(np.dot(n.astype(np.float64), centre) + np.float64(o))
+    if hgt == 0.0:
+        nz = n[n != 0]
+        flip = nz.size > 0 and nz[0] < 0
+    else:
+        flip = hgt < 0.0
+    return (-n, -o) if flip else (n, o)
+
+
+def plane_from_moments(m):
+    """Least-squares plane of the moments (f64 [10]: count, sums, second moments): the eigenvector of the smallest eigenvalue
+    of the covariance (numpy.linalg.eigh, f64), offset = -n . mean, both rounded to f32."""
+    m = np.asarray(m, dtype=np.float64)
+    cnt = m[0]
+    mean = m[1:4] / cnt
+    sec = np.array([[m[4], m[5], m[6]], [m[5], m[7], m[8]], [m[6], m[8], m[9]]], dtype=np.float64) / cnt
+    cov = sec - np.outer(mean, mean)
+    _, vec = np.linalg.eigh(cov)
+    n = vec[:, 0]
+    return n.astype(np.float32), np.float32(-np.dot(n, mean))
+
+
+def fit_table_plane(depth, camera, tol=0.005, hypotheses=512, rng=None, refit=True, min_cross2=1e-8, mask=None, z_range=None,
+                    depth_scale=None, cam_to_world=None, crop_box=None):
+    """The dominant plane of one depth frame [H, W] by RANSAC on the GPU -> TablePlane.
+    depth_to_cloud (its options: mask, z_range, depth_scale, cam_to_world, crop_box) gives the n points; the triples are
+    rng.integers(0, n, (hypotheses, 3)) drawn on the host (rng=None: np.random.default_rng(0)); ONE gldm_plane_ransac call
+    scores them and ONE read-back brings the counts; the best is the highest count, ties to the lowest index.  With refit,
+    one gldm_plane_moments call over its inliers and the smallest eigenvector of their f64 covariance replace it.  The
+    camera centre (translation of cam_to_world, else the origin) gets positive height.  Fewer than 3 points, or every
+    hypothesis degenerate: ValueError."""
+    _need_cuda(depth, "depth")
+    if depth.ndim != 2:
+        raise ValueError(f"fit_table_plane takes one frame [H, W], not {tuple(depth.shape)}")
+    t = int(hypotheses)
+    if not 1 <= t <= RANSAC_MAX_HYPOTHESES:
+        raise ValueError(f"hypotheses must be 1 .. {RANSAC_MAX_HYPOTHESES}, not {t}")
+    cloud = depth_to_cloud(depth, camera, mask=mask, z_range=z_range, depth_scale=depth_scale, cam_to_world=cam_to_world,
+                           crop_box=crop_box)
+    n = cloud.shape[0]
+    if n < 3:
+        raise ValueError(f"the frame keeps {n} points; a plane needs 3")
+    rng = np.random.default_rng(0) if rng is None else rng
+    triples = np.asarray(rng.integers(0, n, (t, 3)), dtype=np.int32)
+    planes, counts = plane_ransac(cloud, torch.from_numpy(triples), tol, min_cross2)
+    host = counts.cpu().numpy()   # the one read-back of the T counts
+    best = int(np.argmax(host))   # the first of the highest
+    if host[best] < 0:
+        raise ValueError(f"all {t} hypotheses are degenerate (repeated or collinear points); no plane")
+    plane = planes[best].cpu().numpy()
+    normal, offset = plane[:3], plane[3]
+    if refit:
+        normal, offset = plane_from_moments(plane_moments(cloud, plane, tol).cpu().numpy())
+    normal, offset = orient_plane(normal, offset, _camera_centre(cam_to_world))
+    return TablePlane(normal, offset, inliers=int(host[best]), hypothesis=best)
+
+
+def segment_tabletop(depth, camera, plane=None, height_range=(0.01, 0.5), link_dist=0.01, min_pixels=32, max_objects=64,
+                     mask=None, z_range=None, depth_scale=None, cam_to_world=None, crop_box=None, tol=0.005, hypotheses=512,
+                     rng=None, refit=True, min_cross2=1e-8, return_stats=False):
+    """One depth frame [H, W] -> an instance-label image of the objects on the table, one HIP entry (gldm_segment_tabletop,
+    DESIGN.md 4.12).  plane: a TablePlane or 4 numbers (a, b, c, d); None fits one with fit_table_plane (tol, hypotheses, rng,
+    refit, min_cross2).  Foreground = pixels depth_to_cloud keeps (same options) whose height over the plane lies in
+    (height_range[0], height_range[1]]; 4-neighbours closer than link_dist in 3-D are linked; components of at least
+    min_pixels pixels are labelled 1 .. K (K <= max_objects <= 64) by falling pixel count, ties to the lower first pixel.
+    -> (labels [H, W] int32 on the device, num_labels, plane); with return_stats also (label_pixels, label_root) host lists."""
+    _need_cuda(depth, "depth")
+    if depth.ndim != 2:
+        raise ValueError(f"segment_tabletop takes one frame [H, W], not {tuple(depth.shape)}")
+    d = depth.contiguous()
+    h, w = d.shape
+    if (h, w) != (camera.height, camera.width):
+        raise ValueError(f"depth frames are {h} x {w}, the camera model is {camera.height} x {camera.width}")
+    if plane is None:
+        plane = fit_table_plane(depth, camera, tol=tol, hypotheses=hypotheses, rng=rng, refit=refit, min_cross2=min_cross2,
+                                mask=mask, z_range=z_range, depth_scale=depth_scale, cam_to_world=cam_to_world,
+                                crop_box=crop_box)
+    pl = plane.as_array() if isinstance(plane, TablePlane) else _host_floats(plane, 4, "plane")
+    k = int(max_objects)
+    if not 1 <= k <= MAX_LABELS:
+        raise ValueError(f"max_objects must be 1 .. {MAX_LABELS}, not {k}")
+    if int(min_pixels) < 1:
+        raise ValueError(f"min_pixels must be at least 1, not {min_pixels}")
+    is_u16, m8, z_min, z_max, xf, lo, hi = _depth_options(d.unsqueeze(0), depth, mask, z_range, depth_scale, cam_to_world,
+                                                          crop_box)
+    dev = d.device
+    fx, fy, cx, cy = camera.intrinsics
+    lib = L.lib()
+    nbytes = lib.gldm_segment_tabletop_workspace_bytes(h, w)
+    if nbytes < 0:
+        raise L.GldmError(f"gldm_segment_tabletop: {lib.gldm_status_string(int(nbytes)).decode()} ({h} x {w}; "
+                          "1 <= H*W <= 2^24)")
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    labels = torch.empty((h, w), dtype=torch.int32, device=dev)
+    stats = torch.empty(1 + 2 * k, dtype=torch.int32, device=dev)   # num_labels, label_pixels, label_root: one read-back
+    hp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+    with torch.cuda.device(dev):
+        L.call("gldm_segment_tabletop", L.ptr(d), int(is_u16), float(depth_scale or 1.0), L.ptr(m8), h, w, fx, fy, cx, cy,
+               z_min, z_max, hp(xf), hp(lo), hp(hi), hp(pl), float(height_range[0]), float(height_range[1]),
+               float(link_dist), int(min_pixels), k, L.ptr(ws), nbytes, L.ptr(labels), L.ptr(stats[0:1]),
+               L.ptr(stats[1:1 + k]), L.ptr(stats[1 + k:]), L.current_stream(dev))
+    host = stats.tolist()   # the one read-back
+    num = host[0]
+    if not isinstance(plane, TablePlane):
+        plane = TablePlane(pl[:3], pl[3])
+    if return_stats:
+        return labels, num, plane, host[1:1 + k], host[1 + k:]
+    return labels, num, plane

@@ -191,6 +191,68 @@ int gldm_depth_to_objects(const void *depth /*[frames,h,w] f32 or u16*/, int dep
                           int32_t *start /*[frames,K]*/, int32_t *count /*[frames,K]*/,
                           int32_t *pixel /*[frames,h*w] or NULL*/, gldm_stream_t stream);
 
+/* ------------------------------------------------ tabletop segmentation (the reference has no counterpart)
+ * Arithmetic of all three entries: f32, every product, difference, sum, quotient and square root rounds once, in the written
+ * order (no contraction, IEEE division and sqrt).  A point q is an INLIER of plane (nx, ny, nz, d) iff
+ *   fabsf(((nx*qx + ny*qy) + nz*qz) + d) <= tol        (NaN never passes).
+ *
+ * gldm_plane_ransac: T plane hypotheses against N points.  points [n,3] f32; triples [t,3] int32 (device).  For the triple
+ * (i, j, k) with p0, p1, p2 the points at i, j, k:  e1 = p1 - p0, e2 = p2 - p0,
+ *   c = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x),  l2 = (cx*cx + cy*cy) + cz*cz,  n = c / sqrtf(l2),
+ *   d = -((nx*p0x + ny*p0y) + nz*p0z).
+ * out_plane [t,4] = (nx, ny, nz, d), out_count [t] = the exact number of inliers among the n points.  A hypothesis with a
+ * repeated index, an index outside [0, n) or !(l2 >= min_cross2) is degenerate: plane 0, count -1.
+ * Envelope, checked before any pointer or the device is touched: 1 <= n (GLDM_ERR_INVALID_ARG) <= 2^24
+ * (GLDM_ERR_UNSUPPORTED), 1 <= t (INVALID_ARG) <= 4096 (UNSUPPORTED), tol and min_cross2 not NaN (INVALID_ARG).
+ * workspace: gldm_plane_ransac_workspace_bytes(n, t) bytes (a negative GLDM_ERR_* status outside the envelope),
+ * uninitialised, private to the stream until the work has finished.  Two launches; counts are combined with integer
+ * atomics, so two calls are bitwise equal; no workgroup waits for another.  gldm_plane_ransac_tile_points(): the points
+ * per workgroup of the count launch. */
+long long gldm_plane_ransac_workspace_bytes(int n, int t);
+int gldm_plane_ransac_tile_points(void);
+int gldm_plane_ransac(const float *points /*[n,3]*/, int n, const int32_t *triples /*[t,3]*/, int t, float tol,
+                      float min_cross2, void *workspace, long long workspace_bytes, float *out_plane /*[t,4]*/,
+                      int32_t *out_count /*[t]*/, gldm_stream_t stream);
+
+/* Moments of the inliers of one plane (host [4]) for a least-squares refit: out [10] f64 (device) = count, Sx, Sy, Sz, Sxx,
+ * Sxy, Sxz, Syy, Syz, Szz.  Products are taken in f64 from the f32 coordinates (exact).  The order of summation is fixed:
+ * per-tile partial sums in a fixed tree, then one workgroup over the tiles in ascending order, so two calls are bitwise
+ * equal.  Envelope: 1 <= n <= 2^24 as above, tol not NaN.  workspace: gldm_plane_moments_workspace_bytes(n) bytes (10 f64
+ * per tile), 8-byte aligned, uninitialised.  Two launches. */
+long long gldm_plane_moments_workspace_bytes(int n);
+int gldm_plane_moments(const float *points /*[n,3]*/, int n, const float *plane /*host [4]*/, float tol, void *workspace,
+                       long long workspace_bytes, double *out /*[10]*/, gldm_stream_t stream);
+
+/* One depth frame -> an instance-label image of the objects standing on a table.  depth / mask / intrinsics / window /
+ * cam_to_world / box: those of gldm_depth_to_cloud with frames = 1 (the same inlined predicate and deprojection).
+ *   foreground  the pixel is kept by that predicate and hgt = ((a*x + b*y) + c*z) + d of its point (x, y, z) under
+ *               plane = (a, b, c, d) (host [4]) satisfies hgt > h_min && hgt <= h_max
+ *   links       two 4-neighbours are linked iff both are foreground and ((dx*dx + dy*dy) + dz*dz) <= link2, dx, dy, dz the
+ *               differences of their points, link2 = link_dist * link_dist formed once in f32 on the host
+ *   components  the transitive closure of the links; a component's root is its lowest pixel index v*w + u
+ *   labels      components of at least min_pixels pixels, ranked by falling pixel count, ties to the lower root; the first
+ *               max_labels of them are labels 1 .. K, every other pixel is 0
+ * labels [h,w] int32: every pixel written; num_labels [1] = K; label_pixels / label_root [max_labels]: pixel count and root
+ * of label k + 1, 0 / -1 past K.  All four are exact and independent of the execution order.
+ * Envelope, checked before any pointer or the device is touched: h, w >= 1 (GLDM_ERR_INVALID_ARG), h*w <= 2^24
+ * (GLDM_ERR_UNSUPPORTED), gldm_depth_to_cloud's conditions on fx, fy, cx, cy, z_min, z_max, h_min < h_max, link_dist >= 0
+ * (inf allowed), min_pixels >= 1, 1 <= max_labels (INVALID_ARG) <= 64 (UNSUPPORTED), no NaN in plane.
+ * workspace: gldm_segment_tabletop_workspace_bytes(h, w) bytes (16 per pixel + 8), 8-byte aligned, uninitialised, private
+ * to the stream until the work has finished.  Six launches back to back (union-find inside tiles in LDS, unions across
+ * tile edges, flatten + sizes, candidate roots, top-K selection in one workgroup, write), no host round trip.  Unions hang
+ * the higher root under the lower, so every find / union loop ends on its own data and no workgroup waits for another.
+ * gldm_segment_tile_shape: the tile of the first launch (pixels wide, pixels high). */
+long long gldm_segment_tabletop_workspace_bytes(int h, int w);
+int gldm_segment_tile_shape(int *tw, int *th);
+int gldm_segment_tabletop(const void *depth /*[h,w] f32 or u16*/, int depth_is_u16, float depth_scale,
+                          const uint8_t *mask /*[h,w] or NULL*/, int h, int w, float fx, float fy, float cx, float cy,
+                          float z_min, float z_max, const float *cam_to_world /*host [12] or NULL*/,
+                          const float *box_lo /*host [3] or NULL*/, const float *box_hi /*host [3] or NULL*/,
+                          const float *plane /*host [4]*/, float h_min, float h_max, float link_dist, int min_pixels,
+                          int max_labels, void *workspace, long long workspace_bytes, int32_t *labels /*[h,w]*/,
+                          int32_t *num_labels /*[1]*/, int32_t *label_pixels /*[max_labels]*/,
+                          int32_t *label_root /*[max_labels]*/, gldm_stream_t stream);
+
 /* ref: tools/inference.py:570-591 (InferenceLDM.normalize_input) and
  * grasp_ldm/inference/inference_base.py:181-212: pc_out = ((pc - mean_points(pc)) - shift) / scale
  * per axis (shift = _INPUT_PC_SHIFT, scale = _INPUT_PC_SCALE of set_normalization_params :103-130),

@@ -21,7 +21,10 @@ without any of these flags nothing changes), --depth_file FILE --camera_json FIL
 pixels are the object, and for --collision_free / --min_contacts without --scene_file the whole frame is the scene;
 exclusive with --pc_file and --synthetic), --labels_file FILE [--min_object_points N] (with --depth_file: an instance-label
 image, object k = label k; every object with at least N points gets its grasps in one batch, infer_on_scene; --out gains
-object_label, object_points, scene_rank).  `--inference_steps` is honoured (the reference
+object_label, object_points, scene_rank), --segment_tabletop [--table_tol T] [--object_height MIN MAX] [--link_dist D]
+[--min_object_pixels N] [--ransac_hypotheses T] [--segment_seed S] (with --depth_file, instead of --labels_file: the labels
+are made on the GPU from the frame itself -- a RANSAC table plane, then the connected components above it,
+infer_on_tabletop; --out gains labels, table_plane and the --labels_file keys).  `--inference_steps` is honoured (the reference
 silently ignores it: it passes use_fast_sampler=False, tools/generate_grasps.py:69-79).
 """
 import argparse
@@ -101,6 +104,21 @@ def parse_args(argv=None):
                         "label k >= 1: grasps for every object of the frame in one batch")
     p.add_argument("--min_object_points", type=int, default=None, metavar="N",
                    help="with --labels_file: skip objects with fewer than N points (default 32)")
+    p.add_argument("--segment_tabletop", action="store_true",
+                   help="with --depth_file: find the table plane and the objects standing on it on the GPU and generate "
+                        "grasps for every object (excludes --labels_file)")
+    p.add_argument("--table_tol", type=float, default=None, metavar="T",
+                   help="with --segment_tabletop: inlier distance of the table plane fit, metres (default 0.005)")
+    p.add_argument("--object_height", type=float, nargs=2, default=None, metavar=("MIN", "MAX"),
+                   help="with --segment_tabletop: object pixels lie MIN < height <= MAX metres over the table (default 0.01 0.5)")
+    p.add_argument("--link_dist", type=float, default=None, metavar="D",
+                   help="with --segment_tabletop: neighbouring pixels at most D metres apart belong together (default 0.01)")
+    p.add_argument("--min_object_pixels", type=int, default=None, metavar="N",
+                   help="with --segment_tabletop: drop components of fewer than N pixels (default 32)")
+    p.add_argument("--ransac_hypotheses", type=int, default=None, metavar="T",
+                   help="with --segment_tabletop: plane hypotheses to score, 1 .. 4096 (default 512)")
+    p.add_argument("--segment_seed", type=int, default=None, metavar="S",
+                   help="with --segment_tabletop: seed of the hypothesis draws (default 0)")
     p.add_argument("--depth_scale", type=float, default=None, metavar="S",
                    help="with --depth_file of raw 16-bit units: metres per unit (e.g. 0.001)")
     p.add_argument("--z_range", type=float, nargs=2, default=None, metavar=("MIN", "MAX"),
@@ -124,12 +142,43 @@ def check_depth_flags(args):
             raise SystemExit("--refine_from runs on --pc_file / --synthetic clouds")
         if args.scene_file and len(args.scene_file) != 1:
             raise SystemExit("--scene_file: one file for the one --depth_file frame")
-        if args.min_object_points is not None and not args.labels_file:
+        if args.segment_tabletop and args.labels_file:
+            raise SystemExit("--segment_tabletop makes the labels itself: it excludes --labels_file")
+        if args.min_object_points is not None and not (args.labels_file or args.segment_tabletop):
             raise SystemExit("--min_object_points goes with --labels_file")
+        for flag in SEGMENT_FLAGS:
+            if getattr(args, flag) is not None and not args.segment_tabletop:
+                raise SystemExit(f"--{flag} goes with --segment_tabletop")
         return
+    if args.segment_tabletop:
+        raise SystemExit("--segment_tabletop goes with --depth_file")
+    for flag in SEGMENT_FLAGS:
+        if getattr(args, flag) is not None:
+            raise SystemExit(f"--{flag} goes with --segment_tabletop")
     for flag in ("camera_json", "mask_file", "labels_file", "min_object_points", "depth_scale", "z_range", "crop_box"):
         if getattr(args, flag) is not None:
             raise SystemExit(f"--{flag} goes with --depth_file")
+
+
+SEGMENT_FLAGS = ("table_tol", "object_height", "link_dist", "min_object_pixels", "ransac_hypotheses", "segment_seed")
+
+
+def segmentation_options(args):
+    """segment_tabletop's options from the --segment_tabletop flags (unset flags keep its defaults)."""
+    opts = {}
+    if args.table_tol is not None:
+        opts["tol"] = args.table_tol
+    if args.object_height is not None:
+        opts["height_range"] = (args.object_height[0], args.object_height[1])
+    if args.link_dist is not None:
+        opts["link_dist"] = args.link_dist
+    if args.min_object_pixels is not None:
+        opts["min_pixels"] = args.min_object_pixels
+    if args.ransac_hypotheses is not None:
+        opts["hypotheses"] = args.ransac_hypotheses
+    if args.segment_seed is not None:
+        opts["rng"] = np.random.default_rng(args.segment_seed)
+    return opts
 
 
 def read_mask_file(path):
@@ -167,12 +216,21 @@ def run_depth(args, model, selection):
     mask = read_mask_file(args.mask_file).to(args.device) if args.mask_file else None
     n_pts = args.num_points or encoder_points(model.model)
     box = None if args.crop_box is None else (args.crop_box[:3], args.crop_box[3:])
-    if args.labels_file:
-        labels = read_labels_file(args.labels_file).to(args.device)
-        res = model.infer_on_scene(depth, cam, labels, num_grasps=args.num_grasps, num_points=n_pts,
-                                   min_object_points=32 if args.min_object_points is None else args.min_object_points,
-                                   use_farthest_point=not args.random_resample, mask=mask, z_range=args.z_range,
-                                   depth_scale=args.depth_scale, crop_box=box, **selection_kwargs(args, selection, 0))
+    if args.labels_file or args.segment_tabletop:
+        common = dict(num_grasps=args.num_grasps, num_points=n_pts,
+                      min_object_points=32 if args.min_object_points is None else args.min_object_points,
+                      use_farthest_point=not args.random_resample, mask=mask, z_range=args.z_range,
+                      depth_scale=args.depth_scale, crop_box=box, **selection_kwargs(args, selection, 0))
+        if args.segment_tabletop:
+            try:
+                res = model.infer_on_tabletop(depth, cam, segmentation=segmentation_options(args), **common)
+            except ValueError as e:
+                raise SystemExit(f"{args.depth_file}: {e}")
+            tp = res["table_plane"]
+            print(f"{args.depth_file}: table plane n = {tp.normal.tolist()}, d = {tp.offset:.6f} ({tp.inliers} inliers)")
+        else:
+            labels = read_labels_file(args.labels_file).to(args.device)
+            res = model.infer_on_scene(depth, cam, labels, **common)
         conf = res["confidence"].flatten()
         conf = conf[~torch.isnan(conf)]
         print(f"{args.depth_file}: {tuple(depth.shape)} depth, objects {res['object_label'].tolist()} with "
@@ -388,6 +446,9 @@ def finish(args, results):
                  for k in ("latent_mu", "latent_logvar", "success", "selected_index", "selected_count", "selected_gap",
                            "clearance", "contacts", "object_label", "object_points", "scene_rank")
                  if all(r.get(k) is not None for r in results)}
+        if all(r.get("table_plane") is not None for r in results):   # --segment_tabletop: one frame per result
+            extra["labels"] = torch.stack([r["labels"] for r in results]).cpu().numpy()
+            extra["table_plane"] = np.stack([r["table_plane"].as_array() for r in results])
         np.savez_compressed(args.out, grasps=torch.cat([r["grasps"] for r in results]).cpu().numpy(),
                             grasp_tmrp=torch.cat([r["grasp_tmrp"] for r in results]).cpu().numpy(),
                             confidence=torch.cat([r["confidence"] for r in results]).cpu().numpy(), **extra)
