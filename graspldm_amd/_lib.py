@@ -24,7 +24,7 @@ _ull = ctypes.c_ulonglong
 _vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 
 _SIGNATURES = {
-    # name: argtypes  (all return int)
+    # name: argtypes  (all return int, but the *_workspace_bytes entries: long long)
     "gldm_ball_query": [_vp, _vp, _i, _i, _i, _f, _i, _vp, _vp],
     "gldm_grouping_forward": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
     "gldm_gather_features_forward": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
@@ -71,14 +71,14 @@ _SIGNATURES = {
     "gldm_pointwise_mlp_f16x2_add": [_vp, _vp, _vp, _vp, _ll, _ll, _ll, _i, _i, _i, _i, _i, _vp, _vp],
     "gldm_pointwise_mlp2_f16x2": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp],
     "gldm_point_attention": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _ll, _vp, _vp],
-    "gldm_point_attention_workspace_bytes": [_i, _i, _i],   # returns long long (restype set in lib())
+    "gldm_point_attention_workspace_bytes": [_i, _i, _i],   # returns long long
     "gldm_groupnorm_swish_points": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp],
     "gldm_pointwise_rows": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
     "gldm_point_attention_fused": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
     "gldm_groupnorm_affine": [_vp, _vp, _i, _i, _i, _vp, _vp],
     "gldm_groupnorm_swish_points_sum": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp],
     "gldm_grasp_scene": [_vp, _vp, _vp, _vp, _f, _f, _i, _i, _i, _i, _vp, _vp],
-    "gldm_cls_head_workspace_bytes": [_i, _i, _i, _i],   # returns long long (restype set in lib())
+    "gldm_cls_head_workspace_bytes": [_i, _i, _i, _i],   # returns long long
     "gldm_cls_head": [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _vp, _ll, _vp, _vp, _vp],
     "gldm_sa_mlp_forward": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "gldm_sa_mlp_forward_f16x2": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -89,24 +89,24 @@ _SIGNATURES = {
     "gldm_grasp_clearance_chunk": [],
     "gldm_grasp_clearance": [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp],
     "gldm_select_grasps": [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
-    "gldm_farthest_points_euclid_large_workspace_bytes": [_i, _i],   # returns long long (restype set in lib())
+    "gldm_farthest_points_euclid_large_workspace_bytes": [_i, _i],   # returns long long
     "gldm_farthest_points_euclid_large_slice": [_i],
     "gldm_farthest_points_euclid_large": [_vp, _vp, _i, _i, _i, _vp, _ll, _vp, _vp],
-    "gldm_depth_to_cloud_workspace_bytes": [_i, _i, _i],   # returns long long (restype set in lib())
+    "gldm_depth_to_cloud_workspace_bytes": [_i, _i, _i],   # returns long long
     "gldm_depth_to_cloud_tile_pixels": [],
     "gldm_depth_to_cloud": [_vp, _i, _f, _vp, _i, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp],
     "gldm_unet1d": [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "gldm_depth_to_objects_workspace_bytes": [_i, _i, _i, _i],   # returns long long (restype set in lib())
+    "gldm_depth_to_objects_workspace_bytes": [_i, _i, _i, _i],   # returns long long
     "gldm_depth_to_objects": [_vp, _i, _f, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _ll, _vp, _vp,
                               _vp, _vp, _vp],
-    "gldm_farthest_points_euclid_ragged_workspace_bytes": [_i, _i],   # returns long long (restype set in lib())
+    "gldm_farthest_points_euclid_ragged_workspace_bytes": [_i, _i],   # returns long long
     "gldm_farthest_points_euclid_ragged": [_vp, _vp, _vp, _i, _i, _i, _vp, _ll, _vp, _vp],
-    "gldm_plane_ransac_workspace_bytes": [_i, _i],   # returns long long (restype set in lib())
+    "gldm_plane_ransac_workspace_bytes": [_i, _i],   # returns long long
     "gldm_plane_ransac_tile_points": [],
     "gldm_plane_ransac": [_vp, _i, _vp, _i, _f, _f, _vp, _ll, _vp, _vp, _vp],
-    "gldm_plane_moments_workspace_bytes": [_i],   # returns long long (restype set in lib())
+    "gldm_plane_moments_workspace_bytes": [_i],   # returns long long
     "gldm_plane_moments": [_vp, _i, _vp, _f, _vp, _ll, _vp, _vp],
-    "gldm_segment_tabletop_workspace_bytes": [_i, _i],   # returns long long (restype set in lib())
+    "gldm_segment_tabletop_workspace_bytes": [_i, _i],   # returns long long
     "gldm_segment_tile_shape": [ctypes.POINTER(_i), ctypes.POINTER(_i)],
     "gldm_segment_tabletop": [_vp, _i, _f, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _i, _vp,
                               _ll, _vp, _vp, _vp, _vp, _vp],
@@ -153,22 +153,13 @@ def lib():
     for name, argtypes in _SIGNATURES.items():
         fn = getattr(h, name)
         fn.argtypes = argtypes
-        fn.restype = _i
+        fn.restype = _ll if name.endswith("_workspace_bytes") else _i
     h.gldm_r1d_workspace_bytes.argtypes = [_vp, _i]
     h.gldm_r1d_workspace_bytes.restype = ctypes.c_longlong
     h.gldm_r1d_tile_columns.argtypes = [_vp]
     h.gldm_r1d_tile_columns.restype = _i
     h.gldm_conv3d_partial_floats.argtypes = [_i, _i, _i]
     h.gldm_conv3d_partial_floats.restype = ctypes.c_longlong
-    h.gldm_point_attention_workspace_bytes.restype = ctypes.c_longlong
-    h.gldm_cls_head_workspace_bytes.restype = ctypes.c_longlong
-    h.gldm_farthest_points_euclid_large_workspace_bytes.restype = ctypes.c_longlong
-    h.gldm_depth_to_cloud_workspace_bytes.restype = ctypes.c_longlong
-    h.gldm_depth_to_objects_workspace_bytes.restype = ctypes.c_longlong
-    h.gldm_farthest_points_euclid_ragged_workspace_bytes.restype = ctypes.c_longlong
-    h.gldm_plane_ransac_workspace_bytes.restype = ctypes.c_longlong
-    h.gldm_plane_moments_workspace_bytes.restype = ctypes.c_longlong
-    h.gldm_segment_tabletop_workspace_bytes.restype = ctypes.c_longlong
     h.gldm_squeeze_parts.argtypes = []
     h.gldm_squeeze_parts.restype = _i
     _lib = h
@@ -185,6 +176,21 @@ def call(name, *args):
 def ptr(t):
     """Device pointer of a tensor (None -> NULL)."""
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def workspace(name, sizes, dtype, device, envelope):
+    """The workspace of entry `name` for the shape `sizes` (the arguments of `name`_workspace_bytes): (an uninitialised
+    tensor of `dtype` covering the bytes, the bytes); (None, 0) where the entry needs none.  A shape outside the entry's
+    envelope raises GldmError with the status string and `envelope`, the caller's words for shape and limits."""
+    import torch
+    h = lib()
+    nbytes = getattr(h, name + "_workspace_bytes")(*sizes)
+    if nbytes < 0:
+        raise GldmError(f"{name}: {h.gldm_status_string(int(nbytes)).decode()} ({envelope})")
+    if nbytes == 0:
+        return None, 0
+    item = torch.empty((), dtype=dtype).element_size()
+    return torch.empty((nbytes + item - 1) // item, dtype=dtype, device=device), nbytes
 
 
 def current_stream(device=None):

@@ -7,9 +7,7 @@
 //  * ball query is a wave-per-centre ordered compaction: 64 candidates per
 //    step, __ballot + prefix popcount keep the reference's "first U in index
 //    order" semantics exactly;
-//  * FPS keeps coordinates and running distances in registers/LDS for all M
-//    rounds, one barrier per round, 64-bit (distance, tie-key) wave arg-max;
-//    clouds beyond 8192 points: one launch per round over slices of the cloud;
+//  * farthest-point sampling has a source of its own, fps.hip;
 //  * the voxel scatter-mean is deterministic: points are bitonic-sorted by
 //    (voxel, index) in LDS and each voxel is summed in ascending point index;
 //  * distance / interpolation arithmetic is compiled with -ffp-contract=off so
@@ -133,371 +131,6 @@ __global__ __launch_bounds__(256) void gather_kernel(const float *__restrict__ f
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= m) return;
   out[((size_t)b * c + l) * m + j] = feat[((size_t)b * c + l) * n + idx[(size_t)b * m + j]];
-}
-
-// ------------------------------------------------------------------- FPS --
-// One workgroup per cloud.  Thread t owns points t, t+T, t+2T, ... (kept in
-// registers together with their running min-distance).  Round winner = arg-max
-// of a 64-bit key: high word = distance bits (distances are >= +0 so the bit
-// pattern is monotone), low word = ~((k mod 512) << 22 | k), which reproduces
-// the reference's tie resolution (strict '>' inside a 512-stride scan, strict
-// '<' in the shared-memory tree -> lowest slot, then lowest k).
-constexpr int kFpsMaxPerThread = 8;
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const unsigned long long o = __shfl_xor(v, off, kWave);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
-// kRule 0: the reference's CUDA kernel (sampling.cu:86-167): coords [3][n], squared distances, start 1e38.
-// kRule 1: the reference's host-side greedy sampler PointCloudHelpers.farthest_points
-//          (grasp_ldm/utils/pointcloud_helpers.py:160-217, used by regularize_pc_point_count :124-158):
-//          points [n][3], EUCLIDEAN distance sqrt((dx^2 + dy^2) + dz^2) in f32 (numpy's summation order),
-//          start 1e7, np.argmax tie rule = lowest index.
-template <int kThreads, int kPerThread, int kRule>
-__global__ __launch_bounds__(kThreads) void fps_kernel(const float *__restrict__ coords, int n, int m,
-                                                       int32_t *__restrict__ out) {
-  extern __shared__ float s_xyz[];  // [3][n]
-  __shared__ unsigned long long s_part[2][kThreads / kWave];
-  const int b = blockIdx.x;
-  coords += (size_t)b * 3 * n;
-  out += (size_t)b * m;
-  const int tid = threadIdx.x;
-  if (kRule == 0) {
-    for (int i = tid; i < 3 * n; i += kThreads) s_xyz[i] = coords[i];
-  } else {
-    for (int i = tid; i < 3 * n; i += kThreads) s_xyz[(i % 3) * n + i / 3] = coords[i];
-  }
-  float x[kPerThread], y[kPerThread], z[kPerThread], dist[kPerThread];
-#pragma unroll
-  for (int q = 0; q < kPerThread; ++q) {
-    const int k = tid + q * kThreads;
-    const bool ok = k < n;
-    x[q] = ok ? coords[kRule == 0 ? k : 3 * k] : 0.f;
-    y[q] = ok ? coords[kRule == 0 ? k + n : 3 * k + 1] : 0.f;
-    z[q] = ok ? coords[kRule == 0 ? k + 2 * n : 3 * k + 2] : 0.f;
-    dist[q] = kRule == 0 ? 1e38f : 1e7f;
-  }
-  if (tid == 0) out[0] = 0;
-  __syncthreads();
-  int old = 0;
-  const int wave = tid >> 6, lane = tid & 63;
-  constexpr int kWaves = kThreads / kWave;
-  for (int j = 1; j < m; ++j) {
-    const float x1 = s_xyz[old], y1 = s_xyz[old + n], z1 = s_xyz[old + 2 * n];
-    unsigned long long best = 0ull;  // below every real key (low word of a real key is never 0)
-#pragma unroll
-    for (int q = 0; q < kPerThread; ++q) {
-      const int k = tid + q * kThreads;
-      if (k < n) {
-        float d = (x[q] - x1) * (x[q] - x1) + (y[q] - y1) * (y[q] - y1) + (z[q] - z1) * (z[q] - z1);
-        if (kRule == 1) d = __fsqrt_rn(d);
-        const float d2 = d < dist[q] ? d : dist[q];
-        dist[q] = d2;
-        const unsigned int tie = kRule == 0 ? ~(((unsigned int)(k & 511) << 22) | (unsigned int)k) : ~(unsigned int)k;
-        const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | tie;
-        best = key > best ? key : best;
-      }
-    }
-    best = wave_max_u64(best);
-    if (kWaves > 1) {
-      if (lane == 0) s_part[j & 1][wave] = best;
-      __syncthreads();
-      unsigned long long v = lane < kWaves ? s_part[j & 1][lane] : 0ull;
-#pragma unroll
-      for (int off = kWaves / 2; off >= 1; off >>= 1) {
-        const unsigned long long o = __shfl_xor(v, off, kWave);
-        v = o > v ? o : v;
-      }
-      best = __shfl(v, 0, kWave);
-    }
-    old = (int)((~(unsigned int)best) & 0x3FFFFFu);
-    if (tid == 0) out[j] = old;
-  }
-}
-
-// One WAVE per cloud (n <= 1024): lane l owns points l, l + 64, ... (kPer of them, in registers with their running
-// min-distances), so a round is 10 VALU instructions per point, an in-lane arg-max and ONE wave reduction -- no LDS
-// exchange, no barrier (the 16-wave form above spends most of a round's 1.2 us in its two reductions and the barrier
-// between them: 0.62 ms per 1024 -> 512 sampling whatever the batch).  The reduction runs on the two 32-bit halves of the
-// key one after the other (distance bits, then the tie word among the lanes that hold the maximal distance): four DPP row
-// steps + four v_readlane each.  The previous winner's coordinates come from LDS (a broadcast read).  Same keys, same
-// arithmetic (-ffp-contract=off) as fps_kernel: bit-identical picks.
-template <int CTRL>
-__device__ __forceinline__ unsigned dpp_shr_u32(unsigned v) {   // lanes without a source read 0 (the identity of max)
-  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
-}
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
-  v = max(v, dpp_shr_u32<0x111>(v));   // row_shr:1
-  v = max(v, dpp_shr_u32<0x112>(v));   // row_shr:2
-  v = max(v, dpp_shr_u32<0x114>(v));   // row_shr:4
-  v = max(v, dpp_shr_u32<0x118>(v));   // row_shr:8: lane 15 of every row holds the row's maximum
-  const unsigned a = __builtin_amdgcn_readlane(v, 15), b = __builtin_amdgcn_readlane(v, 31);
-  const unsigned c = __builtin_amdgcn_readlane(v, 47), d = __builtin_amdgcn_readlane(v, 63);
-  return max(max(a, b), max(c, d));
-}
-template <int kPer, int kRule>
-__global__ __launch_bounds__(64) void fps_wave_kernel(const float *__restrict__ coords, int n, int m,
-                                                      int32_t *__restrict__ out) {
-  extern __shared__ float s_xyz[];  // [3][n]
-  const int b = blockIdx.x, lane = threadIdx.x;
-  coords += (size_t)b * 3 * n;
-  out += (size_t)b * m;
-  // Slots beyond n: distance 0 for ever (min(d, 0) = 0) and tie word 0, i.e. key 0, below every real key (whose low word
-  // is never 0): the round needs no per-point test (16 exec-masked branches per round otherwise).
-  float x[kPer], y[kPer], z[kPer], dist[kPer];
-  unsigned tiew[kPer];
-#pragma unroll
-  for (int q = 0; q < kPer; ++q) {
-    const int k = lane + 64 * q;
-    const bool ok = k < n;
-    x[q] = ok ? coords[kRule == 0 ? k : 3 * k] : 0.f;
-    y[q] = ok ? coords[kRule == 0 ? k + n : 3 * k + 1] : 0.f;
-    z[q] = ok ? coords[kRule == 0 ? k + 2 * n : 3 * k + 2] : 0.f;
-    dist[q] = ok ? (kRule == 0 ? 1e38f : 1e7f) : 0.f;
-    const unsigned int tie = kRule == 0 ? ~(((unsigned int)(k & 511) << 22) | (unsigned int)k) : ~(unsigned int)k;
-    tiew[q] = ok ? tie : 0u;
-    if (ok) {
-      s_xyz[k] = x[q];
-      s_xyz[k + n] = y[q];
-      s_xyz[k + 2 * n] = z[q];
-    }
-  }
-  if (lane == 0) out[0] = 0;
-  __syncthreads();
-  int old = 0;
-  for (int j = 1; j < m; ++j) {
-    const float x1 = s_xyz[old], y1 = s_xyz[old + n], z1 = s_xyz[old + 2 * n];
-    unsigned long long best = 0ull;
-#pragma unroll
-    for (int q = 0; q < kPer; ++q) {
-      float d = (x[q] - x1) * (x[q] - x1) + (y[q] - y1) * (y[q] - y1) + (z[q] - z1) * (z[q] - z1);
-      if (kRule == 1) d = __fsqrt_rn(d);
-      const float d2 = d < dist[q] ? d : dist[q];
-      dist[q] = d2;
-      const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | tiew[q];
-      best = key > best ? key : best;
-    }
-    const unsigned hi = (unsigned)(best >> 32), lo = (unsigned)best;
-    const unsigned hmax = wave_max_u32(hi);
-    const unsigned lmax = wave_max_u32(hi == hmax ? lo : 0u);
-    old = (int)((~lmax) & 0x3FFFFFu);
-    if (lane == 0) out[j] = old;
-  }
-}
-
-// Rule-1 selection on clouds beyond one workgroup's registers (8192 < n <= 2^22): a cloud is cut into `slices` runs of
-// `slice` consecutive points, one workgroup each, and a round is ONE LAUNCH over (slices, b) -- the grid-wide decision of a
-// round happens at the launch boundary, no workgroup ever waits for another.  Launch r:
-//   1. every workgroup reduces the partial keys that launch r-1 left (one per slice, at most kFpsLargeMaxSlices; exact:
-//      the same 64-bit key as above, max distance bits then lowest index) to pick r (r = 0: index 0) -- redundantly, which
-//      costs a few hundred L2 reads and saves a launch; slice 0 writes out[r];
-//   2. unless r is the last round, it updates its slice's running minima (global workspace, start 1e7 taken as a constant in
-//      launch 0, so the workspace needs no initialisation) with the distance to pick r and leaves its own partial key in the
-//      other half of the double-buffered partials.
-// Slice i is workgroup i in every round, so a slice's points and minima are re-read by the same XCD's L2 each round.
-// `counts` (optional): the live rows of each cloud (row stride n); rows past it are never read; a cloud with
-// counts[b] <= m gets 0 .. counts[b]-1 then -1 (the reference's nclusters >= N -> arange case).
-constexpr int kFpsLargeBlock = 256;
-constexpr int kFpsLargeMinSlice = 1024;
-constexpr int kFpsLargeMaxSlices = 512;
-constexpr int kFpsLargeMaxN = 1 << 22;   // the index field of the key
-constexpr int kFpsLargeMaxM = 8192;
-
-__global__ __launch_bounds__(kFpsLargeBlock) void fps_large_round_kernel(const float *__restrict__ points, int n, int m,
-                                                                         int slice, const int32_t *__restrict__ counts,
-                                                                         float *__restrict__ mind,
-                                                                         unsigned long long *__restrict__ partials, int r,
-                                                                         int32_t *__restrict__ out) {
-  __shared__ unsigned long long s_part[kFpsLargeBlock / kWave];
-  const int s = blockIdx.x, slices = gridDim.x, b = blockIdx.y, tid = threadIdx.x;
-  int cnt = counts ? counts[b] : n;
-  cnt = cnt < 0 ? 0 : (cnt > n ? n : cnt);
-  out += (size_t)b * m;
-  if (cnt <= m) {
-    if (s == 0 && tid == 0) out[r] = r < cnt ? r : -1;
-    return;
-  }
-  points += (size_t)b * 3 * n;
-  mind += (size_t)b * n;
-  const unsigned long long *prev = partials + ((size_t)((r + 1) & 1) * gridDim.y + b) * slices;
-  unsigned long long *mine = partials + ((size_t)(r & 1) * gridDim.y + b) * slices;
-  int pick = 0;
-  if (r > 0) {
-    unsigned long long v = 0ull;
-    for (int i = tid; i < slices; i += kFpsLargeBlock) {
-      const unsigned long long o = prev[i];
-      v = o > v ? o : v;
-    }
-    v = wave_max_u64(v);
-    if ((tid & 63) == 0) s_part[tid >> 6] = v;
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < kFpsLargeBlock / kWave; ++w) v = s_part[w] > v ? s_part[w] : v;
-    pick = (int)((~(unsigned int)v) & 0x3FFFFFu);   // < cnt: only live rows ever left a non-zero key
-    __syncthreads();
-  }
-  if (s == 0 && tid == 0) out[r] = pick;
-  if (r == m - 1) return;
-  const float x1 = points[3 * (size_t)pick], y1 = points[3 * (size_t)pick + 1], z1 = points[3 * (size_t)pick + 2];
-  const int k0 = s * slice;
-  const int k1 = (k0 + slice < cnt) ? k0 + slice : cnt;   // k0 >= cnt: an empty slice, key 0 (below every real key)
-  unsigned long long best = 0ull;
-  for (int k = k0 + tid; k < k1; k += kFpsLargeBlock) {
-    const float x = points[3 * (size_t)k], y = points[3 * (size_t)k + 1], z = points[3 * (size_t)k + 2];
-    const float d = __fsqrt_rn((x - x1) * (x - x1) + (y - y1) * (y - y1) + (z - z1) * (z - z1));
-    const float old = r == 0 ? 1e7f : mind[k];
-    const float d2 = d < old ? d : old;
-    mind[k] = d2;
-    const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | ~(unsigned int)k;
-    best = key > best ? key : best;
-  }
-  best = wave_max_u64(best);
-  if ((tid & 63) == 0) s_part[tid >> 6] = best;
-  __syncthreads();
-  if (tid == 0) {
-#pragma unroll
-    for (int w = 1; w < kFpsLargeBlock / kWave; ++w) best = s_part[w] > best ? s_part[w] : best;
-    mine[s] = best;
-  }
-}
-
-// Rule-1 selection over clouds of DIFFERENT sizes packed in one [rows, 3] array (gldm_farthest_points_euclid_ragged): cloud b
-// is rows start[b] .. start[b] + min(count[b], n_max).  Two forms, the keys and the arithmetic of the kernels above, so
-// every cloud gets the picks it would get alone:
-//   fps_ragged_block_kernel  one workgroup per cloud for counts <= 8192 (fps_kernel<1024, 8, 1> with the live row count read
-//                            per cloud, LDS sized for min(n_max, 8192) rows); also writes the 0 .. count-1, -1 rows of the
-//                            clouds with count <= m.  Workgroups of larger clouds leave at once.
-//   fps_ragged_round_kernel  fps_large_round_kernel over (slices(n_max), b) for counts > 8192 (> m, always), rows read at
-//                            start[b]; minima [b, n_max]; workgroups of smaller clouds and of slices past the count leave
-//                            at once, and the partials of those slices are never read.
-constexpr int kFpsRaggedThreads = 1024;
-constexpr int kFpsBlockMaxN = kFpsRaggedThreads * kFpsMaxPerThread;   // 8192
-
-__device__ __forceinline__ int ragged_count(const int32_t *__restrict__ count, int b, int n_max) {
-  const int c = count[b];
-  return c < 0 ? 0 : (c > n_max ? n_max : c);
-}
-
-__global__ __launch_bounds__(kFpsRaggedThreads) void fps_ragged_block_kernel(const float *__restrict__ points,
-                                                                             const int32_t *__restrict__ start,
-                                                                             const int32_t *__restrict__ count, int n_max,
-                                                                             int m, int32_t *__restrict__ out) {
-  extern __shared__ float s_xyz[];  // [3][n], n <= min(n_max, 8192)
-  constexpr int kThreads = kFpsRaggedThreads, kPerThread = kFpsMaxPerThread, kWaves = kThreads / kWave;
-  __shared__ unsigned long long s_part[2][kWaves];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int n = ragged_count(count, b, n_max);
-  if (n > kFpsBlockMaxN) return;   // the round launches serve it
-  out += (size_t)b * m;
-  if (n <= m) {
-    for (int j = tid; j < m; j += kThreads) out[j] = j < n ? j : -1;
-    return;
-  }
-  const float *coords = points + 3 * (size_t)start[b];
-  for (int i = tid; i < 3 * n; i += kThreads) s_xyz[(i % 3) * n + i / 3] = coords[i];
-  float x[kPerThread], y[kPerThread], z[kPerThread], dist[kPerThread];
-#pragma unroll
-  for (int q = 0; q < kPerThread; ++q) {
-    const int k = tid + q * kThreads;
-    const bool ok = k < n;
-    x[q] = ok ? coords[3 * k] : 0.f;
-    y[q] = ok ? coords[3 * k + 1] : 0.f;
-    z[q] = ok ? coords[3 * k + 2] : 0.f;
-    dist[q] = 1e7f;
-  }
-  if (tid == 0) out[0] = 0;
-  __syncthreads();
-  int old = 0;
-  const int wave = tid >> 6, lane = tid & 63;
-  for (int j = 1; j < m; ++j) {
-    const float x1 = s_xyz[old], y1 = s_xyz[old + n], z1 = s_xyz[old + 2 * n];
-    unsigned long long best = 0ull;  // below every real key (low word of a real key is never 0)
-#pragma unroll
-    for (int q = 0; q < kPerThread; ++q) {
-      const int k = tid + q * kThreads;
-      if (k < n) {
-        const float d = __fsqrt_rn((x[q] - x1) * (x[q] - x1) + (y[q] - y1) * (y[q] - y1) + (z[q] - z1) * (z[q] - z1));
-        const float d2 = d < dist[q] ? d : dist[q];
-        dist[q] = d2;
-        const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | ~(unsigned int)k;
-        best = key > best ? key : best;
-      }
-    }
-    best = wave_max_u64(best);
-    if (lane == 0) s_part[j & 1][wave] = best;
-    __syncthreads();
-    unsigned long long v = lane < kWaves ? s_part[j & 1][lane] : 0ull;
-#pragma unroll
-    for (int off = kWaves / 2; off >= 1; off >>= 1) {
-      const unsigned long long o = __shfl_xor(v, off, kWave);
-      v = o > v ? o : v;
-    }
-    best = __shfl(v, 0, kWave);
-    old = (int)((~(unsigned int)best) & 0x3FFFFFu);
-    if (tid == 0) out[j] = old;
-  }
-}
-
-__global__ __launch_bounds__(kFpsLargeBlock) void fps_ragged_round_kernel(const float *__restrict__ points,
-                                                                          const int32_t *__restrict__ start,
-                                                                          const int32_t *__restrict__ count, int n_max, int m,
-                                                                          int slice, float *__restrict__ mind,
-                                                                          unsigned long long *__restrict__ partials, int r,
-                                                                          int32_t *__restrict__ out) {
-  __shared__ unsigned long long s_part[kFpsLargeBlock / kWave];
-  const int s = blockIdx.x, slices = gridDim.x, b = blockIdx.y, tid = threadIdx.x;
-  const int cnt = ragged_count(count, b, n_max);
-  if (cnt <= kFpsBlockMaxN) return;   // the one-workgroup form served it
-  const int live = (cnt + slice - 1) / slice;   // slices that hold rows
-  if (s >= live) return;
-  out += (size_t)b * m;
-  points += 3 * (size_t)start[b];
-  mind += (size_t)b * n_max;
-  const unsigned long long *prev = partials + ((size_t)((r + 1) & 1) * gridDim.y + b) * slices;
-  unsigned long long *mine = partials + ((size_t)(r & 1) * gridDim.y + b) * slices;
-  int pick = 0;
-  if (r > 0) {
-    unsigned long long v = 0ull;
-    for (int i = tid; i < live; i += kFpsLargeBlock) {
-      const unsigned long long o = prev[i];
-      v = o > v ? o : v;
-    }
-    v = wave_max_u64(v);
-    if ((tid & 63) == 0) s_part[tid >> 6] = v;
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < kFpsLargeBlock / kWave; ++w) v = s_part[w] > v ? s_part[w] : v;
-    pick = (int)((~(unsigned int)v) & 0x3FFFFFu);   // < cnt: every live slice left the key of a live row
-    __syncthreads();
-  }
-  if (s == 0 && tid == 0) out[r] = pick;
-  if (r == m - 1) return;
-  const float x1 = points[3 * (size_t)pick], y1 = points[3 * (size_t)pick + 1], z1 = points[3 * (size_t)pick + 2];
-  const int k0 = s * slice;   // < cnt
-  const int k1 = (k0 + slice < cnt) ? k0 + slice : cnt;
-  unsigned long long best = 0ull;
-  for (int k = k0 + tid; k < k1; k += kFpsLargeBlock) {
-    const float x = points[3 * (size_t)k], y = points[3 * (size_t)k + 1], z = points[3 * (size_t)k + 2];
-    const float d = __fsqrt_rn((x - x1) * (x - x1) + (y - y1) * (y - y1) + (z - z1) * (z - z1));
-    const float old = r == 0 ? 1e7f : mind[k];
-    const float d2 = d < old ? d : old;
-    mind[k] = d2;
-    const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | ~(unsigned int)k;
-    best = key > best ? key : best;
-  }
-  best = wave_max_u64(best);
-  if ((tid & 63) == 0) s_part[tid >> 6] = best;
-  __syncthreads();
-  if (tid == 0) {
-#pragma unroll
-    for (int w = 1; w < kFpsLargeBlock / kWave; ++w) best = s_part[w] > best ? s_part[w] : best;
-    mine[s] = best;
-  }
 }
 
 // -------------------------------------------------- 3-NN + interpolation --
@@ -1081,30 +714,6 @@ GLDM_API int gldm_gather_features_forward(const float *features, const int32_t *
 }
 
 namespace {
-template <int kThreads, int kPerThread, int kRule>
-int launch_fps(const float *coords, int b, int n, int m, int32_t *out, hipStream_t s) {
-  hipLaunchKernelGGL((fps_kernel<kThreads, kPerThread, kRule>), dim3(b), dim3(kThreads), (size_t)3 * n * sizeof(float),
-                     s, coords, n, m, out);
-  return launch_status();
-}
-template <int kPer, int kRule>
-int launch_fps_wave(const float *coords, int b, int n, int m, int32_t *out, hipStream_t s) {
-  hipLaunchKernelGGL((fps_wave_kernel<kPer, kRule>), dim3(b), dim3(64), (size_t)3 * n * sizeof(float), s, coords, n, m, out);
-  return launch_status();
-}
-template <int kRule>
-int dispatch_fps(const float *coords, int b, int n, int m, int32_t *out_idx, hipStream_t s) {
-  // up to 1024 points: one wave per cloud, no barrier in the round (fps_wave_kernel)
-  if (n <= 64) return launch_fps_wave<1, kRule>(coords, b, n, m, out_idx, s);
-  if (n <= 128) return launch_fps_wave<2, kRule>(coords, b, n, m, out_idx, s);
-  if (n <= 256) return launch_fps_wave<4, kRule>(coords, b, n, m, out_idx, s);
-  if (n <= 512) return launch_fps_wave<8, kRule>(coords, b, n, m, out_idx, s);
-  if (n <= 1024) return launch_fps_wave<16, kRule>(coords, b, n, m, out_idx, s);
-  if (n <= 2048) return launch_fps<1024, 2, kRule>(coords, b, n, m, out_idx, s);
-  if (n <= 4096) return launch_fps<1024, 4, kRule>(coords, b, n, m, out_idx, s);
-  return launch_fps<1024, 8, kRule>(coords, b, n, m, out_idx, s);
-}
-
 // Raw-cloud front end: centre + scale a sensor cloud [n][3] (tools/inference.py:570-591 normalize_input) and
 // gather rows of it by index (point-count regularisation).  The mean is accumulated in f64 in a fixed tree.
 constexpr int kNcBlock = 256;
@@ -1154,117 +763,6 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float *__restric
   out[(size_t)b * 3 * m + i] = pc[((size_t)b * n + idx[(size_t)b * m + j]) * 3 + a];
 }
 }  // namespace
-
-GLDM_API int gldm_furthest_point_sampling(const float *coords, int b, int n, int m, int32_t *out_idx,
-                                          gldm_stream_t stream) {
-  if (!coords || !out_idx || b <= 0 || n <= 0 || m < 0) return GLDM_ERR_INVALID_ARG;
-  if (m == 0) return GLDM_OK;
-  if (n > 1024 * kFpsMaxPerThread) return GLDM_ERR_UNSUPPORTED;
-  return dispatch_fps<0>(coords, b, n, m, out_idx, as_stream(stream));
-}
-
-GLDM_API int gldm_farthest_points_euclid(const float *points, int b, int n, int m, int32_t *out_idx,
-                                         gldm_stream_t stream) {
-  if (!points || !out_idx || b <= 0 || n <= 0 || m < 0 || m > n) return GLDM_ERR_INVALID_ARG;
-  if (m == 0) return GLDM_OK;
-  if (n > 1024 * kFpsMaxPerThread) return GLDM_ERR_UNSUPPORTED;
-  return dispatch_fps<1>(points, b, n, m, out_idx, as_stream(stream));
-}
-
-namespace {
-// 0, or the status of a shape outside the envelope of the large selection
-int fps_large_check(int b, int n, int m) {
-  if (b <= 0 || n <= 0 || m < 0) return GLDM_ERR_INVALID_ARG;
-  if (n <= 1024 * kFpsMaxPerThread || n > kFpsLargeMaxN || m > kFpsLargeMaxM || b > 65535) return GLDM_ERR_UNSUPPORTED;
-  return GLDM_OK;
-}
-int fps_large_slice(int n) {
-  int slice = kFpsLargeMinSlice;
-  while (ceil_div(n, slice) > kFpsLargeMaxSlices) slice *= 2;
-  return slice;
-}
-long long fps_large_minima_bytes(int b, int n) { return (((long long)b * n * 4) + 7) / 8 * 8; }
-}  // namespace
-
-GLDM_API int gldm_farthest_points_euclid_large_slice(int n) {
-  if (n <= 1024 * kFpsMaxPerThread || n > kFpsLargeMaxN) return GLDM_ERR_UNSUPPORTED;
-  return fps_large_slice(n);
-}
-
-GLDM_API long long gldm_farthest_points_euclid_large_workspace_bytes(int b, int n) {
-  const int st = fps_large_check(b, n, 1);
-  if (st != GLDM_OK) return st;
-  return fps_large_minima_bytes(b, n) + 2ll * b * ceil_div(n, fps_large_slice(n)) * (long long)sizeof(unsigned long long);
-}
-
-GLDM_API int gldm_farthest_points_euclid_large(const float *points, const int32_t *counts, int b, int n, int m,
-                                               void *workspace, long long workspace_bytes, int32_t *out_idx,
-                                               gldm_stream_t stream) {
-  const int st = fps_large_check(b, n, m);   // the envelope before any pointer
-  if (st != GLDM_OK) return st;
-  if (m > n) return GLDM_ERR_INVALID_ARG;
-  if (!points || !out_idx || !workspace || (reinterpret_cast<uintptr_t>(workspace) & 7u)) return GLDM_ERR_INVALID_ARG;
-  if (m == 0) return GLDM_OK;
-  if (workspace_bytes < gldm_farthest_points_euclid_large_workspace_bytes(b, n)) return GLDM_ERR_WORKSPACE;
-  const int slice = fps_large_slice(n), slices = ceil_div(n, slice);
-  float *mind = static_cast<float *>(workspace);
-  unsigned long long *partials =
-      reinterpret_cast<unsigned long long *>(static_cast<char *>(workspace) + fps_large_minima_bytes(b, n));
-  hipStream_t s = as_stream(stream);
-  for (int r = 0; r < m; ++r) {   // one launch per round, enqueued back to back; no synchronisation here
-    hipLaunchKernelGGL(fps_large_round_kernel, dim3(slices, b), dim3(kFpsLargeBlock), 0, s, points, n, m, slice, counts,
-                       mind, partials, r, out_idx);
-    const int ls = launch_status();
-    if (ls != GLDM_OK) return ls;
-  }
-  return GLDM_OK;
-}
-
-namespace {
-// 0, or the status of a shape outside the envelope of the ragged selection
-int fps_ragged_check(int b, int n_max, int m) {
-  if (b <= 0 || n_max <= 0 || m < 0) return GLDM_ERR_INVALID_ARG;
-  if (n_max > kFpsLargeMaxN || m > kFpsLargeMaxM || b > 65535) return GLDM_ERR_UNSUPPORTED;
-  return GLDM_OK;
-}
-}  // namespace
-
-GLDM_API long long gldm_farthest_points_euclid_ragged_workspace_bytes(int b, int n_max) {
-  const int st = fps_ragged_check(b, n_max, 1);
-  if (st != GLDM_OK) return st;
-  if (n_max <= kFpsBlockMaxN) return 0;
-  return fps_large_minima_bytes(b, n_max) +
-         2ll * b * ceil_div(n_max, fps_large_slice(n_max)) * (long long)sizeof(unsigned long long);
-}
-
-GLDM_API int gldm_farthest_points_euclid_ragged(const float *points, const int32_t *start, const int32_t *count, int b,
-                                                int n_max, int m, void *workspace, long long workspace_bytes,
-                                                int32_t *out_idx, gldm_stream_t stream) {
-  const int st = fps_ragged_check(b, n_max, m);   // the envelope before any pointer
-  if (st != GLDM_OK) return st;
-  const bool large = n_max > kFpsBlockMaxN;
-  if (!points || !start || !count || !out_idx) return GLDM_ERR_INVALID_ARG;
-  if (large && (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 7u))) return GLDM_ERR_INVALID_ARG;
-  if (m == 0) return GLDM_OK;
-  if (large && workspace_bytes < gldm_farthest_points_euclid_ragged_workspace_bytes(b, n_max)) return GLDM_ERR_WORKSPACE;
-  hipStream_t s = as_stream(stream);
-  const int lds_rows = large ? kFpsBlockMaxN : n_max;
-  hipLaunchKernelGGL(fps_ragged_block_kernel, dim3(b), dim3(kFpsRaggedThreads), (size_t)3 * lds_rows * sizeof(float), s,
-                     points, start, count, n_max, m, out_idx);
-  int ls = launch_status();
-  if (ls != GLDM_OK || !large) return ls;
-  const int slice = fps_large_slice(n_max), slices = ceil_div(n_max, slice);
-  float *mind = static_cast<float *>(workspace);
-  unsigned long long *partials =
-      reinterpret_cast<unsigned long long *>(static_cast<char *>(workspace) + fps_large_minima_bytes(b, n_max));
-  for (int r = 0; r < m; ++r) {   // one launch per round, enqueued back to back; no synchronisation here
-    hipLaunchKernelGGL(fps_ragged_round_kernel, dim3(slices, b), dim3(kFpsLargeBlock), 0, s, points, start, count, n_max, m,
-                       slice, mind, partials, r, out_idx);
-    ls = launch_status();
-    if (ls != GLDM_OK) return ls;
-  }
-  return GLDM_OK;
-}
 
 GLDM_API int gldm_normalize_cloud(const float *pc, int b, int n, float shift_x, float shift_y, float shift_z,
                                   float scale_x, float scale_y, float scale_z, float *pc_out, float *mean_out,

@@ -18,6 +18,7 @@ table (gldm_plane_ransac, gldm_plane_moments) and `segment_tabletop` labels the 
 (gldm_segment_tabletop).
 """
 import ctypes
+import typing
 
 import numpy as np
 import torch
@@ -52,6 +53,9 @@ def gather_points(pc, idx):
     return out
 
 
+FPS_SMALL_MAX = 8192   # gldm_farthest_points_euclid's ceiling; larger clouds take gldm_farthest_points_euclid_large
+
+
 def farthest_point_indices(pc, nclusters):
     """Centre indices of PointCloudHelpers.farthest_points(pc, nclusters, distance_by_translation_point,
     return_center_indexes=True) (pointcloud_helpers.py:160-223) for every cloud of pc [B,N,3] / [N,3]:
@@ -68,9 +72,6 @@ def farthest_point_indices(pc, nclusters):
     return idx
 
 
-FPS_SMALL_MAX = 8192   # gldm_farthest_points_euclid's ceiling; larger clouds take gldm_farthest_points_euclid_large
-
-
 def farthest_point_indices_large(pc, nclusters, counts=None, out=None):
     """gldm_farthest_points_euclid_large on pc [B,N,3] with 8192 < N <= 2^22: the same indices as
     farthest_point_indices, one launch per round over many workgroups.  counts (int32 [B] on the device, optional): the
@@ -79,20 +80,33 @@ def farthest_point_indices_large(pc, nclusters, counts=None, out=None):
     pcb = _as_batch(pc)
     b, n, _ = pcb.shape
     m = int(nclusters)
-    h = L.lib()
-    nbytes = h.gldm_farthest_points_euclid_large_workspace_bytes(b, n)
-    if nbytes < 0:
-        raise L.GldmError(f"gldm_farthest_points_euclid_large: {h.gldm_status_string(int(nbytes)).decode()} "
-                          f"(b = {b}, n = {n}; 8192 < n <= 2^22)")
+    ws, nbytes = L.workspace("gldm_farthest_points_euclid_large", (b, n), torch.int64, pcb.device,
+                             f"b = {b}, n = {n}; 8192 < n <= 2^22")
     if counts is not None:
         _need_cuda(counts, "counts")
         counts = counts.to(device=pcb.device, dtype=torch.int32).reshape(b).contiguous()
     idx = torch.empty((b, m), dtype=torch.int32, device=pcb.device) if out is None else out
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=pcb.device)
     with torch.cuda.device(pcb.device):
         L.call("gldm_farthest_points_euclid_large", L.ptr(pcb), L.ptr(counts), b, n, m, L.ptr(ws), nbytes, L.ptr(idx),
                L.current_stream(pcb.device))
     return idx
+
+
+def _drawn_rows(n, num_points, use_farthest_point, rng):
+    """The rows (int64 [num_points]) that bring one cloud of n rows to num_points, drawn on the host with the generator
+    calls of pointcloud_helpers.py:124-158 (`rng`: a np.random.RandomState / Generator-like object with `.choice`; None =
+    the global np.random the reference draws from): n > num_points: num_points of them without replacement; n <
+    num_points: all of them, then num_points - n drawn with replacement.  None where n > num_points and
+    use_farthest_point: take the farthest-point selection (no draw)."""
+    rng = np.random if rng is None else rng
+    if n > num_points:
+        if use_farthest_point:
+            return None
+        return torch.from_numpy(np.asarray(rng.choice(range(n), size=num_points, replace=False))).long()
+    if n < num_points:
+        extra = torch.from_numpy(np.asarray(rng.choice(range(n), size=num_points - n)))
+        return torch.cat([torch.arange(n), extra.long()])
+    return torch.arange(n)
 
 
 class PointCloudHelpers:
@@ -113,20 +127,11 @@ class PointCloudHelpers:
         Generator-like object with `.choice`; default = the global np.random the reference draws from."""
         _need_cuda(pc)
         assert pc.ndim == 2
-        rng = np.random if rng is None else rng
-        n = pc.shape[0]
-        if n > npoints:
-            if use_farthest_point:
-                idx = farthest_point_indices(pc, npoints)
-            else:
-                idx = torch.from_numpy(np.asarray(rng.choice(range(n), size=npoints, replace=False))).unsqueeze(0)
-            return gather_points(pc, idx)[0]
-        required = npoints - n
-        if required > 0:
-            extra = torch.from_numpy(np.asarray(rng.choice(range(n), size=required))).unsqueeze(0)
-            idx = torch.cat([torch.arange(n).unsqueeze(0), extra.long()], dim=1)
-            return gather_points(pc, idx)[0]
-        return pc.contiguous().float()
+        if pc.shape[0] == npoints:
+            return pc.contiguous().float()
+        idx = _drawn_rows(pc.shape[0], npoints, use_farthest_point, rng)
+        idx = farthest_point_indices(pc, npoints) if idx is None else idx.unsqueeze(0)
+        return gather_points(pc, idx)[0]
 
     @staticmethod
     def regularize_pointcloud(pc, num_points):
@@ -213,31 +218,15 @@ def depth_to_cloud(depth, camera, mask=None, z_range=None, depth_scale=None, cam
     Kept pixels come in ascending pixel index v * W + u (the order of torch.where(depth > 0)).
     -> [n, 3] for an [H, W] input, a list of F clouds [n_f, 3] for [F, H, W] (views of one buffer, cut after ONE
     read-back of the counts); with return_pixels also the int32 source pixel indices in the same form."""
-    _need_cuda(depth, "depth")
-    if depth.ndim not in (2, 3):
-        raise ValueError(f"depth must be [H, W] or [F, H, W], not {tuple(depth.shape)}")
-    single = depth.ndim == 2
-    d = (depth.unsqueeze(0) if single else depth).contiguous()
-    f, h, w = d.shape
-    if (h, w) != (camera.height, camera.width):
-        raise ValueError(f"depth frames are {h} x {w}, the camera model is {camera.height} x {camera.width}")
-    is_u16, m8, z_min, z_max, xf, lo, hi = _depth_options(d, depth, mask, z_range, depth_scale, cam_to_world, crop_box)
-    dev = d.device
-    fx, fy, cx, cy = camera.intrinsics
-    lib = L.lib()
-    nbytes = lib.gldm_depth_to_cloud_workspace_bytes(f, h, w)
-    if nbytes < 0:
-        raise L.GldmError(f"gldm_depth_to_cloud: {lib.gldm_status_string(int(nbytes)).decode()} (frames {f}, {h} x {w}; "
-                          "1 <= H*W <= 2^24)")
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+    fr = _depth_frames(depth, camera, mask, z_range, depth_scale, cam_to_world, crop_box)
+    f, h, w, dev, single = fr.f, fr.h, fr.w, fr.device, fr.single
+    ws, nbytes = L.workspace("gldm_depth_to_cloud", (f, h, w), torch.int32, dev, f"frames {f}, {h} x {w}; 1 <= H*W <= 2^24")
     points = torch.empty((f, h * w, 3), dtype=torch.float32, device=dev)
     count = torch.empty(f, dtype=torch.int32, device=dev)
     pixel = torch.empty((f, h * w), dtype=torch.int32, device=dev) if return_pixels else None
-    hp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
     with torch.cuda.device(dev):
-        L.call("gldm_depth_to_cloud", L.ptr(d), int(is_u16), float(depth_scale or 1.0), L.ptr(m8), f, h, w, fx, fy, cx, cy,
-               z_min, z_max, hp(xf), hp(lo), hp(hi), L.ptr(ws), nbytes, L.ptr(points), L.ptr(count), L.ptr(pixel),
-               L.current_stream(dev))
+        L.call("gldm_depth_to_cloud", *fr.source, f, h, w, *fr.optics, L.ptr(ws), nbytes, L.ptr(points), L.ptr(count),
+               L.ptr(pixel), L.current_stream(dev))
     counts = count.tolist()   # the one read-back
     clouds = [points[i, :c] for i, c in enumerate(counts)]
     if not return_pixels:
@@ -276,42 +265,63 @@ def _depth_to_objects_packed(depth, camera, labels, num_labels=None, mask=None, 
     lists [F][K] from the one read-back, start relative to the frame's row 0."""
     _need_cuda(depth, "depth")
     _need_cuda(labels, "labels")
-    if depth.ndim not in (2, 3):
-        raise ValueError(f"depth must be [H, W] or [F, H, W], not {tuple(depth.shape)}")
     if tuple(labels.shape) != tuple(depth.shape):
         raise ValueError(f"labels {tuple(labels.shape)} do not match depth {tuple(depth.shape)}")
     if labels.dtype.is_floating_point or labels.dtype == torch.bool:
         raise ValueError(f"labels must be an integer tensor, not {labels.dtype}")
-    single = depth.ndim == 2
-    d = (depth.unsqueeze(0) if single else depth).contiguous()
-    f, h, w = d.shape
-    if (h, w) != (camera.height, camera.width):
-        raise ValueError(f"depth frames are {h} x {w}, the camera model is {camera.height} x {camera.width}")
-    is_u16, m8, z_min, z_max, xf, lo, hi = _depth_options(d, depth, mask, z_range, depth_scale, cam_to_world, crop_box)
-    dev = d.device
+    fr = _depth_frames(depth, camera, mask, z_range, depth_scale, cam_to_world, crop_box)
+    f, h, w, dev = fr.f, fr.h, fr.w, fr.device
     lab = labels.reshape(f, h, w).to(device=dev, dtype=torch.int32).contiguous()
     k = max(int(lab.max()), 1) if num_labels is None else int(num_labels)
     if k > MAX_LABELS:
         raise NotImplementedError(f"num_labels = {k}: gldm_depth_to_objects takes at most {MAX_LABELS} labels per call")
     if k < 1:
         raise ValueError(f"num_labels must be at least 1, not {k}")
-    fx, fy, cx, cy = camera.intrinsics
-    lib = L.lib()
-    nbytes = lib.gldm_depth_to_objects_workspace_bytes(f, h, w, k)
-    if nbytes < 0:
-        raise L.GldmError(f"gldm_depth_to_objects: {lib.gldm_status_string(int(nbytes)).decode()} (frames {f}, {h} x {w}, "
-                          f"{k} labels; 1 <= H*W <= 2^24)")
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+    ws, nbytes = L.workspace("gldm_depth_to_objects", (f, h, w, k), torch.int32, dev,
+                             f"frames {f}, {h} x {w}, {k} labels; 1 <= H*W <= 2^24")
     points = torch.empty((f, h * w, 3), dtype=torch.float32, device=dev)
     sc = torch.empty((2, f, k), dtype=torch.int32, device=dev)   # start, count: one buffer, one read-back
     pixel = torch.empty((f, h * w), dtype=torch.int32, device=dev) if return_pixels else None
-    hp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
     with torch.cuda.device(dev):
-        L.call("gldm_depth_to_objects", L.ptr(d), int(is_u16), float(depth_scale or 1.0), L.ptr(m8), L.ptr(lab), k, f, h, w,
-               fx, fy, cx, cy, z_min, z_max, hp(xf), hp(lo), hp(hi), L.ptr(ws), nbytes, L.ptr(points), L.ptr(sc[0]),
-               L.ptr(sc[1]), L.ptr(pixel), L.current_stream(dev))
+        L.call("gldm_depth_to_objects", *fr.source, L.ptr(lab), k, f, h, w, *fr.optics, L.ptr(ws), nbytes, L.ptr(points),
+               L.ptr(sc[0]), L.ptr(sc[1]), L.ptr(pixel), L.current_stream(dev))
     starts, counts = sc.tolist()   # the one read-back
     return points, pixel, starts, counts
+
+
+def _host_ptr(a):
+    """Pointer to a host numpy array (None -> NULL); the array must outlive the call it is passed to."""
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+class _DepthFrames(typing.NamedTuple):
+    """What the depth entries (gldm_depth_to_cloud, gldm_depth_to_objects, gldm_segment_tabletop) share."""
+    frames: torch.Tensor   # [F, H, W], contiguous
+    single: bool           # the caller gave one frame [H, W]
+    f: int
+    h: int
+    w: int
+    device: torch.device
+    source: tuple          # the entries' leading arguments, in gldm.h's order: depth, is_u16, depth_scale, mask
+    optics: tuple          # those behind the shape: fx, fy, cx, cy, z_min, z_max, cam_to_world, crop_lo, crop_hi
+    alive: tuple           # the mask and the host arrays behind the pointers above: they live as long as the record
+
+
+def _depth_frames(depth, camera, mask, z_range, depth_scale, cam_to_world, crop_box):
+    """The checks and conversions in front of every depth entry: depth [H, W] or [F, H, W] against the camera model, the
+    optional arguments through _depth_options -> _DepthFrames."""
+    _need_cuda(depth, "depth")
+    if depth.ndim not in (2, 3):
+        raise ValueError(f"depth must be [H, W] or [F, H, W], not {tuple(depth.shape)}")
+    single = depth.ndim == 2
+    d = (depth.unsqueeze(0) if single else depth).contiguous()
+    f, h, w = d.shape
+    if (h, w) != (camera.height, camera.width):
+        raise ValueError(f"depth frames are {h} x {w}, the camera model is {camera.height} x {camera.width}")
+    is_u16, m8, z_min, z_max, xf, lo, hi = _depth_options(d, depth, mask, z_range, depth_scale, cam_to_world, crop_box)
+    fx, fy, cx, cy = camera.intrinsics
+    return _DepthFrames(d, single, f, h, w, d.device, (L.ptr(d), int(is_u16), float(depth_scale or 1.0), L.ptr(m8)),
+                        (fx, fy, cx, cy, z_min, z_max, _host_ptr(xf), _host_ptr(lo), _host_ptr(hi)), (m8, xf, lo, hi))
 
 
 def _depth_options(d, depth, mask, z_range, depth_scale, cam_to_world, crop_box):
@@ -362,13 +372,9 @@ def farthest_point_indices_ragged(packed, start, count, n_max, nclusters):
     b, m, n_max = start.shape[0], int(nclusters), int(n_max)
     if count.shape[0] != b:
         raise ValueError(f"start holds {b} clouds, count {count.shape[0]}")
-    h = L.lib()
-    nbytes = h.gldm_farthest_points_euclid_ragged_workspace_bytes(b, n_max)
-    if nbytes < 0:
-        raise L.GldmError(f"gldm_farthest_points_euclid_ragged: {h.gldm_status_string(int(nbytes)).decode()} "
-                          f"(b = {b}, n_max = {n_max}; 1 <= n_max <= 2^22)")
+    ws, nbytes = L.workspace("gldm_farthest_points_euclid_ragged", (b, n_max), torch.int64, dev,
+                             f"b = {b}, n_max = {n_max}; 1 <= n_max <= 2^22")
     idx = torch.empty((b, m), dtype=torch.int32, device=dev)
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev) if nbytes else None
     with torch.cuda.device(dev):
         L.call("gldm_farthest_points_euclid_ragged", L.ptr(pts), L.ptr(start), L.ptr(count), b, n_max, m, L.ptr(ws), nbytes,
                L.ptr(idx), L.current_stream(dev))
@@ -394,23 +400,17 @@ def regularize_objects(packed, start, count, num_points, use_farthest_point=True
             raise ValueError(f"cloud {i} is empty")
         if s < 0 or s + c > packed.shape[0]:
             raise ValueError(f"cloud {i}: rows {s} .. {s + c} leave packed [{packed.shape[0]}, 3]")
-    rng = np.random if rng is None else rng
     pts = packed.contiguous().float()
     dev = pts.device
     b = len(start)
     idx = torch.zeros((b, num_points), dtype=torch.int64)
     far = []
     for i, n in enumerate(count):   # the draws, in the order the per-cloud function makes them
-        if n > num_points:
-            if use_farthest_point:
-                far.append(i)
-            else:
-                idx[i] = torch.from_numpy(np.asarray(rng.choice(range(n), size=num_points, replace=False)))
-        elif n < num_points:
-            extra = torch.from_numpy(np.asarray(rng.choice(range(n), size=num_points - n)))
-            idx[i] = torch.cat([torch.arange(n), extra.long()])
+        drawn = _drawn_rows(n, num_points, use_farthest_point, rng)
+        if drawn is None:
+            far.append(i)
         else:
-            idx[i] = torch.arange(n)
+            idx[i] = drawn
     rows = (idx + torch.tensor(start, dtype=torch.int64).unsqueeze(1)).to(device=dev, dtype=torch.int32)
     if far:
         fs = torch.tensor([start[i] for i in far], dtype=torch.int32, device=dev)
@@ -576,12 +576,8 @@ def plane_ransac(points, triples, tol, min_cross2=1e-8):
     dev = pts.device
     tri = torch.as_tensor(triples).to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
     n, t = pts.shape[0], tri.shape[0]
-    lib = L.lib()
-    nbytes = lib.gldm_plane_ransac_workspace_bytes(n, t)
-    if nbytes < 0:
-        raise L.GldmError(f"gldm_plane_ransac: {lib.gldm_status_string(int(nbytes)).decode()} (n = {n}, t = {t}; "
-                          f"1 <= n <= 2^24, 1 <= t <= {RANSAC_MAX_HYPOTHESES})")
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+    ws, nbytes = L.workspace("gldm_plane_ransac", (n, t), torch.int32, dev,
+                             f"n = {n}, t = {t}; 1 <= n <= 2^24, 1 <= t <= {RANSAC_MAX_HYPOTHESES}")
     planes = torch.empty((t, 4), dtype=torch.float32, device=dev)
     counts = torch.empty(t, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
@@ -600,14 +596,10 @@ def plane_moments(points, plane, tol):
     dev = pts.device
     pl = _host_floats(plane, 4, "plane")
     n = pts.shape[0]
-    lib = L.lib()
-    nbytes = lib.gldm_plane_moments_workspace_bytes(n)
-    if nbytes < 0:
-        raise L.GldmError(f"gldm_plane_moments: {lib.gldm_status_string(int(nbytes)).decode()} (n = {n}; 1 <= n <= 2^24)")
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    ws, nbytes = L.workspace("gldm_plane_moments", (n,), torch.float64, dev, f"n = {n}; 1 <= n <= 2^24")
     out = torch.empty(10, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        L.call("gldm_plane_moments", L.ptr(pts), n, pl.ctypes.data_as(ctypes.c_void_p), float(tol), L.ptr(ws), nbytes,
+        L.call("gldm_plane_moments", L.ptr(pts), n, _host_ptr(pl), float(tol), L.ptr(ws), nbytes,
                L.ptr(out), L.current_stream(dev))
     return out
 
@@ -693,10 +685,8 @@ def segment_tabletop(depth, camera, plane=None, height_range=(0.01, 0.5), link_d
     _need_cuda(depth, "depth")
     if depth.ndim != 2:
         raise ValueError(f"segment_tabletop takes one frame [H, W], not {tuple(depth.shape)}")
-    d = depth.contiguous()
-    h, w = d.shape
-    if (h, w) != (camera.height, camera.width):
-        raise ValueError(f"depth frames are {h} x {w}, the camera model is {camera.height} x {camera.width}")
+    fr = _depth_frames(depth, camera, mask, z_range, depth_scale, cam_to_world, crop_box)
+    h, w, dev = fr.h, fr.w, fr.device
     if plane is None:
         plane = fit_table_plane(depth, camera, tol=tol, hypotheses=hypotheses, rng=rng, refit=refit, min_cross2=min_cross2,
                                 mask=mask, z_range=z_range, depth_scale=depth_scale, cam_to_world=cam_to_world,
@@ -707,24 +697,13 @@ def segment_tabletop(depth, camera, plane=None, height_range=(0.01, 0.5), link_d
         raise ValueError(f"max_objects must be 1 .. {MAX_LABELS}, not {k}")
     if int(min_pixels) < 1:
         raise ValueError(f"min_pixels must be at least 1, not {min_pixels}")
-    is_u16, m8, z_min, z_max, xf, lo, hi = _depth_options(d.unsqueeze(0), depth, mask, z_range, depth_scale, cam_to_world,
-                                                          crop_box)
-    dev = d.device
-    fx, fy, cx, cy = camera.intrinsics
-    lib = L.lib()
-    nbytes = lib.gldm_segment_tabletop_workspace_bytes(h, w)
-    if nbytes < 0:
-        raise L.GldmError(f"gldm_segment_tabletop: {lib.gldm_status_string(int(nbytes)).decode()} ({h} x {w}; "
-                          "1 <= H*W <= 2^24)")
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    ws, nbytes = L.workspace("gldm_segment_tabletop", (h, w), torch.int64, dev, f"{h} x {w}; 1 <= H*W <= 2^24")
     labels = torch.empty((h, w), dtype=torch.int32, device=dev)
     stats = torch.empty(1 + 2 * k, dtype=torch.int32, device=dev)   # num_labels, label_pixels, label_root: one read-back
-    hp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
     with torch.cuda.device(dev):
-        L.call("gldm_segment_tabletop", L.ptr(d), int(is_u16), float(depth_scale or 1.0), L.ptr(m8), h, w, fx, fy, cx, cy,
-               z_min, z_max, hp(xf), hp(lo), hp(hi), hp(pl), float(height_range[0]), float(height_range[1]),
-               float(link_dist), int(min_pixels), k, L.ptr(ws), nbytes, L.ptr(labels), L.ptr(stats[0:1]),
-               L.ptr(stats[1:1 + k]), L.ptr(stats[1 + k:]), L.current_stream(dev))
+        L.call("gldm_segment_tabletop", *fr.source, h, w, *fr.optics, _host_ptr(pl), float(height_range[0]),
+               float(height_range[1]), float(link_dist), int(min_pixels), k, L.ptr(ws), nbytes, L.ptr(labels),
+               L.ptr(stats[0:1]), L.ptr(stats[1:1 + k]), L.ptr(stats[1 + k:]), L.current_stream(dev))
     host = stats.tolist()   # the one read-back
     num = host[0]
     if not isinstance(plane, TablePlane):

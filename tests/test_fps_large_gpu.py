@@ -1,4 +1,4 @@
-"""GPU: gldm_farthest_points_euclid_large (csrc/point_ops.hip) against oracle.front_end.farthest_points, the numpy
+"""GPU: gldm_farthest_points_euclid_large (csrc/fps.hip) against oracle.front_end.farthest_points, the numpy
 restatement pinned to the reference by tests/golden/front_end.npz.  Indices must be equal.
 
 The kernel cuts a cloud into slices of gldm_farthest_points_euclid_large_slice(n) rows (1024 up to n = 2^19, then doubling

@@ -1,4 +1,4 @@
-"""GPU: gldm_farthest_points_euclid_ragged (csrc/point_ops.hip) -- one call over clouds of different sizes -- against
+"""GPU: gldm_farthest_points_euclid_ragged (csrc/fps.hip) -- one call over clouds of different sizes -- against
 oracle.front_end.farthest_points per cloud and against the existing entries per cloud (gldm_farthest_points_euclid up to
 8192 rows, gldm_farthest_points_euclid_large beyond); and pointcloud.regularize_objects against the per-cloud
 PointCloudHelpers.regularize_pc_point_count.  Indices are integers: everything is exact."""

@@ -62,6 +62,21 @@ def test_farthest_points_golden_bit_exact():
 
 
 @gpu
+def test_farthest_points_three_clouds_past_one_wave_vs_oracle():
+    """The per-cloud offset of the one-workgroup form (n > 1024) with more than one cloud: three different clouds in one
+    call, each against the oracle and against the same call on that cloud alone."""
+    from oracle import front_end as F
+    from graspldm_amd.pointcloud import farthest_point_indices
+    pcs = np.random.RandomState(11).standard_normal((3, 1500, 3)).astype(np.float32)
+    dev = torch.from_numpy(pcs).cuda()
+    got = farthest_point_indices(dev, 40)
+    assert got.shape == (3, 40)
+    for b in range(3):
+        assert np.array_equal(got[b].cpu().numpy(), F.farthest_points(pcs[b], 40)), b
+        assert torch.equal(got[b], farthest_point_indices(dev[b], 40)[0]), b
+
+
+@gpu
 def test_farthest_points_random_clouds_vs_oracle():
     from oracle import front_end as F
     from graspldm_amd.pointcloud import farthest_point_indices

@@ -34,7 +34,7 @@ def _surface_cloud(b, n):
 
 
 @pytest.mark.parametrize("b,n,m", [(2, 1024, 512), (3, 512, 128), (1, 100, 100), (2, 64, 16), (1, 4096, 1024),
-                                   (2, 777, 300), (1, 2048, 64), (1, 8192, 32)])
+                                   (2, 777, 300), (1, 2048, 64), (1, 8192, 32), (3, 1500, 40)])
 def test_fps_indices_exact(hip, cpu, b, n, m):
     pts = _surface_cloud(b, n) if n in (1024, 4096) else _cloud(b, n, n)
     got = hip.furthest_point_sampling(pts.cuda(), m).cpu()

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Timing of the depth front end (csrc/depth_cloud.hip, the large farthest-point selection of csrc/point_ops.hip,
+"""Timing of the depth front end (csrc/depth_cloud.hip, the large farthest-point selection of csrc/fps.hip,
 InferenceLDM.infer_on_depth) on one MI355X.  HIP events around warmed calls, medians of --iterations with min-max, as
 tools/bench_grasp_select.py.
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Timing of the labelled-frame front end (gldm_depth_to_objects in csrc/depth_cloud.hip, gldm_farthest_points_euclid_ragged
-in csrc/point_ops.hip, InferenceLDM.infer_on_scene) on one MI355X.  HIP events around warmed calls, medians of --iterations
+in csrc/fps.hip, InferenceLDM.infer_on_scene) on one MI355X.  HIP events around warmed calls, medians of --iterations
 with min-max, as tools/bench_depth.py.  One 480 x 640 frame, a plane with 8 objects of 28800, 12000, 8100, 4800, 2000,
 1200, 750 and 400 pixels (two above 8192: the round launches; 750 and 400 are resampled up to 1024).
 
