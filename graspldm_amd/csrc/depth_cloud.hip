@@ -24,9 +24,7 @@
 #include <stdint.h>
 
 #include "depth_deproject.h"   // DepthParams, load_depth, deproject, make_params: shared with tabletop.hip
-#include "gldm.h"
-
-#define GLDM_API extern "C" __attribute__((visibility("default")))
+#include "host_util.h"
 
 namespace {
 
@@ -37,9 +35,6 @@ constexpr int kPerThread = 8;
 constexpr int kTile = kBlock * kPerThread;   // 2048 pixels
 constexpr int kMaxPixels = 1 << 24;
 constexpr int kMaxFrames = 65535;            // grid.y
-
-inline int launch_status() { return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH; }
-inline hipStream_t as_stream(gldm_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 // Sum of v over the workgroup, in every thread (s_red: kWaves ints).
 __device__ __forceinline__ int block_sum(int v, int *s_red) {

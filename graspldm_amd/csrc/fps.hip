@@ -13,17 +13,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gldm.h"
-
-#define GLDM_API extern "C" __attribute__((visibility("default")))
+#include "host_util.h"
 
 namespace {
 
 constexpr int kWave = 64;
-
-inline int launch_status() { return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH; }
-inline hipStream_t as_stream(gldm_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 // ------------------------------------------------------- the key, the rules --
 // Round winner = arg-max of a 64-bit key: high word = distance bits (distances are >= +0 so the bit pattern is monotone),

@@ -1,4 +1,4 @@
-// mfma_core.h -- what the kernel sources share (all but point_ops.hip, fps.hip and sa_msg.hip; the probes under tools/micro include
+// mfma_core.h -- what the kernel sources share (all but point_ops.hip, neighbors.hip, voxel_points.hip, fps.hip and sa_msg.hip, which take host_util.h; the probes under tools/micro include
 // it too).  Device code only, __forceinline__ in an anonymous namespace: nothing here is a symbol.
 //   * types and LDS maps: Geo<NC> (a workgroup's NC activation columns as [channel][column] f32 rows, XOR-swizzled: swz),
 //     PG<LL> (the same tensors as pre-split f16 planes in B-fragment order), Ctx;

@@ -26,9 +26,7 @@
 #include <stdint.h>
 
 #include "depth_deproject.h"
-#include "gldm.h"
-
-#define GLDM_API extern "C" __attribute__((visibility("default")))
+#include "host_util.h"
 
 namespace {
 
@@ -43,9 +41,6 @@ constexpr int kHypChunk = 64;                // hypotheses per workgroup of the 
                                              // 126 point tiles that is 1008 workgroups, four per CU, enough waves per SIMD
                                              // to cover the scalar load in front of every hypothesis (256: one wave per SIMD)
 constexpr int kMoments = 10;
-
-inline int launch_status() { return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH; }
-inline hipStream_t as_stream(gldm_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 __device__ __forceinline__ bool plane_inlier(float nx, float ny, float nz, float d, float tol, float x, float y, float z) {
   return fabsf(((nx * x + ny * y) + nz * z) + d) <= tol;   // NaN never passes

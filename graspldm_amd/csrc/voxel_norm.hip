@@ -216,15 +216,9 @@ __global__ __launch_bounds__(256) void devoxelize_cl_kernel(const float *__restr
   for (int it = tid; it < 64 * quads; it += 256) {
     const int pt = it / quads, qd = it - pt * quads;
     const int i = min(p0 + pt, n - 1);
-    const float x = coords[i], y = coords[i + n], z = coords[i + 2 * n];
-    const float xl = floorf(x), yl = floorf(y), zl = floorf(z);
-    const float xd1 = x - xl, yd1 = y - yl, zd1 = z - zl;
-    const float xd0 = 1.0f - xd1, yd0 = 1.0f - yd1, zd0 = 1.0f - zd1;
-    const float w[8] = {xd0 * yd0 * zd0, xd0 * yd0 * zd1, xd0 * yd1 * zd0, xd0 * yd1 * zd1,
-                        xd1 * yd0 * zd0, xd1 * yd0 * zd1, xd1 * yd1 * zd0, xd1 * yd1 * zd1};
-    const int i000 = (int)xl * r2 + (int)yl * r + (int)zl;
-    const int zh = zd1 > 0 ? 1 : 0, yh = yd1 > 0 ? r : 0, xh = xd1 > 0 ? r2 : 0;
-    const int idx[8] = {i000, i000 + zh, i000 + yh, i000 + yh + zh, i000 + xh, i000 + xh + zh, i000 + xh + yh, i000 + xh + yh + zh};
+    float w[8];
+    int idx[8];
+    trilinear_corners(coords[i], coords[i + n], coords[i + 2 * n], r, w, idx);
     f32x4 v[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) v[k] = f4[(size_t)idx[k] * quads + qd];
@@ -266,27 +260,20 @@ __global__ __launch_bounds__(256) void devoxelize_fused_kernel(const float *__re
   outs += (size_t)b * c * n;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const float x = coords[i], y = coords[i + n], z = coords[i + 2 * n];
-  const float xl = floorf(x), yl = floorf(y), zl = floorf(z);
-  const float xd1 = x - xl, yd1 = y - yl, zd1 = z - zl;
-  const float xd0 = 1.0f - xd1, yd0 = 1.0f - yd1, zd0 = 1.0f - zd1;
-  const float w000 = xd0 * yd0 * zd0, w001 = xd0 * yd0 * zd1, w010 = xd0 * yd1 * zd0, w011 = xd0 * yd1 * zd1;
-  const float w100 = xd1 * yd0 * zd0, w101 = xd1 * yd0 * zd1, w110 = xd1 * yd1 * zd0, w111 = xd1 * yd1 * zd1;
-  const int i000 = (int)xl * r2 + (int)yl * r + (int)zl;
-  const int zh = zd1 > 0 ? 1 : 0, yh = yd1 > 0 ? r : 0, xh = xd1 > 0 ? r2 : 0;
-  const int i001 = i000 + zh, i010 = i000 + yh, i011 = i010 + zh;
-  const int i100 = i000 + xh, i101 = i100 + zh, i110 = i100 + yh, i111 = i110 + zh;
+  float w[8];
+  int id[8];
+  trilinear_corners(coords[i], coords[i + n], coords[i + 2 * n], r, w, id);
   const int c0 = blockIdx.y * 16, c1 = min(c0 + 16, c);
   for (int l = c0; l < c1; ++l) {
     const float *f = feat + (size_t)l * r3;
-    float f0 = f[i000], f1 = f[i001], f2 = f[i010], f3 = f[i011], f4 = f[i100], f5 = f[i101], f6 = f[i110], f7 = f[i111];
+    float f0 = f[id[0]], f1 = f[id[1]], f2 = f[id[2]], f3 = f[id[3]], f4 = f[id[4]], f5 = f[id[5]], f6 = f[id[6]], f7 = f[id[7]];
     if (coef) {
       const float a = coef[((size_t)b * c + l) * 2], s = coef[((size_t)b * c + l) * 2 + 1];
       f0 = swish_fast(fmaf(f0, a, s)); f1 = swish_fast(fmaf(f1, a, s)); f2 = swish_fast(fmaf(f2, a, s));
       f3 = swish_fast(fmaf(f3, a, s)); f4 = swish_fast(fmaf(f4, a, s)); f5 = swish_fast(fmaf(f5, a, s));
       f6 = swish_fast(fmaf(f6, a, s)); f7 = swish_fast(fmaf(f7, a, s));
     }
-    const float v = w000 * f0 + w001 * f1 + w010 * f2 + w011 * f3 + w100 * f4 + w101 * f5 + w110 * f6 + w111 * f7;
+    const float v = w[0] * f0 + w[1] * f1 + w[2] * f2 + w[3] * f3 + w[4] * f4 + w[5] * f5 + w[6] * f6 + w[7] * f7;
     const float gt = gate ? gate[(size_t)b * c + l] : 1.0f;
     const float ad = add ? add[((size_t)b * c + l) * n + i] : 0.f;
     outs[(size_t)l * n + i] = gt * v + ad;

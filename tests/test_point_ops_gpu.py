@@ -199,6 +199,41 @@ def test_sa_group_equals_ballquery_module(hip, cpu, b, c, n, m, u, r):
     assert torch.equal(out.cpu(), exp)
 
 
+# gldm_sa_group around its staging rule (csrc/ball_query.h, bq_stage_points): the cloud's coordinates go to LDS while
+# n <= 5120 AND they fit beside the kernel's own LDS (16 centres: 16 u index slots + 48 centre floats) within 64 KiB;
+# otherwise the kernel reads them through L2.  u = 64: 4288 B fixed, so n = 5104 is the largest staged cloud (65 536 B
+# exactly) and 5105..5120 take the L2 form; u = 128: 8384 B fixed, L2 form from n = 4763.
+@pytest.mark.parametrize("n,m,u,c,r,far", [
+    (5200, 5, 7, 3, 0.12, 3),        # n > 5120: the L2 form; run = 35 is no multiple of 4: the scalar feature loop
+    (5120, 16, 64, 0, 0.3, None),    # would be 65 728 B staged: L2 form
+    (5120, 16, 128, 4, 0.35, None),  # would be 69 824 B staged: L2 form
+    (5104, 16, 64, 0, 0.3, None),    # the largest staged request at this u
+])
+def test_sa_group_staging_boundary(hip, cpu, n, m, u, c, r, far):
+    from graspldm_amd import _lib as L
+    pts = _cloud(1, n, 22)
+    ctr = pts[:, :, :m].clone()
+    if far is not None:
+        ctr[:, :, far] = 50.0                                       # an empty ball: all zeros
+    feat = torch.randn(1, c, n, generator=torch.Generator().manual_seed(23)) if c else None
+    idx = cpu.ball_query(ctr, pts, r, u)
+    full = idx[0, :, -1] != idx[0, :, 0]                            # a ball with fewer than u points ends in its first hit
+    assert full.any() and not full.all()                            # the radius leaves both kinds
+    exp = cpu.grouping_forward(pts, idx) - ctr.unsqueeze(-1)
+    if c:
+        exp = torch.cat([exp, cpu.grouping_forward(feat, idx)], dim=1)
+    dp, dc, df = pts.cuda(), ctr.cuda(), (feat.cuda() if c else None)
+    runs = []
+    for _ in range(2):
+        out = torch.full((1, 3 + c, m, u), float("nan"), device="cuda")
+        io = torch.full((1, m, u), -1, dtype=torch.int32, device="cuda")
+        L.call("gldm_sa_group", L.ptr(dp), L.ptr(dc), L.ptr(df), 1, c, n, m, r, u, L.ptr(out), L.ptr(io), L.current_stream())
+        runs.append((io.cpu(), out.cpu()))
+    assert torch.equal(runs[0][0], idx)
+    assert torch.equal(runs[0][1], exp)
+    assert torch.equal(runs[1][0], runs[0][0]) and torch.equal(runs[1][1], runs[0][1])
+
+
 def test_backend_argument_checks_on_gpu(hip):
     x = torch.zeros(1, 3, 8, device="cuda")
     with pytest.raises(RuntimeError, match="contiguous"):

@@ -2,7 +2,7 @@
 
 The reference's CUDA kernels are compiled by nvcc with contraction on (its default): the squared distance is evaluated as
 fma(dz, dz, fma(dy, dy, dx*dx)) there, while the oracle (oracle/point_ops.c, -ffp-contract=off) and the HIP kernels
-(point_ops.hip, -ffp-contract=off) round every product and every sum.  The two forms differ by an ulp now and then, which
+(neighbors.hip with ball_query.h, fps.hip; -ffp-contract=off) round every product and every sum.  The two forms differ by an ulp now and then, which
 matters only at the strict comparisons: ball query `d2 < r2` (ball_query.cu:34-47) and FPS's running arg-max
 (sampling.cu:86-167).  This script evaluates both forms in exact f32 semantics (numpy f32 for the plain form; the fused
 form through f64, where a product of two f32 is exact) on the clouds of the golden fixtures and counts the decisions that
