@@ -88,6 +88,10 @@ _SIGNATURES = {
     "gldm_unet1d_supported": [_vp, _i],
     "gldm_grasp_clearance_chunk": [],
     "gldm_grasp_clearance": [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp],
+    "gldm_grasp_contact_normals": [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _f, _f, _vp, _vp, _vp],
+    "gldm_knn_radius_workspace_bytes": [_i, _i],   # returns long long
+    "gldm_knn_radius": [_vp, _i, _i, _i, _f, _vp, _ll, _vp, _vp, _vp, _vp],
+    "gldm_point_normals": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
     "gldm_select_grasps": [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
     "gldm_farthest_points_euclid_large_workspace_bytes": [_i, _i],   # returns long long
     "gldm_farthest_points_euclid_large_slice": [_i],

@@ -2,6 +2,8 @@
 //
 //   gldm_grasp_clearance  distance of the open gripper's segments (grasp_ldm/utils/gripper.py:26-31) to a whole scene cloud,
 //                         and the number of scene points inside the finger-sweep tubes (:33-47, :80-103), per pose.
+//   gldm_grasp_contact_normals  the same contact set split by finger, and how many of each side's contacts have their
+//                         surface normal inside the friction cone around the pose's closing axis.
 //   gldm_select_grasps    top-k or greedy farthest-pose ("diverse") selection per cloud, under the control-point distance of
 //                         grasp_ldm/losses/loss.py:77-127.
 //
@@ -80,12 +82,20 @@ __global__ __launch_bounds__(256) void clearance_init_kernel(float *__restrict__
 // distance and its contact count; they meet across lanes, waves and workgroups as a min of non-negative floats (ordered
 // like their bit patterns) and an integer sum: exact, so no bit depends on the split.  sqrt is monotone and correctly
 // rounded, hence min(cap, sqrt(min d2)) is the same number wherever the sqrt is taken.
+// kNormals (gldm_grasp_contact_normals): the same scan, broad phase and contact test; instead of the body distance a lane
+// keeps four counts per pose -- contacts of side 0 (q.x > 0) and side 1, and those of each side whose normal satisfies
+// |(R00*nx + R10*ny) + R20*nz| >= cos_friction (a zero normal never does) -- written to side[pose][2] and aligned[pose][2].
+template <bool kNormals>
 __global__ __launch_bounds__(kChunk) void clearance_kernel(const float *__restrict__ scene, const float *__restrict__ H,
                                                            int ns, int g, int slices, int tiles, ClearArgs a,
-                                                           float *__restrict__ clearance, int32_t *__restrict__ contacts) {
+                                                           float *__restrict__ clearance, int32_t *__restrict__ contacts,
+                                                           const float *__restrict__ normals, float cos_friction,
+                                                           int32_t *__restrict__ side, int32_t *__restrict__ aligned) {
+  constexpr int kCounts = kNormals ? 4 : 1;
   __shared__ float pts[kChunk * 3];
-  __shared__ float red_d[kChunk / 64][kPoseTile];
-  __shared__ int red_c[kChunk / 64][kPoseTile];
+  __shared__ float nrm[kNormals ? kChunk * 3 : 1];           // the chunk's normals, staged like its points
+  __shared__ float red_d[kChunk / 64][kNormals ? 1 : kPoseTile];
+  __shared__ int red_c[kChunk / 64][kPoseTile * kCounts];
   const int tid = threadIdx.x;
   const unsigned bid = blockIdx.x;
   const int slice = bid % slices;
@@ -96,12 +106,13 @@ __global__ __launch_bounds__(kChunk) void clearance_kernel(const float *__restri
   const float *cloud_pts = scene + (long long)cloud * ns * 3;
   const float *poses = H + ((long long)cloud * g + g0) * 16;
 
-  float best[kPoseTile];
-  int hits[kPoseTile];
+  [[maybe_unused]] float best[kPoseTile];   // the body distance: not kept under kNormals
+  int hits[kPoseTile][kCounts];
 #pragma unroll
   for (int p = 0; p < kPoseTile; ++p) {
-    best[p] = __builtin_inff();
-    hits[p] = 0;
+    if constexpr (!kNormals) best[p] = __builtin_inff();
+#pragma unroll
+    for (int c = 0; c < kCounts; ++c) hits[p][c] = 0;
   }
 
   const int chunks = (ns + kChunk - 1) / kChunk;
@@ -113,11 +124,18 @@ __global__ __launch_bounds__(kChunk) void clearance_kernel(const float *__restri
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       const int f = tid + k * kChunk;
-      if (f < cnt * 3) pts[f] = src[f];
+      if (f < cnt * 3) {
+        pts[f] = src[f];
+        if constexpr (kNormals) nrm[f] = normals[((long long)cloud * ns + p0) * 3 + f];
+      }
     }
     __syncthreads();
     const bool live = tid < cnt;
     const float x = live ? pts[tid * 3 + 0] : 0.f, y = live ? pts[tid * 3 + 1] : 0.f, z = live ? pts[tid * 3 + 2] : 0.f;
+    float nx = 0.f, ny = 0.f, nz = 0.f;
+    if constexpr (kNormals) {
+      if (live) nx = nrm[tid * 3 + 0], ny = nrm[tid * 3 + 1], nz = nrm[tid * 3 + 2];
+    }
 #pragma unroll
     for (int p = 0; p < kPoseTile; ++p) {
       if (p < gn) {   // wave-uniform
@@ -132,10 +150,20 @@ __global__ __launch_bounds__(kChunk) void clearance_kernel(const float *__restri
         if (__ballot(near) != 0ull) {   // a chunk nowhere near this pose costs nine multiplies per lane
           // every lane of the wave walks the segments (uniform control flow: scalar loop, scalar segment loads);
           // `near` only selects what is kept
-          const float db = seg_min_d2(a.body, qx, qy, qz);
           const float dsw = seg_min_d2(a.sweep, qx, qy, qz);
-          best[p] = near ? fminf(best[p], db) : best[p];
-          hits[p] += (near && dsw <= a.r2) ? 1 : 0;   // an empty sweep family gives +inf: no contact
+          const bool hit = near && dsw <= a.r2;   // an empty sweep family gives +inf: no contact
+          if constexpr (kNormals) {
+            const bool left = qx > 0.f;
+            const bool cone = fabsf((hp[0] * nx + hp[4] * ny) + hp[8] * nz) >= cos_friction && (nx != 0.f || ny != 0.f || nz != 0.f);
+            hits[p][0] += (hit && left) ? 1 : 0;
+            hits[p][1] += (hit && !left) ? 1 : 0;
+            hits[p][2] += (hit && left && cone) ? 1 : 0;
+            hits[p][3] += (hit && !left && cone) ? 1 : 0;
+          } else {
+            const float db = seg_min_d2(a.body, qx, qy, qz);
+            best[p] = near ? fminf(best[p], db) : best[p];
+            hits[p][0] += hit ? 1 : 0;
+          }
         }
       }
     }
@@ -145,20 +173,31 @@ __global__ __launch_bounds__(kChunk) void clearance_kernel(const float *__restri
   const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
   for (int p = 0; p < kPoseTile; ++p) {
-    float d = best[p];
-    int c = hits[p];
+    if constexpr (!kNormals) {
+      float d = best[p];
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      d = fminf(d, __shfl_xor(d, off));
-      c += __shfl_xor(c, off);
+      for (int off = 32; off > 0; off >>= 1) d = fminf(d, __shfl_xor(d, off));
+      if (lane == 0) red_d[wave][p] = d;
     }
-    if (lane == 0) {
-      red_d[wave][p] = d;
-      red_c[wave][p] = c;
+#pragma unroll
+    for (int k = 0; k < kCounts; ++k) {
+      int c = hits[p][k];
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+      if (lane == 0) red_c[wave][p * kCounts + k] = c;
     }
   }
   __syncthreads();
-  if (tid < gn) {
+  if constexpr (kNormals) {
+    if (tid < gn * 4) {   // thread = (pose of the tile, count)
+      int c = red_c[0][tid];
+#pragma unroll
+      for (int w = 1; w < kChunk / 64; ++w) c += red_c[w][tid];
+      const long long row = (long long)cloud * g + g0 + (tid >> 2);
+      int32_t *out = (tid & 2) ? aligned : side;
+      if (c != 0) atomicAdd(out + row * 2 + (tid & 1), c);
+    }
+  } else if (tid < gn) {
     float d = red_d[0][tid];
     int c = red_c[0][tid];
 #pragma unroll
@@ -343,12 +382,15 @@ bool fill_segments(const float *seg, int n, SegSet *out) {
   out->n = n;
   for (int i = 0; i < kMaxSeg; ++i) {
     const bool on = i < n;
-    const float *a = seg + i * 6, *b = seg + i * 6 + 3;
-    for (int c = 0; on && c < 6; ++c)
-      if (!isfinite(a[c])) return false;
     Seg &o = out->s[i];
-    o.ax = on ? a[0] : 0.f, o.ay = on ? a[1] : 0.f, o.az = on ? a[2] : 0.f;
-    o.dx = on ? b[0] - a[0] : 0.f, o.dy = on ? b[1] - a[1] : 0.f, o.dz = on ? b[2] - a[2] : 0.f;
+    o.ax = o.ay = o.az = o.dx = o.dy = o.dz = 0.f;
+    if (on) {   // seg may be null for an empty family: no pointer is formed from it then
+      const float *a = seg + i * 6, *b = seg + i * 6 + 3;
+      for (int c = 0; c < 6; ++c)
+        if (!isfinite(a[c])) return false;
+      o.ax = a[0], o.ay = a[1], o.az = a[2];
+      o.dx = b[0] - a[0], o.dy = b[1] - a[1], o.dz = b[2] - a[2];
+    }
     const float len2 = o.dx * o.dx + o.dy * o.dy + o.dz * o.dz;
     o.inv = len2 > 0.f ? 1.f / len2 : 0.f;
     o.pad = 0.f;
@@ -357,29 +399,10 @@ bool fill_segments(const float *seg, int n, SegSet *out) {
   return true;
 }
 
-}  // namespace
-
-GLDM_API int gldm_grasp_clearance_chunk(void) { return kChunk; }
-
-GLDM_API int gldm_grasp_clearance(const float *scene, const float *H, int b, int g, int ns, const float *body, int sb,
-                                  const float *sweep, int ss, float r_sweep, float cap, float *clearance, int32_t *contacts,
-                                  gldm_stream_t stream) {
-  // the envelope first: no pointer is read and the device is not touched outside it
-  if (b <= 0 || g <= 0 || ns <= 0 || sb < 0 || ss < 0) return GLDM_ERR_INVALID_ARG;
-  if (ns > kMaxNs || sb < 1 || sb > kMaxSeg || ss > kMaxSeg) return GLDM_ERR_UNSUPPORTED;
-  if (!scene || !H || !body || (ss > 0 && !sweep) || !clearance || !contacts) return GLDM_ERR_INVALID_ARG;
-  if (!(cap > 0.f) || !isfinite(cap) || !(r_sweep >= 0.f) || !isfinite(r_sweep)) return GLDM_ERR_INVALID_ARG;
-  const long long poses = (long long)b * g;
-  const long long tiles = (g + kPoseTile - 1) / kPoseTile;
-  const int chunks = (ns + kChunk - 1) / kChunk;
-  // enough workgroups to fill the chip, no more slices than chunks
-  long long slices = 4096 / (b * tiles);
-  slices = slices < 1 ? 1 : (slices > chunks ? chunks : slices);
-  const long long blocks = slices * tiles * b;
-  if (poses > 0x7fffffffll || blocks > 0x7fffffffll) return GLDM_ERR_UNSUPPORTED;
-
-  ClearArgs a;
-  if (!fill_segments(body, sb, &a.body) || !fill_segments(sweep, ss, &a.sweep)) return GLDM_ERR_INVALID_ARG;
+// The kernel's arguments from the two segment families (host arrays; body may be empty: sb = 0): false for a non-finite
+// segment or reach.
+bool fill_clear_args(const float *body, int sb, const float *sweep, int ss, float r_sweep, float cap, ClearArgs *a) {
+  if (!fill_segments(body, sb, &a->body) || !fill_segments(sweep, ss, &a->sweep)) return false;
   // bounding sphere of all end points (segments are convex: the end points suffice), centred on their box
   double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
   for (int fam = 0; fam < 2; ++fam) {
@@ -404,17 +427,79 @@ GLDM_API int gldm_grasp_clearance(const float *scene, const float *H, int b, int
   // f32 q, so their disagreement is the rounding of a dozen operations on magnitudes <= reach: the 1e-3 margin is
   // four orders of magnitude above it.
   const double reach = (rho + fmax((double)cap, (double)r_sweep)) * 1.001;
-  a.cx = (float)ctr[0], a.cy = (float)ctr[1], a.cz = (float)ctr[2];
-  a.reach2 = (float)(reach * reach);
-  a.r2 = r_sweep * r_sweep;
-  a.cap = cap;
-  if (!isfinite(a.reach2)) return GLDM_ERR_INVALID_ARG;
+  a->cx = (float)ctr[0], a->cy = (float)ctr[1], a->cz = (float)ctr[2];
+  a->reach2 = (float)(reach * reach);
+  a->r2 = r_sweep * r_sweep;
+  a->cap = cap;
+  return isfinite(a->reach2);
+}
+
+// The launch shape both entries share: slices x pose tiles x clouds workgroups.
+struct ClearGrid {
+  long long poses, blocks;
+  int slices, tiles;
+};
+bool clear_grid(int b, int g, int ns, ClearGrid *gr) {
+  const long long tiles = (g + kPoseTile - 1) / kPoseTile;
+  const int chunks = (ns + kChunk - 1) / kChunk;
+  // enough workgroups to fill the chip, no more slices than chunks
+  long long slices = 4096 / (b * tiles);
+  slices = slices < 1 ? 1 : (slices > chunks ? chunks : slices);
+  gr->poses = (long long)b * g;
+  gr->blocks = slices * tiles * b;
+  gr->slices = (int)slices;
+  gr->tiles = (int)tiles;
+  return gr->poses <= 0x7fffffffll && gr->blocks <= 0x7fffffffll;
+}
+
+}  // namespace
+
+GLDM_API int gldm_grasp_clearance_chunk(void) { return kChunk; }
+
+GLDM_API int gldm_grasp_clearance(const float *scene, const float *H, int b, int g, int ns, const float *body, int sb,
+                                  const float *sweep, int ss, float r_sweep, float cap, float *clearance, int32_t *contacts,
+                                  gldm_stream_t stream) {
+  // the envelope first: no pointer is read and the device is not touched outside it
+  if (b <= 0 || g <= 0 || ns <= 0 || sb < 0 || ss < 0) return GLDM_ERR_INVALID_ARG;
+  if (ns > kMaxNs || sb < 1 || sb > kMaxSeg || ss > kMaxSeg) return GLDM_ERR_UNSUPPORTED;
+  if (!scene || !H || !body || (ss > 0 && !sweep) || !clearance || !contacts) return GLDM_ERR_INVALID_ARG;
+  if (!(cap > 0.f) || !isfinite(cap) || !(r_sweep >= 0.f) || !isfinite(r_sweep)) return GLDM_ERR_INVALID_ARG;
+  ClearGrid gr;
+  if (!clear_grid(b, g, ns, &gr)) return GLDM_ERR_UNSUPPORTED;
+
+  ClearArgs a;
+  if (!fill_clear_args(body, sb, sweep, ss, r_sweep, cap, &a)) return GLDM_ERR_INVALID_ARG;
 
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(clearance_init_kernel, dim3((unsigned)((poses + 255) / 256)), dim3(256), 0, st, clearance, contacts, poses, cap);
+  hipLaunchKernelGGL(clearance_init_kernel, dim3((unsigned)((gr.poses + 255) / 256)), dim3(256), 0, st, clearance, contacts,
+                     gr.poses, cap);
   if (hipGetLastError() != hipSuccess) return GLDM_ERR_LAUNCH;
-  hipLaunchKernelGGL(clearance_kernel, dim3((unsigned)blocks), dim3(kChunk), 0, st, scene, H, ns, g, (int)slices, (int)tiles, a,
-                     clearance, contacts);
+  hipLaunchKernelGGL(clearance_kernel<false>, dim3((unsigned)gr.blocks), dim3(kChunk), 0, st, scene, H, ns, g, gr.slices, gr.tiles,
+                     a, clearance, contacts, nullptr, 0.f, nullptr, nullptr);
+  return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
+}
+
+GLDM_API int gldm_grasp_contact_normals(const float *scene, const float *normals, const float *H, int b, int g, int ns,
+                                        const float *sweep, int ss, float r_sweep, float cos_friction, int32_t *contacts_side,
+                                        int32_t *aligned, gldm_stream_t stream) {
+  // the envelope of gldm_grasp_clearance, checked first in the same way
+  if (b <= 0 || g <= 0 || ns <= 0 || ss < 0) return GLDM_ERR_INVALID_ARG;
+  if (ns > kMaxNs || ss > kMaxSeg) return GLDM_ERR_UNSUPPORTED;
+  if (!scene || !normals || !H || (ss > 0 && !sweep) || !contacts_side || !aligned) return GLDM_ERR_INVALID_ARG;
+  if (!(r_sweep >= 0.f) || !isfinite(r_sweep) || !(cos_friction >= 0.f) || !(cos_friction <= 1.f)) return GLDM_ERR_INVALID_ARG;
+  ClearGrid gr;
+  if (!clear_grid(b, g, ns, &gr) || gr.poses * 2 > 0x7fffffffll) return GLDM_ERR_UNSUPPORTED;
+  // the sweep family alone: its bounding sphere plus r_sweep is the reach; every contact lies inside it, as it lies inside
+  // the larger sphere of gldm_grasp_clearance, so both entries count the same points
+  ClearArgs a;
+  if (!fill_clear_args(nullptr, 0, sweep, ss, r_sweep, 0.f, &a)) return GLDM_ERR_INVALID_ARG;
+
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const size_t bytes = (size_t)gr.poses * 2 * sizeof(int32_t);
+  if (hipMemsetAsync(contacts_side, 0, bytes, st) != hipSuccess || hipMemsetAsync(aligned, 0, bytes, st) != hipSuccess)
+    return GLDM_ERR_LAUNCH;
+  hipLaunchKernelGGL(clearance_kernel<true>, dim3((unsigned)gr.blocks), dim3(kChunk), 0, st, scene, H, ns, g, gr.slices, gr.tiles,
+                     a, nullptr, nullptr, normals, cos_friction, contacts_side, aligned);
   return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
 }
 

@@ -6,6 +6,8 @@
                     which the reference only draws.
   select_grasps     gldm_select_grasps: the best k of a cloud's candidates, or k diverse ones (greedy farthest pose under
                     the control-point distance of grasp_ldm/losses/loss.py:77-127), one workgroup per cloud.
+  contact_normals   gldm_grasp_contact_normals: those contacts split by finger, and how many of each side face the fingers
+                    (surface normal inside the friction cone around the pose's closing axis).
   GraspSelection    what a caller asks of `_InferenceBase.select_grasps` (inference.py).
 """
 import ctypes
@@ -103,6 +105,52 @@ def grasp_clearance(scene, H, *, body_segments=None, sweep_segments=None, sweep_
     return clearance, contacts
 
 
+def contact_normals(scene, normals, H, *, sweep_segments=None, sweep_radius=gripper.SWEEP_RADIUS, friction_angle_deg=30.0):
+    """gldm_grasp_contact_normals: scene and its unit normals [B, Ns, 3] (or [Ns, 3]; pointcloud.estimate_normals), poses H
+    [B, G, 4, 4] (or [G, 4, 4]) -> (contacts_side [B, G, 2], aligned [B, G, 2]) int32.  contacts_side: grasp_clearance's
+    contacts split by finger (side 0: q.x > 0, the left finger of gripper.OPEN_SEGMENTS; side 1: the rest); aligned: those
+    whose normal lies within friction_angle_deg of the pose's closing axis (first column of R), either way round.  A zero
+    normal is never aligned."""
+    from . import _lib as L
+    _need_cuda(scene, "scene")
+    _need_cuda(normals, "normals")
+    H = _poses(H)
+    if scene.ndim == 2:
+        scene = scene.unsqueeze(0)
+    if normals.ndim == 2:
+        normals = normals.unsqueeze(0)
+    if scene.ndim != 3 or scene.shape[-1] != 3 or scene.shape[0] != H.shape[0]:
+        raise RuntimeError(f"scene must be [B,Ns,3] with B = {H.shape[0]} clouds (or [Ns,3] for one), not {tuple(scene.shape)}")
+    if tuple(normals.shape) != tuple(scene.shape):
+        raise RuntimeError(f"normals {tuple(normals.shape)} do not match the scene {tuple(scene.shape)}")
+    if scene.device != H.device or normals.device != H.device:
+        raise RuntimeError("scene, normals and H must live on the same device")
+    sweep, ss = _host_floats(gripper.SWEEP_SEGMENTS if sweep_segments is None else sweep_segments, "sweep_segments", 6)
+    b, g = H.shape[:2]
+    ns = scene.shape[1]
+    if not clearance_supported(ns, 1, ss):
+        raise NotImplementedError(f"gldm_grasp_contact_normals takes 1..{MAX_SCENE_POINTS} scene points per cloud and "
+                                  f"0..{MAX_SEGMENTS} sweep segments, not Ns={ns}, Ss={ss}")
+    if not (math.isfinite(sweep_radius) and sweep_radius >= 0):
+        raise ValueError("sweep_radius must be >= 0")
+    if not (math.isfinite(friction_angle_deg) and 0.0 < friction_angle_deg <= 90.0):
+        raise ValueError(f"friction_angle_deg must lie in (0, 90], not {friction_angle_deg!r}")
+    scene, normals = scene.contiguous().float(), normals.contiguous().float()
+    _check_finite((("the scene points", scene), ("the scene normals", normals), ("the grasp poses", H)))
+    side = torch.empty(b, g, 2, dtype=torch.int32, device=H.device)
+    aligned = torch.empty(b, g, 2, dtype=torch.int32, device=H.device)
+    with torch.cuda.device(H.device):
+        L.call("gldm_grasp_contact_normals", L.ptr(scene), L.ptr(normals), L.ptr(H), b, g, ns, sweep if ss else None, ss,
+               ctypes.c_float(sweep_radius), ctypes.c_float(friction_cos(friction_angle_deg)), L.ptr(side), L.ptr(aligned),
+               L.current_stream(H.device))
+    return side, aligned
+
+
+def friction_cos(friction_angle_deg):
+    """cos of the friction angle as gldm_grasp_contact_normals takes it: formed in f64, rounded once to f32."""
+    return float(torch.tensor(math.cos(math.radians(friction_angle_deg)), dtype=torch.float64).float())
+
+
 def select_grasps(H, score, keep=None, k=None, diverse=False, control_points=None, min_separation=0.0):
     """Which k of each cloud's candidates to hand on: H [B, G, 4, 4] (or [G, 4, 4]), score [B, G], keep [B, G] bool or None
     -> (index [B, k] int32, -1 behind the last pick; count [B] int32; gap [B, k] f32).
@@ -141,7 +189,10 @@ class GraspSelection:
     """What to keep of a result dict (`_InferenceBase.select_grasps`).  Filters, cheapest first: min_confidence on the
     decoder's confidence; collision_free (clearance of the open gripper to the scene > body_radius) and min_contacts (scene
     points between the fingers) from one clearance launch; min_success on the classifier's probability, scored for the
-    survivors only.  Then top_k (None: every survivor) by `score_by`, or `diverse` ones at least min_separation apart."""
+    survivors only.  Then top_k (None: every survivor) by `score_by`, or `diverse` ones at least min_separation apart.
+    min_aligned_contacts (after the clearance filter, one contact_normals launch): at least that many contacts whose surface
+    normal lies within friction_angle_deg of the closing axis -- in total, or with both_fingers on each finger's side; the
+    scene's normals are estimated from normals_k neighbours within normals_radius where the caller gives none."""
     min_confidence: Optional[float] = None
     min_success: Optional[float] = None
     collision_free: bool = False
@@ -151,6 +202,11 @@ class GraspSelection:
     diverse: bool = False
     min_separation: float = 0.0
     score_by: str = "confidence"
+    min_aligned_contacts: int = 0
+    friction_angle_deg: float = 30.0
+    both_fingers: bool = False
+    normals_k: int = 12
+    normals_radius: float = 0.05
 
     def __post_init__(self):
         for name in ("min_confidence", "min_success"):
@@ -167,10 +223,31 @@ class GraspSelection:
             raise ValueError(f"min_separation must be >= 0, not {self.min_separation!r}")
         if self.score_by not in SCORE_BY:
             raise ValueError(f"score_by must be one of {SCORE_BY}, not {self.score_by!r}")
+        if not (isinstance(self.min_aligned_contacts, int) and not isinstance(self.min_aligned_contacts, bool)
+                and self.min_aligned_contacts >= 0):
+            raise ValueError(f"min_aligned_contacts must be an integer >= 0, not {self.min_aligned_contacts!r}")
+        if not (isinstance(self.friction_angle_deg, (int, float)) and not isinstance(self.friction_angle_deg, bool)
+                and math.isfinite(self.friction_angle_deg) and 0.0 < self.friction_angle_deg <= 90.0):
+            raise ValueError(f"friction_angle_deg must lie in (0, 90], not {self.friction_angle_deg!r}")
+        if not isinstance(self.both_fingers, bool):
+            raise ValueError(f"both_fingers must be a bool, not {self.both_fingers!r}")
+        if not (isinstance(self.normals_k, int) and not isinstance(self.normals_k, bool) and 3 <= self.normals_k <= 16):
+            raise ValueError(f"normals_k must be an integer in 3 .. 16 (a plane needs 3 neighbours), not {self.normals_k!r}")
+        if not (isinstance(self.normals_radius, (int, float)) and not isinstance(self.normals_radius, bool)
+                and math.isfinite(self.normals_radius) and self.normals_radius > 0):
+            raise ValueError(f"normals_radius must be > 0, not {self.normals_radius!r}")
 
     @property
     def needs_clearance(self):
         return bool(self.collision_free) or self.min_contacts > 0
+
+    @property
+    def needs_normals(self):
+        return self.min_aligned_contacts > 0
+
+    @property
+    def needs_scene(self):
+        return self.needs_clearance or self.needs_normals
 
     @property
     def needs_success(self):

@@ -94,12 +94,14 @@ class _InferenceBase:
         return self.select_grasps(out, selection, scene_pc=scene_pc, pc=pc, metas=metas)
 
     @torch.no_grad()
-    def select_grasps(self, results, selection, scene_pc=None, pc=None, metas=None):
+    def select_grasps(self, results, selection, scene_pc=None, pc=None, metas=None, scene_normals=None):
         """Filter and select the poses of a result dict (graspldm_amd.grasp_select.GraspSelection) -> a NEW dict; `results`
         is not modified.  scene_pc [B, Ns, 3] (or [Ns, 3]): the whole scene in the frame of results["pc"] -- table and
         clutter included --, default results["pc"] itself.  pc / metas: the normalised cloud(s) and metas the results were
         generated from; needed only where the classifier has to run (generate_grasps(..., selection=) passes them).
-        Cheap first: confidence mask -> one clearance launch (only if collision_free / min_contacts ask for it) -> the
+        Cheap first: confidence mask -> one clearance launch (only if collision_free / min_contacts ask for it) -> one
+        contact-normals launch (only if min_aligned_contacts asks for it; scene_normals [B, Ns, 3]: the scene's unit
+        normals, estimated here with pointcloud.estimate_normals when None; adds aligned_contacts [B, G, 2]) -> the
         classifier on the survivors (only if min_success / score_by need it) -> top-k or diverse launch -> with a classifier
         attached and not yet run, the classifier on the k selected poses.
         grasps, grasp_tmrp, confidence (success, latent_* when present) come back gathered to [B, K, ...], NaN in the slots
@@ -114,17 +116,33 @@ class _InferenceBase:
         keep = torch.ones(b, g, dtype=torch.bool, device=self.device)
         if selection.min_confidence is not None:
             keep &= conf >= selection.min_confidence
-        clearance = contacts = None
-        if selection.needs_clearance:
+        clearance = contacts = aligned = None
+        if selection.needs_scene:
             scene = results["pc"] if scene_pc is None else scene_pc
             scene = (scene.unsqueeze(0) if scene.ndim == 2 else scene).to(self.device)
-            if scene.shape[0] == 1 and b > 1:
+            shared = scene.shape[0] == 1 and b > 1   # one scene for every cloud of the batch
+            if shared:
                 scene = scene.expand(b, -1, -1)
+        if selection.needs_clearance:
             clearance, contacts = gs.grasp_clearance(scene, H, max_clearance=max(0.05, 2.0 * selection.body_radius))
             if selection.collision_free:
                 keep &= clearance > selection.body_radius
             if selection.min_contacts > 0:
                 keep &= contacts >= selection.min_contacts
+        if selection.needs_normals:
+            if scene_normals is None:
+                from .pointcloud import estimate_normals
+                src = scene[:1] if shared else scene
+                normals = estimate_normals(src, max_radius=selection.normals_radius, k=selection.normals_k)[0]
+            else:
+                normals = (scene_normals.unsqueeze(0) if scene_normals.ndim == 2 else scene_normals).to(self.device)
+            if normals.shape[0] == 1 and b > 1:
+                normals = normals.expand(b, -1, -1)
+            _, aligned = gs.contact_normals(scene, normals, H, friction_angle_deg=selection.friction_angle_deg)
+            if selection.both_fingers:
+                keep &= (aligned >= selection.min_aligned_contacts).all(dim=-1)
+            else:
+                keep &= aligned.sum(dim=-1) >= selection.min_aligned_contacts
         success = results.get("success")
         success = None if success is None else success.to(self.device).reshape(b, g)
 
@@ -182,6 +200,8 @@ class _InferenceBase:
                 sel[:, :n] = torch.where(v, score(Hs).reshape(b, n), sel[:, :n])
             out["success"] = sel.unsqueeze(-1)
         out.update(selected_index=index, selected_count=count, selected_gap=gap, clearance=clearance, contacts=contacts)
+        if aligned is not None:   # the key exists only where the filter was asked for
+            out["aligned_contacts"] = aligned
         return out
 
     def set_classifier(self, model, gripper_points=None):
@@ -284,8 +304,9 @@ class _InferenceBase:
         depth [H, W] or [F, H, W] (CUDA; float32 metres or raw 16-bit units with depth_scale), camera: a
         graspldm_amd.camera.Camera.  Object cloud of every frame = the deprojection under `mask` / `crop_box` inside
         `z_range` (pointcloud.depth_to_cloud), then prepare_pointcloud (num_points, farthest-point selection by default),
-        then generate_grasps: exactly infer_on_pointcloud on that cloud.  When `selection` asks for collision_free or
-        min_contacts and no scene_pc is given, the scene is the same frame without mask and crop, inside z_range.
+        then generate_grasps: exactly infer_on_pointcloud on that cloud.  When `selection` asks for collision_free,
+        min_contacts or min_aligned_contacts and no scene_pc is given, the scene is the same frame without mask and crop,
+        inside z_range.
         Poses are in the camera frame, or in the world frame with cam_to_world (3 x 4 / 4 x 4).  A frame whose object
         cloud is empty raises ValueError before anything is generated.  F frames -> results of batch F."""
         from .pointcloud import PointCloudHelpers, depth_to_cloud
@@ -299,7 +320,7 @@ class _InferenceBase:
             if c.shape[0] == 0:
                 raise ValueError(f"frame {f}: the object cloud is empty (no pixel passes the mask, the depth window "
                                  "and the crop box)")
-        if selection is not None and scene_pc is None and selection.needs_clearance:
+        if selection is not None and scene_pc is None and selection.needs_scene:
             scenes = depth_to_cloud(depth, camera, **kw)
             if single:
                 scene_pc = scenes
@@ -331,8 +352,8 @@ class _InferenceBase:
         labels.max()); the other arguments as infer_on_depth.  Objects with fewer than min_object_points points are skipped;
         the kept ones (ascending label) go through pointcloud.regularize_objects (num_points; None only if they all have
         the same size), normalize_input and generate_grasps: exactly generate_grasps on the stacked clouds.  When
-        `selection` asks for collision_free or min_contacts and no scene_pc is given, the scene is the same frame without
-        labels, mask and crop, inside z_range, as one [1, Ns, 3] cloud for every object.
+        `selection` asks for collision_free, min_contacts or min_aligned_contacts and no scene_pc is given, the scene is the
+        same frame without labels, mask and crop, inside z_range, as one [1, Ns, 3] cloud for every object.
         Added keys: object_label [B] and object_points [B] (label and raw point count of every row of the batch),
         scene_rank [n, 2] int64: (object row, slot) of every pose that is not NaN, by falling score (selection.score_by;
         confidence without a selection), ties to the lower object, then the lower slot."""
@@ -357,7 +378,7 @@ class _InferenceBase:
             batch = torch.stack([packed[s:s + c] for s, c in zip(ks, kc)])
         else:
             batch = regularize_objects(packed, ks, kc, num_points, use_farthest_point)
-        if selection is not None and scene_pc is None and selection.needs_clearance:
+        if selection is not None and scene_pc is None and selection.needs_scene:
             scene_pc = depth_to_cloud(depth, camera, **kw).unsqueeze(0)
         extra = {} if selection is None else dict(selection=selection, scene_pc=scene_pc)
         pcn, metas = self.normalize_input(batch)

@@ -15,7 +15,8 @@ from disk, and clouds of more than 8192 points take gldm_farthest_points_euclid_
 `regularize_objects` brings clouds of different sizes to one point count with one ragged selection
 (gldm_farthest_points_euclid_ragged) and one gather.  Without a label image `fit_table_plane` finds the
 table (gldm_plane_ransac, gldm_plane_moments) and `segment_tabletop` labels the objects standing on it
-(gldm_segment_tabletop).
+(gldm_segment_tabletop).  `estimate_normals` gives a sensor cloud its surface normals (gldm_knn_radius,
+gldm_point_normals; estimate_normals_cam_from_pc, pointcloud_helpers.py:74-122).
 """
 import ctypes
 import typing
@@ -150,6 +151,29 @@ class PointCloudHelpers:
         else:
             return pc.contiguous().float().unsqueeze(0)
         return gather_points(pc, idx.unsqueeze(0))
+
+    @staticmethod
+    def estimate_normals_cam_from_pc(pc_cam, max_radius=0.05, k=12):
+        """pointcloud_helpers.py:74-97 on one cloud [N,3] in camera coordinates -> [N,3] normals towards the camera
+        (estimate_normals below; the zero vector where fewer than 3 neighbours lie within max_radius)."""
+        _need_cuda(pc_cam, "pc_cam")
+        if pc_cam.ndim != 2:
+            raise ValueError(f"pc_cam must be [N, 3], not {tuple(pc_cam.shape)}")
+        return estimate_normals(pc_cam, max_radius=max_radius, k=k)[0]
+
+    @staticmethod
+    def vectorized_normal_computation(pc, neighbors):
+        """pointcloud_helpers.py:99-122: pc [N,3], neighbors [N,k,3] -> [N,3] (the `neighbors` form of gldm_point_normals)."""
+        pcb = _as_batch(pc)
+        _need_cuda(neighbors, "neighbors")
+        nb = neighbors.to(pcb.device).float().contiguous()
+        if pc.ndim != 2 or nb.ndim != 3 or nb.shape[0] != pcb.shape[1] or nb.shape[2] != 3:
+            raise ValueError(f"pc must be [N, 3] and neighbors [N, k, 3], not {tuple(pc.shape)} and {tuple(neighbors.shape)}")
+        k = nb.shape[1]
+        _check_knn_envelope(pcb.shape[1], k)
+        _finite_cloud(pcb)
+        _finite_cloud(nb)
+        return _point_normals(pcb, None, nb, k, None)[0]
 
 
 def _vec(v, n, device):
@@ -711,3 +735,73 @@ def segment_tabletop(depth, camera, plane=None, height_range=(0.01, 0.5), link_d
     if return_stats:
         return labels, num, plane, host[1:1 + k], host[1 + k:]
     return labels, num, plane
+
+
+# ------------------------------------------------------------------------------------------------ surface normals --
+# the k nearest neighbours within a radius (gldm_knn_radius) and the smallest eigenvector of every
+# neighbourhood (gldm_point_normals): estimate_normals_cam_from_pc / vectorized_normal_computation of
+# grasp_ldm/utils/pointcloud_helpers.py:74-122 without the round trip through scipy and numpy.
+KNN_MAX_K = 16          # gldm_knn_radius' ceiling on k
+KNN_MAX_POINTS = 1 << 20   # ... and on the points of one cloud
+
+
+def _check_knn_envelope(n, k):
+    if not 1 <= int(k) <= KNN_MAX_K:
+        raise NotImplementedError(f"k = {k}: gldm_knn_radius keeps 1 .. {KNN_MAX_K} neighbours per point")
+    if not 1 <= n <= KNN_MAX_POINTS:
+        raise NotImplementedError(f"n = {n}: gldm_knn_radius takes 1 .. 2^20 = {KNN_MAX_POINTS} points per cloud")
+
+
+def _finite_cloud(pcb):
+    if not bool(torch.isfinite(pcb).all()):
+        raise L.GldmError("the points hold non-finite values")
+
+
+def knn_radius(pc, k, max_radius):
+    """gldm_knn_radius on pc [N,3] or [B,N,3]: for every point the up to k nearest points of its cloud within max_radius,
+    itself included, ordered by (squared distance, index) -> (idx int32 [..,N,k], d2 f32 [..,N,k], found int32 [..,N]);
+    slots behind found carry idx = N and d2 = +inf (cKDTree.query's convention).  d2 = (dx*dx + dy*dy) + dz*dz in f32."""
+    pcb = _as_batch(pc)
+    b, n, _ = pcb.shape
+    k = int(k)
+    _check_knn_envelope(n, k)
+    r = float(max_radius)
+    if not (r >= 0.0 and r * r <= FLT_MAX):   # r2 finite in f32 (NaN fails both): +inf is the padding of d2
+        raise ValueError(f"max_radius must be >= 0 with a finite square in f32, not {max_radius!r}")
+    _finite_cloud(pcb)
+    dev = pcb.device
+    ws, nbytes = L.workspace("gldm_knn_radius", (b, n), torch.float32, dev, f"b = {b}, n = {n}; 1 <= n <= 2^20")
+    idx = torch.empty((b, n, k), dtype=torch.int32, device=dev)
+    d2 = torch.empty((b, n, k), dtype=torch.float32, device=dev)
+    found = torch.empty((b, n), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.call("gldm_knn_radius", L.ptr(pcb), b, n, k, float(max_radius), L.ptr(ws), nbytes, L.ptr(idx), L.ptr(d2),
+               L.ptr(found), L.current_stream(dev))
+    if pc.ndim == 2:
+        return idx[0], d2[0], found[0]
+    return idx, d2, found
+
+
+def _point_normals(pcb, idx, neighbors, k, view_point):
+    b, n, _ = pcb.shape
+    view = _host_floats(np.zeros(3, dtype=np.float32) if view_point is None else view_point, 3, "view_point")
+    if not np.isfinite(view).all():
+        raise ValueError("view_point must be finite")
+    normals = torch.empty((b, n, 3), dtype=torch.float32, device=pcb.device)
+    with torch.cuda.device(pcb.device):
+        L.call("gldm_point_normals", L.ptr(pcb), L.ptr(idx), L.ptr(neighbors), b, n, k, _host_ptr(view), L.ptr(normals),
+               L.current_stream(pcb.device))
+    return normals
+
+
+def estimate_normals(pc, max_radius=0.05, k=12, view_point=None):
+    """Surface normals of pc [N,3] or [B,N,3] -> (normals f32 of pc's shape, found int32 [..,N]): per point the
+    eigenvector of the smallest eigenvalue of sum (q - p)(q - p)^T over its up to k nearest neighbours q within max_radius
+    (knn_radius), unit length, turned so that dot(normal, p - view_point) < 0 (view_point: 3 numbers, default the origin:
+    towards the camera).  Points with found < 3 get the zero vector."""
+    pcb = _as_batch(pc)
+    idx, _, found = knn_radius(pcb, k, max_radius)
+    normals = _point_normals(pcb, idx.contiguous(), None, int(k), view_point)
+    if pc.ndim == 2:
+        return normals[0], found[0]
+    return normals, found

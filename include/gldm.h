@@ -824,6 +824,39 @@ int gldm_cls_head(const float *x /*[b,c,n]*/, const void *w1, const float *b1 /*
                   const float *l /*[n]*/, float c0, int b, int c, int rows, int n, int exact_f32, void *workspace,
                   long long workspace_bytes, float *logit /*[b]*/, float *prob /*[b]*/, gldm_stream_t stream);
 
+/* ------------------------------------------------ surface normals (additive, ABI 14; csrc/normals.hip) */
+
+/* The search of estimate_normals_cam_from_pc (grasp_ldm/utils/pointcloud_helpers.py:74-97: cKDTree.query(k,
+ * distance_upper_bound)).  pc [b,n,3] f32, finite.  For every point i of every cloud: the up to k points j of the same cloud
+ * with the smallest squared distances among those with d2 <= r2, the point itself included, where
+ *   d2(i, j) = (dx*dx + dy*dy) + dz*dz  in f32, differences first, one rounding per operation;  r2 = max_radius * max_radius
+ * ordered by (d2, j) ascending (ties to the lower index).  idx [b,n,k] int32, d2 [b,n,k] f32 (or NULL), found [b,n] int32 =
+ * the number of neighbours; slots behind found carry idx = n and d2 = +inf (scipy's convention).  A pure function of the
+ * inputs: bitwise repeatable, independent of the launch shape and of the broad phase (boxes of 256-point chunks in the
+ * workspace; a chunk is skipped only when the box-to-box distance, formed in the arithmetic of d2, exceeds the bound, which
+ * no point pair can then meet).  A cloud in pixel order (gldm_depth_to_cloud) skips most chunks; a shuffled one degrades to
+ * the full scan.  Two launches; no workgroup waits for another.
+ * Envelope, checked before any pointer or the device is touched: b, n >= 1, max_radius >= 0 with a finite
+ * r2 (GLDM_ERR_INVALID_ARG: +inf is the padding of d2, so no real neighbour may carry it);
+ * 1 <= k <= 16, n <= 2^20 (GLDM_ERR_UNSUPPORTED).  workspace: gldm_knn_radius_workspace_bytes(b, n) bytes (a negative
+ * GLDM_ERR_* status outside the envelope), uninitialised, private to the stream until the work has finished. */
+long long gldm_knn_radius_workspace_bytes(int b, int n);
+int gldm_knn_radius(const float *pc /*[b,n,3]*/, int b, int n, int k, float max_radius, void *workspace,
+                    long long workspace_bytes, int32_t *idx /*[b,n,k]*/, float *d2 /*[b,n,k] or NULL*/,
+                    int32_t *found /*[b,n]*/, gldm_stream_t stream);
+
+/* vectorized_normal_computation (pointcloud_helpers.py:99-122).  Exactly one of idx [b,n,k] (gldm_knn_radius's; a slot
+ * with idx outside [0, n) counts as the point itself) and neighbors [b,n,k,3] is given.  Per point: diffs = neighbour -
+ * point in f32; the six sums of diffs^T diffs in f64 (products of f32 values are exact there; the reference's division by
+ * k^2 does not change a direction and is dropped); the eigenvector of the smallest eigenvalue by cyclic Jacobi in f64, a
+ * fixed number of sweeps; normalised; negated where dot(normal, point - view) >= 0 (view: HOST [3]; 0 = the reference's
+ * "towards the camera", :120-121); rounded to f32.  Where fewer than 3 slots are live (idx form: inside [0, n); neighbors
+ * form: all k) no plane is defined and the normal is the zero vector; the reference returns an arbitrary eigenvector of a
+ * rank-deficient matrix there.  Envelope: that of gldm_knn_radius; view finite. */
+int gldm_point_normals(const float *pc /*[b,n,3]*/, const int32_t *idx /*[b,n,k] or NULL*/,
+                       const float *neighbors /*[b,n,k,3] or NULL*/, int b, int n, int k, const float *view /*host [3]*/,
+                       float *normals /*[b,n,3]*/, gldm_stream_t stream);
+
 /* ------------------------------------------------ grasp selection (additive, ABI 14; csrc/grasp_select.hip) */
 
 /* Gripper clearance and finger-sweep contacts of every pose against a whole scene cloud.  The geometry is the
@@ -847,6 +880,23 @@ int gldm_grasp_clearance(const float *scene /*[b,ns,3]*/, const float *H /*[b*g,
                          const float *body /*host [sb,2,3]*/, int sb, const float *sweep /*host [ss,2,3] or NULL*/, int ss,
                          float r_sweep, float cap, float *clearance /*[b*g]*/, int32_t *contacts /*[b*g]*/,
                          gldm_stream_t stream);
+
+/* The contacts of gldm_grasp_clearance judged by the friction cone (additive, ABI 14).  normals [b,ns,3]: unit surface
+ * normals of the scene points (gldm_point_normals; a zero vector = no normal).  The contact set is that of
+ * gldm_grasp_clearance -- points whose smallest squared distance to a sweep segment is <= r_sweep^2, q = R^T (p - t) formed
+ * by the same instructions -- split by finger: side 0 is q.x > 0 (the left finger of the open gripper, gripper.py:26-31),
+ * side 1 the rest.
+ *   contacts_side[(c*g + i)*2 + s] = contacts of side s; the two sum to gldm_grasp_clearance's contacts, bit for bit
+ *   aligned[(c*g + i)*2 + s]       = those with fabsf((R00*nx + R10*ny) + R20*nz) >= cos_friction and n != 0: the normal
+ *                                    lies within the friction angle of the pose's closing axis (first column of R), either
+ *                                    way round, so the frame in which the normals were oriented does not matter
+ * Integer sums behind a clearing memset: exact, bitwise repeatable, independent of how the scene is split.  One scan with
+ * gldm_grasp_clearance (a template flag of the same kernel); the broad phase uses the sweep family's own bounding sphere.
+ * Envelope as gldm_grasp_clearance (1 <= ns <= 2^24, 0 <= ss <= 8 or GLDM_ERR_UNSUPPORTED); 0 <= cos_friction <= 1. */
+int gldm_grasp_contact_normals(const float *scene /*[b,ns,3]*/, const float *normals /*[b,ns,3]*/,
+                               const float *H /*[b*g,4,4]*/, int b, int g, int ns, const float *sweep /*host [ss,2,3] or NULL*/,
+                               int ss, float r_sweep, float cos_friction, int32_t *contacts_side /*[b,g,2]*/,
+                               int32_t *aligned /*[b,g,2]*/, gldm_stream_t stream);
 
 /* Which k of a cloud's g candidate poses to keep: one workgroup per cloud, the rounds run inside the launch.
  * score [b*g] f32 (finite); keep [b*g] uint8 or NULL (all); ctrl [np,3]: HOST array of gripper control points.

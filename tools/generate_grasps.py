@@ -16,9 +16,13 @@ sample / cloud file in order --, un-normalised, in the cloud's frame; --num_gras
 [--min_separation M] (geometric filtering and selection of the generated poses, graspldm_amd/grasp_select.py: the gripper
 must clear the scene, N scene points must lie between the fingers, thresholds on confidence and on the classifier's
 success, the best K or K diverse ones; --out gains selected_index, selected_count, selected_gap, clearance, contacts;
-without any of these flags nothing changes), --depth_file FILE --camera_json FILE [--mask_file FILE] [--depth_scale S]
+without any of these flags nothing changes), --min_aligned_contacts N [--friction_angle DEG] [--both_fingers] [--normals_k K]
+[--normals_radius R] (friction-cone contact filter: at least N contacts between the fingers whose surface normal lies within
+DEG of the closing axis, with --both_fingers on each finger's side; the scene's normals are estimated on the GPU from K
+neighbours within R metres; --out gains aligned_contacts), --depth_file FILE --camera_json FILE [--mask_file FILE] [--depth_scale S]
 [--z_range MIN MAX] [--crop_box x0 y0 z0 x1 y1 z1] (generate on a depth frame: deprojected on the GPU, the masked / cropped
-pixels are the object, and for --collision_free / --min_contacts without --scene_file the whole frame is the scene;
+pixels are the object, and for --collision_free / --min_contacts / --min_aligned_contacts without --scene_file the whole
+frame is the scene;
 exclusive with --pc_file and --synthetic), --labels_file FILE [--min_object_points N] (with --depth_file: an instance-label
 image, object k = label k; every object with at least N points gets its grasps in one batch, infer_on_scene; --out gains
 object_label, object_points, scene_rank), --segment_tabletop [--table_tol T] [--object_height MIN MAX] [--link_dist D]
@@ -77,12 +81,24 @@ def parse_args(argv=None):
     p.add_argument("--sort_by_success", action="store_true",
                    help="with --classifier_config: order each cloud's grasps by falling success probability in --out")
     p.add_argument("--scene_file", type=str, action="append", default=None, metavar="FILE",
-                   help="the whole scene (table, clutter) for --collision_free / --min_contacts, read like --pc_file and in the "
-                        "frame of the --pc_file cloud: one file, or one per cloud (default: the cloud itself)")
+                   help="the whole scene (table, clutter) for --collision_free / --min_contacts / --min_aligned_contacts, read "
+                        "like --pc_file and in the frame of the --pc_file cloud: one file, or one per cloud (default: the "
+                        "cloud itself)")
     p.add_argument("--collision_free", action="store_true",
                    help="keep only poses whose open gripper stays clear of every scene point")
     p.add_argument("--min_contacts", type=int, default=0, metavar="N",
                    help="keep only poses with at least N scene points between the fingers")
+    p.add_argument("--min_aligned_contacts", type=int, default=0, metavar="N",
+                   help="keep only poses with at least N contacts whose surface normal lies inside the friction cone around "
+                        "the closing axis (the scene's normals are estimated on the GPU)")
+    p.add_argument("--friction_angle", type=float, default=30.0, metavar="DEG",
+                   help="with --min_aligned_contacts: half-angle of the friction cone in degrees, in (0, 90]")
+    p.add_argument("--both_fingers", action="store_true",
+                   help="with --min_aligned_contacts: require the N aligned contacts on each finger's side, not in total")
+    p.add_argument("--normals_k", type=int, default=12, metavar="K",
+                   help="with --min_aligned_contacts: neighbours per scene point for the normal estimate (3 .. 16)")
+    p.add_argument("--normals_radius", type=float, default=0.05, metavar="R",
+                   help="with --min_aligned_contacts: search radius of those neighbours in metres")
     p.add_argument("--min_confidence", type=float, default=None, metavar="X", help="keep only poses with confidence >= X")
     p.add_argument("--min_success", type=float, default=None, metavar="X",
                    help="with --classifier_config: keep only poses with success probability >= X (only the poses that "
@@ -248,16 +264,20 @@ def run_depth(args, model, selection):
 
 def build_selection(args):
     """The GraspSelection of the selection flags, or None when none of them is set (nothing changes then)."""
+    if not args.min_aligned_contacts and (args.both_fingers or args.friction_angle != 30.0 or args.normals_k != 12
+                                          or args.normals_radius != 0.05):
+        raise SystemExit("--friction_angle / --both_fingers / --normals_k / --normals_radius go with --min_aligned_contacts")
     asked = (args.collision_free or args.min_contacts or args.min_confidence is not None or args.min_success is not None
-             or args.top_k is not None or args.diverse or args.min_separation or args.scene_file)
+             or args.top_k is not None or args.diverse or args.min_separation or args.scene_file
+             or args.min_aligned_contacts)
     if not asked:
         return None
     if args.min_success is not None and not args.classifier_config:
         raise SystemExit("--min_success needs --classifier_config")
     if args.top_k is not None and args.top_k < 1:
         raise SystemExit("--top_k must be at least 1")
-    if args.scene_file and not (args.collision_free or args.min_contacts):
-        raise SystemExit("--scene_file is read by --collision_free / --min_contacts only")
+    if args.scene_file and not (args.collision_free or args.min_contacts or args.min_aligned_contacts):
+        raise SystemExit("--scene_file is read by --collision_free / --min_contacts / --min_aligned_contacts only")
     if args.scene_file and len(args.scene_file) not in (1, len(args.pc_file) if args.pc_file else args.num_samples):
         raise SystemExit("--scene_file: one file, or one per cloud")
     from graspldm_amd.grasp_select import GraspSelection
@@ -265,7 +285,9 @@ def build_selection(args):
         return GraspSelection(min_confidence=args.min_confidence, min_success=args.min_success,
                               collision_free=args.collision_free, min_contacts=args.min_contacts, top_k=args.top_k,
                               diverse=args.diverse, min_separation=args.min_separation,
-                              score_by="success" if args.min_success is not None else "confidence")
+                              score_by="success" if args.min_success is not None else "confidence",
+                              min_aligned_contacts=args.min_aligned_contacts, friction_angle_deg=args.friction_angle,
+                              both_fingers=args.both_fingers, normals_k=args.normals_k, normals_radius=args.normals_radius)
     except ValueError as e:
         raise SystemExit(str(e))
 
@@ -444,7 +466,7 @@ def finish(args, results):
     if args.out:
         extra = {k: torch.cat([r[k] for r in results]).cpu().numpy()
                  for k in ("latent_mu", "latent_logvar", "success", "selected_index", "selected_count", "selected_gap",
-                           "clearance", "contacts", "object_label", "object_points", "scene_rank")
+                           "clearance", "contacts", "aligned_contacts", "object_label", "object_points", "scene_rank")
                  if all(r.get(k) is not None for r in results)}
         if all(r.get("table_plane") is not None for r in results):   # --segment_tabletop: one frame per result
             extra["labels"] = torch.stack([r["labels"] for r in results]).cpu().numpy()
