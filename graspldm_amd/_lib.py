@@ -10,7 +10,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # GLDM_LIB: another build of the same library (diagnostic builds: make -C graspldm_amd/csrc EXTRA=... OUT=...)
 LIB_PATH = os.environ.get("GLDM_LIB") or os.path.join(_PKG, "libgldm_hip.so")
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 class GldmError(RuntimeError):
@@ -24,7 +24,7 @@ _ull = ctypes.c_ulonglong
 _vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 
 _SIGNATURES = {
-    # name: argtypes  (all return int, but the *_workspace_bytes entries: long long)
+    # name: argtypes  (all return int, but the *_workspace_bytes / *_lds_bytes entries: long long)
     "gldm_ball_query": [_vp, _vp, _i, _i, _i, _f, _i, _vp, _vp],
     "gldm_grouping_forward": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
     "gldm_gather_features_forward": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
@@ -83,6 +83,11 @@ _SIGNATURES = {
     "gldm_sa_mlp_forward": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "gldm_sa_mlp_forward_f16x2": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "gldm_sa_mlp_forward_f16x2_pre": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    # the shape queries of the three MFMA families of the encoders (ABI 15): the launchers' own planners
+    "gldm_pointwise_mlp_supported": [_i, _i, _i, _i, _i, _i, _i, _i],
+    "gldm_conv3d_k3_supported": [_i, _i, _i, _i],
+    "gldm_sa_mlp_supported": [_i, _i, _i, _vp, _vp],
+    "gldm_sa_mlp_f16x2_lds_bytes": [_i, _i, _i, _i, _vp, _vp, ctypes.POINTER(_ll)],   # returns long long
     "gldm_ball_query_multi": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "gldm_group_max_concat": [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp],
     "gldm_unet1d_supported": [_vp, _i],
@@ -157,7 +162,7 @@ def lib():
     for name, argtypes in _SIGNATURES.items():
         fn = getattr(h, name)
         fn.argtypes = argtypes
-        fn.restype = _ll if name.endswith("_workspace_bytes") else _i
+        fn.restype = _ll if name.endswith(("_workspace_bytes", "_lds_bytes")) else _i
     h.gldm_r1d_workspace_bytes.argtypes = [_vp, _i]
     h.gldm_r1d_workspace_bytes.restype = ctypes.c_longlong
     h.gldm_r1d_tile_columns.argtypes = [_vp]

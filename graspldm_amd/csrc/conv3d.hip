@@ -914,15 +914,48 @@ int launch_conv_halves(const float *x, const float *wp, const float *bias, int b
   return launch_conv<MH, NTW>(x, wp + (size_t)MH * kblocks * 256, bias + half, b, cin, cout - half, r, y, partial, s, out_cl, cout, half);
 }
 
+// The f32-MFMA instantiations, once: X(MT, NTW) for cout in (16 (MT - 1), 16 MT] at r = 4 NTW as one launch, H(MT, NTW, MH) as
+// two launches of MH m-tiles.  conv_f32_plan (the shape query) and conv3d_k3_impl (the dispatch) both read this list.
+#define GLDM_CONV_F32_LIST(X, H)                                                                                          \
+  X(3, 6)   /* 48 ch @ 24^3  (shipped fpc/ppc PVCNN encoder) */                                                            \
+  X(6, 3)   /* 96 ch @ 12^3 */                                                                                             \
+  X(2, 8)   /* 32 ch @ 32^3  (PVCNN2) */                                                                                   \
+  X(4, 4)   /* 64 ch @ 16^3 */                                                                                             \
+  X(8, 2)   /* 128 ch @ 8^3 */                                                                                             \
+  /* half-width / half-resolution variants (the reference's encoder benchmark runs PVCNN / PVCNN2 at 0.5 / 0.5) */       \
+  X(2, 4)   /* 32 ch @ 16^3 */                                                                                             \
+  X(4, 2)   /* 64 ch @ 8^3 */                                                                                              \
+  X(1, 4)   /* 16 ch @ 16^3 */                                                                                             \
+  X(2, 2)   /* 32 ch @ 8^3 */                                                                                              \
+  X(4, 1)   /* 64 ch @ 4^3 */                                                                                              \
+  X(8, 1)   /* 128 ch @ 4^3 */                                                                                             \
+  /* 64 ch @ 32^3 (PVCNN2 at full width under numerics.f32_only(): the split kernel serves it otherwise): 4 m-tiles x 8   \
+     n-tiles of accumulators spilled 58-70 registers as one launch -- two launches of the 32-channel instantiation instead */ \
+  H(4, 8, 2)                                                                                                               \
+  H(16, 2, 8)   /* 256 ch @ 8^3 */                                                                                         \
+  H(8, 4, 4)    /* 128 ch @ 16^3 */
+
+// The shape part of conv3d_k3_impl: a pure function of (cout, r) (every cin >= 1 runs).  GLDM_OK or GLDM_ERR_UNSUPPORTED.
+static int conv_f32_plan(int cin, int cout, int r) {
+  if (cin <= 0 || cout <= 0 || r <= 0) return GLDM_ERR_UNSUPPORTED;
+  if (r % 4 || (size_t)16 * brick_row_stride(r) * 4 > 160 * 1024) return GLDM_ERR_UNSUPPORTED;
+  const int mt = (cout + 15) / 16, ntw = r / 4;
+#define GLDM_CONV_CASE(M, N) if (mt == M && ntw == N) return GLDM_OK;
+#define GLDM_CONV_HALVES(M, N, MH) GLDM_CONV_CASE(M, N)
+  GLDM_CONV_F32_LIST(GLDM_CONV_CASE, GLDM_CONV_HALVES)
+#undef GLDM_CONV_CASE
+#undef GLDM_CONV_HALVES
+  return GLDM_ERR_UNSUPPORTED;
+}
+
 static int conv3d_k3_impl(const float *x, const float *w_packed, const float *bias, int b, int cin, int cout, int r,
                           float *y, float *partial, int out_cl, gldm_stream_t stream) {
   if (!x || !w_packed || !bias || !y || !partial || b <= 0 || cin <= 0 || cout <= 0 || r <= 0)
     return GLDM_ERR_INVALID_ARG;
   if (out_cl && cout % 4) return GLDM_ERR_UNSUPPORTED;
+  if (conv_f32_plan(cin, cout, r) != GLDM_OK) return GLDM_ERR_UNSUPPORTED;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int mt = (cout + 15) / 16, ntw = r / 4;
-  if (r % 4 || (size_t)16 * brick_row_stride(r) * 4 > 160 * 1024) return GLDM_ERR_UNSUPPORTED;
-
 #ifdef GLDM_DEBUG_KNOBS
   struct StampDump {  // diagnostic builds: GLDM_C3_STAMP=1 prints the phase clocks of one mid-grid workgroup per call
     hipStream_t s; int cin, cout, r;
@@ -945,25 +978,12 @@ static int conv3d_k3_impl(const float *x, const float *w_packed, const float *bi
   } dump{s, cin, cout, r};
 #endif
 #define GLDM_CONV_CASE(M, N) \
-  if (mt == M && ntw == N) return launch_conv<M, N>(x, w_packed, bias, b, cin, cout, r, y, partial, s, out_cl)
-  GLDM_CONV_CASE(3, 6);   // 48 ch @ 24^3  (shipped fpc/ppc PVCNN encoder)
-  GLDM_CONV_CASE(6, 3);   // 96 ch @ 12^3
-  GLDM_CONV_CASE(2, 8);   // 32 ch @ 32^3  (PVCNN2)
-  GLDM_CONV_CASE(4, 4);   // 64 ch @ 16^3
-  GLDM_CONV_CASE(8, 2);   // 128 ch @ 8^3
-  // half-width / half-resolution variants (the reference's encoder benchmark runs PVCNN / PVCNN2 at 0.5 / 0.5)
-  GLDM_CONV_CASE(2, 4);   // 32 ch @ 16^3
-  GLDM_CONV_CASE(4, 2);   // 64 ch @ 8^3
-  GLDM_CONV_CASE(1, 4);   // 16 ch @ 16^3
-  GLDM_CONV_CASE(2, 2);   // 32 ch @ 8^3
-  GLDM_CONV_CASE(4, 1);   // 64 ch @ 4^3
-  GLDM_CONV_CASE(8, 1);   // 128 ch @ 4^3
+  if (mt == M && ntw == N) return launch_conv<M, N>(x, w_packed, bias, b, cin, cout, r, y, partial, s, out_cl);
+#define GLDM_CONV_HALVES(M, N, MH) \
+  if (mt == M && ntw == N) return launch_conv_halves<MH, N>(x, w_packed, bias, b, cin, cout, r, y, partial, s, out_cl);
+  GLDM_CONV_F32_LIST(GLDM_CONV_CASE, GLDM_CONV_HALVES)
 #undef GLDM_CONV_CASE
-  // 64 ch @ 32^3 (PVCNN2 at full width under numerics.f32_only(): the split kernel serves it otherwise): 4 m-tiles x 8
-  // n-tiles of accumulators spilled 58-70 registers as one launch -- two launches of the 32-channel instantiation instead
-  if (mt == 4 && ntw == 8) return launch_conv_halves<2, 8>(x, w_packed, bias, b, cin, cout, r, y, partial, s, out_cl);
-  if (mt == 16 && ntw == 2) return launch_conv_halves<8, 2>(x, w_packed, bias, b, cin, cout, r, y, partial, s, out_cl);  // 256 ch @ 8^3
-  if (mt == 8 && ntw == 4) return launch_conv_halves<4, 4>(x, w_packed, bias, b, cin, cout, r, y, partial, s, out_cl);   // 128 ch @ 16^3
+#undef GLDM_CONV_HALVES
   return GLDM_ERR_UNSUPPORTED;
 }
 
@@ -999,18 +1019,61 @@ int launch_conv_pl(const float *x, const float *wp3, const float *bias, int b, i
                  : launch_conv_pl_act<MT, R, ZB, WAVES, false>(x, wp3, bias, b, cin, cout, y, partial, nullptr, out_cl, s);
 }
 
+// (4 x 4 x 12 half bricks at 24^3 -- <3, 24, 12, 4>, two co-resident workgroups of 4 waves -- measured before round 6, on three
+// bf16 planes (48 KiB a half brick), 2.12 ms against 2.05 for the full-z brick: the kernel's 220 registers allow two waves per SIMD either way, and the
+// halves pay a z halo and the weight stream twice.  Kept as an instantiable option, not used.  Round 6, with three f16
+// products instead of six bf16 ones: A/B of the whole encoder on one box 4.69 / 4.72 ms (full brick) against 4.63 / 4.84
+// (halves) -- inside the run-to-run spread, still not used.)
+// Round 6, two more forms of the 24^3 conv measured on one box against this one (whole shipped encoder, 256 clouds, A/B by an
+// environment switch of the diagnostic build; phase stamps of a mid-grid workgroup: taps 31 k of a brick's 70 k cycles,
+// store phases 2.4-5.2 k and barrier waits 2.9-3.8 k per 16-channel block, epilogue 5.4 k):
+//  * block cb + 1 split and stored INSIDE block cb's tap loop, one staging round behind every second tap pair (the other
+//    plane set is free there): the store phases shrank to 0.3-1.1 k, the taps grew 10.4 -> 12.2 k and the barrier waits
+//    3.5 -> 6-7 k -- 4.49-4.50 ms against 4.48: nothing.  The staging VALU work does not hide under the other wave's MFMAs;
+//  * <3, 24, 24, 4>: four waves x six n-tiles (half the weight-fragment deliveries per MFMA), two workgroups per CU, no
+//    staging prefetch across the tap loop (64 registers): 18-24 spilled registers, 4.58 against 4.63 ms: 1 %, not kept.
+//
+// The plane-staging split-f16 instantiations, once: X(cout, r, MT, R, ZB, WAVES), cin % 16 == 0.  conv_split_plan (the shape
+// query) and conv3d_k3_f16x2_impl (the dispatch) both read this list; the few-channel form 3 -> 48 @ 24^3 stands in front of it.
+#define GLDM_CONV_SPLIT_LIST(X)                                                                 \
+  X(48, 24, 3, 24, 24, 8)                                                                        \
+  X(96, 12, 6, 12, 12, 4)                                                                        \
+  /* PVCNN2's power-of-two shapes (round 5; f32-MFMA kernels before) */                          \
+  X(32, 32, 2, 32, 32, 8)                                                                        \
+  X(64, 32, 4, 32, 32, 8)                                                                        \
+  X(32, 16, 2, 16, 16, 4)                                                                        \
+  X(64, 16, 4, 16, 16, 4)                                                                        \
+  X(128, 16, 8, 16, 16, 8)                                                                       \
+  X(64, 8, 4, 8, 8, 4)                                                                           \
+  X(128, 8, 8, 8, 8, 4)                                                                          \
+  X(256, 8, 16, 8, 8, 8)                                                                         \
+  X(128, 4, 8, 4, 4, 4)
+
+constexpr bool conv_split_fewch(int cin, int cout, int r) { return cin == 3 && cout == 48 && r == 24; }   // the first voxel conv
+
+// The shape part of conv3d_k3_f16x2_impl: a pure function of (cin, cout, r).  GLDM_OK or GLDM_ERR_UNSUPPORTED.
+static int conv_split_plan(int cin, int cout, int r) {
+  if (cin <= 0 || cout <= 0 || r <= 0) return GLDM_ERR_UNSUPPORTED;
+  if (conv_split_fewch(cin, cout, r)) return GLDM_OK;
+  if (cin % 16) return GLDM_ERR_UNSUPPORTED;   // the listed kernels: cout == 16 MT exactly, no row guards
+#define GLDM_CONV_CASE(C, RR, MT, R, ZB, WAVES) if (cout == C && r == RR) return GLDM_OK;
+  GLDM_CONV_SPLIT_LIST(GLDM_CONV_CASE)
+#undef GLDM_CONV_CASE
+  return GLDM_ERR_UNSUPPORTED;
+}
+
 static int conv3d_k3_f16x2_impl(const float *x, const float *in_coef, const float *w_split, const float *bias, int b, int cin,
                                  int cout, int r, float *y, float *partial, int out_cl, gldm_stream_t stream) {
   if (!x || !w_split || !bias || !y || !partial || b <= 0 || cin <= 0 || cout <= 0 || r <= 0) return GLDM_ERR_INVALID_ARG;
   if ((in_coef || out_cl) && cin % 16) return GLDM_ERR_UNSUPPORTED;   // both live in the plane-staging kernels
+  if (conv_split_plan(cin, cout, r) != GLDM_OK) return GLDM_ERR_UNSUPPORTED;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (cin == 3 && cout == 48 && r == 24) {   // the first voxel conv: K = 81 packed into three k-blocks
+  if (conv_split_fewch(cin, cout, r)) {   // K = 81 packed into three k-blocks
     constexpr int kZp = 26, kNvox = 36 * kZp;
     const size_t lds_bytes = (size_t)3 * (kNvox + ((kNvox & 31) == 0 ? 8 : 0)) * sizeof(float) + 64;   // + the waves' range words
     hipLaunchKernelGGL((conv3d_k3_fewch_sp_kernel<3, 24, 3, 8>), dim3(36, b), dim3(512), lds_bytes, s, x, w_split, bias, y, partial);
     return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
   }
-  if (cin % 16) return GLDM_ERR_UNSUPPORTED;   // the kernels below: cout == 16 MT exactly, no row guards
 #ifdef GLDM_DEBUG_KNOBS
   struct StampDump {  // diagnostic builds: GLDM_C3_STAMP=1 prints the phase clocks of one mid-grid workgroup per call
     hipStream_t s; int cin, cout, r, b;
@@ -1027,32 +1090,17 @@ static int conv3d_k3_f16x2_impl(const float *x, const float *in_coef, const floa
     }
   } dump{s, cin, cout, r, b};
 #endif
-  // (4 x 4 x 12 half bricks at 24^3 -- <3, 24, 12, 4>, two co-resident workgroups of 4 waves -- measured before round 6, on three
-  // bf16 planes (48 KiB a half brick), 2.12 ms against 2.05 for the full-z brick: the kernel's 220 registers allow two waves per SIMD either way, and the
-  // halves pay a z halo and the weight stream twice.  Kept as an instantiable option, not used.  Round 6, with three f16
-  // products instead of six bf16 ones: A/B of the whole encoder on one box 4.69 / 4.72 ms (full brick) against 4.63 / 4.84
-  // (halves) -- inside the run-to-run spread, still not used.)
-  // Round 6, two more forms of the 24^3 conv measured on one box against this one (whole shipped encoder, 256 clouds, A/B by an
-  // environment switch of the diagnostic build; phase stamps of a mid-grid workgroup: taps 31 k of a brick's 70 k cycles,
-  // store phases 2.4-5.2 k and barrier waits 2.9-3.8 k per 16-channel block, epilogue 5.4 k):
-  //  * block cb + 1 split and stored INSIDE block cb's tap loop, one staging round behind every second tap pair (the other
-  //    plane set is free there): the store phases shrank to 0.3-1.1 k, the taps grew 10.4 -> 12.2 k and the barrier waits
-  //    3.5 -> 6-7 k -- 4.49-4.50 ms against 4.48: nothing.  The staging VALU work does not hide under the other wave's MFMAs;
-  //  * <3, 24, 24, 4>: four waves x six n-tiles (half the weight-fragment deliveries per MFMA), two workgroups per CU, no
-  //    staging prefetch across the tap loop (64 registers): 18-24 spilled registers, 4.58 against 4.63 ms: 1 %, not kept.
-  if (cout == 48 && r == 24) return launch_conv_pl<3, 24, 24, 8>(x, w_split, bias, b, cin, cout, y, partial, in_coef, out_cl, s);
-  if (cout == 96 && r == 12) return launch_conv_pl<6, 12, 12, 4>(x, w_split, bias, b, cin, cout, y, partial, in_coef, out_cl, s);
-  // PVCNN2's power-of-two shapes (round 5; f32-MFMA kernels before): <MT, R, ZB, WAVES>
-  if (cout == 32 && r == 32) return launch_conv_pl<2, 32, 32, 8>(x, w_split, bias, b, cin, cout, y, partial, in_coef, out_cl, s);
-  if (cout == 64 && r == 32) return launch_conv_pl<4, 32, 32, 8>(x, w_split, bias, b, cin, cout, y, partial, in_coef, out_cl, s);
-  if (cout == 32 && r == 16) return launch_conv_pl<2, 16, 16, 4>(x, w_split, bias, b, cin, cout, y, partial, in_coef, out_cl, s);
-  if (cout == 64 && r == 16) return launch_conv_pl<4, 16, 16, 4>(x, w_split, bias, b, cin, cout, y, partial, in_coef, out_cl, s);
-  if (cout == 128 && r == 16) return launch_conv_pl<8, 16, 16, 8>(x, w_split, bias, b, cin, cout, y, partial, in_coef, out_cl, s);
-  if (cout == 64 && r == 8) return launch_conv_pl<4, 8, 8, 4>(x, w_split, bias, b, cin, cout, y, partial, in_coef, out_cl, s);
-  if (cout == 128 && r == 8) return launch_conv_pl<8, 8, 8, 4>(x, w_split, bias, b, cin, cout, y, partial, in_coef, out_cl, s);
-  if (cout == 256 && r == 8) return launch_conv_pl<16, 8, 8, 8>(x, w_split, bias, b, cin, cout, y, partial, in_coef, out_cl, s);
-  if (cout == 128 && r == 4) return launch_conv_pl<8, 4, 4, 4>(x, w_split, bias, b, cin, cout, y, partial, in_coef, out_cl, s);
+#define GLDM_CONV_CASE(C, RR, MT, R, ZB, WAVES) \
+  if (cout == C && r == RR) return launch_conv_pl<MT, R, ZB, WAVES>(x, w_split, bias, b, cin, cout, y, partial, in_coef, out_cl, s);
+  GLDM_CONV_SPLIT_LIST(GLDM_CONV_CASE)
+#undef GLDM_CONV_CASE
   return GLDM_ERR_UNSUPPORTED;
+}
+
+GLDM_API int gldm_conv3d_k3_supported(int kind, int cin, int cout, int r) {
+  if (kind == GLDM_CONV3D_F32) return conv_f32_plan(cin, cout, r);
+  if (kind == GLDM_CONV3D_F16X2) return conv_split_plan(cin, cout, r);
+  return GLDM_ERR_INVALID_ARG;
 }
 
 GLDM_API int gldm_conv3d_k3_f16x2(const float *x, const float *w_split, const float *bias, int b, int cin, int cout, int r,

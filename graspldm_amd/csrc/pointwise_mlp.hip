@@ -538,32 +538,36 @@ __global__ __launch_bounds__(512, 2) void pointwise_mlp_sp_kernel(const PwArgs a
 
 using gldm_dev::cu_count;
 
-int launch_pointwise(const float *x, const float *w0, const float *b0, int cin0, const float *w, const float *bias, int b,
-                     int cin_arg, int cout, int n, int relu, const float *head_w, const float *head_b, int hout, float *y,
-                     float *z, hipStream_t stream, bool split_f16 = false, const float *add = nullptr, long long add_bs = 0,
-                     long long add_rs = 0, long long add_cs = 0, const float *front_gain = nullptr, bool y_point_major = false) {
-  if (y_point_major && (!split_f16 || !y)) return GLDM_ERR_UNSUPPORTED;
-  if (add && !split_f16) return GLDM_ERR_UNSUPPORTED;
+// What launch_pointwise makes of a shape: K as the kernel walks it, the unit and tile widths, and the split form's LDS plan.
+struct PwPlan {
+  int cin;            // K: cin_arg, or (split form without a front layer) padded to whole 128-deep trips of the weight ring
+  int mu, nt;         // m-tiles per unit, 16-point n-tiles per tile
+  int dyn_first, ticket_off, x0_in_planes;
+  size_t lds_bytes;
+};
+
+// The shape part of launch_pointwise: a pure function of the sizes and the form flags (no pointer, no HIP call, no CU
+// count).  cin0 = 0: no front layer; hout = 0: no head.  GLDM_OK and the plan, or GLDM_ERR_UNSUPPORTED.
+int plan_pointwise(bool split_f16, int cin0, int cin_arg, int cout, int n, int hout, bool add, bool y_point_major, PwPlan &p) {
+  if (cin0 < 0 || cin_arg <= 0 || cout <= 0 || n <= 0 || hout < 0 || hout > 16) return GLDM_ERR_UNSUPPORTED;
+  if ((y_point_major || add) && !split_f16) return GLDM_ERR_UNSUPPORTED;
+  const bool front = cin0 > 0, head = hout > 0;
   // The split launch without a front layer takes any multiple of 8 input rows: K is padded to whole 128-deep trips of its
   // weight ring (the caller's fragments carry zero columns there: r1d_pack.mfma_a_fragments_f16x2 of the padded matrix)
-  const int cin_rows = cin_arg;
-  const int cin = (split_f16 && !w0 && cin_arg > 0 && (cin_arg & 7) == 0) ? (cin_arg + 127) & ~127 : cin_arg;
-  if (!x || !w || !bias || b <= 0 || cin <= 0 || cout <= 0 || n <= 0) return GLDM_ERR_INVALID_ARG;
-  if (!y && !head_w) return GLDM_ERR_INVALID_ARG;
-  if (head_w && (!z || hout <= 0 || hout > 16)) return GLDM_ERR_INVALID_ARG;
+  const int cin = (split_f16 && !front && (cin_arg & 7) == 0) ? (cin_arg + 127) & ~127 : cin_arg;
   // k-blocks in pairs, 32-point tiles; output rows: 2 m-tiles x 8 waves per round on the f32 kernel, units of two m-tiles on
   // the split one (fewer than eight units -- 64 .. 224 output rows -- leave waves without a unit idle)
   // the split launch hands out its output rows in units of two m-tiles, or of one where two would leave waves idle (fewer
   // than 256 rows, no front layer / head): then any multiple of 16 rows
   // (narrow inputs only: 32-point planes within half a CU's LDS, i.e. the 32-point tile form stays)
-  const int mu = (split_f16 && !w0 && !head_w && cout < 256 && ((size_t)cin * 32 * 2 * kSplit + 64) * 2 <= (size_t)160 * 1024) ? 1 : 2;
+  const int mu = (split_f16 && !front && !head && cout < 256 && ((size_t)cin * 32 * 2 * kSplit + 64) * 2 <= (size_t)160 * 1024) ? 1 : 2;
   if ((cin & 31) || (split_f16 ? (n & 15) : (n & 31)) || (split_f16 ? (cout & (16 * mu - 1)) : (cout & 255))) return GLDM_ERR_UNSUPPORTED;
-  if ((w0 || head_w) && (cout & 255)) return GLDM_ERR_UNSUPPORTED;   // front layer / head: whole rounds of units only
-  if (w0 && (!b0 || cin0 <= 0 || (cin0 & 31) || (cin & 255))) return GLDM_ERR_UNSUPPORTED;
-  size_t lds_bytes = ((size_t)cin * 32 + 8 * 16 * 32 + (w0 ? (size_t)cin0 * 32 : 0)) * sizeof(float);
+  if ((front || head) && (cout & 255)) return GLDM_ERR_UNSUPPORTED;   // front layer / head: whole rounds of units only
+  if (front && ((cin0 & 31) || (cin & 255))) return GLDM_ERR_UNSUPPORTED;
+  size_t lds_bytes = ((size_t)cin * 32 + 8 * 16 * 32 + (size_t)cin0 * 32) * sizeof(float);
   if (split_f16) {  // `w` and `w0` hold split-f16 fragments: planes of the tile + the front layer's f32 tile
     if (cin & 127) return GLDM_ERR_UNSUPPORTED;  // the A ring walks four 32-deep blocks per trip
-    if (w0 && cin0 > 96) return GLDM_ERR_UNSUPPORTED;  // the front layer keeps its whole split tile in registers (72)
+    if (cin0 > 96) return GLDM_ERR_UNSUPPORTED;  // the front layer keeps its whole split tile in registers (72)
   }
   int dyn_first = 0, ticket_off = 0, nt = 2, x0_in_planes = 0;
   if (split_f16) {
@@ -575,18 +579,18 @@ int launch_pointwise(const float *x, const float *w0, const float *b0, int cin0,
     const int units = cout / (16 * mu);
     auto plan = [&](int ncol, bool x0_under, size_t &planes, size_t &region, int &first) {
       planes = (size_t)cin * ncol * 2 * kSplit;   // bytes: cin x ncol x kSplit f16
-      region = (w0 && !x0_under) ? (size_t)cin0 * ncol * sizeof(float) : 0;
+      region = (front && !x0_under) ? (size_t)cin0 * ncol * sizeof(float) : 0;
       if (planes + region > cap) return false;
       if (x0_under && (size_t)cin0 * ncol * sizeof(float) > planes) return false;
       int drawn = units > 8 ? units - 8 : 0;
-      if (head_w) {
+      if (head) {
         const size_t slot = (size_t)hout * ncol * sizeof(float);
         const int room = (int)((cap - planes) / slot);
         if (drawn > room) drawn = room;
         if (planes < (size_t)8 * 16 * ncol * sizeof(float)) drawn = 0;   // z partials need the planes' space
       }
       first = (units - drawn + 7) & ~7;   // whole rounds are dealt
-      if (head_w && (size_t)(units - first) * hout * ncol * sizeof(float) > region)
+      if (head && (size_t)(units - first) * hout * ncol * sizeof(float) > region)
         region = (size_t)(units - first) * hout * ncol * sizeof(float);
       return planes + region <= cap;
     };
@@ -595,24 +599,42 @@ int launch_pointwise(const float *x, const float *w0, const float *b0, int cin0,
     if ((planes + region + 64) * 2 > (size_t)160 * 1024 && n >= 48) {
       size_t p3 = 0, r3 = 0;
       int f3 = 0;
-      if (plan(48, w0 != nullptr, p3, r3, f3)) {
-        nt = 3; planes = p3; region = r3; dyn_first = f3; x0_in_planes = w0 ? 1 : 0;
+      if (plan(48, front, p3, r3, f3)) {
+        nt = 3; planes = p3; region = r3; dyn_first = f3; x0_in_planes = front ? 1 : 0;
       }
     }
     ticket_off = (int)((planes + region) / sizeof(float));
     lds_bytes = planes + region + 64;   // ticket (16 B) + the eight range words
   }
   if (lds_bytes > 160 * 1024) return GLDM_ERR_UNSUPPORTED;
+  p = PwPlan{cin, mu, nt, dyn_first, ticket_off, x0_in_planes, lds_bytes};
+  return GLDM_OK;
+}
+
+int launch_pointwise(const float *x, const float *w0, const float *b0, int cin0, const float *w, const float *bias, int b,
+                     int cin_arg, int cout, int n, int relu, const float *head_w, const float *head_b, int hout, float *y,
+                     float *z, hipStream_t stream, bool split_f16 = false, const float *add = nullptr, long long add_bs = 0,
+                     long long add_rs = 0, long long add_cs = 0, const float *front_gain = nullptr, bool y_point_major = false) {
+  if (y_point_major && !y) return GLDM_ERR_UNSUPPORTED;
+  if (!x || !w || !bias || b <= 0 || cin_arg <= 0 || cout <= 0 || n <= 0) return GLDM_ERR_INVALID_ARG;
+  if (!y && !head_w) return GLDM_ERR_INVALID_ARG;
+  if (head_w && (!z || hout <= 0 || hout > 16)) return GLDM_ERR_INVALID_ARG;
+  if (w0 && (!b0 || cin0 <= 0)) return GLDM_ERR_UNSUPPORTED;
+  PwPlan p{};
+  const int rc = plan_pointwise(split_f16, w0 ? cin0 : 0, cin_arg, cout, n, head_w ? hout : 0, add != nullptr, y_point_major, p);
+  if (rc != GLDM_OK) return rc;
+  const int cin_rows = cin_arg, cin = p.cin, mu = p.mu, nt = p.nt;
+  const size_t lds_bytes = p.lds_bytes;
   PwArgs a{};
   a.x = x; a.w = w; a.bias = bias; a.head_w = head_w; a.head_b = head_b; a.y = y; a.z = z;
   a.cin = cin; a.cout = cout; a.n = n; a.relu = relu; a.hout = hout;
   a.w0 = w0; a.bias0 = b0; a.cin0 = cin0;
-  a.dyn_first = dyn_first; a.ticket_off = ticket_off; a.x0_in_planes = x0_in_planes;
+  a.dyn_first = p.dyn_first; a.ticket_off = p.ticket_off; a.x0_in_planes = p.x0_in_planes;
   a.add = add; a.add_bs = add_bs; a.add_rs = add_rs; a.add_cs = add_cs;
   // range scales: a lone layer measures its input tile; with a layer in front the caller's gain bounds its output
   a.y_point_major = y_point_major ? 1 : 0;
   a.cin_rows = cin_rows;
-  a.rng_off = ticket_off + 4;
+  a.rng_off = p.ticket_off + 4;
   a.ranged = split_f16 && (!w0 || front_gain);
   if (w0 && front_gain) {
     a.gain0_r = front_gain[0]; a.gain0_b = front_gain[1];
@@ -650,6 +672,12 @@ int launch_pointwise(const float *x, const float *w0, const float *b0, int cin0,
   return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
 }
 }  // namespace
+
+GLDM_API int gldm_pointwise_mlp_supported(int split_f16, int cin0, int cin, int cout, int n, int hout, int with_addend,
+                                          int point_major) {
+  PwPlan p{};
+  return plan_pointwise(split_f16 != 0, cin0, cin, cout, n, hout, with_addend != 0, point_major != 0, p);
+}
 
 GLDM_API int gldm_pointwise_mlp(const float *x, const float *w_packed, const float *bias, int b, int cin, int cout,
                                 int n, int relu, const float *head_w_packed, const float *head_bias, int hout,

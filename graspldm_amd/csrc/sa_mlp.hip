@@ -736,27 +736,17 @@ __global__ __launch_bounds__(512, (PRE && QUADS <= 4) ? 4 : 2) void sa_mlp3_kern
 
 using gldm_dev::cu_count;
 
-// pre != nullptr: the first layer hoisted (sa_mlp3_kernel<.., PRE>): `features` unused, c = 0, cin_pad[0] = rows of pre
-int launch_sa3(const float *points, const float *centers, const float *features, const float *pre, int wa_off, int pre_bcast,
-               const int32_t *idx, const float *weights, int b, int c, int n, int m, int u,
-               int n_layers, const int32_t *cin_pad, const int32_t *cout, const int32_t *w3_off,
-               const int32_t *b_off, const float *range_gain, float *out, gldm_stream_t stream) {
-  if (!points || !centers || !idx || !weights || !out || !cin_pad || !cout || !w3_off || !b_off || b <= 0 || c < 0 ||
-      n <= 0 || m <= 0 || u <= 0)
-    return GLDM_ERR_INVALID_ARG;
-  if (c > 0 && !features) return GLDM_ERR_INVALID_ARG;
-  if (pre && (c != 0 || wa_off < 0 || (wa_off & 3))) return GLDM_ERR_INVALID_ARG;
+// What launch_sa3 makes of a layer plan: the two plane regions and the bytes of one tile.
+struct Sa3Plan {
+  int blocks_a, blocks_b;   // 32-row plane blocks of regions A (the gathered rows, odd hidden layers) and B (even hidden layers)
+  size_t tile_bytes;        // one tile's two plane regions
+  size_t behind_bytes;      // behind the planes: the eight range words and (single-tile kernels) the staged output rows of a run
+};
+
+// The shape part of launch_sa3: a pure function of the sizes and the host tables (no device pointer, no HIP call, no CU
+// count).  pre: the hoisted form (c = 0, cin_pad[0] = rows of pre).  GLDM_OK and the plan, or the launch's status.
+int plan_sa3(bool pre, int c, int u, int n_layers, const int32_t *cin_pad, const int32_t *cout, Sa3Plan &p) {
   if (n_layers < 1 || n_layers > 4 || !(u == 16 || u == 32 || u == 64)) return GLDM_ERR_UNSUPPORTED;
-  SaArgs a{};
-  a.points = points; a.centers = centers; a.feat = c > 0 ? features : nullptr; a.idx = idx; a.weights = weights;
-  a.out = out; a.c = c; a.n = n; a.m = m; a.u = u; a.n_layers = n_layers;
-  a.ranged = range_gain != nullptr;
-  a.pre = pre; a.c1 = pre ? cin_pad[0] : 0; a.wa_off = wa_off; a.pre_bcast = pre_bcast ? 1 : 0;
-  for (int l = 0; l < n_layers && range_gain; ++l) {
-    a.gain_r[l] = range_gain[2 * l];
-    a.gain_b[l] = range_gain[2 * l + 1];
-    if (!(a.gain_r[l] >= 0.f) || !(a.gain_b[l] >= 0.f)) return GLDM_ERR_INVALID_ARG;
-  }
   int blocks_a = 0, blocks_b = 0;
   for (int l = 0; l < n_layers; ++l) {
     const int kb = cin_pad[l] >> 5, mt = cout[l] >> 4;
@@ -767,15 +757,44 @@ int launch_sa3(const float *points, const float *centers, const float *features,
       int &blk = (l & 1) ? blocks_a : blocks_b;
       blk = blk > (cout[l] >> 5) ? blk : (cout[l] >> 5);
     }
-    a.cin_pad[l] = cin_pad[l]; a.cout[l] = cout[l]; a.w_off[l] = w3_off[l]; a.b_off[l] = b_off[l];
   }
   if (!pre && (cin_pad[0] < 3 + c || cin_pad[0] > 32 * kSa3Quads)) return GLDM_ERR_UNSUPPORTED;
   if (pre && cin_pad[0] > 256) return GLDM_ERR_UNSUPPORTED;
   blocks_a = blocks_a > (cin_pad[0] >> 5) ? blocks_a : (cin_pad[0] >> 5);
   const size_t tile_bytes = (size_t)(blocks_a + blocks_b) * kSaBlockFloats * sizeof(float);
-  // behind the planes: the eight range words and (single-tile kernels) the staged output rows of a run
-  const size_t kRngBytes = 64 + (size_t)cout[n_layers - 1] * kSaRun * sizeof(float);
-  if (tile_bytes + kRngBytes > 160 * 1024) return GLDM_ERR_UNSUPPORTED;
+  const size_t behind_bytes = 64 + (size_t)cout[n_layers - 1] * kSaRun * sizeof(float);
+  if (tile_bytes + behind_bytes > 160 * 1024) return GLDM_ERR_UNSUPPORTED;
+  p = Sa3Plan{blocks_a, blocks_b, tile_bytes, behind_bytes};
+  return GLDM_OK;
+}
+
+// pre != nullptr: the first layer hoisted (sa_mlp3_kernel<.., PRE>): `features` unused, c = 0, cin_pad[0] = rows of pre
+int launch_sa3(const float *points, const float *centers, const float *features, const float *pre, int wa_off, int pre_bcast,
+               const int32_t *idx, const float *weights, int b, int c, int n, int m, int u,
+               int n_layers, const int32_t *cin_pad, const int32_t *cout, const int32_t *w3_off,
+               const int32_t *b_off, const float *range_gain, float *out, gldm_stream_t stream) {
+  if (!points || !centers || !idx || !weights || !out || !cin_pad || !cout || !w3_off || !b_off || b <= 0 || c < 0 ||
+      n <= 0 || m <= 0 || u <= 0)
+    return GLDM_ERR_INVALID_ARG;
+  if (c > 0 && !features) return GLDM_ERR_INVALID_ARG;
+  if (pre && (c != 0 || wa_off < 0 || (wa_off & 3))) return GLDM_ERR_INVALID_ARG;
+  Sa3Plan p{};
+  const int rc = plan_sa3(pre != nullptr, c, u, n_layers, cin_pad, cout, p);
+  if (rc != GLDM_OK) return rc;
+  SaArgs a{};
+  a.points = points; a.centers = centers; a.feat = c > 0 ? features : nullptr; a.idx = idx; a.weights = weights;
+  a.out = out; a.c = c; a.n = n; a.m = m; a.u = u; a.n_layers = n_layers;
+  a.ranged = range_gain != nullptr;
+  a.pre = pre; a.c1 = pre ? cin_pad[0] : 0; a.wa_off = wa_off; a.pre_bcast = pre_bcast ? 1 : 0;
+  for (int l = 0; l < n_layers; ++l) {
+    a.cin_pad[l] = cin_pad[l]; a.cout[l] = cout[l]; a.w_off[l] = w3_off[l]; a.b_off[l] = b_off[l];
+    if (!range_gain) continue;
+    a.gain_r[l] = range_gain[2 * l];
+    a.gain_b[l] = range_gain[2 * l + 1];
+    if (!(a.gain_r[l] >= 0.f) || !(a.gain_b[l] >= 0.f)) return GLDM_ERR_INVALID_ARG;
+  }
+  const int blocks_a = p.blocks_a, blocks_b = p.blocks_b;
+  const size_t tile_bytes = p.tile_bytes, kRngBytes = p.behind_bytes;
   const int cpt = 64 / u, tpc = (m + cpt - 1) / cpt, total = tpc * b;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   // narrow nets (32-row inputs, every K in {32, 64, 128}): the multi-tile kernel -- the layer's weights once per
@@ -831,6 +850,62 @@ GLDM_API int gldm_sa_mlp_forward_f16x2_pre(const float *points, const float *cen
                     b_off, range_gain, out, stream);
 }
 
+namespace {
+// What gldm_sa_mlp_forward makes of a layer plan: the 128-column kernel where it fits, else the 64-column one.
+struct SaF32Plan {
+  bool wide;          // 128-column tiles (sa_mlp2_kernel)
+  int rows_a;         // its region A
+  size_t lds_bytes;   // its two regions
+};
+
+// The shape part of gldm_sa_mlp_forward: a pure function of the sizes and the host tables, as plan_sa3.
+int plan_sa_f32(int c, int u, int n_layers, const int32_t *cin_pad, const int32_t *cout, SaF32Plan &p) {
+  if (n_layers < 1 || n_layers > 4) return GLDM_ERR_UNSUPPORTED;
+  if (u > 64 || (64 % u) != 0) return GLDM_ERR_UNSUPPORTED;
+  for (int l = 0; l < n_layers; ++l) {
+    const int mt = (cout[l] + 15) >> 4;
+    if (cin_pad[l] <= 0 || (cin_pad[l] & 15) || cin_pad[l] > kMaxC || cout[l] > kMaxC ||
+        !(mt == 1 || mt == 2 || mt == 4 || mt == 8 || mt == 12 || mt == 16) || (cout[l] & 15))
+      return GLDM_ERR_UNSUPPORTED;
+    if (l > 0 && cin_pad[l] != cout[l - 1]) return GLDM_ERR_INVALID_ARG;
+  }
+  if (cin_pad[0] < 3 + c) return GLDM_ERR_INVALID_ARG;
+  // 128-column tiles when the layer plan fits: widths 32 / 64 / 128 / 256 k, U a multiple of 16, both regions in LDS
+  bool ok = (u == 16 || u == 32 || u == 64) && c <= 4 * kSaFly;
+  int rows_a = cin_pad[0], rows_b = 0;
+  for (int l = 0; l < n_layers && ok; ++l) {
+    const int mt = cout[l] >> 4;
+    ok = (mt == 2 || mt == 4 || (mt >= 8 && (mt & 7) == 0)) && (cin_pad[l] & 31) == 0;
+    if (l + 1 < n_layers) {  // stored outputs: even layers -> B, odd layers -> A
+      if (l & 1) rows_a = rows_a > cout[l] ? rows_a : cout[l];
+      else rows_b = rows_b > cout[l] ? rows_b : cout[l];
+    } else if (ok) {  // the max runs on one wave's n-tiles: a centre's U / 16 tiles must not straddle two waves
+      const int nt = mt >= 8 ? 8 : (mt == 4 ? 4 : 2);
+      ok = (u >> 4) <= nt;
+    }
+  }
+  const size_t lds2 = (size_t)(rows_a + rows_b) * 128 * sizeof(float);
+  p = SaF32Plan{ok && lds2 <= 160 * 1024, rows_a, lds2};
+  return GLDM_OK;
+}
+}  // namespace
+
+GLDM_API int gldm_sa_mlp_supported(int c, int u, int n_layers, const int32_t *cin_pad, const int32_t *cout) {
+  if (!cin_pad || !cout || c < 0 || u <= 0) return GLDM_ERR_INVALID_ARG;
+  SaF32Plan p{};
+  return plan_sa_f32(c, u, n_layers, cin_pad, cout, p);
+}
+
+GLDM_API long long gldm_sa_mlp_f16x2_lds_bytes(int pre, int c, int u, int n_layers, const int32_t *cin_pad, const int32_t *cout,
+                                                long long *plane_bytes) {
+  if (!cin_pad || !cout || c < 0 || u <= 0 || (pre && c != 0)) return GLDM_ERR_INVALID_ARG;
+  Sa3Plan p{};
+  const int rc = plan_sa3(pre != 0, c, u, n_layers, cin_pad, cout, p);
+  if (rc != GLDM_OK) return rc;
+  if (plane_bytes) *plane_bytes = (long long)p.tile_bytes;
+  return (long long)(p.tile_bytes + p.behind_bytes);
+}
+
 GLDM_API int gldm_sa_mlp_forward(const float *points, const float *centers, const float *features,
                                  const int32_t *idx, const float *weights, int b, int c, int n, int m, int u,
                                  int n_layers, const int32_t *cin_pad, const int32_t *cout, const int32_t *w_off,
@@ -839,47 +914,26 @@ GLDM_API int gldm_sa_mlp_forward(const float *points, const float *centers, cons
       n <= 0 || m <= 0 || u <= 0)
     return GLDM_ERR_INVALID_ARG;
   if (c > 0 && !features) return GLDM_ERR_INVALID_ARG;
-  if (n_layers < 1 || n_layers > 4) return GLDM_ERR_UNSUPPORTED;
-  if (u > 64 || (64 % u) != 0) return GLDM_ERR_UNSUPPORTED;
+  SaF32Plan p{};
+  const int rc = plan_sa_f32(c, u, n_layers, cin_pad, cout, p);
+  if (rc != GLDM_OK) return rc;
   SaArgs a{};
   a.points = points; a.centers = centers; a.feat = c > 0 ? features : nullptr; a.idx = idx; a.weights = weights;
   a.out = out; a.c = c; a.n = n; a.m = m; a.u = u; a.n_layers = n_layers;
   for (int l = 0; l < n_layers; ++l) {
-    const int mt = (cout[l] + 15) >> 4;
-    if (cin_pad[l] <= 0 || (cin_pad[l] & 15) || cin_pad[l] > kMaxC || cout[l] > kMaxC ||
-        !(mt == 1 || mt == 2 || mt == 4 || mt == 8 || mt == 12 || mt == 16) || (cout[l] & 15))
-      return GLDM_ERR_UNSUPPORTED;
-    if (l > 0 && cin_pad[l] != cout[l - 1]) return GLDM_ERR_INVALID_ARG;
     a.cin_pad[l] = cin_pad[l]; a.cout[l] = cout[l]; a.w_off[l] = w_off[l]; a.b_off[l] = b_off[l];
   }
-  if (cin_pad[0] < 3 + c) return GLDM_ERR_INVALID_ARG;
-  {  // 128-column tiles when the layer plan fits: widths 32 / 64 / 128 / 256 k, U a multiple of 16, both regions in LDS
-    bool ok = (u == 16 || u == 32 || u == 64) && n_layers >= 1 && c <= 4 * kSaFly;
-    int rows_a = cin_pad[0], rows_b = 0;
-    for (int l = 0; l < n_layers && ok; ++l) {
-      const int mt = cout[l] >> 4;
-      ok = (mt == 2 || mt == 4 || (mt >= 8 && (mt & 7) == 0)) && (cin_pad[l] & 31) == 0;
-      if (l + 1 < n_layers) {  // stored outputs: even layers -> B, odd layers -> A
-        if (l & 1) rows_a = rows_a > cout[l] ? rows_a : cout[l];
-        else rows_b = rows_b > cout[l] ? rows_b : cout[l];
-      } else if (ok) {  // the max runs on one wave's n-tiles: a centre's U / 16 tiles must not straddle two waves
-        const int nt = mt >= 8 ? 8 : (mt == 4 ? 4 : 2);
-        ok = (u >> 4) <= nt;
-      }
-    }
-    const size_t lds2 = (size_t)(rows_a + rows_b) * 128 * sizeof(float);
 #ifdef GLDM_DEBUG_KNOBS
-    static const bool tile64 = getenv("GLDM_SA_TILE64") != nullptr;  // diagnostic builds: force the 64-column kernel
+  static const bool tile64 = getenv("GLDM_SA_TILE64") != nullptr;  // diagnostic builds: force the 64-column kernel
 #else
-    constexpr bool tile64 = false;  // the shipped library reads no environment
+  constexpr bool tile64 = false;  // the shipped library reads no environment
 #endif
-    if (ok && lds2 <= 160 * 1024 && !tile64) {
-      const int cpt2 = 128 / u, tpc = (m + cpt2 - 1) / cpt2, total = tpc * b;
-      const int grid = total < cu_count() ? total : cu_count();
-      gldm_dev::launch_dynamic_lds<sa_mlp2_kernel>(dim3(grid), dim3(512), 160 * 1024, lds2, reinterpret_cast<hipStream_t>(stream),
-                                                   a, rows_a, tpc, total);
-      return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
-    }
+  if (p.wide && !tile64) {
+    const int cpt2 = 128 / u, tpc = (m + cpt2 - 1) / cpt2, total = tpc * b;
+    const int grid = total < cu_count() ? total : cu_count();
+    gldm_dev::launch_dynamic_lds<sa_mlp2_kernel>(dim3(grid), dim3(512), 160 * 1024, p.lds_bytes, reinterpret_cast<hipStream_t>(stream),
+                                                 a, p.rows_a, tpc, total);
+    return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
   }
   const size_t lds_bytes = (size_t)(Geo<64>::kBufH + kMaxC * 64) * sizeof(float);
   const int cpt = 64 / u;

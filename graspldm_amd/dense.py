@@ -7,12 +7,10 @@ longer sets MIOPEN_FIND_MODE.  Voxel convs have no library path either (csrc/con
 for shapes without an MFMA instantiation).  Never a CPU path: CPU tensors are rejected like everywhere else in this package.
 """
 import ctypes
+from functools import lru_cache
 from typing import NamedTuple, Optional
 
 import torch
-
-LDS_BYTES = 160 * 1024   # a CU's LDS: the dynamic-LDS limit every launcher plans against
-
 
 def range_gain(w2d, bias):
     """(largest row sum of |W|, largest |bias|) of a folded layer as a host float[2]: |W x + b| <= gain[0] max|x| + gain[1].
@@ -67,28 +65,41 @@ def pack_head(wh):
     return mfma_a_fragments(w)
 
 
-SPLIT_PAD_MIN_CIN = 32   # narrowest input the split launch takes with K padded to 128 (below: the lane-per-point kernel)
+# Which shapes a launch takes is the library's answer (gldm_pointwise_mlp_supported: launch_pointwise's own planner,
+# csrc/pointwise_mlp.hip).  What stands next to that answer in a predicate below is routing policy, each term a named constant.
+SPLIT_PAD_MIN_CIN = 32    # policy: narrowest input sent to the split launch with K padded to 128 (below: the lane-per-point kernel; DESIGN.md, kernel table)
+SPLIT_TILE_POINTS = 32    # policy: the routes send whole 32-point tiles, though the split launch takes n % 16 (no 16-point tail has been run or timed)
+SPLIT_MIN_COUT = 64       # policy: fewer output rows stay on pointwise_small / pointwise_any ("below the split launch's 64 rows")
+SPLIT_MAX_K = 768         # policy: K after padding, the bound of the former three-plane plan (48 floats per channel in 160 KiB); the launch takes 1152 -- not lifted unmeasured
+_ANY_COUT, _ANY_N = 256, 32   # a channel-only question (a packer's, no tensor yet) is asked at one round of units and one tile
 
 
-def _tiles_ok(x):
-    """x is [B, C, N], contiguous, N in whole 32-point tiles.  None: the channel half of a predicate alone (what a packer asks)."""
-    return x is None or (x.ndim == 3 and x.is_contiguous() and x.shape[-1] % 32 == 0)
+def _points(x):
+    """N of x [B, C, N] contiguous, else None; x = None (the channel half of a predicate alone: what a packer asks): one tile."""
+    if x is None:
+        return _ANY_N
+    return x.shape[-1] if x.ndim == 3 and x.is_contiguous() else None
 
 
-def _f32_units(cin, cout):
-    """Units of the f32 launch: K in pairs of 16-deep blocks, output rows in rounds of two m-tiles on eight waves."""
-    return cin % 32 == 0 and cout % 256 == 0
+@lru_cache(maxsize=4096)
+def _takes(split, cin0, cin, cout, n):
+    """launch_pointwise's own answer for one form and shape, without head, addend or point-major output; cached per shape
+    (the predicates are asked on every forward)."""
+    from . import _lib as L
+    return n is not None and L.lib().gldm_pointwise_mlp_supported(int(split), int(cin0), int(cin), int(cout), int(n), 0, 0, 0) == 0
+
+
+def _split_policy(cin, cin0):
+    from .numerics import split_enabled
+    return split_enabled() and (cin0 > 0 or cin >= SPLIT_PAD_MIN_CIN) and (cin + 127) // 128 * 128 <= SPLIT_MAX_K
 
 
 def split_supported(cin, cin0=0):
-    """Channel rules of launch_pointwise's split-f16 form (csrc/pointwise_mlp.hip; gldm_pointwise_mlp*_f16x2): A ring of
-    four 32-deep blocks, the tile as planes (48 floats per channel) + the front layer's f32 tile (split once per wave into
-    registers: cin0 <= 96).  Without a front layer any multiple of 8 input rows from 32 up: K is zero-padded to whole
-    trips of the ring (split_fragments)."""
-    from .numerics import split_enabled
-    kpad = (cin + 127) // 128 * 128
-    ok_k = cin % 128 == 0 or (cin0 == 0 and cin % 8 == 0 and cin >= SPLIT_PAD_MIN_CIN)
-    return split_enabled() and ok_k and cin0 % 32 == 0 and cin0 <= 96 and 4 * (48 * kpad + 32 * cin0) + 16 <= LDS_BYTES
+    """Channel half of launch_pointwise's split-f16 form (csrc/pointwise_mlp.hip; gldm_pointwise_mlp*_f16x2), cin0 > 0: with
+    a front layer of cin0 input rows.  The library's answer at one round of units and one tile, and the routing policy: K
+    within SPLIT_MAX_K (the launch keeps the tile as two f16 planes, 128 bytes per channel, and takes more), inputs from
+    SPLIT_PAD_MIN_CIN rows up (without a front layer K is zero-padded to whole trips of the weight ring: split_fragments)."""
+    return _split_policy(cin, cin0) and _takes(True, cin0, cin, _ANY_COUT, _ANY_N)
 
 
 def split_fragments(w2d):
@@ -103,24 +114,24 @@ def split_fragments(w2d):
 
 
 def fused_mlp_supported(x, cin, cout):
-    """launch_pointwise's f32 form, one layer (csrc/pointwise_mlp.hip; gldm_pointwise_mlp)."""
-    return _tiles_ok(x) and _f32_units(cin, cout) and 4 * (32 * cin + 4096) <= LDS_BYTES
+    """launch_pointwise's f32 form, one layer (csrc/pointwise_mlp.hip; gldm_pointwise_mlp): the library's answer."""
+    return _takes(False, 0, cin, cout, _points(x))
 
 
 def split_mlp_supported(x, cin, cout):
     """launch_pointwise's split-f16 form without a front layer or head (csrc/pointwise_mlp.hip; gldm_pointwise_mlp_f16x2
-    and its _pm / _add forms): output rows in units of two m-tiles, or of one where two would leave waves idle (fewer than
-    256 rows) and the 32-point planes fit half a CU's LDS.  Fewer than 256 rows still run several times the any-shape
-    kernel's rate: the 128-row feature-propagation layers of PointNet++ / PVCNN2."""
-    kpad = (cin + 127) // 128 * 128
-    one_tile_units = cout < 256 and (kpad * 128 + 64) * 2 <= LDS_BYTES
-    return _tiles_ok(x) and cout >= 64 and cout % (16 if one_tile_units else 32) == 0 and split_supported(cin)
+    and its _pm / _add forms): the library's answer (output rows in units of two m-tiles, or of one where two would leave
+    waves idle) and the routing policy: split_supported's, whole SPLIT_TILE_POINTS tiles, SPLIT_MIN_COUT rows or more.
+    Fewer than 256 rows still run several times the any-shape kernel's rate: the 128-row feature-propagation layers of
+    PointNet++ / PVCNN2."""
+    n = _points(x)
+    return (n is not None and n % SPLIT_TILE_POINTS == 0 and cout >= SPLIT_MIN_COUT and _split_policy(cin, 0)
+            and _takes(True, 0, cin, cout, n))
 
 
 def fused_mlp2_supported(x, cin0, cin, cout):
     """launch_pointwise's f32 form with a front layer (csrc/pointwise_mlp.hip; gldm_pointwise_mlp2): cin0 -> cin -> cout."""
-    return (_tiles_ok(x) and _f32_units(cin0, cin) and _f32_units(cin, cout)
-            and 4 * (32 * (cin + cin0) + 4096) <= LDS_BYTES)
+    return cin0 > 0 and _takes(False, cin0, cin, cout, _points(x))
 
 
 def pointwise_mlp(x, w_packed, bias, cout, relu, head=None, keep_y=True, front=None, split=False):
@@ -222,7 +233,7 @@ def _pack_folded(conv, bn, device):
     wp = ws = None
     ws_k = 0
     try:   # a folded weight beyond the f16 range (|w| >= 65504: a huge BatchNorm gain) keeps the f32-pipe kernels
-        if _f32_units(cin, cout):
+        if fused_mlp_supported(None, cin, cout):
             wp = mfma_a_fragments(w.cpu()).to(device)
             # split fragments, K as it is: main layers of the split launch (cin % 128 == 0) and its narrow front layers
             if split_supported(cin) or cin <= 128:

@@ -2,6 +2,7 @@
 fold eval-mode BatchNorm into each 1x1 conv of a SharedMLP (shared_mlp.py:6-35) and lay the
 weights out in MFMA A-fragment order: f32 (v_mfma_f32_16x16x4_f32, K padded to a multiple of 16) and split-f16."""
 import ctypes
+from functools import lru_cache
 from typing import NamedTuple, Optional
 
 import torch
@@ -11,77 +12,87 @@ from . import dense
 from ._cache import cached
 from .r1d_pack import _Buf, mfma_a_fragments, mfma_a_fragments_f16x2
 
-_OK_MTILES = (1, 2, 4, 8, 12, 16)
 # modules without features (first layer = three coordinate products + bias): on the VALU of the gather threads (the hoisted
 # form with a broadcast row) instead of a K = 32 block of the matrix pipe -- set by measurement, see DESIGN.md
 # SSG-SA1 (3 -> 64 -> 64 -> 128, 512 centres x 64 at 256 clouds): hoisted in the single-tile kernel 1.81 ms, first layer on the
 # matrix pipe in the multi-tile kernel 1.47 ms, hoisted in the multi-tile kernel (two tiles per pass) 1.22 ms
 PRE_WITHOUT_FEATURES = True
-_SA_RUN = 8   # centres per staged run (csrc/sa_mlp.hip: kSaRun)
+
+# Which layer plans a launch takes is the library's answer (gldm_sa_mlp_supported, gldm_sa_mlp_f16x2_lds_bytes: the planners
+# of gldm_sa_mlp_forward and launch_sa3, csrc/sa_mlp.hip), cached per shape.  What stands next to it in a predicate below is
+# routing policy, each term a named constant; numerics.split_enabled() stays outside the cache.
+PLANNED_PLANES = (3, 2)        # policy: split_plan_ok counts the plane regions as the three bf16 planes of ABI 5-8 (12288 bytes per 32-row block) where launch_sa3 keeps two f16 ones (8192); DESIGN.md, PointNet2MSG -- not lifted unmeasured
+PLANNED_LDS_BYTES = 160 * 1024       # policy: the LDS that figure was planned against
+MSG_MAX_POOLED_ROWS = 256            # policy: pooled rows wider than 256 -- no fused kernel has run them (PointNet2MSG)
+MSG_MAX_LAYERS = 4                   # policy: a branch as deep as every route takes it whole (the hoisted form alone would take a fifth layer; no f32 launch stands behind it)
+_F32_WIDTHS = (16, 32, 64, 128, 192, 256)   # packing: hidden widths the f32 tables pad to (_f32_width)
+_PLANE_WIDTHS = (32, 64, 128, 256)          # packing: hidden widths the split tables pad to (_plane_width)
+
+
+def _pad32(c):
+    return (c + 31) // 32 * 32
+
+
+@lru_cache(maxsize=None)
+def _f32_takes(c, u, cin_pad, cout):
+    """gldm_sa_mlp_forward's own answer for a layer plan (tuples as its tables hold them, c feature rows)."""
+    arr = ctypes.c_int32 * len(cout)
+    return L.lib().gldm_sa_mlp_supported(c, u, len(cout), arr(*cin_pad), arr(*cout)) == 0
+
+
+@lru_cache(maxsize=None)
+def _sa3_bytes(pre, u, cin_pad, cout):
+    """launch_sa3's own answer for a layer plan: (dynamic LDS of its single-tile launch, the plane regions' share), or None."""
+    arr = ctypes.c_int32 * len(cout)
+    planes = ctypes.c_longlong(0)
+    total = L.lib().gldm_sa_mlp_f16x2_lds_bytes(int(pre), 0, u, len(cout), arr(*cin_pad), arr(*cout), ctypes.byref(planes))
+    return None if total < 0 else (int(total), int(planes.value))
+
+
+def _tables(kpad0, couts):
+    """(cin_pad, cout) as a layer table holds them: every later layer reads the rows of the one in front."""
+    couts = tuple(int(c) for c in couts)
+    return (int(kpad0),) + couts[:-1], couts
 
 
 def fusable(shared_mlp, num_neighbors):
+    """gldm_sa_mlp_forward takes the module's widths as they are (csrc/sa_mlp.hip; the library's answer)."""
     layers = shared_mlp.layers
-    n = len(layers) // 3
-    if n < 1 or n > 4 or 64 % int(num_neighbors) != 0:
-        return False
-    for i in range(n):
-        cout = layers[3 * i].weight.shape[0]
-        if cout % 16 or cout > 256 or (cout // 16) not in _OK_MTILES:
-            return False
-    return (layers[0].weight.shape[1] + 31) // 32 * 32 <= 256
-
-
-_PLANE_WIDTHS = (32, 64, 128, 256)   # hidden widths launch_sa3 takes (m-tile counts 2 / 4 / 8 / 16)
-_SA_BLOCK_BYTES = 2 * 1024 * 4       # one 32-row block of a 64-column tile's hi + lo planes (csrc/mfma_core.h: PG<4>::kBlockFloats)
-_SA_BLOCK_BYTES_PLANNED = 3072 * 4   # the figure split_plan_ok has always planned with (three planes): never the more permissive
-
-
-def _sa3_shape_ok(kpad0, couts, num_neighbors, block_bytes, kpad0_max=288):
-    """launch_sa3's shape checks (csrc/sa_mlp.hip) for widths as the tables hold them: kpad0 = rows of the first layer's
-    input, couts = every layer's (padded) rows.  LDS: the two plane regions at `block_bytes` per 32-row block, and behind
-    them the eight range words and the staged output rows of a run (64 + cout_last * 8 * 4 bytes), in a CU's 160 KiB."""
-    if int(num_neighbors) not in (16, 32, 64) or not 1 <= len(couts) <= 4:
-        return False
-    kpad = [kpad0] + list(couts[:-1])
-    if any(k <= 0 or k % 32 or not (k // 32 <= 6 or k // 32 in (8, 9)) for k in kpad) or any(c <= 0 or c % 16 for c in couts):
-        return False
-    if any(c not in _PLANE_WIDTHS for c in couts[:-1]) or kpad0 > kpad0_max:
-        return False
-    blocks_a = max([kpad0 // 32] + [couts[l] // 32 for l in range(1, len(couts) - 1, 2)])
-    blocks_b = max([0] + [couts[l] // 32 for l in range(0, len(couts) - 1, 2)])
-    return (blocks_a + blocks_b) * block_bytes + 64 + couts[-1] * _SA_RUN * 4 <= dense.LDS_BYTES
+    couts = [layers[3 * i].weight.shape[0] for i in range(len(layers) // 3)]
+    cin = layers[0].weight.shape[1]
+    return bool(couts) and _f32_takes(max(cin - 3, 0), int(num_neighbors), *_tables(_pad32(cin), couts))
 
 
 def split_plan_ok(cins, couts, num_neighbors):
-    """Shapes launch_sa3 takes (csrc/sa_mlp.hip; gldm_sa_mlp_forward_f16x2 and, with the tables of the layers behind a
-    hoisted first one, gldm_sa_mlp_forward_f16x2_pre): 64-column tiles on split-f16 planes."""
+    """Shapes SaMlpPlan.run sends to launch_sa3 (csrc/sa_mlp.hip; gldm_sa_mlp_forward_f16x2 and, with the tables of the
+    layers behind a hoisted first one, gldm_sa_mlp_forward_f16x2_pre): the library's answer, and the routing policy -- the
+    launch's LDS with its plane regions counted at PLANNED_PLANES within PLANNED_LDS_BYTES.  The policy refuses plans
+    the launcher takes ([259] -> [128, 256] at U = 16: 13 plane blocks + a 256-row output are 114,752 bytes)."""
     from .numerics import split_enabled
-    if not split_enabled() or not 1 <= len(couts) <= 4:
+    if not split_enabled() or not couts:
         return False
     # hidden widths are packed padded to the 32-row plane blocks (zero weight rows, zero bias: ReLU leaves zeros, and the
     # next layer's weights over those rows are zero): a 16-wide hidden layer (half-width PVCNN2) runs as a 32-wide one
-    couts = [(c + 31) // 32 * 32 for c in couts[:-1]] + [couts[-1]]
-    return _sa3_shape_ok((cins[0] + 31) // 32 * 32, couts, num_neighbors, _SA_BLOCK_BYTES_PLANNED)
-
-
+    couts = [_pad32(c) for c in couts[:-1]] + [couts[-1]]
+    lds = _sa3_bytes(False, int(num_neighbors), *_tables(_pad32(cins[0]), couts))   # (all of it, its plane regions)
+    return lds is not None and lds[0] - lds[1] + lds[1] * PLANNED_PLANES[0] // PLANNED_PLANES[1] <= PLANNED_LDS_BYTES
 
 
 def _plane_width(c):
     """A hidden width as the split tables pack it: the next width the kernels take (96 -> 128, 196 -> 256; zero weight rows
     and zero bias, ReLU leaves zeros, the next layer's weights over those rows are zero); beyond 256: whole plane blocks."""
-    return next((w for w in _PLANE_WIDTHS if w >= c), (c + 31) // 32 * 32)
+    return next((w for w in _PLANE_WIDTHS if w >= c), _pad32(c))
 
 
 def _f32_width(c):
-    """The same for the f32 tables: the next width gldm_sa_mlp_forward has an m-tile count for (_OK_MTILES)."""
-    return next((16 * t for t in _OK_MTILES if 16 * t >= c), c)
+    """The same for the f32 tables: the next width gldm_sa_mlp_forward has an m-tile count for."""
+    return next((w for w in _F32_WIDTHS if w >= c), c)
 
 
 def sa3_takes(kpad0, couts, num_neighbors, pre=False):
-    """What launch_sa3 itself takes, at its own LDS figure (8192 bytes per plane block): kpad0 = rows of the first layer's
-    input, or of the per-point layer's output when `pre`.  split_plan_ok asks the same helper with its larger figure."""
-    return _sa3_shape_ok(kpad0, couts, num_neighbors, _SA_BLOCK_BYTES, 256 if pre else 288)
+    """What launch_sa3 itself takes (the library's answer): kpad0 = rows of the first layer's input, or of the per-point
+    layer's output when `pre`.  split_plan_ok asks the same planner and adds its policy."""
+    return bool(couts) and _sa3_bytes(bool(pre), int(num_neighbors), *_tables(kpad0, couts)) is not None
 
 
 def msg_fold(num_neighbors):
@@ -98,27 +109,25 @@ def msg_route(cin, couts, num_neighbors, hoist=True):
       'split'    gldm_sa_mlp_forward_f16x2
       'f32'      gldm_sa_mlp_forward, hidden widths padded to _f32_width
       'f32_pre'  gldm_sa_mlp_forward with the first layer hoisted (inputs wider than its 256 rows)
-    The split routes are what launch_sa3 takes (sa3_takes: its width sets and its LDS bound, planes + 64 + cout_last * 8 * 4
-    bytes)."""
+    Every route is what its launch takes (sa3_takes, gldm_sa_mlp_supported); policy: pooled rows within MSG_MAX_POOLED_ROWS,
+    MSG_MAX_LAYERS layers."""
     from .numerics import split_enabled
     u, _ = msg_fold(num_neighbors)
     couts = [int(c) for c in couts]
     n = len(couts)
-    if not 1 <= n <= 4 or u < 1 or 64 % u or couts[-1] > 256:   # pooled rows wider than 256: no fused kernel has run them
+    if not 1 <= n <= MSG_MAX_LAYERS or couts[-1] > MSG_MAX_POOLED_ROWS:
         return None
     if split_enabled():
         pc = [_plane_width(c) for c in couts[:-1]] + couts[-1:]
-        split_ok = sa3_takes((cin + 31) // 32 * 32, pc, u)
-        if n >= 2 and (hoist or not split_ok) and sa3_takes((couts[0] + 31) // 32 * 32, pc[1:], u, pre=True):
+        split_ok = sa3_takes(_pad32(cin), pc, u)
+        if n >= 2 and (hoist or not split_ok) and sa3_takes(_pad32(couts[0]), pc[1:], u, pre=True):
             return "pre"
         if split_ok:
             return "split"
     fc = [_f32_width(c) for c in couts[:-1]] + couts[-1:]
-    if any(c % 16 or c > 256 or (c // 16) not in _OK_MTILES for c in fc):
-        return None
-    if (cin + 31) // 32 * 32 <= 256:
+    if _f32_takes(max(cin - 3, 0), u, *_tables(_pad32(cin), fc)):
         return "f32"
-    if n >= 2 and cin > 3 and (3 + fc[0] + 31) // 32 * 32 <= 256:
+    if n >= 2 and cin > 3 and _f32_takes(fc[0], u, *_tables(_pad32(3 + fc[0]), fc)):
         return "f32_pre"
     return None
 

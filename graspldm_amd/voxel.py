@@ -7,18 +7,21 @@ import torch
 from . import _lib as L
 from .r1d_pack import mfma_a_fragments
 
-SUPPORTED = {(3, 6), (6, 3), (2, 8), (4, 4), (8, 2), (4, 8), (2, 4), (4, 2), (1, 4), (2, 2), (4, 1), (8, 1),
-             (16, 2), (8, 4)}  # (cout/16, r/4) instantiated in conv3d.hip (the last two as two half-width launches)
+# Which (cin, cout, r) a conv kernel is instantiated for is the library's answer (gldm_conv3d_k3_supported reads the list
+# the dispatch reads, csrc/conv3d.hip).  What stands next to it in a predicate below is routing policy.
+_F32, _F16X2 = 0, 1       # include/gldm.h: gldm_conv3d_kind
+CONV_ROW_TILE = 16        # policy: whole 16-row m-tiles only (the f32 kernels guard a partial last tile; pack_conv3d has never packed one)
+FIRST_VOXEL_CONV = (3, 48, 24)   # policy: the shipped encoder's first conv has an f32 form of its own under f32_only() (DESIGN_HISTORY.md, round 6)
 
 
-# (cout, r) of the plane-staging split-f16 kernel (gldm_conv3d_k3_f16x2; cin % 16 == 0): the shipped encoder's two shapes
-# and, since round 5, PVCNN2's power-of-two ones
-SPLIT_SHAPES = {(48, 24), (96, 12), (32, 32), (64, 32), (32, 16), (64, 16), (128, 16), (64, 8), (128, 8), (256, 8), (128, 4)}
+def _instantiated(kind, cin, cout, r):
+    return L.lib().gldm_conv3d_k3_supported(kind, int(cin), int(cout), int(r)) == 0
 
 
 def conv_supported(cout, r):
-    """Shapes launch_conv / launch_conv_halves have an f32-MFMA instantiation for (csrc/conv3d.hip; gldm_conv3d_k3[_cl])."""
-    return cout % 16 == 0 and r % 4 == 0 and (cout // 16, r // 4) in SUPPORTED
+    """Shapes launch_conv / launch_conv_halves have an f32-MFMA instantiation for (csrc/conv3d.hip; gldm_conv3d_k3[_cl]:
+    any cin)."""
+    return cout % CONV_ROW_TILE == 0 and _instantiated(_F32, 1, cout, r)
 
 
 def pack_conv3d(weight):
@@ -31,15 +34,15 @@ def pack_conv3d(weight):
 
 
 def split_conv_supported(cin, cout, r):
-    """Shapes conv3d_k3_f16x2_impl dispatches (csrc/conv3d.hip; gldm_conv3d_k3_f16x2[_gn]: SPLIT_SHAPES with cin % 16 == 0,
-    and the shipped encoder's first conv 3 -> 48 @ 24^3 with K = 81 packed into three 32-deep blocks)."""
-    if (cin, cout, r) == (3, 48, 24):
-        from .numerics import split_enabled
-        return split_enabled()   # under f32_only() its f32 form runs (K padded to 27 x 16: slower, exact f32 products)
-    if cin % 16 or (cout, r) not in SPLIT_SHAPES:
-        return False
+    """Shapes conv3d_k3_f16x2_impl dispatches (csrc/conv3d.hip; gldm_conv3d_k3_f16x2[_gn]: the listed (cout, r) with
+    cin % 16 == 0, and the shipped encoder's first conv 3 -> 48 @ 24^3 with K = 81 packed into three 32-deep blocks), where
+    the split arithmetic is on -- or the shape has no f32 instantiation and so keeps its only MFMA kernel."""
     from .numerics import split_enabled
-    return split_enabled() or not conv_supported(cout, r)   # a shape without an f32 instantiation keeps its only MFMA kernel
+    if not _instantiated(_F16X2, cin, cout, r):
+        return False
+    if (cin, cout, r) == FIRST_VOXEL_CONV:
+        return split_enabled()   # under f32_only() its f32 form runs (K padded to 27 x 16: slower, exact f32 products)
+    return split_enabled() or not conv_supported(cout, r)
 
 
 def pack_conv3d_fewch_f16x2(weight):

@@ -542,6 +542,19 @@ int gldm_sa_mlp_forward_f16x2_pre(const float *points /*[b,3,n]*/, const float *
                                    const float *range_gain /*host [n_layers][2] or NULL*/,
                                    float *out /*[b,cout_last,m]*/, gldm_stream_t stream);
 
+/* Shape queries of the three launches above (ABI 15): each is the launch's own planner behind a thin wrapper, a pure
+ * function of the sizes and the HOST tables (no device pointer, nothing launched), and answers the status the launch gives
+ * the same shape before it looks at gains or launches.
+ * gldm_sa_mlp_supported: GLDM_OK where gldm_sa_mlp_forward runs (c, u, n_layers, cin_pad[], cout[]), else its status
+ * (GLDM_ERR_UNSUPPORTED; GLDM_ERR_INVALID_ARG for a null table, u <= 0, c < 0, cin_pad[l] != cout[l - 1] or cin_pad[0] < 3 + c).
+ * gldm_sa_mlp_f16x2_lds_bytes: the dynamic LDS of the single-tile launch of gldm_sa_mlp_forward_f16x2 (pre == 0) or
+ * gldm_sa_mlp_forward_f16x2_pre (pre != 0: c = 0, cin_pad[0] = rows of `pre`): the two plane regions + the eight range words +
+ * the staged run of output rows, in bytes; a negative GLDM_ERR_* status where the launch takes no such shape (the
+ * *_workspace_bytes convention).  plane_bytes (optional): the plane regions' share of that figure. */
+int gldm_sa_mlp_supported(int c, int u, int n_layers, const int32_t *cin_pad, const int32_t *cout);
+long long gldm_sa_mlp_f16x2_lds_bytes(int pre, int c, int u, int n_layers, const int32_t *cin_pad, const int32_t *cout,
+                                      long long *plane_bytes /*or NULL*/);
+
 /* ref: grasp_ldm/models/modules/ext/pvcnn/modules/shared_mlp.py:6-35 (Conv1d k = 1 + eval BatchNorm folded + ReLU),
  * one layer, in the native [b, c, n] layout: y = act(W x + bias).  `w_packed` = the folded weight [cout, cin] in MFMA
  * A-fragment order (graspldm_amd/r1d_pack.py: mfma_a_fragments).  Optional fused head on the accumulators:
@@ -587,7 +600,9 @@ int gldm_linear_rows(const float *x /*[rows,n]*/, const float *w /*[nout,n]*/, c
  * input tile is split once while it is staged.  Since ABI 6 the front layer's weights `w0_split` are split-f16 fragments
  * too (cin0 % 32 == 0, cin0 <= 96; its f32 input tile is split once per wave into registers); `head_w_packed` stays f32
  * fragments.  cin % 128 == 0, cout % 32 == 0 (with a front layer or a head: % 256; fewer than 256 output rows leave waves
- * idle), n % 32 == 0, 4 (48 cin + 32 cin0) + 16 <= 160 KiB. */
+ * idle), n % 16 == 0, the tile's two f16 planes (128 bytes per channel of a 32-point tile) + the front layer's f32 tile
+ * + 64 bytes <= 160 KiB: cin <= 1152 (until ABI 8 three bf16 planes, 4 (48 cin + 32 cin0) + 16 bytes).  The exact rule is
+ * gldm_pointwise_mlp_supported's answer. */
 /* (ABI 10: without a front layer cin may be any multiple of 8 -- `w_split` then holds the fragments of W zero-padded to a
  * multiple of 128 columns, the K the launch walks; cout any multiple of 16 below 256 rows, of 32 from there.) */
 int gldm_pointwise_mlp_f16x2(const float *x /*[b,cin,n]*/, const float *w_split, const float *bias /*[cout]*/,
@@ -618,6 +633,12 @@ int gldm_pointwise_mlp2_f16x2(const float *x /*[b,cin0,n]*/, const float *w0_spl
                                const float *head_w_packed, const float *head_bias, int hout,
                                const float *front_gain /*host [2] or NULL*/,
                                float *y /*[b,cout,n] or NULL*/, float *z /*[b,hout,n] or NULL*/, gldm_stream_t stream);
+
+/* Shape query of the six gldm_pointwise_mlp* launches (ABI 15): their common planner behind a thin wrapper, a pure function of
+ * the sizes and the form.  split_f16: the *_f16x2 forms; cin0: rows of the front layer's input (gldm_pointwise_mlp2*), 0 for no
+ * front layer; hout: rows of the head, 0 for none; with_addend / point_major: the _add / _pm forms (split only).  GLDM_OK
+ * where the launch of that form runs the shape, GLDM_ERR_UNSUPPORTED otherwise (a non-positive size included). */
+int gldm_pointwise_mlp_supported(int split_f16, int cin0, int cin, int cout, int n, int hout, int with_addend, int point_major);
 
 /* ref: grasp_ldm/models/modules/ext/pvcnn/modules/pointnet.py:40-44 (PointNetAModule: `features.max(dim=-1)`, the global
  * pooling over a cloud's centres).  out[row] = max over x[row][0..n) for rows = b * c; NaN propagates as in torch.max. */
@@ -657,6 +678,14 @@ int gldm_conv3d_k3_generic(const float *x /*[b,cin,r^3]*/, const float *w /*[cou
 int gldm_conv3d_k3_f16x2(const float *x /*[b,cin,r^3]*/, const float *w_split, const float *bias /*[cout]*/,
                           int b, int cin, int cout, int r, float *y /*[b,cout,r^3]*/, float *partial,
                           gldm_stream_t stream);
+
+/* Shape query of the MFMA convs (ABI 15): GLDM_OK where gldm_conv3d_k3 / _cl (GLDM_CONV3D_F32: any cin, the listed
+ * (m-tiles of cout, r)) or gldm_conv3d_k3_f16x2 / _gn (GLDM_CONV3D_F16X2: the listed (cout, r) with cin % 16 == 0, and
+ * 3 -> 48 at r = 24) has an instantiation, GLDM_ERR_UNSUPPORTED otherwise; another kind: GLDM_ERR_INVALID_ARG.  It reads the
+ * list the dispatch reads (csrc/conv3d.hip).  The forms' own conditions (_cl: cout % 4 == 0; _gn: cin % 16 == 0) stay with
+ * the entries. */
+enum gldm_conv3d_kind { GLDM_CONV3D_F32 = 0, GLDM_CONV3D_F16X2 = 1 };
+int gldm_conv3d_k3_supported(int kind, int cin, int cout, int r);
 
 /* ref: pvconv.py:57-66 (Conv3d -> GroupNorm(8) -> Swish -> Conv3d): a conv of the voxel stack with its neighbours' work
  * folded in.  in_coef [b, cin, 2] (optional) = (a, s) from gldm_groupnorm_coef: x is the previous conv's RAW output and

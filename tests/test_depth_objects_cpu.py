@@ -75,7 +75,7 @@ def test_depth_to_objects_envelope_without_a_device():
     assert call(depth=None) == INVALID and call(labels=None) == INVALID and call(work=None) == INVALID
     assert call(points=None) == INVALID and call(start=None) == INVALID and call(count=None) == INVALID
     assert call(nbytes=7) == WORKSPACE
-    assert h.gldm_abi_version() == 14
+    assert h.gldm_abi_version() == 15
 
 
 def test_fps_ragged_envelope_without_a_device():

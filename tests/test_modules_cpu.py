@@ -302,9 +302,12 @@ def test_pad_cin32_and_16_position_descriptors():
 def test_f32_only_switch_changes_what_is_packed_and_chosen(fpc_state_dict):
     """numerics.f32_only(): descriptors name no split copy (-> sample-major f32 engine), the split shape predicates say no
     wherever an f32 kernel exists, and the switch restores itself.  In the default mode the predicates say what the C
-    launchers take: launch_sa3 reserves 64 + 32 cout_last bytes behind the planes (13 plane blocks + a 256-row output do
-    not fit the CU's 160 KiB), and launch_pointwise hands out one-m-tile units (cout % 16) only where cout < 256 and the
-    32-point planes fit half the LDS ((128 K + 64) 2 <= 160 KiB, K padded to 128: K <= 512), units of 32 rows otherwise."""
+    launchers take AND what the routing policy keeps.  split_plan_ok refuses [259] -> [128, 256] at U = 16 and
+    [259] -> [128, 128, 256] at U = 32 because of its planning figure (sa_pack.PLANNED_PLANES: 13 plane blocks counted at
+    12288 bytes + 64 + 32 x 256 bytes exceed 160 KiB), not because of the launcher: launch_sa3 holds 8192 bytes per block
+    and takes both in 114,752 bytes (tests/test_envelope_cpu.py pins that side).  launch_pointwise hands out one-m-tile
+    units (cout % 16) only where cout < 256 and the 32-point planes fit half the LDS ((128 K + 64) 2 <= 160 KiB, K padded
+    to 128: K <= 512), units of 32 rows otherwise: that bound is the library's own."""
     from graspldm_amd import numerics, voxel, dense
     from graspldm_amd.r1d_pack import pack_resnet1d
     from graspldm_amd.sa_pack import split_plan_ok

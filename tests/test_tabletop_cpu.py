@@ -163,7 +163,7 @@ def test_segment_tabletop_envelope_without_a_device():
     assert call(depth=None) == INVALID and call(work=None) == INVALID and call(labels=None) == INVALID
     assert call(num=None) == INVALID and call(pixels=None) == INVALID and call(root=None) == INVALID
     assert call(nbytes=4 * 4 * 16 + 7) == WORKSPACE
-    assert h.gldm_abi_version() == 14   # additive: no existing signature changed
+    assert h.gldm_abi_version() == 15   # 14 -> 15 added the encoder shape queries: no existing signature changed
 
 
 def test_python_entry_points_reject_what_the_kernels_cannot_take():

@@ -164,7 +164,7 @@ def test_new_entries_reject_bad_arguments_without_launching():
     assert h.gldm_groupnorm_coef(p, p, p, 2, 1088, 4, 8, 1e-5, p, None) == -1      # 136 per group
     assert h.gldm_groupnorm_coef(p, p, p, 2, 1032, 4, 8, 1e-5, p, None) == -1      # 129 per group
     assert h.gldm_groupnorm_coef(p, p, p, 2, 60, 4, 8, 1e-5, p, None) == -1        # c % groups
-    assert h.gldm_abi_version() == L.ABI_VERSION == 14
+    assert h.gldm_abi_version() == L.ABI_VERSION == 15
 
 
 def test_switch_off_leaves_the_modules_as_they_were():
