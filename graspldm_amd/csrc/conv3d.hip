@@ -920,6 +920,7 @@ int launch_conv_halves(const float *x, const float *wp, const float *bias, int b
   X(3, 6)   /* 48 ch @ 24^3  (shipped fpc/ppc PVCNN encoder) */                                                            \
   X(6, 3)   /* 96 ch @ 12^3 */                                                                                             \
   X(2, 8)   /* 32 ch @ 32^3  (PVCNN2) */                                                                                   \
+  X(3, 8)   /* 33 .. 48 ch @ 32^3 */                                                                                       \
   X(4, 4)   /* 64 ch @ 16^3 */                                                                                             \
   X(8, 2)   /* 128 ch @ 8^3 */                                                                                             \
   /* half-width / half-resolution variants (the reference's encoder benchmark runs PVCNN / PVCNN2 at 0.5 / 0.5) */       \

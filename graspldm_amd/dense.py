@@ -68,9 +68,9 @@ def pack_head(wh):
 # Which shapes a launch takes is the library's answer (gldm_pointwise_mlp_supported: launch_pointwise's own planner,
 # csrc/pointwise_mlp.hip).  What stands next to that answer in a predicate below is routing policy, each term a named constant.
 SPLIT_PAD_MIN_CIN = 32    # policy: narrowest input sent to the split launch with K padded to 128 (below: the lane-per-point kernel; DESIGN.md, kernel table)
-SPLIT_TILE_POINTS = 32    # policy: the routes send whole 32-point tiles, though the split launch takes n % 16 (no 16-point tail has been run or timed)
+SPLIT_TILE_POINTS = 32    # policy: the routes send whole 32-point tiles, though the split launch takes n % 16 (16-point tails run and compared, not timed: tests/test_envelope_gpu.py::test_pointwise_accepted_shapes)
 SPLIT_MIN_COUT = 64       # policy: fewer output rows stay on pointwise_small / pointwise_any ("below the split launch's 64 rows")
-SPLIT_MAX_K = 768         # policy: K after padding, the bound of the former three-plane plan (48 floats per channel in 160 KiB); the launch takes 1152 -- not lifted unmeasured
+SPLIT_MAX_K = 768         # policy: K after padding, the bound of the former three-plane plan (48 floats per channel in 160 KiB); the launch takes 1152 (896 .. 1152 run and compared, not timed: tests/test_envelope_gpu.py::test_pointwise_accepted_shapes) -- not lifted untimed
 _ANY_COUT, _ANY_N = 256, 32   # a channel-only question (a packer's, no tensor yet) is asked at one round of units and one tile
 
 

@@ -21,9 +21,9 @@ PRE_WITHOUT_FEATURES = True
 # Which layer plans a launch takes is the library's answer (gldm_sa_mlp_supported, gldm_sa_mlp_f16x2_lds_bytes: the planners
 # of gldm_sa_mlp_forward and launch_sa3, csrc/sa_mlp.hip), cached per shape.  What stands next to it in a predicate below is
 # routing policy, each term a named constant; numerics.split_enabled() stays outside the cache.
-PLANNED_PLANES = (3, 2)        # policy: split_plan_ok counts the plane regions as the three bf16 planes of ABI 5-8 (12288 bytes per 32-row block) where launch_sa3 keeps two f16 ones (8192); DESIGN.md, PointNet2MSG -- not lifted unmeasured
+PLANNED_PLANES = (3, 2)        # policy: split_plan_ok counts the plane regions as the three bf16 planes of ABI 5-8 (12288 bytes per 32-row block) where launch_sa3 keeps two f16 ones (8192); DESIGN.md, PointNet2MSG -- the two plans it refuses run and compared, not timed (tests/test_envelope_gpu.py::test_sa_run_with_the_planning_figure_at_the_launch_s_own): not lifted untimed
 PLANNED_LDS_BYTES = 160 * 1024       # policy: the LDS that figure was planned against
-MSG_MAX_POOLED_ROWS = 256            # policy: pooled rows wider than 256 -- no fused kernel has run them (PointNet2MSG)
+MSG_MAX_POOLED_ROWS = 256            # policy: pooled rows wider than 256 -- 512 / 1008 / 1024 rows run and compared, not timed (tests/test_envelope_gpu.py::test_sa_run_msg_with_a_policy_constant_at_the_launch_s_bound, test_sa_mlp_accepted_plans; DESIGN.md, PointNet2MSG)
 MSG_MAX_LAYERS = 4                   # policy: a branch as deep as every route takes it whole (the hoisted form alone would take a fifth layer; no f32 launch stands behind it)
 _F32_WIDTHS = (16, 32, 64, 128, 192, 256)   # packing: hidden widths the f32 tables pad to (_f32_width)
 _PLANE_WIDTHS = (32, 64, 128, 256)          # packing: hidden widths the split tables pad to (_plane_width)

@@ -128,6 +128,8 @@ CONV = [
     ((F16X2, 3, 32, 32), UNSUPPORTED), ((F16X2, 24, 48, 24), UNSUPPORTED), ((F16X2, 48, 48, 12), UNSUPPORTED),
     ((F16X2, 48, 40, 24), UNSUPPORTED), ((F16X2, 16, 16, 16), UNSUPPORTED),
     ((2, 48, 48, 24), INVALID),
+    # (rows are appended: a test's id carries its row's index)  f32 at 32^3: 2, 3 (33 .. 48 rows) and 2 x 2 m-tiles
+    ((F32, 5, 33, 32), OK), ((F32, 5, 48, 32), OK), ((F32, 5, 80, 32), UNSUPPORTED),
 ]
 
 
