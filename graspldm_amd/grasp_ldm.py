@@ -119,7 +119,8 @@ class GraspLatentDDM(nn.Module):
         are NaN then): the synchronising form of the check every launch makes without a host sync.  The inference harness
         calls the same check before results leave the device; direct callers of generate_grasps call this."""
         denoiser = self.diffusion_model.net if self.is_elucidated_diffusion else self.diffusion_model.model
-        eng = getattr(denoiser, "_engine", None)
+        from ._cache import cached_value
+        eng = cached_value(denoiser, "_engine")
         if eng is not None:
             eng.check()
 

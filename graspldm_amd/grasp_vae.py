@@ -40,30 +40,26 @@ class ConditionalGraspPoseDecoder(nn.Module):
             raise NotImplementedError("quality heads (num_output_qualities > 0) are not on the shipped hot path")
         self.num_qualities = None
         self.out_features = (6, 1)
-        self._engine, self._key = None, None
+        self._engine = None   # the _cache.cached entry of _get_engine()
+
+    def _pack(self, device, rows):
+        sd = {k: v.detach().float().cpu() for k, v in self.state_dict().items()}
+        if isinstance(self.net, Unet1D):
+            from .unet1d import UnetCoreEngine
+            self.net.cond_rows = rows
+            return UnetCoreEngine.decoder(self.net.engine(device), sd)
+        from .r1d import R1dEngine, pack_resnet1d
+        packed = pack_resnet1d(sd, "net.", groups=self.net.groups, seq_len=self.feature_resolution,
+                               cond_rows=rows, decoder=dict(
+                                   in_w=sd["in_layer.weight"], in_b=sd["in_layer.bias"],
+                                   tmrp_w=sd["tmrp.weight"], tmrp_b=sd["tmrp.bias"],
+                                   cls_w=sd["class_logits.weight"], cls_b=sd["class_logits.bias"]))
+        return R1dEngine(packed, device)
 
     def _get_engine(self, device, rows):
-        from ._cache import params_key, publish
-        key = params_key(self.parameters(), device, rows)
-        if isinstance(self.net, Unet1D):
-            if self._engine is None or self._key != key:
-                from .unet1d import UnetCoreEngine
-                self.net.cond_rows = rows
-                sd = {k: v.detach().float().cpu() for k, v in self.state_dict().items()}
-                self._engine, self._key = UnetCoreEngine.decoder(self.net.engine(device), sd), key
-                publish(device)
-            return self._engine
-        if self._engine is None or self._key != key:
-            from .r1d import R1dEngine, pack_resnet1d
-            sd = {k: v.detach().float().cpu() for k, v in self.state_dict().items()}
-            packed = pack_resnet1d(sd, "net.", groups=self.net.groups, seq_len=self.feature_resolution,
-                                   cond_rows=rows, decoder=dict(
-                                       in_w=sd["in_layer.weight"], in_b=sd["in_layer.bias"],
-                                       tmrp_w=sd["tmrp.weight"], tmrp_b=sd["tmrp.bias"],
-                                       cls_w=sd["class_logits.weight"], cls_b=sd["class_logits.bias"]))
-            self._engine, self._key = R1dEngine(packed, device), key
-            publish(device)
-        return self._engine
+        from ._cache import cached, params_key
+        return cached(self, "_engine", params_key(self.parameters(), device, rows), lambda: self._pack(device, rows), device,
+                      required=True)
 
     @torch.no_grad()
     def forward(self, z_h, cond=None, samples_per_cond=1):
@@ -90,8 +86,8 @@ class ConditionalGraspPoseEncoder(nn.Module):
         self.in_layer = nn.Linear(self.in_features, feature_resolution)
         self.net = self.MODELS[_get(config, "type")](dim=feature_resolution, **args)
         self.out_layer = nn.Linear(self.net.out_features, self.out_features)
-        self._engine, self._key = None, None          # fused with a bottleneck
-        self._engine_plain, self._key_plain = None, None  # out_layer only (forward() on its own)
+        self._engine = None         # _cache.cached entries of _get_engine(): fused with a bottleneck,
+        self._engine_plain = None   # and out_layer only (forward() on its own)
 
     def _pack(self, device, rows, bottleneck):
         from .r1d import R1dEngine, pack_resnet1d
@@ -113,18 +109,10 @@ class ConditionalGraspPoseEncoder(nn.Module):
         return R1dEngine(packed, device)
 
     def _get_engine(self, device, rows, bottleneck=None):
-        from ._cache import params_key, publish
+        from ._cache import cached, params_key
         params = list(self.parameters()) + (list(bottleneck.parameters()) if bottleneck is not None else [])
-        key = params_key(params, device, rows)
-        if bottleneck is not None:
-            if self._engine is None or self._key != key:
-                self._engine, self._key = self._pack(device, rows, bottleneck), key
-                publish(device)
-            return self._engine
-        if self._engine_plain is None or self._key_plain != key:
-            self._engine_plain, self._key_plain = self._pack(device, rows, None), key
-            publish(device)
-        return self._engine_plain
+        return cached(self, "_engine" if bottleneck is not None else "_engine_plain", params_key(params, device, rows),
+                      lambda: self._pack(device, rows, bottleneck), device, required=True)
 
     @torch.no_grad()
     def forward(self, x, cond, samples_per_cond=1):

@@ -53,8 +53,9 @@ class _InferenceBase:
     def _results(self, pc, metas, tmrp, cls_logit, num_pcs, num_grasps, all_steps=(), score=True):
         # before anything leaves the device: a lost hand-off inside the fused sampling launch raises here
         # (status, not silent garbage: the reference exits the process on a CUDA error, cuda_utils.cuh:28-37)
+        from ._cache import cached_value
         for m in self.model.modules():
-            eng = getattr(m, "_engine", None)
+            eng = cached_value(m, "_engine")
             if eng is not None:
                 eng.check()
         if not bool(torch.isfinite(pc).all()):

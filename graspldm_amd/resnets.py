@@ -116,28 +116,22 @@ class _ResNet1DBase(nn.Module):
             raise NotImplementedError("learned variance (2 output channels) is not on the generation hot path")
         self.final_res_block = block_klass(dims[-1], dims[-1], emb_dim=emb_dim)
         self.final_conv = nn.Conv1d(dims[-1], self.out_channels, 1)
-        self._engine = None
-        self._engine_key = None
+        self._engine = None   # the _cache.cached entry of engine()
         self.max_timesteps = 1000
 
     # ---- engine plumbing
-    def _param_key(self, device):
-        from ._cache import params_key
-        return params_key(self.parameters(), device, self.max_timesteps)
-
     def engine(self, device, decoder=None, prefix=""):
-        key = self._param_key(device)
-        if self._engine is None or self._engine_key != key:
+        from ._cache import cached, params_key
+        rows = getattr(self, "cond_rows", 3)
+
+        def build():
             sd = {k: v.detach().float().cpu() for k, v in self.state_dict().items()}
             has_time = getattr(self, "time_mlp", None) is not None
             packed = pack_resnet1d(sd, "", groups=self.groups, seq_len=self.in_features,
-                                   num_steps=self.max_timesteps if has_time else None, decoder=decoder,
-                                   cond_rows=getattr(self, "cond_rows", 3))
-            self._engine = R1dEngine(packed, device)
-            self._engine_key = key
-            from ._cache import publish
-            publish(device)
-        return self._engine
+                                   num_steps=self.max_timesteps if has_time else None, decoder=decoder, cond_rows=rows)
+            return R1dEngine(packed, device)
+        return cached(self, "_engine", params_key(self.parameters(), device, self.max_timesteps, rows), build, device,
+                      required=True)
 
     def _cond_rows_of(self, z_cond):
         rows = 1 if z_cond.ndim == 2 else z_cond.shape[1]
@@ -353,22 +347,20 @@ class Unet1D(nn.Module):
         self.out_channels = 1
         self.final_res_block = block_klass(dim * 2, dim, emb_dim=emb_dim)
         self.final_conv = nn.Conv1d(dim, self.out_channels, 1)
-        self._engine = None
-        self._engine_key = None
+        self._engine = None   # the _cache.cached entry of engine()
         self.cond_rows = 1 if self.is_input_conditioned else 0
         self.max_timesteps = 1000
 
     def engine(self, device, **unused):
-        from ._cache import params_key, publish
+        from ._cache import cached, params_key
         from .unet1d import UnetEngine
-        key = params_key(self.parameters(), device, self.max_timesteps, self.cond_rows)
-        if self._engine is None or self._engine_key != key:
+
+        def build():
             sd = {k: v.detach().float().cpu() for k, v in self.state_dict().items()}
-            self._engine = UnetEngine(sd, self.groups, self.cond_rows, self.is_time_conditioned,
-                                      self.max_timesteps if self.is_time_conditioned else None, device)
-            self._engine_key = key
-            publish(device)
-        return self._engine
+            return UnetEngine(sd, self.groups, self.cond_rows, self.is_time_conditioned,
+                              self.max_timesteps if self.is_time_conditioned else None, device)
+        return cached(self, "_engine", params_key(self.parameters(), device, self.max_timesteps, self.cond_rows), build, device,
+                      required=True)
 
     def _cond_rows_of(self, z_cond):
         if z_cond is None:
