@@ -85,24 +85,38 @@ __device__ __forceinline__ void u_conv(float *lds, const float *__restrict__ w, 
             a[0] = *(const u32x4 *)(wf + lane * 4);
             a[1] = *(const u32x4 *)(wf + 256 + lane * 4);
             // Range: the data sets these operands' magnitude (residual stream, stem output, skips), so a
-            // block whose largest magnitude leaves f16's comfortable range is split as x / s, s a power of two from the
-            // wave's 16 columns x 32 channels, and s is folded back on the block's accumulators; s = 1 otherwise (same bits)
+            // COLUMN whose largest magnitude among the block's 32 channels leaves f16's comfortable range is split as
+            // x / s, s a power of two, and s is folded back on the column's accumulators (a lane's four belong to its
+            // column).  One s per column, not per wave: when L < 16 the wave's 16 columns span several samples, and a
+            // loud sample's s would push its neighbours' planes into f16's subnormals.  The branch is wave uniform (any
+            // column out of range); inside it a column with s = 1 still accumulates on the matrix pipe, so every column
+            // keeps the bits it has without loud neighbours, and a block with no such column takes the plain path.
+            // Written as two unlikely detours around ONE split + product so that the plain path falls straight through
+            // (an if / else with a product each made it the taken side of a branch: 0.3 % of case A's time).
             float m = 0.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(x[j]));
-            m = half_max(row_pair_max(row16_max(m)));
-            const float sc = range_pow2(__uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(m))));
-            if (sc != 1.0f) {
+            m = half_max(row_pair_max(m));   // the column's four lane groups: lanes i, i ^ 16, i ^ 32, i ^ 48
+            // range_pow2(m) != 1, on the biased exponent (m >= 0): floor(log2 m) in [-100, -8) or [14, 100]
+            const unsigned be = __float_as_uint(m) >> 23;
+            const bool any = (__builtin_amdgcn_ballot_w64(be - 27u < 92u) | __builtin_amdgcn_ballot_w64(be - 141u < 87u)) != 0;
+            float sc = 1.0f;
+            f32x4 cin = acc;
+            if (__builtin_expect(any, 0)) {
+              sc = range_pow2(m);
               const float inv = pow2_inv(sc);
 #pragma unroll
               for (int j = 0; j < 8; ++j) x[j] *= inv;
-              split_planes8(x, bp);
-              f32x4 part = {0.f, 0.f, 0.f, 0.f};
-              part = mfma_split(a, bp, part);
-              acc += part * sc;
+#pragma unroll
+              for (int r = 0; r < 4; ++r) cin[r] = sc != 1.0f ? 0.f : acc[r];
+            }
+            split_planes8(x, bp);
+            const f32x4 part = mfma_split(a, bp, cin);
+            if (__builtin_expect(any, 0)) {
+#pragma unroll
+              for (int r = 0; r < 4; ++r) acc[r] = sc != 1.0f ? acc[r] + part[r] * sc : part[r];
             } else {
-              split_planes8(x, bp);
-              acc = mfma_split(a, bp, acc);
+              acc = part;
             }
           }
         }

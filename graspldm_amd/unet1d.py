@@ -11,12 +11,16 @@ from .unet1d_pack import UnetDesc, pack_unet1d
 
 
 def check_supported(desc, seq_len):
-    """The Python-side envelope check IS the library's (decided before any HIP call): NotImplementedError naming the limit."""
+    """The library's shape query (gldm_unet1d_supported), asked before any HIP call: NotImplementedError naming the limit.
+    Passing it is necessary, not sufficient: the widest shapes inside the envelope do not fit the 160 KiB of LDS even with
+    one sample per tile, and the packer refuses those (unet1d_pack.choose_tile_samples: NotImplementedError as well, and
+    also before any HIP call)."""
     st = L.lib().gldm_unet1d_supported(ctypes.cast(ctypes.pointer(desc), ctypes.c_void_p), int(seq_len))
     if st != 0:
         raise NotImplementedError(
             f"Unet1D outside the fused kernel's envelope (dim in {{16, 32}}, 2..4 dim_mults, widths multiples of 16 up to 256, "
-            f"groups 4 or 8, 2 <= L <= 16 with L % 2**(levels-1) == 0): dim={desc.dim}, widths={list(desc.widths)[:desc.n_levels + 1]}, "
+            f"groups 4 or 8, 2 <= L <= 16 with L % 2**(levels-1) == 0; inside it the packer still refuses a shape whose LDS map "
+            f"exceeds 160 KiB): dim={desc.dim}, widths={list(desc.widths)[:desc.n_levels + 1]}, "
             f"groups={desc.groups}, L={seq_len}")
 
 

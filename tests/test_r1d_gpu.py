@@ -100,6 +100,37 @@ def test_g5_ddpm_trajectory_golden(engines):
     assert _err(x0, g["x0"]) < 1e-4, _err(x0, g["x0"])
 
 
+def test_ddpm_fixed_small_unclipped_first_steps(engines, fpc_state_dict):
+    """clip_sample=False with the fixed_small variance table (the step is shared with the Unet1D kernel; no other test of
+    this engine sets either): the first 8 steps of the 1000-step schedule from x_T, 21 samples, against the oracle stepped
+    by DDPMScheduler(variance_type="fixed_small", clip_sample=False).  With clipping the same reference ends 4.8e-2 away."""
+    from graspldm_amd.diffusion import make_schedule_tables
+    from graspldm_amd.r1d import SCHED_DDPM
+    from oracle import schedulers
+    from oracle import torch_ref as R
+    den, _ = engines
+    g = torch.Generator().manual_seed(31)
+    n = 21
+    x_T, z = torch.randn(n, 1, 4, generator=g), torch.randn(n, 3, 64, generator=g)
+    noise = torch.randn(8, n, 1, 4, generator=g)
+    ts, coef = make_schedule_tables("ddpm", 1000, 5e-5, 1e-3, "linear", "fixed_small", None)
+    ts, coef = ts[:8].contiguous(), coef[:8].contiguous()
+    out = den.denoise(x_T.cuda(), den.cond_embed(z.cuda()), 1, timesteps=ts.cuda(), sched_kind=SCHED_DDPM, clip_sample=False,
+                      coef=coef.cuda(), step_noise=noise.cuda())
+    ends = {}
+    for clip in (False, True):
+        sched = schedulers.DDPMScheduler(variance_type="fixed_small", num_train_timesteps=1000, beta_start=5e-5, beta_end=1e-3,
+                                         beta_schedule="linear", clip_sample=clip)
+        x = x_T.clone()
+        for i, t in enumerate(ts.tolist()):
+            eps = R.resnet1d_forward(fpc_state_dict, "diffusion_model.model.", x, z_cond=z,
+                                     time=torch.full((n,), t, dtype=torch.long))
+            x = sched.step(eps, t, x, noise=noise[i]).prev_sample
+        ends[clip] = x
+    assert _err(ends[False], ends[True]) > 1e-2, "clipping does not change this trajectory: the case would test nothing"
+    assert _err(out, ends[False]) < 1e-4, _err(out, ends[False])
+
+
 def test_g6_pose_epilogue_golden():
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")

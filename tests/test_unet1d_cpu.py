@@ -23,7 +23,7 @@ def _schema():
 def _net(name):
     from graspldm_amd.resnets import Unet1D
     from graspldm_amd.synthetic import load_synthetic_weights
-    c = U.CASES[name]
+    c = U.LDS_REFUSED[name] if name in U.LDS_REFUSED else U.config(name)
     return load_synthetic_weights(Unet1D(**c["args"]), seed=c["seed"])
 
 
@@ -137,22 +137,22 @@ def test_time_tables():
     assert tab.shape == (1000, 64) and torch.equal(tab, want)
 
 
-@pytest.mark.parametrize("exact", [False, True])
-@pytest.mark.parametrize("name", sorted(U.CASES))
-def test_program_on_the_cpu_reproduces_the_restatement(name, exact):
-    """The packed program (ops, LDS map, fragments) interpreted with torch equals the f64 restatement to the weights'
-    rounding: pins the packer and the bounds check without a GPU."""
+def _program_vs_restatement(name, exact, n):
+    """Packs configuration `name`, checks the program's bounds and interprets it on n samples: (packed, the largest
+    difference from the f64 restatement)."""
     from graspldm_amd import numerics
     from graspldm_amd.unet1d_pack import check_program, pack_unet1d, run_program_cpu
-    c = U.CASES[name]
+    c = U.config(name)
     sd = _sd(name)
-    x, z, t = U.case_inputs(name, 3)
+    x, z, t = U.case_inputs(name, n)
     rows = 0 if z is None else (1 if z.ndim == 2 else z.shape[1])
     with numerics.f32_only(exact):
         pk = pack_unet1d(sd, "", c["args"]["resnet_block_groups"], c["L"], cond_rows=rows,
                          time_cond=c["args"]["is_time_conditioned"], num_steps=1000)
     assert bool(pk["desc"].exact_f32) == exact and pk["desc"].lds_floats * 4 <= 160 * 1024
     check_program(pk["desc"], pk["ops"])
+    n = min(n, pk["desc"].tile_samples)
+    x, z, t = x[:n], (z[:n] if z is not None else None), (t[:n] if t is not None else None)
     cemb = None
     if z is not None:
         zz = z if z.ndim == 3 else z[:, None]
@@ -162,7 +162,16 @@ def test_program_on_the_cpu_reproduces_the_restatement(name, exact):
     out = run_program_cpu(pk, x[:, 0], te, cemb)
     ref = U.unet1d_forward({k: v.double() for k, v in sd.items()}, "", x.double(), z.double() if z is not None else None, t,
                            groups=c["args"]["resnet_block_groups"], temb=te.double() if te is not None else None)
-    err = float((out - ref[:, 0]).abs().max())
+    return pk, float((out - ref[:, 0]).abs().max())
+
+
+@pytest.mark.parametrize("exact", [False, True])
+@pytest.mark.parametrize("name", sorted(U.CASES))
+def test_program_on_the_cpu_reproduces_the_restatement(name, exact):
+    """The packed program (ops, LDS map, fragments) interpreted with torch equals the f64 restatement to the weights'
+    rounding: pins the packer and the bounds check without a GPU."""
+    pk, err = _program_vs_restatement(name, exact, 3)
+    assert pk["desc"].tile_samples >= 3
     print(f"case {name} {'f32' if exact else 'split'}: program vs restatement {err:.2e}")
     assert err <= 2e-6
 
@@ -219,6 +228,113 @@ def test_supported_agrees_with_the_python_envelope():
             check_supported(_desc(**bad), 16)
     with pytest.raises(NotImplementedError, match="L=12"):
         check_supported(_desc(), 12)
+
+
+def _query(c):
+    """gldm_unet1d_supported on a configuration of unet1d_ref."""
+    from graspldm_amd import _lib as L
+    from graspldm_amd.unet1d import header_desc
+    a = c["args"]
+    rows = 0 if c["z_shape"] is None else (1 if len(c["z_shape"]) == 1 else c["z_shape"][0])
+    d = header_desc(a["dim"], [a["dim"]] + [a["dim"] * m for m in a["dim_mults"]], a["resnet_block_groups"], rows,
+                    a["is_time_conditioned"])
+    return L.lib().gldm_unet1d_supported(ctypes.cast(ctypes.pointer(d), ctypes.c_void_p), c["L"])
+
+
+_PACKED = {}
+
+
+@pytest.mark.parametrize("exact", [False, True])
+@pytest.mark.parametrize("name", sorted(U.ENVELOPE))
+def test_envelope_row_packs_and_its_program_reproduces_the_restatement(name, exact):
+    """Every ENVELOPE row: accepted by the query, packed, bounds-checked, and its program on the CPU (up to 3 samples of a
+    tile) within 2e-6 of the f64 restatement."""
+    assert _query(U.ENVELOPE[name]) == 0
+    pk, err = _program_vs_restatement(name, exact, 3)
+    if not exact:
+        _PACKED[name] = pk
+    d = pk["desc"]
+    print(f"row {name} {'f32' if exact else 'split'}: tile {d.tile_samples}, LDS {d.lds_floats * 4 / 1024:.1f} KiB, "
+          f"program vs restatement {err:.2e}")
+    assert err <= 2e-6
+
+
+@pytest.mark.parametrize("name", sorted(U.LDS_REFUSED))
+def test_shapes_inside_the_envelope_that_the_packer_refuses_for_lds(name):
+    """The query's envelope is necessary, not sufficient: these pass it and UnetEngine.plan refuses them, naming LDS, before
+    any HIP call (no device is touched: the engine is only given a device's name)."""
+    from graspldm_amd.unet1d import UnetEngine
+    c = U.LDS_REFUSED[name]
+    assert _query(c) == 0
+    eng = UnetEngine(_sd(name), c["args"]["resnet_block_groups"], 0, False, None, "cuda:0")
+    with pytest.raises(NotImplementedError, match="160 KiB of LDS"):
+        eng.plan(c["L"])
+
+
+def test_check_supported_says_that_lds_can_still_refuse():
+    from graspldm_amd.unet1d import check_supported
+    assert "LDS" in check_supported.__doc__
+    with pytest.raises(NotImplementedError, match="LDS"):
+        check_supported(_desc(groups=2), 16)
+
+
+def _properties(c, pk):
+    """What one configuration (and the layout the packer chose for it) contributes to the envelope's coverage."""
+    from graspldm_amd.unet1d_pack import level_lengths
+    a, d = c["args"], pk["desc"]
+    widths = [a["dim"] * m for m in a["dim_mults"]]
+    rows = 0 if c["z_shape"] is None else (1 if len(c["z_shape"]) == 1 else c["z_shape"][0])
+    deepest = level_lengths(c["L"], len(widths))[-1]
+    time = "none" if not a["is_time_conditioned"] else ("fourier" if a.get("learned_sinusoidal_cond") else "plain")
+    got = {f"dim {a['dim']}", f"{len(widths)} levels", f"groups {a['resnet_block_groups']}", f"cond rows {rows}",
+           f"time {time}", f"deepest length {deepest}", f"L {c['L']}", f"tile {d.tile_samples}"}
+    got |= {"width 16 mod 32 above 16" for w in widths if w % 32 == 16 and w > 16}
+    got |= {"width 256" for w in widths if w == 256}
+    got |= {"decreasing widths" for u, v in zip(widths, widths[1:]) if v < u}
+    if d.tile_samples * c["L"] % 16:
+        got.add("ragged last column block")
+    if d.lds_floats * 4 > 150 * 1024:
+        got.add("LDS above 150 KiB")
+    return got
+
+
+REQUIRED = {"dim 16", "dim 32", "2 levels", "3 levels", "4 levels", "groups 4", "groups 8", "cond rows 0", "cond rows 1",
+            "cond rows 2", "cond rows 3", "cond rows 4", "time none", "time fourier", "time plain",
+            "width 16 mod 32 above 16", "width 256", "decreasing widths", "deepest length 3", "deepest length 5",
+            "deepest length 7", "L 2", "L 16", "tile 1", "tile 16", "ragged last column block", "LDS above 150 KiB"}
+
+
+def test_cases_and_envelope_cover_the_listed_corners():
+    """Fails when CASES and ENVELOPE together (with the tile sizes the packer chooses today) lose one of REQUIRED."""
+    from graspldm_amd.unet1d_pack import pack_unet1d
+    got = set()
+    for name in sorted(U.CASES) + sorted(U.ENVELOPE):
+        c = U.config(name)
+        if name not in _PACKED:
+            rows = 0 if c["z_shape"] is None else (1 if len(c["z_shape"]) == 1 else c["z_shape"][0])
+            _PACKED[name] = pack_unet1d(_sd(name), "", c["args"]["resnet_block_groups"], c["L"], cond_rows=rows,
+                                        time_cond=c["args"]["is_time_conditioned"], num_steps=1000)
+        got |= _properties(c, _PACKED[name])
+    assert not REQUIRED - got, sorted(REQUIRED - got)
+
+
+@pytest.mark.parametrize("name, admitted", [("N", (1, 2, 3, 5, 7, 11)), ("O", (1, 2, 3, 5, 7, 11, 16))])
+def test_tile_sizes_the_bounds_check_admits(name, admitted):
+    """pack_unet1d(tile_samples=S) for S in {1, 2, 3, 5, 7, 11, 16}: the layouts check_program admits are the ones
+    tests/test_unet1d_envelope_gpu.py forces (FORCED there); the others exceed the 160 KiB of LDS."""
+    from graspldm_amd.unet1d_pack import pack_unet1d
+    c = U.ENVELOPE[name]
+    rows = 0 if c["z_shape"] is None else (1 if len(c["z_shape"]) == 1 else c["z_shape"][0])
+    ok = []
+    for s in (1, 2, 3, 5, 7, 11, 16):
+        try:
+            pk = pack_unet1d(_sd(name), "", c["args"]["resnet_block_groups"], c["L"], cond_rows=rows, tile_samples=s)
+        except AssertionError as e:
+            assert "LDS over 160 KiB" in str(e)
+            continue
+        assert pk["desc"].tile_samples == s
+        ok.append(s)
+    assert tuple(ok) == admitted
 
 
 def test_null_pointers_return_a_status():

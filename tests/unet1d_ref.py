@@ -105,10 +105,53 @@ CASES = {
 GOLDEN_ROWS = 6
 
 
+def _row(dim, mults, groups, L, rows=0, time=None, seed=0):
+    """One ENVELOPE row: `rows` conditioning rows per sample (0: no input conditioning; 1: z_cond [n, 64]; R > 1: [n, R, 64]),
+    time None / "fourier" (learned_sinusoidal_cond) / "plain" (SinusoidalPosEmb(dim))."""
+    args = dict(dim=dim, dim_mults=mults, is_time_conditioned=time is not None, resnet_block_groups=groups)
+    if time == "fourier":
+        args["learned_sinusoidal_cond"] = True
+    if rows:
+        args["input_conditioning_dims"] = 64
+    return dict(args=args, L=L, z_shape=None if rows == 0 else ((64,) if rows == 1 else (rows, 64)), seed=seed)
+
+
+# Corners of the envelope gldm_unet1d_supported accepts that CASES leaves out (tests/test_unet1d_cpu.py holds the list
+# of properties CASES and ENVELOPE must cover between them, tests/test_unet1d_envelope_gpu.py runs every row): widths
+# that are no power of two or no multiple of 32, in decreasing order, up to 256; deepest levels of 3, 5 and 7 positions;
+# tiles of 1 to 16 samples whose columns do not fill their last 16-column block; LDS maps up to the 160 KiB limit.
+ENVELOPE = {
+    "F": _row(16, (1, 3), 8, 6, seed=31),                        # widths 16 16 48; lengths 6 3; tile 10: 60 columns
+    "G": _row(16, (1, 2, 4), 4, 12, 1, "fourier", seed=32),      # lengths 12 6 3; tile 5: 60 columns
+    "H": _row(32, (1, 2, 4, 8), 8, 16, 1, "fourier", seed=33),   # tile 3, 151.6 KiB
+    "I": _row(32, (1, 2, 4, 8), 4, 8, seed=34),                  # lengths 8 4 2 1; tile 4
+    "J": _row(16, (16, 1), 8, 14, 1, seed=35),                   # widths 16 256 16; lengths 14 7; tile 1: 14 columns
+    "K": _row(16, (5, 7, 9, 11), 4, 16, 0, "plain", seed=36),    # widths 80 112 144 176; tile 3, 150.5 KiB
+    "M": _row(16, (1, 1), 8, 2, seed=37),                        # lengths 2 1; tile 16
+    "N": _row(16, (1, 2), 8, 10, seed=38),                       # lengths 10 5; tile 6: 60 columns
+    "O": _row(16, (2, 6), 4, 4, 4, seed=39),                     # widths 16 32 96: two-source convs of 96 + 32 and 32 + 16
+    "P": _row(32, (1, 3), 8, 2, 2, seed=40),                     # widths 32 32 96; tile 16
+    "Q": _row(32, (8, 8), 4, 16, 1, "fourier", seed=41),         # widths 32 256 256; tile 1
+    "S": _row(32, (8, 8, 8), 4, 16, seed=42),                    # tile 1, 151.9 KiB
+    "U": _row(32, (2, 4, 8, 8), 4, 16, seed=43),                 # tile 2, 158.0 KiB
+    "X": _row(16, (1, 2, 4, 8), 8, 8, 1, "fourier", seed=44),    # lengths 8 4 2 1 with conditioning and time
+}
+# Inside the query's envelope, yet refused by the packer: the LDS map exceeds 160 KiB with one sample per tile.
+LDS_REFUSED = {
+    "R1": _row(32, (4, 8, 8, 8), 4, 16, seed=51),
+    "R2": _row(32, (8, 8, 8, 8), 4, 8, seed=52),
+    "R3": _row(16, (16, 16, 16, 16), 4, 8, seed=53),
+}
+
+
+def config(name):
+    return CASES[name] if name in CASES else ENVELOPE[name]
+
+
 def case_inputs(name, n, samples_per_cond=1):
-    """(x [n,1,L], z_cond [n / samples_per_cond, ...] or None, time int64 [n] or None) of a golden configuration: drawn
-    from the case's own generator, a different timestep per sample.  The first rows do not depend on n."""
-    c = CASES[name]
+    """(x [n,1,L], z_cond [n / samples_per_cond, ...] or None, time int64 [n] or None) of a configuration of CASES or
+    ENVELOPE: drawn from the case's own generator, a different timestep per sample.  The first rows do not depend on n."""
+    c = config(name)
     g = torch.Generator().manual_seed(1000 + c["seed"])
     x = torch.randn(4096, 1, c["L"], generator=g)[:n]
     z = None
