@@ -323,7 +323,7 @@ __device__ __forceinline__ void resblock4_valu(const Ctx &c, const int (&o)[kOpI
   }
 #pragma unroll
   for (int kq = 0; kq < 4; ++kq) {
-    f32x4 gq = f32x4{0.f, 0.f, 0.f, 0.f};  // G[4 j + kq], j = 0..3 (E = 16: the whole embedding)
+    f32x4 gq = f32x4{0.f, 0.f, 0.f, 0.f};  // G[4 j + kq], j = 0..3: the first 16 entries (E = 16: the whole embedding)
 #pragma unroll
     for (int j = 0; j < 4; ++j) gq[j] = 4 * j + kq < E ? G[4 * j + kq] : 0.f;
 #pragma unroll
@@ -333,6 +333,25 @@ __device__ __forceinline__ void resblock4_valu(const Ctx &c, const int (&o)[kOpI
         sc[k] += wss[kq][k][0][j] * gq[j];
         sh[k] += wss[kq][k][1][j] * gq[j];
       }
+  }
+  // a wider embedding (validate() takes E = 32 at 4 positions): its further 16-entry k-blocks, 256 packed floats each
+  for (int kb = 1; kb < (E >> 4); ++kb) {
+#pragma unroll
+    for (int kq = 0; kq < 4; ++kq) {
+      f32x4 gq;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) gq[j] = G[16 * kb + 4 * j + kq];
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const f32x4 ws = *reinterpret_cast<const f32x4 *>(w + ss_w + kb * 256 + (kq * 16 + 2 * h + k) * 4);
+        const f32x4 wh = *reinterpret_cast<const f32x4 *>(w + ss_w + kb * 256 + (kq * 16 + 4 + 2 * h + k) * 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          sc[k] += ws[j] * gq[j];
+          sh[k] += wh[j] * gq[j];
+        }
+      }
+    }
   }
   auto conv3 = [&](const float (&in)[4], const f32x4 (&wc)[4][2], const float (&bc)[2], float (&out)[2]) {
     float lft[4], rgt[4];

@@ -243,9 +243,12 @@ __device__ __forceinline__ void gemm_sm3_pl(const Ctx &c, const float *__restric
         __builtin_amdgcn_sched_barrier(0);
       }
     };
-    for (int kb0 = 0; kb0 < kb32; kb0 += 2) {   // 4 or 8 blocks here
+    for (int kb0 = 0; kb0 < kb32; kb0 += 2) {   // 4 or 8 blocks, or one (a 16- or 32-channel level in front of the 256-channel one)
 #pragma unroll
-      for (int st = 0; st < 6; ++st) step(st, kb0);
+      for (int st = 0; st < 3; ++st) step(st, kb0);
+      if (kb0 == last) break;   // an odd block count: the trip's second block does not exist (its steps would multiply block 0 again)
+#pragma unroll
+      for (int st = 3; st < 6; ++st) step(st, kb0);
     }
   }
 }
@@ -657,8 +660,10 @@ __device__ __forceinline__ void conv_pm3_cin4_any(const Ctx &c, const float *wp,
       const int co = rd * 32 + c.wave * 4 + k;
       if (co < cout) d3[pswz(co, n)] = out[rd][k];
     }
-    // the new residual stream's planes (a wave's 4 channels are one half of an 8-group; cout % 32 == 0)
-    if (rd * 32 < cout && cout <= kPlaneMaxC)
+    // the new residual stream's planes (a wave's 4 channels are one half of an 8-group; cout % 32 == 0).  A 256-channel
+    // level behind the first one keeps them in its one plane set, which starts where the X planes do
+    static_assert(PG<4>::kW == kPlaneX, "the 256-channel level's planes start at the X planes");
+    if (rd * 32 < cout)
       store_planes4(c.lds + kPlaneX, rd * 32 + c.wave * 4, n, out[rd][0], out[rd][1], out[rd][2], out[rd][3]);
   }
 }
