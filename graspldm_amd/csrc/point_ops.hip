@@ -8,7 +8,7 @@
 
 #include "host_util.h"
 
-GLDM_API int gldm_abi_version(void) { return 15; }
+GLDM_API int gldm_abi_version(void) { return GLDM_ABI_VERSION; }
 
 GLDM_API const char *gldm_status_string(int status) {
   switch (status) {

@@ -21,9 +21,6 @@
 namespace {
 
 constexpr int kUThreads = 256, kUWaves = kUThreads / 64;
-constexpr int kUOpInts = 16;
-enum { UOP_CONV = 1, UOP_GN = 2, UOP_ATT = 3, UOP_FINAL = 4, UOP_STEM = 5 };
-constexpr int kEmbPitch = 18;   // EMB rows: 16 columns + 2 (the four lane groups of a B read fall into different banks)
 
 struct UArgs {
   gldm_unet1d_desc d;
@@ -311,21 +308,21 @@ __global__ __launch_bounds__(kUThreads) void unet1d_kernel(const UArgs a) {
             v = silu(te);
           }
         }
-        lds[d.o_emb + e * kEmbPitch + s] = v;
+        lds[d.o_emb + e * GLDM_UNET1D_EMB_PITCH + s] = v;
       }
     }
     __syncthreads();
     for (int i = 0; i < d.n_ops; ++i) {
-      const int *op = prog + i * kUOpInts;
+      const int *op = prog + i * GLDM_UNET1D_OP_INTS;
       const int kind = op[0];
-      if (kind == UOP_CONV) {
+      if (kind == GLDM_UNET1D_OP_CONV) {
         UConv c{op[1], op[2], op[3], op[4], op[5], op[6], op[7], op[8], op[9], op[10], op[11], op[12], op[13], op[14], op[15]};
         u_conv<F32>(lds, w, S, wave, lane, c);
-      } else if (kind == UOP_GN) {
+      } else if (kind == GLDM_UNET1D_OP_GN) {
         u_groupnorm(lds, w, S, wave, lane, op, d.o_ss);
-      } else if (kind == UOP_ATT) {
+      } else if (kind == GLDM_UNET1D_OP_ATT) {
         u_attention<F32>(lds, w, S, tid, wave, lane, op, d);
-      } else if (kind == UOP_STEM) {   // init_conv: Conv1d(1 -> C, k = 7, pad 3) of the latent row
+      } else if (kind == GLDM_UNET1D_OP_STEM) {   // init_conv: Conv1d(1 -> C, k = 7, pad 3) of the latent row
         const int dst = op[1], C = op[2], pitch = op[3], wo = op[4], bo = op[5];
         for (int it = tid; it < C * S * L; it += kUThreads) {
           const int c = it / (S * L), col = it - c * (S * L), s = col / L, p = col - s * L;
@@ -336,7 +333,7 @@ __global__ __launch_bounds__(kUThreads) void unet1d_kernel(const UArgs a) {
           }
           lds[dst + c * pitch + col] = acc;
         }
-      } else if (kind == UOP_FINAL) {  // final_conv: Conv1d(C -> 1, k = 1)
+      } else if (kind == GLDM_UNET1D_OP_FINAL) {  // final_conv: Conv1d(C -> 1, k = 1)
         const int xb = op[1], C = op[2], pitch = op[3], wo = op[4], bo = op[5];
         for (int col = tid; col < S * L; col += kUThreads) {
           float acc = w[bo];

@@ -17,9 +17,10 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from ._abi import CONSTANTS
 from .r1d_pack import SCHED_COEF_STRIDE
 
-SCHED_DPMPP = 3
+SCHED_DPMPP = CONSTANTS["GLDM_SCHED_DPMPP"]
 
 
 def _log(t, eps=1e-20):

@@ -1,12 +1,14 @@
 """Device-side handle of one packed 1-D ResNet (denoiser or pose decoder):
 owns the packed weight buffer on the GPU and calls the fused HIP engine through
 the C ABI (gldm_r1d_cond_embed / gldm_denoise / gldm_decode / gldm_encode)."""
-import ctypes
-
 import torch
 
 from . import _lib as L
+from ._abi import CONSTANTS
 from .r1d_pack import SCHED_DDIM, SCHED_DDPM, SCHED_NONE, SCHED_COEF_STRIDE, pack_resnet1d  # noqa: F401
+
+# bytes of the hand-off error word in a workspace (contract of gldm_r1d_workspace_bytes)
+_WS_ERROR = slice(CONSTANTS["GLDM_R1D_WS_ERROR"], CONSTANTS["GLDM_R1D_WS_ERROR"] + 4)
 
 
 class R1dEngine:
@@ -23,7 +25,7 @@ class R1dEngine:
 
     # -- helpers
     def _desc_ptr(self):
-        return ctypes.cast(ctypes.pointer(self.desc), ctypes.c_void_p)
+        return L.ref(self.desc)
 
     def _workspace(self, n):
         with torch.cuda.device(self.device):   # the size depends on the device's compute-unit count (park scratch per workgroup)
@@ -39,7 +41,7 @@ class R1dEngine:
 
     def workspace_errors(self):
         """Sum of the hand-off error words of every workspace (0 unless a bounded wait expired); synchronises."""
-        return int(sum(int(ws[12:16].view(torch.int32).item()) for ws in self._ws.values()))
+        return int(sum(int(ws[_WS_ERROR].view(torch.int32).item()) for ws in self._ws.values()))
 
     # A step-segment hand-off whose bounded wait expires (csrc/r1d_chain.h: chain_take) poisons its tile with NaN
     # and sets the workspace's error word.  The word is copied to pinned host memory behind every multi-step launch
@@ -49,7 +51,7 @@ class R1dEngine:
         host, _ = self._probe.get(key, (None, None))
         if host is None:
             host = torch.zeros(1, dtype=torch.int32).pin_memory()
-        host.copy_(ws[12:16].view(torch.int32), non_blocking=True)
+        host.copy_(ws[_WS_ERROR].view(torch.int32), non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.device))
         self._probe[key] = (host, ev)
@@ -62,7 +64,7 @@ class R1dEngine:
             ev.synchronize()
         if int(host[0]) != 0:
             host[0] = 0
-            self._ws[key][12:16].zero_()
+            self._ws[key][_WS_ERROR].zero_()
             raise L.GldmError("gldm_denoise: a step-segment hand-off between workgroups timed out (workspace error word "
                               "set); the latents of that launch are invalid (NaN) and must be discarded")
 

@@ -8,46 +8,21 @@ A-fragment order, the combined scale/shift bias, and the time_mlp table
 [T, E] (resnets.py:44-56,517-522), evaluated with the same torch CPU ops the
 reference module uses so that large-argument sin/cos are identical.
 """
-import ctypes
 import math
 
 import torch
 import torch.nn.functional as F
 
-MAX_LEVELS = 6
-MAX_RESBLOCKS = 2 * MAX_LEVELS + 1
-SCHED_NONE, SCHED_DDIM, SCHED_DDPM = 0, 1, 2
-SCHED_COEF_STRIDE = 8
-HEAD_DECODER, HEAD_ENCODER = 0, 1
-MAX_LATENT = 32
+from . import _abi
 
-
-class R1dResblock(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in
-                ("c1_w", "c1_b", "n1_w", "n1_b", "c2_w", "c2_b", "n2_w", "n2_b", "ss_w", "ss_b", "c1_w3", "c2_w3",
-                 "c1_wq", "c2_wq")]
-
-
-class R1dLevel(ctypes.Structure):
-    _fields_ = [("ln_g", ctypes.c_int32), ("qkv_w", ctypes.c_int32 * 2), ("out_w", ctypes.c_int32),
-                ("out_b", ctypes.c_int32), ("ln2_g", ctypes.c_int32), ("down_w", ctypes.c_int32),
-                ("down_b", ctypes.c_int32), ("qkvn_w", ctypes.c_int32), ("qkvn_s", ctypes.c_int32),
-                ("qkvn_w3", ctypes.c_int32), ("out_w3", ctypes.c_int32), ("down_w3", ctypes.c_int32),
-                ("qkvn_wq", ctypes.c_int32), ("out_wq", ctypes.c_int32), ("down_wq", ctypes.c_int32)]
-
-
-class R1dDesc(ctypes.Structure):
-    """Mirror of `gldm_r1d_desc` (include/gldm.h)."""
-    _fields_ = [("seq_len", ctypes.c_int32), ("n_levels", ctypes.c_int32),
-                ("dims", ctypes.c_int32 * (MAX_LEVELS + 1)),
-                ("emb_dim", ctypes.c_int32), ("cond_rows", ctypes.c_int32), ("groups", ctypes.c_int32),
-                ("init_w", ctypes.c_int32), ("init_b", ctypes.c_int32),
-                ("ss_rows", ctypes.c_int32),
-                ("rb", R1dResblock * MAX_RESBLOCKS), ("lv", R1dLevel * MAX_LEVELS),
-                ("final_w", ctypes.c_int32), ("final_b", ctypes.c_int32),
-                ("latent_dim", ctypes.c_int32), ("in_w", ctypes.c_int32), ("in_b", ctypes.c_int32),
-                ("head_w", ctypes.c_int32), ("head_b", ctypes.c_int32), ("n_head", ctypes.c_int32),
-                ("head_kind", ctypes.c_int32)]
+# the descriptor structs and constants of include/gldm.h, under the names the packers and engines use
+_C = _abi.CONSTANTS
+MAX_LEVELS = _C["GLDM_R1D_MAX_LEVELS"]
+SCHED_NONE, SCHED_DDIM, SCHED_DDPM = _C["GLDM_SCHED_NONE"], _C["GLDM_SCHED_DDIM"], _C["GLDM_SCHED_DDPM"]
+SCHED_COEF_STRIDE = _C["GLDM_SCHED_COEF_STRIDE"]
+HEAD_DECODER, HEAD_ENCODER = _C["GLDM_HEAD_DECODER"], _C["GLDM_HEAD_ENCODER"]
+MAX_LATENT = _C["GLDM_R1D_MAX_LATENT"]
+R1dResblock, R1dLevel, R1dDesc = (_abi.STRUCTS[n] for n in ("gldm_r1d_resblock", "gldm_r1d_level", "gldm_r1d_desc"))
 
 
 def mfma_a_fragments(w2d):

@@ -1,8 +1,6 @@
 """Device-side handle of one Unet1D: owns the packed weight buffers on the GPU (one per sequence length met: the
 program's LDS map is laid out for a length) and calls the fused kernel through the C ABI (gldm_unet1d).  Same interface
 as r1d.R1dEngine where GaussianDiffusion1D.sample uses it (`cond_embed`, `denoise`), plus `forward`."""
-import ctypes
-
 import torch
 
 from . import _lib as L
@@ -15,7 +13,7 @@ def check_supported(desc, seq_len):
     Passing it is necessary, not sufficient: the widest shapes inside the envelope do not fit the 160 KiB of LDS even with
     one sample per tile, and the packer refuses those (unet1d_pack.choose_tile_samples: NotImplementedError as well, and
     also before any HIP call)."""
-    st = L.lib().gldm_unet1d_supported(ctypes.cast(ctypes.pointer(desc), ctypes.c_void_p), int(seq_len))
+    st = L.lib().gldm_unet1d_supported(L.ref(desc), int(seq_len))
     if st != 0:
         raise NotImplementedError(
             f"Unet1D outside the fused kernel's envelope (dim in {{16, 32}}, 2..4 dim_mults, widths multiples of 16 up to 256, "
@@ -110,7 +108,7 @@ class UnetEngine:
         if step_noise is not None:
             step_noise = step_noise.contiguous().float()
         with torch.cuda.device(self.device):
-            L.call("gldm_unet1d", ctypes.cast(ctypes.pointer(plan["desc"]), ctypes.c_void_p), L.ptr(plan["weights"]),
+            L.call("gldm_unet1d", L.ref(plan["desc"]), L.ptr(plan["weights"]),
                    L.ptr(plan["temb"]), L.ptr(cemb), int(samples_per_cond), L.ptr(x_in), n, seq_len, L.ptr(timesteps),
                    L.ptr(sample_t), n_steps, int(sched_kind), 1 if clip_sample else 0, L.ptr(coef), L.ptr(step_noise),
                    L.ptr(out), L.current_stream(self.device))

@@ -8,29 +8,24 @@ time-embedding table [T, E], and the network itself as the PROGRAM the kernel in
 laid out (and bounds-checked) here for one sequence length and one tile size.  `run_program_cpu` executes the same program
 with torch on the CPU: the packer and the LDS map are pinned without a GPU.
 """
-import ctypes
 import math
 
 import torch
 import torch.nn.functional as F
 
+from . import _abi
 from .r1d_pack import _Buf, split_f16x2, time_embedding_table, weight_standardize
 
-MAX_LEVELS = 4
-OP_CONV, OP_GN, OP_ATT, OP_FINAL, OP_STEM = 1, 2, 3, 4, 5
-OP_INTS = 16
-EMB_PITCH = 18
+# the descriptor, the limits and the program format of include/gldm.h (csrc/unet1d.hip interprets the same constants)
+_C = _abi.CONSTANTS
+MAX_LEVELS = _C["GLDM_UNET1D_MAX_LEVELS"]
+OP_CONV, OP_GN, OP_ATT, OP_FINAL, OP_STEM = (_C["GLDM_UNET1D_OP_" + n] for n in ("CONV", "GN", "ATT", "FINAL", "STEM"))
+OP_INTS = _C["GLDM_UNET1D_OP_INTS"]
+EMB_PITCH = _C["GLDM_UNET1D_EMB_PITCH"]
+UnetDesc = _abi.STRUCTS["gldm_unet1d_desc"]
 LDS_MAX_BYTES = 160 * 1024
 LDS_TWO_PER_CU = 80 * 1024
 HEADS, DIM_HEAD = 4, 32
-
-
-class UnetDesc(ctypes.Structure):
-    """Mirror of `gldm_unet1d_desc` (include/gldm.h)."""
-    _fields_ = [("dim", ctypes.c_int32), ("n_levels", ctypes.c_int32), ("widths", ctypes.c_int32 * (MAX_LEVELS + 1))] + \
-               [(n, ctypes.c_int32) for n in
-                ("groups", "emb_dim", "cond_rows", "time_cond", "has_emb", "exact_f32", "seq_len", "tile_samples",
-                 "lds_floats", "prog_off", "n_ops", "o_lat", "o_eps", "o_emb", "o_ss", "o_qkv", "o_o", "o_a", "n_floats")]
 
 
 def f32_fragments(w2d):

@@ -5,11 +5,12 @@ the PVD Attention block over the voxels stands in place of the second Swish (pvc
 import torch
 
 from . import _lib as L
+from ._abi import CONSTANTS
 from .r1d_pack import mfma_a_fragments
 
 # Which (cin, cout, r) a conv kernel is instantiated for is the library's answer (gldm_conv3d_k3_supported reads the list
 # the dispatch reads, csrc/conv3d.hip).  What stands next to it in a predicate below is routing policy.
-_F32, _F16X2 = 0, 1       # include/gldm.h: gldm_conv3d_kind
+_F32, _F16X2 = CONSTANTS["GLDM_CONV3D_F32"], CONSTANTS["GLDM_CONV3D_F16X2"]   # gldm_conv3d_kind
 CONV_ROW_TILE = 16        # policy: whole 16-row m-tiles only (the f32 kernels guard a partial last tile: packed by pack_conv3d, run and compared, not timed: tests/test_envelope_gpu.py::test_conv3d_f32_guarded_rows_and_halves)
 FIRST_VOXEL_CONV = (3, 48, 24)   # policy: the shipped encoder's first conv has an f32 form of its own under f32_only() (DESIGN_HISTORY.md, round 6)
 

@@ -32,7 +32,10 @@ enum gldm_status {
   GLDM_ERR_WORKSPACE = -4    /* caller workspace too small */
 };
 
-/* ABI version (bumped on any signature change) and a static message per status. */
+/* ABI version (bumped on any signature change) and a static message per status.  gldm_abi_version() returns the
+ * GLDM_ABI_VERSION the library was built with; the Python binding (graspldm_amd/_abi.py) is derived from this header and
+ * compares the two, so a library built from another revision of the header is refused. */
+#define GLDM_ABI_VERSION 15
 int gldm_abi_version(void);
 const char *gldm_status_string(int status);
 
@@ -947,8 +950,8 @@ int gldm_select_grasps(const float *H /*[b*g,4,4]*/, const float *score /*[b*g]*
 /* ---- Unet1D (additive; ref: grasp_ldm/models/modules/resnets.py:622-857) ------------------------------------------------
  * One kernel carries a tile of `tile_samples` samples through the whole U-net and through every sampler step; the skip
  * stack, the stem's output and the residual stream stay in LDS (csrc/unet1d.hip).  The packed buffer holds the weights and,
- * at `prog_off`, the network as a PROGRAM of n_ops ops of 16 int32 each (graspldm_amd/unet1d_pack.py writes and
- * bounds-checks it; LDS offsets in floats, weight offsets in floats from the buffer's start, -1 = absent):
+ * at `prog_off`, the network as a PROGRAM of n_ops ops of GLDM_UNET1D_OP_INTS int32 each, the first the op's code (enum
+ * gldm_unet1d_op; graspldm_amd/unet1d_pack.py writes and bounds-checks it; LDS offsets in floats, weight offsets in floats from the buffer's start, -1 = absent):
  *   CONV  {1, src0, c0, pitch_in, src1, c1, dst, pitch_out, M, mode, taps, Lin, Lout, w, bias, add}
  *         dst[M][col] = W im2col(src0 | src1) + bias + add.  mode 0: taps centred (k = 1 / 3, resnets.py:130,191,748,767);
  *         1: k = 4, stride 2, pad 1 (Downsample, :75-76); 2: nearest x2 then k = 3, pad 1 (Upsample, :68-72).  A second
@@ -961,6 +964,12 @@ int gldm_select_grasps(const float *H /*[b*g,4,4]*/, const float *score /*[b*g]*
  *         (:211-235), or with ln2_g = -1 Residual(PreNorm(Attention)) (:238-261); qkv_w rows in head-major order
  *         [head][q|k|v][32], out_w one [C x 32] matrix per head
  *   FINAL {4, x, C, pitch, w, b}  final_conv (:776,857)        STEM {5, dst, C, pitch, w, b}  init_conv (:681,805) */
+enum gldm_unet1d_op {
+  GLDM_UNET1D_OP_CONV = 1, GLDM_UNET1D_OP_GN = 2, GLDM_UNET1D_OP_ATT = 3, GLDM_UNET1D_OP_FINAL = 4, GLDM_UNET1D_OP_STEM = 5
+};
+#define GLDM_UNET1D_OP_INTS 16   /* int32 per op */
+/* Pitch of the o_emb rows: 16 columns + 2 (the four lane groups of a B read fall into different banks). */
+#define GLDM_UNET1D_EMB_PITCH 18
 #define GLDM_UNET1D_MAX_LEVELS 4
 typedef struct gldm_unet1d_desc {
   int32_t dim, n_levels;
@@ -975,7 +984,7 @@ typedef struct gldm_unet1d_desc {
   int32_t lds_floats;   /* dynamic LDS of a workgroup                                                           */
   int32_t prog_off, n_ops;
   int32_t o_lat, o_eps; /* [tile_samples][L] current latent row / network output                                */
-  int32_t o_emb;        /* [emb_dim][18] summed SiLU(embedding) per sample column                               */
+  int32_t o_emb;        /* [emb_dim][GLDM_UNET1D_EMB_PITCH] summed SiLU(embedding) per sample column            */
   int32_t o_ss;         /* [2 C][tile_samples] scale (+1, summed over R) and shift rows of the running block    */
   int32_t o_qkv, o_o, o_a; /* attention: one head's q|k|v rows [96][pitch], its output [32][pitch], A [S][L][L]  */
   int32_t n_floats;     /* length of the packed buffer                                                          */

@@ -33,9 +33,133 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_python_binding_covers_every_declared_symbol():
-    from graspldm_amd import _lib
-    bound = set(_lib._SIGNATURES) | {"gldm_abi_version", "gldm_status_string", "gldm_r1d_workspace_bytes", "gldm_r1d_tile_columns", "gldm_conv3d_partial_floats", "gldm_squeeze_parts"}
-    assert set(_declared()) <= bound, sorted(set(_declared()) - bound)
+    """Every name the loose pattern finds in the header is bound on the loaded library, argument and return types both, with
+    what graspldm_amd/_abi.py derived from its prototype (nothing is bound by hand, nothing falls back to ctypes' defaults)."""
+    from graspldm_amd import _abi, _lib
+    h = _lib.lib()
+    assert set(_declared()) == set(_abi.PROTOTYPES) == set(_lib._SIGNATURES)
+    for name in _declared():
+        restype, argtypes = _abi.PROTOTYPES[name]
+        fn = getattr(h, name)
+        assert fn.restype is restype and restype is not None, name
+        assert list(fn.argtypes) == argtypes == _lib._SIGNATURES[name], name
+
+
+_i, _f, _ll, _ull, _vp = ctypes.c_int, ctypes.c_float, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_void_p
+# literal signatures of entries that between them use every mapping of the parser
+PINNED = {
+    "gldm_abi_version": (_i, []),
+    "gldm_status_string": (ctypes.c_char_p, [_i]),
+    "gldm_denoise_rng": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _ull, _ll, _vp, _vp, _vp, _vp]),
+    "gldm_normalize_cloud": (_i, [_vp, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp]),
+    "gldm_sa_mlp_f16x2_lds_bytes": (_ll, [_i, _i, _i, _i, _vp, _vp, _vp]),
+    "gldm_conv3d_partial_floats": (_ll, [_i, _i, _i]),
+    "gldm_r1d_workspace_bytes": (_ll, [_vp, _i]),
+    "gldm_unet1d": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "gldm_ball_query_multi": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "gldm_segment_tile_shape": (_i, [_vp, _vp]),
+    "gldm_bias_act": (_i, [_vp, _vp, _i, _i, _ll, _i, _vp]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(PINNED))
+def test_derived_signature_matches_the_pinned_literal(name):
+    from graspldm_amd import _abi
+    assert _abi.PROTOTYPES[name] == PINNED[name]
+
+
+def _layout_lines(abi):
+    """What the C program of the next test prints, from the ctypes classes and the constants dict."""
+    lines = []
+    for sname, cls in abi.STRUCTS.items():
+        lines.append(f"{sname} {ctypes.sizeof(cls)}")
+        for fname, _ in cls._fields_:
+            f = getattr(cls, fname)
+            lines.append(f"{sname}.{fname} {f.offset} {f.size}")
+    return lines + [f"{k} {v}" for k, v in abi.CONSTANTS.items()]
+
+
+def test_struct_layouts_and_constants_match_the_c_compiler(tmp_path):
+    """The check that does not go through the parser: a C program including gldm.h prints sizeof of every struct, offsetof
+    and size of every field and the value of every constant; the host compiler's answers equal the derived ones line by line."""
+    import subprocess
+    from graspldm_amd import _abi
+    assert list(_abi.STRUCTS) == ["gldm_r1d_resblock", "gldm_r1d_level", "gldm_r1d_desc", "gldm_unet1d_desc"]
+    assert [ctypes.sizeof(c) for c in _abi.STRUCTS.values()] == [56, 64, 1208, 104]
+    assert len(_abi.CONSTANTS) >= 27 and _abi.CONSTANTS["GLDM_ABI_VERSION"] == 15
+    body = []
+    for sname, cls in _abi.STRUCTS.items():
+        body.append(f'printf("{sname} %zu\\n", sizeof({sname}));')
+        for fname, _ in cls._fields_:
+            body.append(f'printf("{sname}.{fname} %zu %zu\\n", offsetof({sname}, {fname}), sizeof((({sname} *)0)->{fname}));')
+    body += [f'printf("{k} %lld\\n", (long long)({k}));' for k in _abi.CONSTANTS]
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "gldm.h"\nint main(void) {\n  '
+                   + "\n  ".join(body) + "\n  return 0;\n}\n")
+    exe = tmp_path / "layout"
+    subprocess.run([os.environ.get("CC", "cc"), "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src),
+                    "-o", str(exe)], check=True, capture_output=True, text=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines()
+    want = _layout_lines(_abi)
+    assert out == want, [(a, b) for a, b in zip(out, want) if a != b][:10]
+
+
+GOOD = """
+/* int gldm_in_a_comment(float (*f)(int)); */
+#define GLDM_N 3
+#define GLDM_M (2 * GLDM_N + 1)   /* 7 */
+enum gldm_kind { GLDM_A, GLDM_B = GLDM_M - 2, GLDM_C };
+typedef void *gldm_stream_t;
+typedef struct gldm_in { int32_t a, b[2]; } gldm_in;
+typedef struct gldm_out {
+  int32_t n;
+  gldm_in one, many[GLDM_M];
+} gldm_out;
+int gldm_f(const gldm_out *d, const float *x /*[n]*/, int32_t *const *rows, int n, float eps, long long big,
+           unsigned long long seed, gldm_stream_t stream);
+long long gldm_g(void);
+const char *gldm_h(int status);
+"""
+
+
+def test_parser_on_synthetic_text():
+    from graspldm_amd import _abi
+    protos, structs, consts = _abi.parse(GOOD)
+    assert consts == {"GLDM_N": 3, "GLDM_M": 7, "GLDM_A": 0, "GLDM_B": 5, "GLDM_C": 6}
+    assert protos == {"gldm_f": (_i, [_vp, _vp, _vp, _i, _f, _ll, _ull, _vp]), "gldm_g": (_ll, []),
+                      "gldm_h": (ctypes.c_char_p, [_i])}
+    assert list(structs) == ["gldm_in", "gldm_out"] and ctypes.sizeof(structs["gldm_in"]) == 12
+    out = structs["gldm_out"]
+    assert ctypes.sizeof(out) == 4 + 12 + 7 * 12 and out.many.offset == 16 and out.one.size == 12
+    d = out()
+    d.many[6].b[1] = 9
+    assert bytes(d)[-4:] == (9).to_bytes(4, "little")
+
+
+@pytest.mark.parametrize("bad", [
+    "int gldm_x(size_t n);",                                        # unknown type word
+    "int gldm_x(const half *p);",                                   # unknown pointee
+    "void gldm_x(int n);",                                          # unknown return type
+    "int gldm_x(int (*callback)(int), int n);",                     # function-pointer parameter
+    "typedef struct gldm_s { int32_t a; float b; } gldm_s;",        # float field
+    "typedef struct gldm_s { int32_t *a; } gldm_s;",                # pointer field
+    "typedef struct gldm_s { int32_t a[GLDM_UNDEFINED]; } gldm_s;",  # array size that is no known constant
+    "typedef struct gldm_s { int32_t a; } gldm_s;\nint gldm_x(gldm_s by_value, int n);",   # struct by value
+    "int gldm_x(int n) __attribute__((deprecated));",               # a declared gldm_x( the prototype pattern misses
+    "int gldm_ok(int n);\nint gldm_x(int n, ...)\n;int gldm_y(int (*f)(void));",
+    "#define GLDM_EPS 1e-5f",                                       # a constant that is no integer
+])
+def test_parser_raises_on_what_it_does_not_understand(bad):
+    from graspldm_amd import _abi
+    with pytest.raises(_abi.GldmError):
+        _abi.parse("typedef void *gldm_stream_t;\n" + bad + "\n")
+
+
+def test_missing_header_is_an_error(monkeypatch, tmp_path):
+    from graspldm_amd import _abi
+    monkeypatch.setattr(_abi, "HEADER", str(tmp_path / "gldm.h"))
+    with pytest.raises(_abi.GldmError, match="missing"):
+        _abi._load()
 
 
 def test_invalid_arguments_return_status_not_exit():
