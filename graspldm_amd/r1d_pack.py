@@ -37,14 +37,25 @@ def mfma_a_fragments(w2d):
 
 
 class SplitRangeError(ValueError):
-    """A weight does not fit the f16 split (|w| >= 65504): the caller packs the layer for its f32-pipe kernel instead."""
+    """A weight does not fit the f16 split (|w| >= 65504, or so small that the split loses it: SplitPrecisionError): the
+    caller packs the layer for its f32-pipe kernel instead."""
+
+
+class SplitPrecisionError(SplitRangeError):
+    """The split form of a matrix is not accurate enough (split_fits): the small end of the f16 range."""
+
+
+SPLIT_TAU = 5e-6   # a quarter of the 2e-5 single-forward parity bar (the margin tests/test_r1d_envelope_cpu.py gives the oracle)
 
 
 def split_f16x2(w):
     """f32 -> (hi, lo) f16, round to nearest at each stage: hi + lo == w up to 2^-22 |w| while |w| >= 2^-3; below that lo
     is an f16 SUBNORMAL (the matrix pipe keeps those: tools/micro/mfma_f16_split) and the error is 2^-25 ABSOLUTE -- a
     weight of 0.03 keeps ~20 bits, one of 1e-3 ~15 (what the CPU restatement measures: 1.7e-6 on a denoiser forward against
-    5.4e-7 for three bf16 pieces; the bar is 2e-5).  Values beyond the f16 range (|w| >= 65504) raise SplitRangeError."""
+    5.4e-7 for three bf16 pieces; the bar is 2e-5).  Values beyond the f16 range (|w| >= 65504) raise SplitRangeError.
+    The small end is not decided here but per matrix: the fragment packers (mfma_a_fragments_f16x2,
+    unet1d_pack.f16x2_fragments) ask split_fits and raise SplitPrecisionError where a row or a column of the matrix would
+    lose more than SPLIT_TAU of itself, and the layer then takes its f32 form like one beyond 65504."""
     w = w.detach().float()
     if w.numel() and not float(w.abs().max()) < 65504.0:
         raise SplitRangeError("split-f16 operands must stay below 65504 in magnitude (got %g)" % float(w.abs().max()))
@@ -53,17 +64,61 @@ def split_f16x2(w):
     return hi, lo
 
 
+def _planes_fit(w, hi, lo, tau):
+    w = w.detach().double()
+    r2 = (w - hi.double() - lo.double()) ** 2           # exact: the three terms and their difference are f64-representable
+    w2 = w * w
+    return all(bool((r2.sum(dim=d) <= tau * tau * w2.sum(dim=d)).all()) for d in (1, 0))
+
+
+def split_fits(w2d, tau=SPLIT_TAU):
+    """Whether the split form of a packed [M, K] matrix (padding included) is accurate enough: with the exact residual
+    r = w - (hi + lo), ||r||_2 <= tau ||w||_2 over every output row AND over every input column (all-zero rows and columns,
+    the padding, pass: 0 <= 0).  Data-free; a weight beyond the f16 range does not fit either.
+
+    Derivation.  The split GEMM's weight-side error on output i is sum_k r_ik x_k.  For inputs of comparable size and no
+    particular alignment that is ||r_i|| rms(x) against an output of ||w_i|| rms(x): the row ratio IS the relative rms
+    error of that output row against its own magnitude (a BatchNorm fold's quiet rows are re-amplified by the next
+    normalisation, so each row is held to itself, not to the tensor's loudest).  Where input channels carry different units
+    (a first layer: coordinates next to raw features) the terms of one column dominate and the same ratio, taken down the
+    column, bounds them; a conv's taps are separate columns here, which is the stricter reading and needs no knowledge of
+    the K layout (quad_perm32, pad_cin32, the voxel convs' tap pairs all permute or pad columns).  Not per element: any
+    trained layer has weights near zero, and they contribute nothing to either norm ratio.  tau = SPLIT_TAU, a quarter of the
+    2e-5 forward bar, from the bar and not from the kernels.  Below |w| = 2^-3 the residual is uniform within 2^-25
+    (rms 2^-25 / sqrt(3) = 1.7e-8), so a Kaiming matrix W = randn / sqrt(K) 2^-k has the ratio 1.7e-8 sqrt(K) 2^k:
+    the rule accepts k <= 4 at K = 128 and k <= 2 at K = 1536 (tests/test_weight_range_cpu.py measures both)."""
+    w = w2d.detach().float()
+    try:
+        hi, lo = split_f16x2(w)
+    except SplitRangeError:
+        return False
+    return _planes_fit(w, hi, lo, tau)
+
+
+def split_planes(w2d):
+    """split_f16x2 of a packed [M, K] matrix for a kernel that multiplies it in split form: SplitRangeError beyond the f16
+    range, SplitPrecisionError where split_fits says no.  Under numerics.f32_only() nothing multiplies the planes (the
+    descriptors name no split copy), so nothing is asked."""
+    from .numerics import split_enabled
+    hi, lo = split_f16x2(w2d)
+    if split_enabled() and not _planes_fit(w2d, hi, lo, SPLIT_TAU):
+        raise SplitPrecisionError("a row or a column of this %d x %d matrix is too small for split-f16 operands: its split form "
+                                  "loses more than %g of it (r1d_pack.split_fits)" % (w2d.shape[0], w2d.shape[1], SPLIT_TAU))
+    return hi, lo
+
+
 def mfma_a_fragments_f16x2(w2d):
     """[M, K] (K % 32 == 0) -> f32-typed bit container of the split-f16 A fragments of v_mfma_f32_16x16x32_f16:
     [M/16][K/32][plane hi|lo][lane 64][8 f16], lane l = W[16 mt + (l & 15)][32 kb + 8 (l >> 4) + j]
-    (include/gldm.h).  512 floats per (m-tile, 32-deep k-block)."""
+    (include/gldm.h).  512 floats per (m-tile, 32-deep k-block).  Raises SplitRangeError where the matrix does not fit the
+    split (split_planes)."""
     m, k = w2d.shape
     if k % 32:
         raise ValueError("split-f16 fragments need K % 32 == 0")
     mt = (m + 15) // 16
     wp = torch.zeros(mt * 16, k, dtype=torch.float32)
     wp[:m] = w2d
-    planes = torch.stack(split_f16x2(wp))                          # [2, M, K] f16
+    planes = torch.stack(split_planes(wp))                         # [2, M, K] f16
     planes = planes.view(2, mt, 16, k // 32, 4, 8)                 # (plane, mt, i, kb, g, j): k = 32 kb + 8 g + j
     frag = planes.permute(1, 3, 0, 4, 2, 5).contiguous()           # (mt, kb, plane, g, i, j): lane = 16 g + i
     return frag.reshape(-1, 8).view(torch.float32).reshape(-1)     # bit pattern kept: 8 f16 = 4 floats
@@ -133,6 +188,18 @@ def time_embedding_table(sd, p, num_steps):
 
 
 def pack_resnet1d(sd, p, groups, seq_len, cond_rows=3, num_steps=None, decoder=None, encoder=None):
+    """_pack_resnet1d; where a split copy would not be accurate enough (SplitPrecisionError: an engine has no per-layer
+    f32 form to fall back to), the whole network in the exact form numerics.f32_only() packs -- the descriptor names no
+    split copy and the sample-major engine runs exact f32 products."""
+    try:
+        return _pack_resnet1d(sd, p, groups, seq_len, cond_rows, num_steps, decoder, encoder)
+    except SplitPrecisionError:
+        from .numerics import f32_only
+        with f32_only():
+            return _pack_resnet1d(sd, p, groups, seq_len, cond_rows, num_steps, decoder, encoder)
+
+
+def _pack_resnet1d(sd, p, groups, seq_len, cond_rows=3, num_steps=None, decoder=None, encoder=None):
     """sd: flat state dict (CPU f32), p: prefix of the ResNet1D / TimeConditionedResNet1D.
     decoder: None or dict(in_w, in_b, tmrp_w, tmrp_b, cls_w, cls_b) for the pose decoder.
     encoder: None or dict(in_w, in_b, out_w, out_b, mu_w, mu_b, logvar_w, logvar_b) for the grasp encoder (exclusive with

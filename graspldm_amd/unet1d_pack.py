@@ -14,7 +14,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _abi
-from .r1d_pack import _Buf, split_f16x2, time_embedding_table, weight_standardize
+from .r1d_pack import SplitPrecisionError, _Buf, split_planes, time_embedding_table, weight_standardize
 
 # the descriptor, the limits and the program format of include/gldm.h (csrc/unet1d.hip interprets the same constants)
 _C = _abi.CONSTANTS
@@ -39,7 +39,7 @@ def f32_fragments(w2d):
 def f16x2_fragments(w2d):
     """[M, K] -> [M/16][K/32][plane hi|lo][lane 64][8 f16] as an f32-typed bit container (include/gldm.h)."""
     m, k = w2d.shape
-    planes = torch.stack(split_f16x2(w2d)).reshape(2, m // 16, 16, k // 32, 4, 8)   # (plane, mt, i, kb, g, j)
+    planes = torch.stack(split_planes(w2d)).reshape(2, m // 16, 16, k // 32, 4, 8)   # (plane, mt, i, kb, g, j)
     frag = planes.permute(1, 3, 0, 4, 2, 5).contiguous()
     return frag.reshape(-1, 8).view(torch.float32).reshape(-1)
 
@@ -204,6 +204,17 @@ def choose_tile_samples(prog):
 
 
 def pack_unet1d(sd, p, groups, seq_len, cond_rows=0, time_cond=False, num_steps=None, tile_samples=None):
+    """_pack_unet1d; where a matrix would not be accurate enough in split form (SplitPrecisionError), the whole network in
+    the exact_f32 form numerics.f32_only() packs: the kernel has one arithmetic per descriptor."""
+    try:
+        return _pack_unet1d(sd, p, groups, seq_len, cond_rows, time_cond, num_steps, tile_samples)
+    except SplitPrecisionError:
+        from .numerics import f32_only
+        with f32_only():
+            return _pack_unet1d(sd, p, groups, seq_len, cond_rows, time_cond, num_steps, tile_samples)
+
+
+def _pack_unet1d(sd, p, groups, seq_len, cond_rows=0, time_cond=False, num_steps=None, tile_samples=None):
     """sd: flat state dict (CPU f32), p: prefix of the Unet1D.  cond_rows: 0 without z_cond, 1 for [n, Dc], R for [n, R, Dc].
     -> dict(desc, weights, temb [T, E] | None, cond_w0/b0/w2/b2 | None, ops (the resolved program rows), lds (name -> offset))."""
     from .numerics import split_enabled

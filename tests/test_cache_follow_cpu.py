@@ -294,3 +294,44 @@ def test_source_list_encoder_folded_head():
         enc.__dict__.pop("_head_cache", None)
         return enc._folded_head()
     _check_source_list(cand, src, build)
+
+
+# ------------------------------------------------------------------------------- the split rule lives under the same keys
+def test_folded_layer_crosses_the_split_rule_in_both_directions():
+    """r1d_pack.split_fits is decided inside the build the key guards: a running_var grown by 2^24 (folded rows at 2^-12)
+    drops the split fragments of that weight version and keeps the f32 ones, the old statistics bring them back bit for
+    bit, and nothing is re-decided while the key stands."""
+    from graspldm_amd import dense
+    from graspldm_amd.synthetic import load_synthetic_weights
+    conv = load_synthetic_weights(nn.Conv1d(128, 256, 1), seed=1)
+    bn = load_synthetic_weights(nn.BatchNorm1d(256), seed=2).eval()
+    first = dense.folded_conv_bn(conv, bn, CPU)
+    assert first.ws is not None and first.wp is not None and dense.folded_conv_bn(conv, bn, CPU) is first
+    with torch.no_grad():
+        bn.running_var.mul_(2.0 ** 24)
+    small = dense.folded_conv_bn(conv, bn, CPU)
+    assert small is not first and small.ws is None and small.ws_main is None and small.wp is not None
+    assert dense.folded_conv_bn(conv, bn, CPU) is small
+    with torch.no_grad():
+        bn.running_var.mul_(2.0 ** -24)
+    back = dense.folded_conv_bn(conv, bn, CPU)
+    assert back is not small and torch.equal(back.ws, first.ws) and torch.equal(back.wp, first.wp)
+
+
+def test_engine_crosses_the_split_rule_in_both_directions(recorder):
+    """The same at an engine site: a downsample conv at 2^-12 rebuilds the engine in the exact form (no split copy named),
+    the old weight rebuilds it with its split copies, and an untouched network is served from the entry."""
+    m, _, get, _ = _time_resnet()
+    first = get()
+    packed = lambda e: e.args[0]["desc"]   # noqa: E731
+    assert packed(first).lv[1].down_w3 != 0 and get() is first
+    with torch.no_grad():
+        m.blocks[1][3].weight.mul_(2.0 ** -12)
+    small = get()
+    assert small is not first and get() is small
+    assert all(lv.down_w3 == 0 and lv.out_w3 == 0 and lv.qkvn_w3 == 0 for lv in packed(small).lv)
+    with torch.no_grad():
+        m.blocks[1][3].weight.mul_(2.0 ** 12)
+    back = get()
+    assert back is not small and packed(back).lv[1].down_w3 == packed(first).lv[1].down_w3
+    assert torch.equal(back.args[0]["weights"], first.args[0]["weights"])

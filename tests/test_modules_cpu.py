@@ -209,8 +209,9 @@ def test_modules_refuse_cpu_tensors():
 def test_split_f16_fragments_are_tight_and_in_mfma_order():
     """mfma_a_fragments_f16x2 (include/gldm.h, "Split-f16 weight fragments"): hi + lo == w up to 2^-22 |w| (and 2^-25
     where the lo part is an f16 subnormal), and lane l of fragment (mt, kb, plane) holds
-    W[16 mt + (l & 15)][32 kb + 8 (l >> 4) + j].  Values beyond the f16 range are refused."""
-    from graspldm_amd.r1d_pack import mfma_a_fragments_f16x2, split_f16x2
+    W[16 mt + (l & 15)][32 kb + 8 (l >> 4) + j].  Values beyond the f16 range are refused, and so is a matrix with columns
+    too small for the split (split_fits: the 1e-6-sized columns of the first matrix)."""
+    from graspldm_amd.r1d_pack import SplitPrecisionError, mfma_a_fragments_f16x2, split_f16x2
     g = torch.Generator().manual_seed(0)
     w = torch.randn(40, 96, generator=g) * torch.logspace(-6, 3, 96).unsqueeze(0)   # wide dynamic range
     hi, lo = split_f16x2(w)
@@ -218,6 +219,10 @@ def test_split_f16_fragments_are_tight_and_in_mfma_order():
     err = (hi.float() + lo.float() - w).abs()
     assert (err <= torch.maximum(w.abs() * 2.0 ** -22, torch.full_like(w, 2.0 ** -25))).all()
     assert (lo.float().abs() <= hi.float().abs() * 2.0 ** -10 + 2.0 ** -24).all()
+    with pytest.raises(SplitPrecisionError):
+        mfma_a_fragments_f16x2(w)
+    w = torch.randn(40, 96, generator=g) * torch.logspace(-2, 3, 96).unsqueeze(0)   # the range the split form is packed for
+    hi, lo = split_f16x2(w)
     f = mfma_a_fragments_f16x2(w)
     assert f.dtype == torch.float32 and f.numel() == 3 * 3 * 2 * 64 * 4          # 3 m-tiles (40 -> 48 rows) x 3 k-blocks
     fb = f.view(torch.float16).view(3, 3, 2, 64, 8)
