@@ -26,6 +26,7 @@ namespace {
 
 constexpr int kHeadCols = 64;      // points per workgroup
 constexpr int kHeadRowsPass = 128; // rows of W1' per pass: 4 waves x 2 m-tiles
+constexpr int kHeadFoldKb = 4;     // exact_f32: 32-deep K blocks per partial sum
 constexpr int kHeadMaxRows = 512, kHeadMaxC = 2048, kHeadMaxN = 1 << 20;
 
 inline bool head_shape_ok(int c, int rows, int n) {
@@ -152,9 +153,31 @@ __global__ __launch_bounds__(256) void cls_head_kernel(const float *__restrict__
 #pragma unroll
     for (int mi = 0; mi < MT; ++mi) mt[mi] = min(mt0 + MT * wave + mi, mtiles - 1);   // clamped for the loads, masked below
 
+    // EX: folded into a total every kHeadFoldKb K blocks.  One f32 chain over c = 2048 is 512 dependent roundings at the
+    // magnitude of the finished row: 1.6 times the bar on a logit whose terms cancel.  Folded: 32 steps and c / 128 totals.
+    [[maybe_unused]] f32x4 total[EX ? MT : 1][EX ? NT : 1];
+    if constexpr (EX) {
+#pragma unroll
+      for (int mi = 0; mi < MT; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < NT; ++ni) total[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    auto fold = [&]() {
+      if constexpr (EX) {
+#pragma unroll
+        for (int mi = 0; mi < MT; ++mi)
+#pragma unroll
+          for (int ni = 0; ni < NT; ++ni) {
+            total[mi][ni] += acc[mi][ni];
+            acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+          }
+      }
+    };
+
     float v[8];
     fetch(0, v);
     for (int kb = 0; kb < kb32; ++kb) {
+      if (EX && kb && kb % kHeadFoldKb == 0) fold();
       stage(v);
       __syncthreads();
       if (kb + 1 < kb32) fetch(kb + 1, v);   // in flight while this slab multiplies
@@ -194,6 +217,13 @@ __global__ __launch_bounds__(256) void cls_head_kernel(const float *__restrict__
           for (int ni = 0; ni < NT; ++ni) acc[mi][ni] = mfma_split(a[mi], b[ni], acc[mi][ni]);
       }
       __syncthreads();
+    }
+    if constexpr (EX) {
+      fold();
+#pragma unroll
+      for (int mi = 0; mi < MT; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < NT; ++ni) acc[mi][ni] = total[mi][ni];
     }
 
     // epilogue on the accumulators: acc[mi][ni][r] = row 16 mt + 4 g + r, column 16 ni + r16

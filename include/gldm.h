@@ -762,7 +762,8 @@ int gldm_bias_act(float *y /*[b,c,n]*/, const float *bias /*[c]*/, int b, int c,
  * the block's input).  c % 16 == 0, 16 <= c <= 1024; n % 32 == 0, 32 <= n <= 4096; GLDM_ERR_UNSUPPORTED otherwise.
  * Default arithmetic: both products as three v_mfma_f32_16x16x32_f16 over hi / lo f16 pieces, f32 accumulation; every
  * 16-row group of an operand is split as x / s (s a power of two from the group's largest magnitude, folded back on the
- * accumulators) and P is split as 2^14 P.  exact_f32 != 0: the same stages on v_mfma_f32_16x16x4_f32.  Softmax subtracts
+ * accumulators) and P is split as 2^14 P.  exact_f32 != 0: the same stages on v_mfma_f32_16x16x4_f32, partial sums of 128
+ * channels (keys) added in K order, so that no f32 chain is longer than 32 steps plus K / 128 totals.  Softmax subtracts
  * the row maximum and divides once per row.  Deterministic (fixed summation order, no atomics); a cloud's result does
  * not depend on b or on its position in the batch.
  * `workspace`: at least gldm_point_attention_workspace_bytes(b, c, n) bytes (at most 256 MiB, or one cloud's need where
@@ -844,7 +845,7 @@ int gldm_grasp_scene(const float *pc /*[bc,np,3]*/, const float *H /*[bc*g,4,4]*
  * multiple of 32 ([rows/16][K/32][plane][lane][8 f16], see "Split-f16 weight fragments"); exact_f32 != 0: f32 A fragments
  * [rows/16][c/16][lane][4].  16-byte aligned.  The GEMM runs on the matrix pipe (three f16 products per f32 product, the
  * 64-point tile split as x / s with s the power of two that brings its largest magnitude into [2^13, 2^14); or
- * v_mfma_f32_16x16x4_f32); ReLU, w2 and
+ * v_mfma_f32_16x16x4_f32 with partial sums of 128 channels added in K order); ReLU, w2 and
  * l[n] are applied on the accumulators, neither [b,rows,n] nor [b,1,n] is written.  The sum over points runs in a fixed
  * order (lanes, waves, then one partial per 64-point tile in `workspace`, added in tile order by a second launch): no
  * atomics, bitwise repeatable, independent of b and of a scene's position.

@@ -40,9 +40,21 @@ def clearance(scene, H, body, sweep, r_sweep, cap):
 def pose_distance(H, ctrl):
     """H [G, 4, 4], ctrl [Np, 3] -> D [G, G] f64: mean squared distance of the control points placed at two poses
     (grasp_ldm/losses/loss.py:77-127), point by point."""
-    H, ctrl = H.double(), torch.as_tensor(ctrl).double()
-    pts = torch.einsum("gij,nj->gni", H[:, :3, :3], ctrl) + H[:, None, :3, 3]
+    pts = placed_points(H, ctrl)
     d = pts[:, None] - pts[None, :]
+    return (d * d).sum(-1).mean(-1)
+
+
+def placed_points(H, ctrl):
+    """H [G, 4, 4], ctrl [Np, 3] -> the control points placed at every pose [G, Np, 3] f64."""
+    H, ctrl = H.double(), torch.as_tensor(ctrl).double()
+    return torch.einsum("gij,nj->gni", H[:, :3, :3], ctrl) + H[:, None, :3, 3]
+
+
+def pose_distance_row(pts, i):
+    """Row i of pose_distance from placed_points' output [G] f64: the same definition, point by point, without the G x G x
+    Np x 3 tensor (6 GB at 2048 poses and 64 control points)."""
+    d = pts[i][None] - pts
     return (d * d).sum(-1).mean(-1)
 
 
@@ -55,7 +67,7 @@ def topk(score, keep, k):
 def diverse(H, score, keep, ctrl, k, min_separation=0.0):
     """One cloud, the greedy of gldm_select_grasps mode 1 in f64 -> (index padded with -1, count, gap list padded with 0,
     margins): margins[r] = (best - second best) / best of the m values at pick r >= 1 (inf when there is no second)."""
-    D = pose_distance(H, ctrl)
+    pts = placed_points(H, ctrl)
     g = H.shape[0]
     alive = [bool(keep[j]) for j in range(g)]
     picks, gaps, margins = [], [], []
@@ -64,7 +76,7 @@ def diverse(H, score, keep, ctrl, k, min_separation=0.0):
         picks.append(first)
         gaps.append(float("inf"))
         alive[first] = False
-        m = D[first].clone()
+        m = pose_distance_row(pts, first)
         while len(picks) < k and any(alive):
             cand = [j for j in range(g) if alive[j]]
             best = max(cand, key=lambda j: (float(m[j]), -j))
@@ -75,6 +87,6 @@ def diverse(H, score, keep, ctrl, k, min_separation=0.0):
             picks.append(best)
             gaps.append(float(m[best]) ** 0.5)
             alive[best] = False
-            m = torch.minimum(m, D[best])
+            m = torch.minimum(m, pose_distance_row(pts, best))
     n = len(picks)
     return picks + [-1] * (k - n), n, gaps + [0.0] * (k - n), margins
