@@ -14,7 +14,7 @@
 // Two workgroups fit per CU (62 KiB LDS each): one stages while the other computes.
 // Every conv's epilogue also emits per-brick per-channel (sum, sum of squares) (voxel_geom.h) so GroupNorm needs
 // no extra pass over the tensor for its statistics (combined in f64, fixed order).
-#include "mfma_core.h"
+#include "mfma_prims.h"
 #include "voxel_geom.h"
 
 namespace {
@@ -27,7 +27,7 @@ __device__ long long g_c3_stamp[32];
 #define GLDM_C3_STAMP(i) do {} while (0)
 #endif
 
-// Not mfma_core.h's dpp_mov: that one is __builtin_amdgcn_mov_dpp, this one update_dpp(0, ...), which has the compiler clear
+// Not mfma_prims.h's dpp_mov: that one is __builtin_amdgcn_mov_dpp, this one update_dpp(0, ...), which has the compiler clear
 // the destination with a v_mov_b32 in front of each.  Swapping it in changes the code of every conv kernel (fewer
 // v_mov_b32, more s_nop around the epilogue's DPP adds); whether that is faster has not been measured, so the form the
 // convs were tuned with stays.
@@ -314,7 +314,7 @@ __global__ __launch_bounds__(kConvThreads, 2) void conv3d_k3_kernel(const float 
 // ---- the same conv on split-f16 operands (the shipped encoder's two shapes: 48 ch @ 24^3 and 96 ch @ 12^3) ------------
 // v_mfma_f32_16x16x32_f16 with every f32 operand written as hi + lo (two f16 numbers, x = hi + lo up to 2^-22 |x|) and
 // the three partial products a_hi b_lo + a_lo b_hi + a_hi b_hi accumulated in f32 (mfma_split): 3/16 of the
-// f32-MFMA time (csrc/mfma_core.h, "split-f16 GEMM core": the measured accuracy is recorded there).  K is walked as (16-channel block, PAIR of taps):
+// f32-MFMA time (csrc/mfma_prims.h, "split-f16 products": the measured accuracy is recorded there).  K is walked as (16-channel block, PAIR of taps):
 // lane group g of a fragment = (tap 2 p + (g >> 1), channels 8 (g & 1) .. + 7); 27 taps = 13 pairs + one half-empty
 // (zero weights).  Work is walked in groups of 3 m-tiles x 3 n-tiles so that the A sets (double buffered), the B planes
 // and the accumulators fit 256 registers.  Weights: graspldm_amd/voxel.py: pack_conv3d_f16x2.
@@ -324,7 +324,7 @@ __global__ __launch_bounds__(kConvThreads, 2) void conv3d_k3_kernel(const float 
 
 constexpr int kPairs = 14;  // tap pairs per 16-channel block (the last one holds tap 26 and zeros)
 
-// Not mfma_core.h's wave_max: this one walks the offsets 32 .. 1, the shared one 1 .. 32 -- the same value, but the
+// Not mfma_prims.h's wave_max: this one walks the offsets 32 .. 1, the shared one 1 .. 32 -- the same value, but the
 // shared one reorders instructions in the twelve kernels that range a brick, and their code is to stay as measured.
 __device__ __forceinline__ float c3_wave_max(float x) {   // x >= 0: every lane ends with the wave's maximum
 #pragma unroll

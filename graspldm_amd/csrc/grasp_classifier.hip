@@ -20,7 +20,7 @@
 // one partial per workgroup in the workspace; a second launch adds a scene's partials in tile order.  No atomics, nothing
 // waits on another workgroup: a scene's logit does not depend on its place in the batch, on b or on any chunking.
 // Tail columns (n % 64) are staged as zeros and carry weight 0.
-#include "mfma_core.h"
+#include "mfma_prims.h"
 
 namespace {
 

@@ -1,4 +1,4 @@
-// host_util.h -- what every entry point of the sources outside the MFMA family (mfma_core.h has its own) needs around a
+// host_util.h -- what every entry point of the sources outside the MFMA family (mfma_prims.h has its own) needs around a
 // launch: the export macro, the status of the launch just made, the stream cast and the grid's rounding-up division.
 #pragma once
 #include <hip/hip_runtime.h>

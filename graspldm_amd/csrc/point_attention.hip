@@ -20,7 +20,7 @@
 // exact_f32: the same four stages with f32 fragments ([lane 64][4 f32] per 16-deep K block) on v_mfma_f32_16x16x4_f32, no
 // scales.  Fixed summation order everywhere, no atomics, nothing waits on another workgroup; a cloud's result does not
 // depend on its position in the batch, on b or on the chunking.
-#include "mfma_core.h"
+#include "mfma_prims.h"
 
 namespace {
 

@@ -23,7 +23,7 @@
 // exact_f32: the same stages on v_mfma_f32_16x16x4_f32 from f32 tiles in LDS, no scales.
 // Fixed summation order, no atomics, nothing waits on another workgroup; a cloud's bits do not depend on b, on its
 // position in the batch or on the stream.
-#include "mfma_core.h"
+#include "mfma_prims.h"
 
 namespace {
 

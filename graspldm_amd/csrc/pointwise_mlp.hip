@@ -1,4 +1,4 @@
-// pointwise_mlp.hip -- fused pointwise MLP layers on the GEMM cores of mfma_core.h.
+// pointwise_mlp.hip -- fused pointwise MLP layers on the tile GEMMs of tile_gemm.h.
 // y[b, :, cols] = act(W x[b, :, cols] + bias) for a k = 1 Conv1d + folded BatchNorm + ReLU of SharedMLP
 // (ext/pvcnn/modules/shared_mlp.py:6-35) in the native [B, C, N] layout, and optionally, on the accumulators
 // before they are stored, the head  z[b, :, cols] = Wh y + bh  (PVCNNEncoder: conv_downscale + out_layer[0]
@@ -14,7 +14,7 @@
 //     block of y straight from the accumulators as the B operand (lane (kq, col) register r = row 4 kq + r = k-step
 //     r of a 16x16x4 MFMA), against head weights packed in that k order; the waves' partial z tiles meet in LDS.
 // Device code first, then launch_pointwise and the entry points.
-#include "mfma_core.h"
+#include "tile_gemm.h"
 
 namespace {
 
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(512, 2) void pointwise_mlp_kernel(const PwArgs a) {
   extern __shared__ float lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  Ctx c{a.w, lds, tid, wave, lane, 0, 2};
+  Ctx c{a.w, lds, tid, wave, lane, 2};
   const int col = lane & 15, kq = lane >> 4;
   const int cblocks = a.cin >> 4, mtiles = a.cout >> 4, mt_per_wave = mtiles >> 3;
   float *zpart = lds + a.cin * NC;  // [8 waves][16 rows][32 cols]

@@ -5,7 +5,7 @@
 //   gldm_pointwise_rows    a few output rows (<= 8) over many channels, memory bound
 //   gldm_linear_rows       Linear over the point axis, a workgroup per row
 //   gldm_bias_act          y = act(y + bias) in place
-#include "mfma_core.h"
+#include "mfma_prims.h"
 
 namespace {
 

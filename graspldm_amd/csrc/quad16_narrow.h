@@ -19,7 +19,7 @@
 //     the q and k accumulators as its operands as they stand (lane index = position on both sides); v is produced
 //     TRANSPOSED -- v^T = xn^T Wv^T, i.e. the to_qkv MFMAs of the v rows with the operands swapped (the normalised column
 //     fragment as A, the weight fragment as B) -- so that its accumulators are the A operand of out = V A, A's the B operand.
-//   * scale / shift of a ResnetBlock: rows of a table -- the per-cloud one of the pose decoder (Ctx::ss_lane), or, for the
+//   * scale / shift of a ResnetBlock: rows of a table -- the per-cloud one of the pose decoder (R1dCtx::ss_lane), or, for the
 //     time-conditioned nets (the `ppc` denoiser: the rows change with the step), 448 rows per sample that ALL EIGHT waves
 //     compute in front of the chain (quad16_ss_rows: the six [2 C x 64] Linears as 28 m-tiles of 16 f32 MFMAs, dealt over the
 //     waves, into LDS behind the ring).  Inside the chain the same Linears cost one wave per sample 448 dependent f32 matrix
@@ -84,8 +84,8 @@ struct QStream16 {
     return (s < 16 ? PG<16>::kH : PG<16>::kX + 4 * PG<16>::kBlockFloats) + (s & 15) * 512;
   }
 };
-static_assert(PG<16>::kH + 16 * 512 <= PG<16>::kX && PG<16>::kX + 4 * PG<16>::kBlockFloats + 16 * 512 <= Geo<64>::kArena, "slot regions");
-static_assert(2 * QStream16<4>::kEnd <= Geo<64>::kLdsFloats - Geo<64>::kMiscQTab && QStream16<1>::kEnd <= QStream16<4>::kEnd, "kMiscQTab size");
+static_assert(PG<16>::kH + 16 * 512 <= PG<16>::kX && PG<16>::kX + 4 * PG<16>::kBlockFloats + 16 * 512 <= R1dGeo<64>::kArena, "slot regions");
+static_assert(2 * QStream16<4>::kEnd <= R1dGeo<64>::kLdsFloats - R1dGeo<64>::kMiscQTab && QStream16<1>::kEnd <= QStream16<4>::kEnd, "kMiscQTab size");
 
 template <int SSF>
 __device__ __forceinline__ void quad16_build_table(const gldm_r1d_desc &d, int *qtab, int tid, int nthreads) {
@@ -142,9 +142,9 @@ __device__ __forceinline__ void q16_gn_stats(const f32x4 (&acc)[MT], float (&mea
 // One ResnetBlock at stream position N0 (ss | conv1 | conv2).  SSF = 1: sst = the sample's scale / shift rows of this
 // block in the per-cloud table ([C] scale, [C] shift); SSF = 4: the Linear on the 64 embedding sums of sample `smp`.
 template <int N0, int MT, int KB, int SSF>
-__device__ __forceinline__ void quad16_resblock(const Ctx &c, QRing &ring, const QRb &rb, const float *sst, f32x4 (&xr)[MT],
+__device__ __forceinline__ void quad16_resblock(const R1dCtx &c, QRing &ring, const QRb &rb, const float *sst, f32x4 (&xr)[MT],
                                                 u32x4 (&xp)[KB][kSplit], int smp) {
-  using GG = Geo<64>;
+  using GG = R1dGeo<64>;
   using std::integral_constant;
   using ST = QStream16<SSF>;
   constexpr int C = 16 * MT, CPG = C / 4;
@@ -361,7 +361,7 @@ __device__ __forceinline__ void quad16_attention_head(const f32x4 (&qa)[2], cons
 
 // Residual(PreNorm(LinearAttention)) at stream position N0 (per head: qkv | to_out), as quad_attention
 template <int N0, int MT, int KB, int SSF>
-__device__ __forceinline__ void quad16_attention(const Ctx &c, QRing &ring, const QLv &lv, f32x4 (&xr)[MT], u32x4 (&xp)[KB][kSplit]) {
+__device__ __forceinline__ void quad16_attention(const R1dCtx &c, QRing &ring, const QLv &lv, f32x4 (&xr)[MT], u32x4 (&xp)[KB][kSplit]) {
   using std::integral_constant;
   using ST = QStream16<SSF>;
   constexpr int C = 16 * MT, kPer = 6 * KB + MT;
@@ -460,9 +460,9 @@ __device__ __forceinline__ void quad16_attention(const Ctx &c, QRing &ring, cons
 // Columns of the MFMA = samples (column & 3); columns 0 .. 3 are stored.  The caller puts a barrier behind it.
 constexpr int kQ16SsRows = 448;
 constexpr int kQ16SsLds = PG<16>::kX + 4 * PG<16>::kBlockFloats + 16 * 512;   // behind the ring's last slot: 2048 floats to the arena's end
-static_assert(kQ16SsLds + 4 * kQ16SsRows <= Geo<64>::kArena, "scale / shift rows behind the ring");
-__device__ __forceinline__ void quad16_ss_rows(const Ctx &c, kernarg_desc *dk) {
-  using GG = Geo<64>;
+static_assert(kQ16SsLds + 4 * kQ16SsRows <= R1dGeo<64>::kArena, "scale / shift rows behind the ring");
+__device__ __forceinline__ void quad16_ss_rows(const R1dCtx &c, kernarg_desc *dk) {
+  using GG = R1dGeo<64>;
   const int col = c.lane & 15, kq = c.lane >> 4;
   const lds_f *Gs = (const lds_f *)(c.lds + GG::kMiscG) + (col & 3) * 64 + kq;
   lds_f *rows = (lds_f *)(c.lds + kQ16SsLds) + (col & 3) * kQ16SsRows;
@@ -505,8 +505,8 @@ __device__ __forceinline__ void quad16_ss_rows(const Ctx &c, kernarg_desc *dk) {
 // sstab: the wave's sample's row of the per-cloud scale / shift table, or null.
 #define GLDM_QDESC() asm volatile("" : "+s"(dk))
 template <int SSF>
-__device__ __forceinline__ void quad16_narrow_levels(const Ctx &c, kernarg_desc *dk, const float *sstab) {
-  using GG = Geo<64>;
+__device__ __forceinline__ void quad16_narrow_levels(const R1dCtx &c, kernarg_desc *dk, const float *sstab) {
+  using GG = R1dGeo<64>;
   using std::integral_constant;
   using ST = QStream16<SSF>;
   using P = Q16Pos<SSF>;

@@ -1,7 +1,7 @@
 // quad_narrow.h -- the narrow levels (4, 32 and 64 channels) of the 4-position latent denoiser, wave-local and
 // register-resident.
 //
-// Included by resnet1d.hip (uses its Ctx, Geo, WStream, split-f16 helpers and cross-lane reductions).
+// Included by resnet1d.hip (uses its R1dCtx, R1dGeo, WStream, split-f16 helpers and cross-lane reductions).
 //
 // Why.  On the position-major engine a narrow level is ~7 barrier-separated phases of 8 cooperating waves, each
 // with a few hundred cycles of matrix work and 4-9 k cycles of latency (cold parameter loads, a cross-wave GroupNorm
@@ -273,8 +273,8 @@ __device__ __forceinline__ void quad_build_table(const gldm_r1d_desc &d, int *qt
   }
 }
 template <class ST = QStream4>
-__device__ __forceinline__ void quad_loader(const Ctx &c) {
-  using GG = Geo<64>;
+__device__ __forceinline__ void quad_loader(const R1dCtx &c) {
+  using GG = R1dGeo<64>;
   lds_i *sync = (lds_i *)(c.lds + GG::kMiscQ);
   const lds_i *qtab = (const lds_i *)(c.lds + GG::kMiscQTab);
   const char *wb = reinterpret_cast<const char *>(c.w) + c.lane * 16;
@@ -357,9 +357,9 @@ struct QRb { int c1_b, n1_w, n1_b, c2_b, n2_w, n2_b, ss_b; };
 // x += act(GN(conv2(act((scale + 1) GN(conv1(x)) + shift)))).  xr: the residual stream, xp: its fragment planes (kept
 // current on exit).
 template <int N0, int MT, int KB>
-__device__ __forceinline__ void quad_resblock(const Ctx &c, QRing &ring, const QRb &rb, f32x4 (&xr)[MT],
+__device__ __forceinline__ void quad_resblock(const R1dCtx &c, QRing &ring, const QRb &rb, f32x4 (&xr)[MT],
                                               u32x4 (&xp)[KB][kSplit], int smp) {
-  using GG = Geo<64>;
+  using GG = R1dGeo<64>;
   using std::integral_constant;
   constexpr int C = 16 * MT, CPG = C / 4;
   const int kq = c.lane >> 4;
@@ -543,7 +543,7 @@ struct QLv { int qkvn_s, out_b, ln2_g; };
 // xr += LN(to_out(attention(to_qkv(LN(xr))))).  The PreNorm is folded into to_qkv as in qkv_att_pm (W' = W diag(g),
 // s = W' 1); a head's output is the B fragment of its slice of to_out as it stands.
 template <int N0, int MT, int KB>
-__device__ __forceinline__ void quad_attention(const Ctx &c, QRing &ring, const QLv &lv, f32x4 (&xr)[MT],
+__device__ __forceinline__ void quad_attention(const R1dCtx &c, QRing &ring, const QLv &lv, f32x4 (&xr)[MT],
                                                u32x4 (&xp)[KB][kSplit]) {
   using std::integral_constant;
   constexpr int C = 16 * MT, kPer = 6 * KB + MT;
@@ -655,7 +655,7 @@ __device__ __forceinline__ float q4_gn(float y, float gamma, float beta) {   // 
   return d * rs * gamma + beta;
 }
 struct QRb4W { f32x4 w1, w2, wss; float b1, g1, be1, b2, g2, be2, ssb0, ssb1; };
-__device__ __forceinline__ QRb4W quad_resblock4_load(const Ctx &c, const QRb4 &rb) {
+__device__ __forceinline__ QRb4W quad_resblock4_load(const R1dCtx &c, const QRb4 &rb) {
   const int i = c.lane & 15, kq = c.lane >> 4;
   const float *w = c.w;
   QRb4W p;
@@ -670,8 +670,8 @@ __device__ __forceinline__ QRb4W quad_resblock4_load(const Ctx &c, const QRb4 &r
   p.ssb0 = w[rb.ss_b + kq]; p.ssb1 = w[rb.ss_b + 4 + kq];
   return p;
 }
-__device__ __forceinline__ float quad_resblock4(const Ctx &c, const QRb4W &p, float x, int smp) {
-  using GG = Geo<64>;
+__device__ __forceinline__ float quad_resblock4(const R1dCtx &c, const QRb4W &p, float x, int smp) {
+  using GG = R1dGeo<64>;
   const int kq = c.lane >> 4;
   f32x4 ss = f32x4{p.ssb0, p.ssb1, 0.f, 0.f};
   const lds_f *Gs = (const lds_f *)(c.lds + GG::kMiscG) + smp * 16;
@@ -688,7 +688,7 @@ struct QLv4 { int qkvn_w, out_b, ln2_g; };
 
 // attention of the 4-channel level: LayerNorm over the lane's column (the four row quarters), to_qkv as K = 4 f32 MFMAs
 // (the lane's normalised value IS the B operand), the common core, to_out (its rows packed at row 4 ch) from the ring.
-__device__ __forceinline__ float quad_attention4(const Ctx &c, QRing &ring, const QLv4 &lv, float x) {
+__device__ __forceinline__ float quad_attention4(const R1dCtx &c, QRing &ring, const QLv4 &lv, float x) {
   using std::integral_constant;
   const int kq = c.lane >> 4;
   const float *w = c.w;
@@ -730,8 +730,8 @@ typedef __attribute__((address_space(4))) const gldm_r1d_desc kernarg_desc;
 // scalar loads through a laundered copy of the pointer: read through a reference to the by-value argument they were all
 // loaded at kernel entry, kept across the whole kernel and spilled (v_readlane in front of every use).
 #define GLDM_QDESC() asm volatile("" : "+s"(dk))
-__device__ __forceinline__ void quad_narrow_levels(const Ctx &c, kernarg_desc *dk) {
-  using GG = Geo<64>;
+__device__ __forceinline__ void quad_narrow_levels(const R1dCtx &c, kernarg_desc *dk) {
+  using GG = R1dGeo<64>;
   using std::integral_constant;
   const int q = c.wave & 3, col = c.lane & 15, kq = c.lane >> 4;   // (wave > 3: GLDM_QEXP_DUP only)
   const int p = col >> 2, sl = col & 3;

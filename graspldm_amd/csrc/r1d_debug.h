@@ -1,7 +1,7 @@
 // r1d_debug.h -- everything diagnostic builds (make EXTRA=-DGLDM_DEBUG_KNOBS) add to r1d_kernel's launch path (resnet1d.hip):
 // the per-wave conv stamps (-DGLDM_WAVE_STAMPS on top), the environment knobs and the stamp report.  In a shipped build the
 // macros expand to nothing and the hooks are empty inline functions: the library reads no environment and prints nothing.
-// (GLDM_SKIP / GLDM_STAMPS, which other sources use too, are in mfma_core.h.)  resnet1d.hip includes it TWICE inside its
+// (GLDM_SKIP / GLDM_STAMPS are in r1d_gemm.h.)  resnet1d.hip includes it TWICE inside its
 // anonymous namespace: in front of the phase headers for the device part (the stamp macros and arrays), and in front of its
 // host side for the hooks, which need what lies between (RunArgs, build_tape, the wave-local chain's g_q_stamp).
 //   GLDM_R1D_SKIP=mask       phase-skip mask (GLDM_SKIP)          GLDM_R1D_STAGGER_US=n  start offset of a CU's second workgroup

@@ -1,14 +1,15 @@
 // r1d_rows.h -- the f32 / generic phases of the 32-column engines r1d_kernel<32, *> (sample-major columns; their convs are
-// mfma_core.h's conv_gemm): LayerNorm over the channels, LinearAttention of one head pair, and the 4-channel ResnetBlock on the
-// VALU of one wave.  Included by resnet1d.hip inside its anonymous namespace, behind r1d_tape.h (kOpInts).
+// tile_gemm.h's 1x1 layers and r1d_gemm.h's conv3_f32): LayerNorm over the channels, LinearAttention of one head pair, and
+// the 4-channel ResnetBlock on the VALU of one wave.  Included by resnet1d.hip inside its anonymous namespace, behind
+// r1d_gemm.h (R1dGeo, R1dCtx) and r1d_tape.h (kOpInts).
 
 // ----------------------------------------------------------- LayerNorm ----
 // dst = LN_channels(src) * g  (or res += LN(src) * g when res != null).  Row slot = wave*kRP + sub
 // (kSlots = kWaves * kRP of them), rows slot + kSlots i.
 template <int NC, int ITERS>
-__device__ __forceinline__ void layer_norm_rows(const Ctx &c, const float *src, float *dst, float *res, int C,
+__device__ __forceinline__ void layer_norm_rows(const R1dCtx &c, const float *src, float *dst, float *res, int C,
                                                 int g_off) {
-  using GG = Geo<NC>;
+  using GG = R1dGeo<NC>;
   float *red1 = c.lds + GG::kMiscRed1, *red2 = c.lds + GG::kMiscRed2;
   const int n = c.lane & (NC - 1), slot = c.wave * GG::kRP + c.lane / NC;
   const lds_f *s3 = (const lds_f *)src;
@@ -62,10 +63,10 @@ __device__ __forceinline__ void layer_norm_rows(const Ctx &c, const float *src, 
 // (sum, M2 about its own mean), ONE barrier, then the parallel-variance merge of the 8 pairs: two barriers per
 // LayerNorm instead of three.
 template <int ITERS>
-__device__ __forceinline__ void layer_norm_rows_1x(const Ctx &c, const float *src, float *dst, float *res, int C,
+__device__ __forceinline__ void layer_norm_rows_1x(const R1dCtx &c, const float *src, float *dst, float *res, int C,
                                                    int g_off) {
   constexpr int NC = 64;
-  using GG = Geo<NC>;
+  using GG = R1dGeo<NC>;
   lds_f *red1 = (lds_f *)(c.lds + GG::kMiscRed1), *red2 = (lds_f *)(c.lds + GG::kMiscRed2);
   const int n = c.lane, slot = c.wave;
   const lds_f *s3 = (const lds_f *)src;
@@ -125,18 +126,18 @@ __device__ __forceinline__ void layer_norm_rows_1x(const Ctx &c, const float *sr
 }
 
 template <int NC>
-__device__ __forceinline__ void layer_norm_pass(const Ctx &c, const float *src, float *dst, float *res, int C, int g_off) {
+__device__ __forceinline__ void layer_norm_pass(const R1dCtx &c, const float *src, float *dst, float *res, int C, int g_off) {
   if (GLDM_SKIP(c, 2)) return;
   C = __builtin_amdgcn_readfirstlane(C);
   if constexpr (NC == 64) {
-    const int it1 = (C + Geo<NC>::kSlots - 1) / Geo<NC>::kSlots;
+    const int it1 = (C + R1dGeo<NC>::kSlots - 1) / R1dGeo<NC>::kSlots;
     if (it1 <= 1) layer_norm_rows_1x<1>(c, src, dst, res, C, g_off);
     else if (it1 <= 4) layer_norm_rows_1x<4>(c, src, dst, res, C, g_off);
     else if (it1 <= 8) layer_norm_rows_1x<8>(c, src, dst, res, C, g_off);
     else layer_norm_rows_1x<16>(c, src, dst, res, C, g_off);
     return;
   }
-  const int it = (C + Geo<NC>::kSlots - 1) / Geo<NC>::kSlots;
+  const int it = (C + R1dGeo<NC>::kSlots - 1) / R1dGeo<NC>::kSlots;
   if (it <= 1) layer_norm_rows<NC, 1>(c, src, dst, res, C, g_off);
   else if (it <= 2) layer_norm_rows<NC, 2>(c, src, dst, res, C, g_off);
   else if (it <= 4) layer_norm_rows<NC, 4>(c, src, dst, res, C, g_off);
@@ -148,9 +149,9 @@ __device__ __forceinline__ void layer_norm_pass(const Ctx &c, const float *src, 
 // qkv: [192][NC] = q(2 heads x 32) | k | v for one head pair; writes 64 rows of o.
 // (Sample-major 32-column engine; the 64-column engine has attention_pair_pm.)
 template <int NC, int L>
-__device__ __forceinline__ void attention_pair(const Ctx &c, float *qkv, float *o_rows) {
+__device__ __forceinline__ void attention_pair(const R1dCtx &c, float *qkv, float *o_rows) {
   if (GLDM_SKIP(c, 4)) return;
-  using GG = Geo<NC>;
+  using GG = R1dGeo<NC>;
   static_assert(NC == 32 && GG::kWaves == 4 && (L == 4 || L == 16), "sample-major engine geometry");
   const lds_f *q3 = (const lds_f *)qkv;
   lds_f *o3 = (lds_f *)o_rows;
@@ -284,8 +285,8 @@ __device__ __forceinline__ void attention_pair(const Ctx &c, float *qkv, float *
 // Weights are read in their packed MFMA-fragment order: conv W[co][ci][tap] at ((ci * 16 + co) * 4 + tap),
 // scale/shift Linear W[row][e] at (((e & 3) * 16 + row) * 4 + (e >> 2)).
 template <int NC>
-__device__ __forceinline__ void resblock4_valu(const Ctx &c, const int (&o)[kOpInts], int E) {
-  using GG = Geo<NC>;
+__device__ __forceinline__ void resblock4_valu(const R1dCtx &c, const int (&o)[kOpInts], int E) {
+  using GG = R1dGeo<NC>;
   if (c.wave != 0) return;
   const int n = c.lane & 31, h = c.lane >> 5, l = n & 3;
   const bool has_l = l != 0, has_r = l != 3;

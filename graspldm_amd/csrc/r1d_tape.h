@@ -10,7 +10,7 @@
 // whole kernel: no calls, no callee-save traffic and no spilled kernel state between phases.
 enum { OP_CONV = 1, OP_RES4 = 2, OP_LN = 3, OP_ATT = 4, OP_QKVLN = 5, OP_OUTLN = 6, OP_QKVATT = 7, OP_QUAD = 8 };
 // An op is kOpInts = 12 ints, o[0] its code; weight / bias / gain entries are float offsets into the packed weights, src / dst
-// float offsets into LDS (Geo<NC>::kBuf*):
+// float offsets into LDS (R1dGeo<NC>::kBuf*):
 //   OP_CONV    w, bias, src, dst, cin, cout, flags, GroupNorm gamma, beta, scale/shift W, scale/shift b
 //              flags (int 7): taps | alias << 8 | GroupNorm epilogue mode << 9 | fused << 11 | (scale/shift table offset / 4) << 12
 //   OP_RES4    conv1 w, b, norm1 gamma, beta, conv2 w, b, norm2 gamma, beta, scale/shift W, b, barrier behind the op
@@ -53,7 +53,7 @@ __host__ __device__ __forceinline__ bool gn_fusable(int C, int groups) {
 
 template <int NC>
 __host__ __device__ __forceinline__ int build_tape(const gldm_r1d_desc &d, int *tape, bool use_quad = true) {
-  using GG = Geo<NC>;
+  using GG = R1dGeo<NC>;
   int n = 0;
   auto emit = [&](int type, int a1 = 0, int a2 = 0, int a3 = 0, int a4 = 0, int a5 = 0, int a6 = 0, int a7 = 0,
                   int a8 = 0, int a9 = 0, int a10 = 0, int a11 = 0) {

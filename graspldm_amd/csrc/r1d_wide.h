@@ -3,18 +3,22 @@
 // in LDS as pre-split planes.  k = 3 convs (gemm_pm3_pl, gemm_sm3_pl) under the GroupNorm / scale-shift / SiLU / residual
 // epilogue (conv_pm3_wave), the 4-channel first level on the VALU (conv_pm3_cin4, resblock4_pm), to_out + LayerNorm + residual
 // (out_ln_*), PreNorm + to_qkv + attention as one op (column_stats8, qkv_att_pm, qkv_att16_pm), the fused ResnetBlock op
-// (resblock_pm).  Included by resnet1d.hip inside its anonymous namespace, behind r1d_tape.h (kOpInts) and r1d_debug.h
-// (GLDM_WV_STAMP) and in front of quad_narrow.h / quad16_narrow.h (sqrt_up).
+// (resblock_pm).  Included by resnet1d.hip inside its anonymous
+// namespace, behind r1d_gemm.h (R1dGeo, R1dCtx, GnEpilogue), r1d_tape.h (kOpInts) and r1d_debug.h (GLDM_WV_STAMP) and in front of
+// quad_narrow.h / quad16_narrow.h (sqrt_up).
 
-constexpr int kPlaneH = 128 * 64;                 // H planes: floats [8192, 16384): 4 blocks of 32 channels
-constexpr int kPlaneX = kPlaneH + 4 * kSplit * 1024;   // X planes: floats [16384, 24576)
+constexpr int kPlaneH = PG<4>::kH, kPlaneX = PG<4>::kX;   // H planes: floats [8192, 16384), X planes: [16384, 24576) (tile_gemm.h)
 constexpr int kPlaneMaxC = 128;
 // The 256-channel level (only ever the last one: a down conv into it and one ResnetBlock) keeps ONE tensor in LDS as
 // planes (8 blocks x 8 KiB = 64 KiB, floats [16384, 32768): behind the level's f32 residual stream X, rows 0..255 =
 // floats [0, 16384)): the down conv writes the planes of the new residual stream X there (and X itself as f32 rows);
 // conv1 reads the planes and, behind its GroupNorm exchange barrier (every wave is past its k-loop), overwrites them with
 // the planes of H; conv2 reads those and adds act(GN(conv)) to the f32 rows for the final 1x1.
-static_assert(PG<4>::kH == kPlaneH && PG<4>::kX == kPlaneX, "plane regions");
+
+// PRE of the k = 3 convs: NoPreA, or PreA (first weight fragments requested by the caller); HOOK of conv_pm3_wave: NoHook, or
+// work to run in the shadow of its epilogue
+struct NoPreA { static constexpr bool on = false; };
+struct NoHook { __device__ __forceinline__ void operator()() const {} };
 
 // First weight fragments of a position-major k = 3 conv, requested by the CALLER ahead of the conv (the fused
 // ResnetBlock op asks for its second conv's while the first conv's epilogue runs): block 0's three tap sets of a
@@ -43,7 +47,7 @@ struct PreA {
 // The conv with the B operand read from pre-split planes: ds_read_b128 per (tile, plane), no VALU.
 // B planes of the next channel block are requested while the current block's MFMAs run (second register set).
 template <int MT, int P0, int NP, class PRE = NoPreA>
-__device__ __forceinline__ void gemm_pm3_pl(const Ctx &c, const float *__restrict__ wp3, int cin, int mt0,
+__device__ __forceinline__ void gemm_pm3_pl(const R1dCtx &c, const float *__restrict__ wp3, int cin, int mt0,
                                             const float *planes, f32x4 (&acc)[MT][NP], const PRE &pre = PRE()) {
   constexpr int PB0 = P0 > 0 ? P0 - 1 : 0, PB1 = P0 + NP < 4 ? P0 + NP : 3, NB = PB1 - PB0 + 1;
   const int col = c.lane & 15, g = c.lane >> 4;
@@ -157,7 +161,7 @@ __device__ __forceinline__ void gemm_pm3_pl(const Ctx &c, const float *__restric
 // T0, NT: the wave's n-tiles (tile = 4 consecutive positions x 4 samples).  Cin = 16 runs as one 32-channel block whose
 // upper half has zero weights (r1d_pack.pad_cin32).
 template <int MT, int T0, int NT, class PRE = NoPreA>
-__device__ __forceinline__ void gemm_sm3_pl(const Ctx &c, const float *__restrict__ wp3, int cin, int mt0,
+__device__ __forceinline__ void gemm_sm3_pl(const R1dCtx &c, const float *__restrict__ wp3, int cin, int mt0,
                                             const float *planes, f32x4 (&acc)[MT][NT], const PRE &pre = PRE()) {
   using G = PG<16>;
   const int col = c.lane & 15, g = c.lane >> 4;
@@ -279,10 +283,11 @@ constexpr float sqrt_up(int n) {   // >= sqrt(n), n a power of two
 // four groups, waves 0-3 one tile each -- waves 4-7 repeat their work with `live` false so that every wave meets the
 // barriers).  The statistics of a sample then also sum over the four positions inside a tile (DPP row rotations).
 template <int MT, int P0, int NP, int GK, int FIN, class PRE, class HOOK, int LL>
-__device__ __forceinline__ void conv_pm3_wave(const Ctx &c, const float *wp, const float *bias, int mt0,
+__device__ __forceinline__ void conv_pm3_wave(const R1dCtx &c, const float *wp, const float *bias, int mt0,
                                               const float *src, int cin, float *dst, int cout, bool alias,
-                                              const GnEpilogue &g, const PRE &pre, const HOOK &hook, bool live) {
-  using GG = Geo<64>;
+                                              const GnEpilogue &g, const PRE &pre = PRE(), const HOOK &hook = HOOK(),
+                                              bool live = true) {
+  using GG = R1dGeo<64>;
   using PGx = PG<LL>;
   const int kq = c.lane >> 4, cl = c.lane & 15;
   const int sm = LL == 16 ? (c.lane & 3) : cl;   // the lane's sample
@@ -579,7 +584,7 @@ __device__ __forceinline__ void conv_pm3_wave(const Ctx &c, const float *wp, con
 // computes output channels 4w .. 4w+3 (cout = 32).  Weights are wave uniform (scalar loads); fma chain in the
 // MFMA's k order (tap major, channel minor) from the bias.  src may alias dst.
 template <int ROUNDS>   // 32 output channels per round (4 per wave); cout == 32 ROUNDS exactly: no per-value guards
-__device__ __forceinline__ void conv_pm3_cin4_rounds(const Ctx &c, const float *wp, const float *bias, const float *src,
+__device__ __forceinline__ void conv_pm3_cin4_rounds(const R1dCtx &c, const float *wp, const float *bias, const float *src,
                                                      float *dst, bool alias) {
   const int n = c.lane, p = n >> 4;
   const lds_f *s3 = (const lds_f *)src;
@@ -618,7 +623,7 @@ __device__ __forceinline__ void conv_pm3_cin4_rounds(const Ctx &c, const float *
       store_planes4(c.lds + kPlaneX, rd * 32 + c.wave * 4, n, out[rd][0], out[rd][1], out[rd][2], out[rd][3]);
   }
 }
-__device__ __forceinline__ void conv_pm3_cin4_any(const Ctx &c, const float *wp, const float *bias, const float *src,
+__device__ __forceinline__ void conv_pm3_cin4_any(const R1dCtx &c, const float *wp, const float *bias, const float *src,
                                               float *dst, int cout, bool alias) {
   const int n = c.lane, p = n >> 4;
   const lds_f *s3 = (const lds_f *)src;
@@ -668,7 +673,7 @@ __device__ __forceinline__ void conv_pm3_cin4_any(const Ctx &c, const float *wp,
   }
 }
 
-__device__ __forceinline__ void conv_pm3_cin4(const Ctx &c, const float *wp, const float *bias, const float *src,
+__device__ __forceinline__ void conv_pm3_cin4(const R1dCtx &c, const float *wp, const float *bias, const float *src,
                                               float *dst, int cout, bool alias) {
   // the shipped 32-channel level without per-value `co < cout` tests (32 branches in the common body); wider first
   // levels on the common body (an instance per width spilled 361 registers across the kernel)
@@ -680,8 +685,8 @@ __device__ __forceinline__ void conv_pm3_cin4(const Ctx &c, const float *wp, con
 // lane carries all 4 channels of its column.  Taps come from the lanes 16 below / above (the neighbouring
 // positions of the same sample), GroupNorm (one channel per group) reduces over lanes n ^ 16, n ^ 32.  Every
 // weight is wave uniform (scalar loads: nothing queues in the vector-memory path).
-__device__ __forceinline__ void resblock4_pm(const Ctx &c, const int (&o)[kOpInts], int E) {
-  using GG = Geo<64>;
+__device__ __forceinline__ void resblock4_pm(const R1dCtx &c, const int (&o)[kOpInts], int E) {
+  using GG = R1dGeo<64>;
   if (c.wave != 0) return;
   const int n = c.lane, sm = n & 15, p = n >> 4;
   const bool has_l = p != 0, has_r = p != 3;
@@ -790,10 +795,10 @@ __device__ __forceinline__ void resblock4_pm(const Ctx &c, const int (&o)[kOpInt
 // the per-value code has no wave-uniform branches (each value used to be its own chain of basic blocks)
 // FIRST: block 0's fragments of the wave's m-tile, requested by the caller ahead of the call (Frag3), or NoFirst.
 template <int NT, int NPW, bool FULL, int LL = 4, class FIRST = NoFirst>
-__device__ __forceinline__ void out_ln_wave(const Ctx &c, const float *wp, const float *bias, int mt0, int nt0,
+__device__ __forceinline__ void out_ln_wave(const R1dCtx &c, const float *wp, const float *bias, int mt0, int nt0,
                                             bool active, int p0, const float *src, int cin, float *xres, int C,
                                             const float *gain, const FIRST &first = FIRST()) {
-  using GG = Geo<64>;
+  using GG = R1dGeo<64>;
   constexpr int NC = 64;
   const int kq = c.lane >> 4, col = c.lane & 15;
   f32x4 acc[1][NT];
@@ -867,7 +872,7 @@ __device__ __forceinline__ void out_ln_wave(const Ctx &c, const float *wp, const
 // The 128-channel level's to_out with its first weight fragments requested by the caller in front of the attention op
 // (run_tape: OP_QKVATT followed by OP_OUTLN run as one case): cold at the top of this op they cost an L2 round trip with all
 // eight waves waiting.
-__device__ __forceinline__ Frag3 out_ln_request(const Ctx &c, int w_off) {
+__device__ __forceinline__ Frag3 out_ln_request(const R1dCtx &c, int w_off) {
   const WStream wv(c.w + w_off, c.lane);
   Frag3 f;
 #pragma unroll
@@ -875,12 +880,12 @@ __device__ __forceinline__ Frag3 out_ln_request(const Ctx &c, int w_off) {
   return f;
 }
 template <int LL = 4>
-__device__ __forceinline__ void out_ln_pm128(const Ctx &c, int w_off, int b_off, const float *src, int cin, float *xres, int g_off,
+__device__ __forceinline__ void out_ln_pm128(const R1dCtx &c, int w_off, int b_off, const float *src, int cin, float *xres, int g_off,
                                              const Frag3 &first) {
   out_ln_wave<4, 8, true, LL, Frag3>(c, c.w + w_off, c.w + b_off, c.wave, 0, true, 0, src, cin, xres, 128, c.w + g_off, first);
 }
 template <int LL = 4>
-__device__ __forceinline__ void out_ln_pm(const Ctx &c, int w_off, int b_off, const float *src, int cin, float *xres,
+__device__ __forceinline__ void out_ln_pm(const R1dCtx &c, int w_off, int b_off, const float *src, int cin, float *xres,
                                           int C, int g_off) {
   const float *wp = c.w + w_off, *bias = c.w + b_off, *gain = c.w + g_off;
   const int mtiles = (C + 15) >> 4, w = c.wave;
@@ -895,9 +900,9 @@ __device__ __forceinline__ void out_ln_pm(const Ctx &c, int w_off, int b_off, co
 // 8 w .. 8 w + 7, lane = (row part, column), two passes over the C / 8 values in its registers (the reference's mean,
 // then sum (x - mean)^2), the parts meet through DPP / permlane swaps, (mean, rstd) go to LDS.
 template <int RP>  // rows per lane: C / 8
-__device__ __forceinline__ void column_stats8(const Ctx &c, const float *src, float inv_c) {
+__device__ __forceinline__ void column_stats8(const R1dCtx &c, const float *src, float inv_c) {
   constexpr int NC = 64;
-  using GG = Geo<NC>;
+  using GG = R1dGeo<NC>;
   const lds_f *s3 = (const lds_f *)src;
   const int n = 8 * c.wave + (c.lane & 7), rp = c.lane >> 3;
   float v[RP], sum = 0.f;
@@ -944,11 +949,11 @@ __device__ __forceinline__ void column_stats8(const Ctx &c, const float *src, fl
 //   * The output leaves as split-f16 planes (it is only ever the B operand of to_out), into the H-plane region.
 // Barriers: statistics, exchange, end (the two phases this replaces had five).
 constexpr int kAttExch = 512 * 64;   // floats [32768, 35840): 8 waves x 24 rows x 16 samples, behind the X planes
-static_assert(kAttExch + 8 * 24 * 16 <= Geo<64>::kArena, "attention exchange slots");
+static_assert(kAttExch + 8 * 24 * 16 <= R1dGeo<64>::kArena, "attention exchange slots");
 template <int KB32>   // C / 32 (0: the 4-channel level)
-__device__ __forceinline__ void qkv_att_pm(const Ctx &c, int w_off, int s_off, const float *src, int C) {
+__device__ __forceinline__ void qkv_att_pm(const R1dCtx &c, int w_off, int s_off, const float *src, int C) {
   constexpr int NC = 64;
-  using GG = Geo<NC>;
+  using GG = R1dGeo<NC>;
   if (GLDM_SKIP(c, 8)) return;
   const int head = c.wave >> 1, half = c.wave & 1;
   const int mt0 = 2 * head + half;   // q rows; k: m-tile + 8, v: + 16
@@ -1102,8 +1107,8 @@ __device__ __forceinline__ void qkv_att_pm(const Ctx &c, int w_off, int s_off, c
 // (quad16_narrow.h, included behind this header, defines the attention core this op shares with the wave-local levels)
 __device__ __forceinline__ void quad16_attention_head(const f32x4 (&qa)[2], const f32x4 (&ka)[2], const f32x4 (&vt)[2], f32x4 (&out)[2]);
 template <int KB32>   // ceil(C / 32): a 16-channel level is one zero-padded block
-__device__ __forceinline__ void qkv_att16_pm(const Ctx &c, int w_off, int s_off, const float *src, int C) {
-  using GG = Geo<64>;
+__device__ __forceinline__ void qkv_att16_pm(const R1dCtx &c, int w_off, int s_off, const float *src, int C) {
+  using GG = R1dGeo<64>;
   using PGx = PG<16>;
   const float *wp = c.w + w_off, *srow = c.w + s_off;
   const int h = c.wave >> 1, s0 = 2 * (c.wave & 1);
@@ -1210,7 +1215,7 @@ __device__ __forceinline__ void zero_plane_pads16(float *lds, int t) {
 // conv (a build that loads no fragments at all runs the step 8 % faster; across two tape ops the compiler waits for
 // such loads at the op switch).  One tape decode and dispatch less, too.
 template <int MT, int P0, int NP, int GK, int LL = 4>
-__device__ __forceinline__ void resblock_pm_wave(const Ctx &c, const float *wp1, const float *b1, const float *wp2,
+__device__ __forceinline__ void resblock_pm_wave(const R1dCtx &c, const float *wp1, const float *b1, const float *wp2,
                                                  const float *b2, int mt0, float *X, float *H, int C,
                                                  const GnEpilogue &g1, const GnEpilogue &g2, long long *stamp2,
                                                  bool live = true) {
@@ -1224,7 +1229,7 @@ __device__ __forceinline__ void resblock_pm_wave(const Ctx &c, const float *wp1,
   conv_pm3_wave<MT, P0, NP, GK, 2, PreA<MT>, NoHook, LL>(c, wp2, b2, mt0, H, C, X, C, false, g2, pa, NoHook(), live);
 }
 template <int LL = 4>
-__device__ __forceinline__ void resblock_pm(const Ctx &c, int w1, int b1, int w2, int b2, float *X, float *H, int C,
+__device__ __forceinline__ void resblock_pm(const R1dCtx &c, int w1, int b1, int w2, int b2, float *X, float *H, int C,
                                             const GnEpilogue &g1, const GnEpilogue &g2, long long *stamp2) {
   const float *wp1 = c.w + w1, *bp1 = c.w + b1, *wp2 = c.w + w2, *bp2 = c.w + b2;
   const int w = c.wave;

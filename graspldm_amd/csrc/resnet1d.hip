@@ -16,11 +16,13 @@
 //   <64, 16>  the shipped pose decoder, grasp encoder and 16-position denoiser: column = 4 position + sample, zero-padded
 //             plane rows so that taps are shifted reads (gemm_sm3_pl); narrow levels in quad16_narrow.h, qkv_att16_pm.
 //   <32, *>   the f32 engine (numerics.f32_only(), and every descriptor outside pm_supported() / pm16_supported()): 4 waves,
-//             two workgroups per CU, sample-major columns, v_mfma_f32_16x16x4_f32 through mfma_core.h's conv_gemm.
+//             two workgroups per CU, sample-major columns, v_mfma_f32_16x16x4_f32 through tile_gemm.h's f32 cores.
 // The step is a tape of ops built on the host (build_tape) and interpreted by run_tape with every phase inlined: in the
 // kernel arguments (RunArgs::pm_tape) for the 64-column engines, built in LDS by the 32-column one.
 // The family, every header included below inside this file's anonymous namespace:
-//   mfma_core.h       types, LDS maps, split-f16 arithmetic, the GEMM cores (shared with the other kernel sources)
+//   tile_gemm.h       (on mfma_prims.h) types, split-f16 arithmetic, reductions; X / H buffers, planes, the tile GEMMs, 1x1 layers:
+//                     shared with the other kernel sources, included at file scope
+//   r1d_gemm.h        the engine's LDS map and launch context (R1dGeo, R1dCtx), GLDM_SKIP, the GroupNorm epilogue, f32 k = 3 convs
 //   r1d_tape.h        the step program: op codes and layout, quad_levels / quad16_levels, build_tape, read_op
 //   r1d_debug.h       diagnostic builds only: wave stamps, environment knobs, the stamp report (included twice: device part, host hooks)
 //   r1d_wide.h        wide-level phases of the 64-column engines: conv_pm3_wave, out_ln_*, qkv_att_pm, qkv_att16_pm, resblock_pm
@@ -28,15 +30,16 @@
 //   quad_narrow.h, quad16_narrow.h   the wave-local narrow levels of the 4- and the 16-position engine
 //   r1d_chain.h       the hand-off between workgroups: ChainHdr, chain_give, chain_take
 //   diffusion_step.h  Philox normals and the scheduler updates (shared with unet1d.hip and pose_ops.hip)
-// Here: RunArgs, run_tape, r1d_kernel, ss_table_kernel; the host side (validation, engine selection, workspace layout, work
+// Here: RunArgs, conv_op, run_tape, r1d_kernel, ss_table_kernel; the host side (validation, engine selection, workspace layout, work
 // plan, launch); the entry points.  The small ops either side of the engine (cond-embed, pose prologue / epilogue, step noise)
 // are pose_ops.hip.
-#include "mfma_core.h"
+#include "tile_gemm.h"
 
 namespace {
 
 constexpr int kMaxSegs = 64;  // tiles (+ one spliced step segment) a persistent workgroup can be given
 
+#include "r1d_gemm.h"
 #include "r1d_tape.h"
 #include "r1d_debug.h"   // the device part
 #include "r1d_wide.h"
@@ -47,7 +50,7 @@ constexpr int kMaxSegs = 64;  // tiles (+ one spliced step segment) a persistent
 #include "diffusion_step.h"
 
 // ---------------------------------------------------------- the network ----
-constexpr int kParkBytes = 256 * 64 * 4;   // one [256][64] f32 tile per workgroup (Ctx::park)
+constexpr int kParkBytes = 256 * 64 * 4;   // one [256][64] f32 tile per workgroup (R1dCtx::park)
 
 struct RunArgs {
   gldm_r1d_desc d;
@@ -78,7 +81,7 @@ struct RunArgs {
   float mix_mu, mix_eps;
   int eps_times_std;
   float *ws;              // workspace: chain header + hand-off granules (+ the decoder's scale/shift table)
-  float *park;            // position-major engine with a 256-channel last level: 64 KiB of scratch per workgroup (Ctx::park)
+  float *park;            // position-major engine with a 256-channel last level: 64 KiB of scratch per workgroup (R1dCtx::park)
   const float *ss_tab;    // [n_cond][ss_stride] scale/shift rows of every ResnetBlock per conditioning cloud, or null
   int ss_stride;
   int skip;               // diagnostic phase-skip mask (GLDM_R1D_SKIP env; 0 in production)
@@ -95,14 +98,60 @@ struct RunArgs {
   int pm_tape[kPmMaxOps * kOpInts];
 };
 
+// A conv op of the tape: dst[cout][NC] = W * im2col(src[cin][NC]) + bias under g's epilogue, the waves splitting the output
+// rows.  Ends with a barrier.  alias: dst overlaps src -> all reads complete (barrier) before any store.
+// Output widths are 16 x {1, 2, 4, 8, 12, 16} rows (validate() enforces it).
+// (Tried and dropped: running the <= 64-channel levels column-parallel, one wave per n-tile with no
+// barriers inside the level: those phases are bound by per-wave issue, not by the barriers, and with
+// half the waves active every op took 1.7-2x longer.  And the opposite, 8 waves per 32-column tile
+// with the statistics of a wide group exchanged between wave pairs: correct, but at 128 VGPRs per
+// wave the k-loops spill and the launch was 5-7 % slower than with 4 waves.)
 template <int NC, int L>
-__device__ __forceinline__ void run_tape(const Ctx &c0, const gldm_r1d_desc &d, const int *tape, kernarg_int *ktape, int n_ops, int E, long long *stamps) {
+__device__ __forceinline__ void conv_op(const R1dCtx &c, int w_off, int b_off, const float *src, int cin, int ktaps,
+                                        float *dst, int cout, bool alias, const GnEpilogue &g) {
+  if (GLDM_SKIP(c, 8)) return;
+  const float *wp = c.w + w_off;
+  const float *bias = b_off >= 0 ? c.w + b_off : nullptr;
+  const int mtiles = (cout + 15) >> 4;
+  const int w = c.wave;
+  if (ktaps == 3) {
+    if constexpr (NC == 64) {
+      // 64-column engines: 8 waves share the m-tiles (L = 4: the three taps tie the 4 position tiles together; L = 16:
+      // tiles of 4 positions x 4 samples, taps by shifted plane reads).  Only the levels' down convs come this way.
+      // (Dealt here and not in a function of r1d_wide.h: one more level of calls changes the kernels' machine code.)
+      constexpr int LL = L == 16 ? 16 : 4;
+      if (LL == 4 && (cin & 15)) conv_pm3_cin4(c, wp, bias, src, dst, cout, alias);
+      else if (mtiles == 16) conv_pm3_wave<2, 0, 4, 0, 0, NoPreA, NoHook, LL>(c, wp, bias, 2 * w, src, cin, dst, cout, alias, g);
+      else if (mtiles == 8) conv_pm3_wave<1, 0, 4, 0, 0, NoPreA, NoHook, LL>(c, wp, bias, w, src, cin, dst, cout, alias, g);
+      else if (mtiles == 4) {
+        if (w < 4) conv_pm3_wave<1, 0, 2, 1, 0, NoPreA, NoHook, LL>(c, wp, bias, w & 3, src, cin, dst, cout, alias, g);
+        else conv_pm3_wave<1, 2, 2, 1, 0, NoPreA, NoHook, LL>(c, wp, bias, w & 3, src, cin, dst, cout, alias, g);
+      } else {  // 2 m-tiles: wave = (m-tile, position / tile)
+        const int pw = w >> 1;
+        if (pw == 0) conv_pm3_wave<1, 0, 1, 2, 0, NoPreA, NoHook, LL>(c, wp, bias, w & 1, src, cin, dst, cout, alias, g);
+        else if (pw == 1) conv_pm3_wave<1, 1, 1, 2, 0, NoPreA, NoHook, LL>(c, wp, bias, w & 1, src, cin, dst, cout, alias, g);
+        else if (pw == 2) conv_pm3_wave<1, 2, 1, 2, 0, NoPreA, NoHook, LL>(c, wp, bias, w & 1, src, cin, dst, cout, alias, g);
+        else conv_pm3_wave<1, 3, 1, 2, 0, NoPreA, NoHook, LL>(c, wp, bias, w & 1, src, cin, dst, cout, alias, g);
+      }
+    } else {
+      conv3_f32<NC, L>(c, wp, bias, src, cin, dst, cout, alias, g);
+    }
+  } else {
+#define GLDM_G1(MT, NT, P, mt0, nt0, on) gemm_passes<NC, L, 1, MT, NT, P>(c, wp, mt0, nt0, on, src, cin, dst, cout, bias, alias, 0)
+    GLDM_DEAL_1X1(NC, c.nta, mtiles, w, GLDM_G1)
+#undef GLDM_G1
+  }
+  __syncthreads();
+}
+
+template <int NC, int L>
+__device__ __forceinline__ void run_tape(const R1dCtx &c0, const gldm_r1d_desc &d, const int *tape, kernarg_int *ktape, int n_ops, int E, long long *stamps) {
   constexpr bool KARG = NC == 64;
   for (int op = 0; op < n_ops; ++op) {
     if (stamps && c0.tid == 0) stamps[op] = (long long)__builtin_readcyclecounter();
     // the lane ids are laundered per op: otherwise every variant's lane-derived LDS offsets are
     // hoisted out of the step loop as invariants and live (spilled) across the whole kernel
-    Ctx c = c0;
+    R1dCtx c = c0;
     asm volatile("" : "+v"(c.tid), "+v"(c.lane));
     int o[kOpInts];
     read_op<KARG>(tape, ktape, op, o);
@@ -126,7 +175,7 @@ __device__ __forceinline__ void run_tape(const Ctx &c0, const gldm_r1d_desc &d, 
         const int mode = GLDM_SKIP(c, 1) ? 0 : (o[7] >> 9) & 3;
         const GnEpilogue g{mode, o[8], o[9], GLDM_SKIP(c, 16) ? -1 : o[10], o[11], E, o[6], o[6] / 4, c.lds + o[4],
                            (o[7] >> kFlagTabShift) << 2};
-        conv_gemm<NC, L>(c, o[1], o[2], c.lds + o[3], o[5], o[7] & 255, c.lds + o[4], o[6], (o[7] & kFlagAlias) != 0, 0, g);
+        conv_op<NC, L>(c, o[1], o[2], c.lds + o[3], o[5], o[7] & 255, c.lds + o[4], o[6], (o[7] & kFlagAlias) != 0, g);
         break;
       }
       case OP_QUAD:
@@ -148,7 +197,7 @@ __device__ __forceinline__ void run_tape(const Ctx &c0, const gldm_r1d_desc &d, 
           kernarg_desc *dkp = (kernarg_desc *)((__attribute__((address_space(4))) const char *)__builtin_amdgcn_kernarg_segment_ptr() +
                                                offsetof(RunArgs, d));
           const float *sstab;   // the wave's sample's scale / shift rows of the six narrow ResnetBlocks
-          if (c.ss_lane) {   // pose decoder: the per-cloud table (wave uniform: the launch has one or not); Ctx::ss_lane of a
+          if (c.ss_lane) {   // pose decoder: the per-cloud table (wave uniform: the launch has one or not); R1dCtx::ss_lane of a
                              // lane whose sample (lane & 3) is the wave's
             const unsigned long long pv = (unsigned long long)c.ss_lane;
             const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)pv, c.wave & 3);
@@ -214,8 +263,8 @@ __device__ __forceinline__ void run_tape(const Ctx &c0, const gldm_r1d_desc &d, 
 }
 
 template <int NC, int L>
-__global__ __launch_bounds__(Geo<NC>::kThreads, 2) void r1d_kernel(const RunArgs a) {
-  using GG = Geo<NC>;
+__global__ __launch_bounds__(R1dGeo<NC>::kThreads, 2) void r1d_kernel(const RunArgs a) {
+  using GG = R1dGeo<NC>;
   extern __shared__ float lds[];
   const gldm_r1d_desc &d = a.d;
   constexpr int S = NC / L;
@@ -228,8 +277,8 @@ __global__ __launch_bounds__(Geo<NC>::kThreads, 2) void r1d_kernel(const RunArgs
   auto samp_of = [](int n) { return PM ? (L == 4 ? (n & 15) : (n & 3)) : n / L; };
   auto pos_of = [](int n) { return PM ? (L == 4 ? (n >> 4) : (n >> 2)) : n % L; };
   auto col_of = [](int sm, int l) { return PM ? (L == 4 ? 16 * l + sm : 4 * l + sm) : sm * L + l; };
-  Ctx c{a.weights, lds, (int)threadIdx.x, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), (int)threadIdx.x & 63,
-        a.skip, GG::kNT};
+  R1dCtx c{{a.weights, lds, (int)threadIdx.x, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), (int)threadIdx.x & 63,
+            GG::kNT}, a.skip};
   if constexpr (PM && L == 16) c.park = a.park + (size_t)blockIdx.x * (kParkBytes / 4);
   const int E = d.emb_dim, R = d.cond_rows;
   float *lat = lds + GG::kMiscLat, *epsr = lds + GG::kMiscEps, *G = lds + GG::kMiscG;
@@ -738,8 +787,8 @@ Plan make_plan(int n_samples, int n_steps, int L, int nc, bool allow_chain = tru
 
 template <int NC, int L>
 int launch_one(const RunArgs &a, int tiles, hipStream_t s) {
-  const size_t lds_bytes = dbg_lds_bytes((size_t)Geo<NC>::kLdsFloats * sizeof(float));
-  gldm_dev::launch_dynamic_lds<r1d_kernel<NC, L>>(dim3(tiles), dim3(Geo<NC>::kThreads), (int)lds_bytes, lds_bytes, s, a);
+  const size_t lds_bytes = dbg_lds_bytes((size_t)R1dGeo<NC>::kLdsFloats * sizeof(float));
+  gldm_dev::launch_dynamic_lds<r1d_kernel<NC, L>>(dim3(tiles), dim3(R1dGeo<NC>::kThreads), (int)lds_bytes, lds_bytes, s, a);
   return hipGetLastError() == hipSuccess ? GLDM_OK : GLDM_ERR_LAUNCH;
 }
 

@@ -1,4 +1,4 @@
-// sa_mlp.hip -- the fused set-abstraction core on the GEMM cores of mfma_core.h.
+// sa_mlp.hip -- the fused set-abstraction core on the tile GEMMs of tile_gemm.h.
 // PointNetSAModule (ext/pvcnn/modules/pointnet.py:100-111) without the FPS:
 //   grouped = cat(p[idx] - centre, f[idx])          (BallQuery.forward)
 //   out[b, :, j] = max_k  SharedMLP2d(grouped)[b, :, j, k]
@@ -9,10 +9,10 @@
 //     f16 planes, layers on the f16 matrix pipe through the hi + lo split (gemm1_pl), range-scaled operands; PRE: the first
 //     layer hoisted into a per-point term; SUBMAX > 1: several tiles per workgroup pass for narrow nets;
 //   * sa_mlp2_kernel = gldm_sa_mlp_forward where the layer plan fits: 128-column f32 tiles, max taken on the accumulators;
-//   * sa_mlp_kernel  = gldm_sa_mlp_forward otherwise: one 64-column f32 tile = 64/U centres x U neighbours on conv_gemm.
+//   * sa_mlp_kernel  = gldm_sa_mlp_forward otherwise: one 64-column f32 tile = 64/U centres x U neighbours on conv_gemm (1x1 layers).
 //     HBM traffic: 12N + 4CN + 12M + 4MU (idx) in, 4 Cout M out per cloud.
 // Device code first, then launch_sa3 and the entry points.
-#include "mfma_core.h"
+#include "tile_gemm.h"
 
 namespace {
 
@@ -40,7 +40,7 @@ __global__ __launch_bounds__(Geo<64>::kThreads, 2) void sa_mlp_kernel(const SaAr
   constexpr int NC = 64;
   extern __shared__ float lds[];
   Ctx c{a.weights, lds, (int)threadIdx.x, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), (int)threadIdx.x & 63,
-        0, GG::kNT};
+        GG::kNT};
   const int b = blockIdx.y, tile = blockIdx.x;
   const int cpt = NC / a.u;                 // centres per tile
   const int j0 = tile * cpt;
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(Geo<64>::kThreads, 2) void sa_mlp_kernel(const SaAr
   // ---- grouped MLP (1x1 convs + folded BN + ReLU), ping-pong X <-> H
   float *src = X, *dst = H;
   for (int l = 0; l < a.n_layers; ++l) {
-    conv_gemm<NC, 4>(c, a.w_off[l], a.b_off[l], src, a.cin_pad[l], 1, dst, a.cout[l], false, 1);   // 1x1 layers only (L is the k = 3 convs' layout)
+    conv_gemm<NC, 4>(c, a.w_off[l], a.b_off[l], src, a.cin_pad[l], dst, a.cout[l], false, 1);   // (L is the k = 3 convs' layout: any)
     float *t = src; src = dst; dst = t;
   }
   // ---- max over the U neighbours of each centre
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(512, 1) void sa_mlp2_kernel(const SaArgs a, int row
   constexpr int NC = 128;
   extern __shared__ float lds[];
   Ctx c{a.weights, lds, (int)threadIdx.x, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), (int)threadIdx.x & 63,
-        0, 8};
+        8};
   const int cpt = NC / a.u;  // centres per tile
   float *A = lds, *B = lds + (size_t)rows_a * NC;
   const int w = c.wave, col = c.tid & (NC - 1), rq = c.tid >> 7;
@@ -468,7 +468,7 @@ __global__ __launch_bounds__(512, (PRE && QUADS <= 4) ? 4 : 2) void sa_mlp3_kern
                                                          int tiles_per_cloud, int total_tiles) {
   extern __shared__ float lds[];
   Ctx c{a.weights, lds, (int)threadIdx.x, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), (int)threadIdx.x & 63,
-        0, 4};
+        4};
   const int cpt = 64 / a.u;  // centres per tile
   const int per = (blocks_a + blocks_b) * kSaBlockFloats;   // floats of one tile's two plane regions
   const int w = c.wave, col = c.lane, qg = c.wave;   // gather: thread = (column, row-quad group)

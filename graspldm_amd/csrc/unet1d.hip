@@ -8,7 +8,7 @@
 // two-source (never materialised) concatenations and the skip stack are decided once on the host, where the LDS map is
 // also bounds-checked (unet1d_pack.check_program); the interpreter below has no network-shape logic of its own.
 //
-// GEMMs: every conv and 1x1 runs on the matrix pipe with f32 accumulation.  Default: split-f16 (mfma_core.h: split_planes8
+// GEMMs: every conv and 1x1 runs on the matrix pipe with f32 accumulation.  Default: split-f16 (mfma_prims.h: split_planes8
 // / mfma_split, weights pre-split on the host as [M/16][K/32][hi|lo][64][8]).  exact_f32: the same walk with
 // [M/16][K/32][64][8 f32] fragments on v_mfma_f32_16x16x4_f32 (lane (i, g) holds k = 32 kb + 8 g + j of row / column i for
 // both operands, so eight 16x16x4 products cover the block).  K runs over [source][tap][32-channel block], every source
@@ -16,7 +16,7 @@
 //   stride-2 k=4 conv (Downsample): taps read positions 2p-1 .. 2p+2, zero outside [0, Lin)
 //   nearest x2 + k=3 conv (Upsample): taps read x[(p + tap - 1) >> 1], zero outside [0, 2 Lin)
 // Norms, softmaxes and the scheduler step are f32 on the VALU; sums over a (sample, group) go through wave_sum (fixed tree).
-#include "mfma_core.h"
+#include "mfma_prims.h"
 
 namespace {
 

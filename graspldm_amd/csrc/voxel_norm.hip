@@ -8,7 +8,7 @@
 //   gldm_groupnorm_affine               x = a y + s over the grid: the norm without the activation
 //   gldm_groupnorm_swish_points[_sum]   GroupNorm + Swish over point features [b, c, n] (+ residual, + per-channel sums):
 //                                       the norms of the attention blocks
-#include "mfma_core.h"
+#include "mfma_prims.h"
 #include "voxel_geom.h"
 
 namespace {

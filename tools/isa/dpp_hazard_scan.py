@@ -4,7 +4,7 @@
 
 gfx9 (gfx950 included) needs 2 wait states between a VALU instruction that writes a VGPR and a DPP instruction that reads
 it as its DPP operand (src0).  The compiler's hazard recogniser inserts them for code it schedules itself; it does not look
-INSIDE an asm statement, and csrc/quad_narrow.h / mfma_core.h carry hand-written v_*_dpp blocks (GLDM_DPP8, fmac_ror,
+INSIDE an asm statement, and csrc/quad_narrow.h / mfma_prims.h carry hand-written v_*_dpp blocks (GLDM_DPP8, fmac_ror,
 dpp_max) whose correctness rests on an s_nop in front and on register allocation never placing a v_mov copy or a reload
 right before them.  This scan walks the final ISA: every instruction is one wait state, `s_nop N` is N + 1; a DPP
 instruction whose src0 register was written by a VALU instruction fewer than 2 wait states earlier is reported.  Exit code 1

@@ -22,7 +22,7 @@ lst() {  # kernel -> the listing that holds it
   case $1 in r1d_*) echo $tmp/r1d.s;; sa_*) echo $tmp/sa.s;; pointwise_mlp*) echo $tmp/pw.s;; pointwise_*|linear_*|bias_*) echo $tmp/ps.s;; conv3d_*) echo $tmp/c3.s;; gn_*|groupnorm_*|se_*|devoxelize_*) echo $tmp/vn.s;; attn_*) echo $tmp/pa.s;; cls_*) echo $tmp/gc.s;; esac
 }
 for k in r1d_kernelILi64ELi4 r1d_kernelILi32ELi16 pointwise_mlp_sp_kernel attn_gemm_kernelILb0ELb0 attn_gemm_kernelILb0ELb1 cls_head_kernelILb0 cls_head_kernelILb1; do python3 tools/isa/sunk_prefetch_scan.py $(lst $k) $k; python3 tools/isa/branch_density.py $(lst $k) $k; done
-# hand-written DPP blocks (quad_narrow.h, quad16_narrow.h, mfma_core.h): no VALU write closer than 2 wait states in front of a DPP read
+# hand-written DPP blocks (quad_narrow.h, quad16_narrow.h, mfma_prims.h): no VALU write closer than 2 wait states in front of a DPP read
 # of the same register -- nothing checks that inside an asm statement; fails the lint on any hit
 rc=0
 for k in r1d_kernelILi64ELi4 r1d_kernelILi64ELi16 r1d_kernelILi32ELi4 r1d_kernelILi32ELi16 sa_mlp3_kernel sa_mlp2_kernel pointwise_mlp_sp_kernel attn_gemm_kernelILb0ELb0 attn_gemm_kernelILb0ELb1 attn_gemm_kernelILb1ELb0 cls_head_kernelILb0 cls_head_kernelILb1; do

@@ -1,19 +1,21 @@
-// Per-shape rate of conv_gemm (the real code: csrc/mfma_core.h, included below) in isolation:
+// Per-shape rate of a conv layer (the real code: csrc/tile_gemm.h's conv_gemm and, for k = 3, csrc/r1d_gemm.h's conv3_f32,
+// included below) in isolation:
 // cycles per call vs the MFMA-bound ideal, with 1 or 2 workgroups per CU.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include tools/micro/gemm_rate.hip -o tools/micro/build/gemm_rate
-#include "../../graspldm_amd/csrc/mfma_core.h"
+#include "../../graspldm_amd/csrc/tile_gemm.h"
 #include <vector>
 
 namespace {
+#include "../../graspldm_amd/csrc/r1d_gemm.h"
 template <int NC, int L>
-__global__ __launch_bounds__(Geo<NC>::kThreads, 2) void gemm_probe(const float *w, int cin, int cout, int taps, int iters,
+__global__ __launch_bounds__(R1dGeo<NC>::kThreads, 2) void gemm_probe(const float *w, int cin, int cout, int taps, int iters,
                                                                   long long *cycles) {
-  using GG = Geo<NC>;
+  using GG = R1dGeo<NC>;
   extern __shared__ float lds[];
 #ifdef GLDM_PROBE_COPIES
   w += ((blockIdx.x / 256) & 1) * (1 << 19);
 #endif
-  Ctx c{w, lds, (int)threadIdx.x, (int)threadIdx.x >> 6, (int)threadIdx.x & 63, 0, GG::kNT};
+  R1dCtx c{{w, lds, (int)threadIdx.x, (int)threadIdx.x >> 6, (int)threadIdx.x & 63, GG::kNT}, 0};
   for (int i = c.tid; i < GG::kLdsFloats; i += GG::kThreads) lds[i] = 0.f;
   __syncthreads();
 #ifdef GLDM_PROBE_SKEW
@@ -25,7 +27,7 @@ __global__ __launch_bounds__(Geo<NC>::kThreads, 2) void gemm_probe(const float *
 #endif
   const long long t0 = __builtin_readcyclecounter();
   for (int i = 0; i < iters; ++i) {
-    Ctx cc = c;
+    R1dCtx cc = c;
     asm volatile("" : "+v"(cc.tid), "+v"(cc.lane));  // as run_tape does: no hoisting of lane-derived offsets
     int ci = cin, co = cout, tp = taps;
     asm volatile("" : "+s"(ci), "+s"(co), "+s"(tp));  // per-op values in the real kernel (read from the tape)
@@ -33,7 +35,12 @@ __global__ __launch_bounds__(Geo<NC>::kThreads, 2) void gemm_probe(const float *
     cc.w = w + (size_t)(i % 48) * (1 << 19);  // 48 x 2 MiB apart: every call streams weights that left L2 (96 MiB cycle)
 #endif
     // 64 columns: 1x1 layers only (main() asks for nothing else; the k = 3 convs of that geometry are the engine's own)
-    conv_gemm<NC, L>(cc, 0, 1 << 18, lds + GG::kBufX, ci, NC == 64 ? 1 : tp, lds + GG::kBufH, co, false);
+    if (NC != 64 && tp == 3) {
+      if constexpr (NC != 64) conv3_f32<NC, L>(cc, cc.w, cc.w + (1 << 18), lds + GG::kBufX, ci, lds + GG::kBufH, co, false, GnEpilogue{0, 0, 0, -1, 0, 0, 0, 0, nullptr});
+      __syncthreads();
+    } else {
+      conv_gemm<NC, L>(cc, 0, 1 << 18, lds + GG::kBufX, ci, lds + GG::kBufH, co, false);
+    }
   }
   const long long t1 = __builtin_readcyclecounter();
   if (c.tid == 0) cycles[blockIdx.x] = t1 - t0;
@@ -42,13 +49,13 @@ __global__ __launch_bounds__(Geo<NC>::kThreads, 2) void gemm_probe(const float *
 template <int NC>
 void run(const float *w, long long *dcyc, int wgs, int cin, int cout, int taps) {
   const int iters = 200;
-  const size_t lds = (size_t)Geo<NC>::kLdsFloats * 4;
+  const size_t lds = (size_t)R1dGeo<NC>::kLdsFloats * 4;
   (void)hipFuncSetAttribute((const void *)gemm_probe<NC, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipEvent_t e0, e1;
   (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-  hipLaunchKernelGGL((gemm_probe<NC, 4>), dim3(wgs), dim3(Geo<NC>::kThreads), lds, 0, w, cin, cout, taps, iters, dcyc);
+  hipLaunchKernelGGL((gemm_probe<NC, 4>), dim3(wgs), dim3(R1dGeo<NC>::kThreads), lds, 0, w, cin, cout, taps, iters, dcyc);
   (void)hipEventRecord(e0, 0);
-  hipLaunchKernelGGL((gemm_probe<NC, 4>), dim3(wgs), dim3(Geo<NC>::kThreads), lds, 0, w, cin, cout, taps, iters, dcyc);
+  hipLaunchKernelGGL((gemm_probe<NC, 4>), dim3(wgs), dim3(R1dGeo<NC>::kThreads), lds, 0, w, cin, cout, taps, iters, dcyc);
   (void)hipEventRecord(e1, 0);
   (void)hipEventSynchronize(e1);
   float ms = 0;

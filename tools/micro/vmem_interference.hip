@@ -1,27 +1,29 @@
 // How long does a short batch of loads take on a CU whose other workgroup streams conv weights?
 // Even workgroups (blockIdx / 256 even) run the engine's 256x256 k=3 conv in a loop; odd ones time a batch of
 // `nload` 16-byte loads (L2-hot, like the parameters of a short op).  Build as tools/micro/gemm_rate.hip.
-#include "../../graspldm_amd/csrc/mfma_core.h"
+#include "../../graspldm_amd/csrc/tile_gemm.h"
 #include <vector>
 
 namespace {
+#include "../../graspldm_amd/csrc/r1d_gemm.h"
 template <int MODE>  // 0: partner idle, 1: partner streams weights
 __global__ __launch_bounds__(256, 2) void probe(const float *w, const float *small, int iters, int nload, long long *cyc,
                                                 float *sink) {
-  using GG = Geo<32>;
+  using GG = R1dGeo<32>;
   extern __shared__ float lds[];
-  Ctx c{w, lds, (int)threadIdx.x, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), (int)threadIdx.x & 63, 0, GG::kNT};
+  R1dCtx c{{w, lds, (int)threadIdx.x, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), (int)threadIdx.x & 63, GG::kNT}, 0};
   for (int i = c.tid; i < GG::kLdsFloats; i += GG::kThreads) lds[i] = 0.f;
   __syncthreads();
   const bool heavy = ((blockIdx.x / 256) & 1) == 0;
   if (heavy) {
     if (MODE == 1) {
       for (int i = 0; i < iters / 4; ++i) {
-        Ctx cc = c;
+        R1dCtx cc = c;
         asm volatile("" : "+v"(cc.tid), "+v"(cc.lane));
-        int ci = 256, co = 256, tp = 3;
-        asm volatile("" : "+s"(ci), "+s"(co), "+s"(tp));
-        conv_gemm<32, 4>(cc, 0, 1 << 18, lds + GG::kBufX, ci, tp, lds + GG::kBufH, co, false);
+        int ci = 256, co = 256;
+        asm volatile("" : "+s"(ci), "+s"(co));
+        conv3_f32<32, 4>(cc, cc.w, cc.w + (1 << 18), lds + GG::kBufX, ci, lds + GG::kBufH, co, false, GnEpilogue{0, 0, 0, -1, 0, 0, 0, 0, nullptr});
+        __syncthreads();
       }
     }
     return;
@@ -70,7 +72,7 @@ int main() {
   (void)hipMalloc(&small, 1 << 20); (void)hipMemset(small, 0, 1 << 20);
   (void)hipMalloc(&sink, 512 * 64 * 4);
   (void)hipMalloc(&dcyc, 512 * sizeof(long long));
-  const size_t lds = (size_t)Geo<32>::kLdsFloats * 4;
+  const size_t lds = (size_t)R1dGeo<32>::kLdsFloats * 4;
   (void)hipFuncSetAttribute((const void *)probe<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   (void)hipFuncSetAttribute((const void *)probe<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const int iters = 400;
