@@ -11,79 +11,23 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "host_util.h"
+#include "knn_scan.h"
 
 namespace {
 
-constexpr int kChunk = 256;        // points staged per step = threads per workgroup = query points per workgroup
-constexpr int kMaxK = 16;
-constexpr int kMaxN = 1 << 20;
 constexpr int kSweeps = 8;         // cyclic Jacobi sweeps over a 3 x 3 matrix in f64 (quadratic convergence: 5 suffice)
-constexpr uint32_t kInfBits = 0x7f800000u;
 
 // A neighbour is one 64-bit key: the bits of d2 (a non-negative float orders like its bit pattern) above the index.  Keys
 // order exactly like (d2, index), so the k smallest keys are the answer whatever order the candidates arrive in.
 __device__ __forceinline__ uint64_t make_key(float d2, int j) { return ((uint64_t)__float_as_uint(d2) << 32) | (uint32_t)j; }
 
-struct Box {
-  float lo[3], hi[3];
-};
-
-// Squared distance between two boxes in the arithmetic of a point pair: per axis the gap g = max(0, alo - bhi, blo - ahi)
-// is a rounded difference of two coordinates that bracket every pair's, and rounding is monotone, so |fl(xi - xj)| >= g for
-// every point i of one box and j of the other; squares and the two sums are monotone as well.  Hence the value returned is
-// <= the d2 the scan computes for ANY such pair: a chunk with box_d2 > bound holds no candidate with d2 <= bound, not even
-// one that ties.  No margin is needed and no bit of the result depends on the skip.
-__device__ __forceinline__ float box_d2(const Box &a, const Box &b) {
-  float g[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) g[c] = fmaxf(0.f, fmaxf(a.lo[c] - b.hi[c], b.lo[c] - a.hi[c]));
-  return (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
-}
-
-// boxes [b, chunks, 6]: lo xyz, hi xyz of every 256-point chunk.
+// boxes [b, chunks, 6]: lo xyz, hi xyz of every 256-point chunk (Box, box_d2 and the body: knn_scan.h).
 __global__ __launch_bounds__(kChunk) void chunk_box_kernel(const float *__restrict__ pc, int n, int chunks,
                                                            float *__restrict__ boxes) {
-  __shared__ float red[kChunk / 64][6];
-  const int tid = threadIdx.x;
   const int ch = blockIdx.x % chunks;
   const int cloud = blockIdx.x / chunks;
   const int p0 = ch * kChunk;
-  const int cnt = min(kChunk, n - p0);
-  const float *src = pc + ((long long)cloud * n + p0) * 3;
-  const int i = min(tid, cnt - 1);   // a lane past the end repeats the last point
-  float v[6];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) v[c] = v[c + 3] = src[i * 3 + c];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      v[c] = fminf(v[c], __shfl_xor(v[c], off));
-      v[c + 3] = fmaxf(v[c + 3], __shfl_xor(v[c + 3], off));
-    }
-  }
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int c = 0; c < 6; ++c) red[tid >> 6][c] = v[c];
-  }
-  __syncthreads();
-  if (tid < 6) {
-    float r = red[0][tid];
-#pragma unroll
-    for (int w = 1; w < kChunk / 64; ++w) r = tid < 3 ? fminf(r, red[w][tid]) : fmaxf(r, red[w][tid]);
-    boxes[((long long)cloud * chunks + ch) * 6 + tid] = r;
-  }
-}
-
-__device__ __forceinline__ Box load_box(const float *__restrict__ boxes, long long at) {
-  Box b;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    b.lo[c] = boxes[at * 6 + c];
-    b.hi[c] = boxes[at * 6 + 3 + c];
-  }
-  return b;
+  chunk_box_body(pc + ((long long)cloud * n + p0) * 3, min(kChunk, n - p0), boxes + ((long long)cloud * chunks + ch) * 6);
 }
 
 // Grid: clouds x chunks.  A workgroup's 256 lanes are the query points of one chunk; every lane keeps its KT smallest keys
@@ -114,23 +58,7 @@ __global__ __launch_bounds__(kChunk) void knn_kernel(const float *__restrict__ p
   for (int s = 0; s < KT; ++s) key[s] = empty;
 
   const Box own_box = load_box(cloud_boxes, own);
-  Box wave_box;   // of this wave's query points (dead lanes repeat the cloud's last point, which is in the chunk)
-  {
-    float v[6] = {qx, qy, qz, qx, qy, qz};
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        v[c] = fminf(v[c], __shfl_xor(v[c], off));
-        v[c + 3] = fmaxf(v[c + 3], __shfl_xor(v[c + 3], off));
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      wave_box.lo[c] = v[c];
-      wave_box.hi[c] = v[c + 3];
-    }
-  }
+  const Box wave_box = wave_query_box(qx, qy, qz);   // dead lanes repeat the cloud's last point, which is in the chunk
   float bound = r2;   // wave-uniform
 
   const int reach = max(own, chunks - 1 - own);
@@ -143,40 +71,20 @@ __global__ __launch_bounds__(kChunk) void knn_kernel(const float *__restrict__ p
       if (box_d2(own_box, cb) > r2) continue;                             // uniform over the workgroup
       const int p0 = ch * kChunk;
       const int cnt = min(kChunk, n - p0);
-      const float *src = cloud_pts + (long long)p0 * 3;
-      __syncthreads();   // the previous chunk has been read
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int f = tid + c * kChunk;
-        if (f < cnt * 3) pts[f] = src[f];
-      }
-      __syncthreads();
+      stage_chunk(pts, cloud_pts + (long long)p0 * 3, cnt);
       if (box_d2(wave_box, cb) > bound) continue;   // wave-uniform; the barriers above are behind this wave already
       for (int c = 0; c < cnt; ++c) {
         const float dx = pts[c * 3 + 0] - qx, dy = pts[c * 3 + 1] - qy, dz = pts[c * 3 + 2] - qz;
         const float d2 = (dx * dx + dy * dy) + dz * dz;
         const uint64_t cand = make_key(d2, p0 + c);
-        const bool in = live && d2 <= r2 && cand < key[KT - 1];
-        if (__ballot(in) != 0ull) {   // most candidates end here: one compare
-          uint64_t carry = in ? cand : ~0ull;
-#pragma unroll
-          for (int s = 0; s < KT; ++s) {
-            const bool lt = carry < key[s];
-            const uint64_t lo = lt ? carry : key[s];
-            carry = lt ? key[s] : carry;
-            key[s] = lo;
-          }
-        }
+        insert_key<uint64_t, KT>(key, cand, live && d2 <= r2 && cand < key[KT - 1]);
       }
       // the wave's largest k-th squared distance: +inf while a live lane's list is short
       uint32_t kth = 0u;
 #pragma unroll
       for (int s = 0; s < KT; ++s)
         if (s == k - 1) kth = (uint32_t)(key[s] >> 32);
-      kth = live ? kth : 0u;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) kth = max(kth, (uint32_t)__shfl_xor((int)kth, off));
-      bound = fminf(r2, __uint_as_float(kth));
+      bound = fminf(r2, __uint_as_float(wave_max_bits(live ? kth : 0u)));
     }
   }
 

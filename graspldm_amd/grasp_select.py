@@ -252,3 +252,36 @@ class GraspSelection:
     @property
     def needs_success(self):
         return self.min_success is not None or self.score_by in ("success", "product")
+
+
+@dataclass(frozen=True)
+class CloudCleanup:
+    """Outlier removal on the object clouds of a depth frame, between deprojection and point-count regularisation
+    (pointcloud.remove_outliers): keep a point iff at least min_neighbors other points of its cloud lie
+    within max_radius (counted up to k) and, with std_ratio (None: off), its mean distance to them is at most mu + std_ratio
+    * sigma of its cloud.  apply_to_scene: filter the scene cloud a GraspSelection is checked against as well."""
+    k: int = 8
+    max_radius: float = 0.01
+    min_neighbors: int = 3
+    std_ratio: Optional[float] = None
+    apply_to_scene: bool = False
+
+    def __post_init__(self):
+        if not (isinstance(self.k, int) and not isinstance(self.k, bool) and 1 <= self.k <= 16):
+            raise ValueError(f"k must be an integer in 1 .. 16, not {self.k!r}")
+        if not (isinstance(self.max_radius, (int, float)) and not isinstance(self.max_radius, bool)
+                and math.isfinite(self.max_radius) and self.max_radius >= 0):
+            raise ValueError(f"max_radius must be >= 0, not {self.max_radius!r}")
+        if not (isinstance(self.min_neighbors, int) and not isinstance(self.min_neighbors, bool)
+                and 0 <= self.min_neighbors <= self.k):
+            raise ValueError(f"min_neighbors must be an integer in 0 .. k = {self.k}, not {self.min_neighbors!r}")
+        if self.std_ratio is not None and not (isinstance(self.std_ratio, (int, float)) and not isinstance(self.std_ratio, bool)
+                                               and not math.isnan(self.std_ratio)):
+            raise ValueError(f"std_ratio must be a number (or None), not {self.std_ratio!r}")
+        if not isinstance(self.apply_to_scene, bool):
+            raise ValueError(f"apply_to_scene must be a bool, not {self.apply_to_scene!r}")
+
+    @property
+    def options(self):
+        """The keyword arguments of pointcloud.remove_outliers."""
+        return dict(k=self.k, max_radius=self.max_radius, min_neighbors=self.min_neighbors, std_ratio=self.std_ratio)

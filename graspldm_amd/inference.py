@@ -299,7 +299,7 @@ class _InferenceBase:
 
     def infer_on_depth(self, depth, camera, mask=None, num_grasps=10, num_points=None, use_farthest_point=True,
                        z_range=None, depth_scale=None, cam_to_world=None, crop_box=None, selection=None, scene_pc=None,
-                       return_intermediate=False):
+                       return_intermediate=False, cleanup=None):
         """From a depth frame to grasps without leaving the GPU (additive; the reference stops at
         Camera.depth_to_pointcloud_torch, grasp_ldm/utils/camera.py:176-215, and leaves the rest to the caller).
         depth [H, W] or [F, H, W] (CUDA; float32 metres or raw 16-bit units with depth_scale), camera: a
@@ -309,20 +309,30 @@ class _InferenceBase:
         min_contacts or min_aligned_contacts and no scene_pc is given, the scene is the same frame without mask and crop,
         inside z_range.
         Poses are in the camera frame, or in the world frame with cam_to_world (3 x 4 / 4 x 4).  A frame whose object
-        cloud is empty raises ValueError before anything is generated.  F frames -> results of batch F."""
-        from .pointcloud import PointCloudHelpers, depth_to_cloud
+        cloud is empty raises ValueError before anything is generated.  F frames -> results of batch F.
+        `cleanup` (a graspldm_amd.grasp_select.CloudCleanup): the object clouds of all frames lose their
+        outliers in one pointcloud.remove_outliers call before anything else sees them; the empty-cloud check refers to the
+        filtered clouds, the results gain object_points and object_points_raw [F] (points after / before the filter), and
+        with cleanup.apply_to_scene the scene cloud taken from the frame is filtered too."""
+        from .pointcloud import depth_to_cloud
         depth = depth.to(self.device) if isinstance(depth, torch.Tensor) else depth
         mask = mask.to(self.device) if isinstance(mask, torch.Tensor) else mask
         kw = dict(z_range=z_range, depth_scale=depth_scale, cam_to_world=cam_to_world)
         clouds = depth_to_cloud(depth, camera, mask=mask, crop_box=crop_box, **kw)
         single = depth.ndim == 2
         clouds = [clouds] if single else clouds
+        if cleanup is not None:
+            raw_counts = [c.shape[0] for c in clouds]
+            clouds = self._clean_clouds(clouds, cleanup)
         for f, c in enumerate(clouds):
             if c.shape[0] == 0:
                 raise ValueError(f"frame {f}: the object cloud is empty (no pixel passes the mask, the depth window "
                                  "and the crop box)")
         if selection is not None and scene_pc is None and selection.needs_scene:
             scenes = depth_to_cloud(depth, camera, **kw)
+            if cleanup is not None and cleanup.apply_to_scene:
+                scenes = self._clean_clouds([scenes] if single else scenes, cleanup)
+                scenes = scenes[0] if single else scenes
             if single:
                 scene_pc = scenes
             elif len({s.shape[0] for s in scenes}) == 1:
@@ -331,6 +341,15 @@ class _InferenceBase:
                 raise ValueError("the frames' scene clouds differ in size and cannot form one batch: pass scene_pc "
                                  "[F, Ns, 3], or call infer_on_depth frame by frame")
         extra = {} if selection is None else dict(selection=selection, scene_pc=scene_pc)
+        out = self._infer_on_clouds(clouds, single, num_grasps, num_points, use_farthest_point, return_intermediate, extra)
+        if cleanup is not None:
+            out["object_points"] = torch.tensor([c.shape[0] for c in clouds], dtype=torch.int64, device=self.device)
+            out["object_points_raw"] = torch.tensor(raw_counts, dtype=torch.int64, device=self.device)
+        return out
+
+    def _infer_on_clouds(self, clouds, single, num_grasps, num_points, use_farthest_point, return_intermediate, extra):
+        """The back half of infer_on_depth: the frames' object clouds -> results of batch F."""
+        from .pointcloud import PointCloudHelpers
         if single:
             return self.infer_on_pointcloud(clouds[0], num_grasps=num_grasps, return_intermediate=return_intermediate,
                                             num_points=num_points, use_farthest_point=use_farthest_point, **extra)
@@ -345,9 +364,29 @@ class _InferenceBase:
         pcn, metas = self.normalize_input(batch)
         return self.generate_grasps(pcn, metas, num_grasps=num_grasps, return_intermediate=return_intermediate, **extra)
 
+    @staticmethod
+    def _clean_objects(packed, starts, counts, cleanup):
+        """The objects of one frame (rows starts[k] .. + counts[k] of packed) through ONE ragged pointcloud.remove_outliers
+        call -> (packed, starts, counts) of the filtered objects."""
+        from .grasp_select import CloudCleanup
+        from .pointcloud import remove_outliers
+        if not isinstance(cleanup, CloudCleanup):
+            raise TypeError("cleanup must be a graspldm_amd.grasp_select.CloudCleanup")
+        out, ostart, ocount, _, _ = remove_outliers(packed, start=starts, count=counts, **cleanup.options)
+        return out, ostart, ocount
+
+    @staticmethod
+    def _clean_clouds(clouds, cleanup):
+        """A list of clouds [n_i, 3] through ONE pointcloud.remove_outliers call -> the list of the filtered clouds."""
+        counts = [c.shape[0] for c in clouds]
+        starts = [sum(counts[:i]) for i in range(len(counts))]
+        packed = clouds[0] if len(clouds) == 1 else torch.cat(clouds)
+        out, ostart, ocount = _InferenceBase._clean_objects(packed, starts, counts, cleanup)
+        return [out[s:s + c] for s, c in zip(ostart, ocount)]
+
     def infer_on_scene(self, depth, camera, labels, num_grasps=10, num_points=None, num_labels=None, min_object_points=32,
                        use_farthest_point=True, mask=None, z_range=None, depth_scale=None, cam_to_world=None, crop_box=None,
-                       selection=None, scene_pc=None):
+                       selection=None, scene_pc=None, cleanup=None):
         """One depth frame [H, W] with an instance-label image -> the grasps of every object, as ONE batch (additive,
         DESIGN.md 4.11).  labels: integer tensor of depth's shape, object k = label k (1 .. num_labels, at most 64; default
         labels.max()); the other arguments as infer_on_depth.  Objects with fewer than min_object_points points are skipped;
@@ -357,7 +396,11 @@ class _InferenceBase:
         same frame without labels, mask and crop, inside z_range, as one [1, Ns, 3] cloud for every object.
         Added keys: object_label [B] and object_points [B] (label and raw point count of every row of the batch),
         scene_rank [n, 2] int64: (object row, slot) of every pose that is not NaN, by falling score (selection.score_by;
-        confidence without a selection), ties to the lower object, then the lower slot."""
+        confidence without a selection), ties to the lower object, then the lower slot.
+        `cleanup` (a graspldm_amd.grasp_select.CloudCleanup): ONE ragged pointcloud.remove_outliers call over
+        all objects of the frame, between the deprojection and regularize_objects; min_object_points, the error above and
+        object_points then refer to the filtered counts and object_points_raw [B] holds the unfiltered ones; with
+        cleanup.apply_to_scene the scene cloud taken from the frame is filtered too."""
         from .pointcloud import _depth_to_objects_packed, depth_to_cloud, regularize_objects
         depth = depth.to(self.device) if isinstance(depth, torch.Tensor) else depth
         labels = labels.to(self.device) if isinstance(labels, torch.Tensor) else labels
@@ -368,6 +411,9 @@ class _InferenceBase:
         points, _, starts, counts = _depth_to_objects_packed(depth, camera, labels, num_labels=num_labels, mask=mask,
                                                              crop_box=crop_box, **kw)
         packed, starts, counts = points[0], starts[0], counts[0]
+        if cleanup is not None:
+            raw_counts = counts
+            packed, starts, counts = self._clean_objects(packed, starts, counts, cleanup)
         kept = [k for k, c in enumerate(counts) if c >= max(int(min_object_points), 1)]
         if not kept:
             raise ValueError(f"no object has at least {min_object_points} points (labels 1 .. {len(counts)} hold "
@@ -380,24 +426,30 @@ class _InferenceBase:
         else:
             batch = regularize_objects(packed, ks, kc, num_points, use_farthest_point)
         if selection is not None and scene_pc is None and selection.needs_scene:
-            scene_pc = depth_to_cloud(depth, camera, **kw).unsqueeze(0)
+            scene_pc = depth_to_cloud(depth, camera, **kw)
+            if cleanup is not None and cleanup.apply_to_scene:
+                scene_pc = self._clean_clouds([scene_pc], cleanup)[0]
+            scene_pc = scene_pc.unsqueeze(0)
         extra = {} if selection is None else dict(selection=selection, scene_pc=scene_pc)
         pcn, metas = self.normalize_input(batch)
         out = self.generate_grasps(pcn, metas, num_grasps=num_grasps, **extra)
         out["object_label"] = torch.tensor([k + 1 for k in kept], dtype=torch.int64, device=self.device)
         out["object_points"] = torch.tensor(kc, dtype=torch.int64, device=self.device)
+        if cleanup is not None:
+            out["object_points_raw"] = torch.tensor([raw_counts[k] for k in kept], dtype=torch.int64, device=self.device)
         out["scene_rank"] = self._scene_rank(out, selection)
         return out
 
     def infer_on_tabletop(self, depth, camera, num_grasps=10, num_points=None, segmentation=None, min_object_points=32,
                           use_farthest_point=True, mask=None, z_range=None, depth_scale=None, cam_to_world=None,
-                          crop_box=None, selection=None, scene_pc=None):
+                          crop_box=None, selection=None, scene_pc=None, cleanup=None):
         """One depth frame [H, W] of objects standing on a table -> the grasps of every object, without a label image
         (additive): pointcloud.segment_tabletop makes the labels on the GPU (a RANSAC table plane, then the
         connected components above it), infer_on_scene does the rest with them.  segmentation: a dict of
         segment_tabletop's own options (plane, height_range, link_dist, min_pixels, max_objects, tol, hypotheses, rng,
         refit, min_cross2); the depth options go to both.  The result of infer_on_scene gains `labels` ([H, W] int32) and
-        `table_plane` (pointcloud.TablePlane).  No object found: ValueError."""
+        `table_plane` (pointcloud.TablePlane).  No object found: ValueError.  `cleanup`: as in infer_on_scene (the labels are made
+        from the unfiltered frame)."""
         from .pointcloud import segment_tabletop
         depth = depth.to(self.device) if isinstance(depth, torch.Tensor) else depth
         mask = mask.to(self.device) if isinstance(mask, torch.Tensor) else mask
@@ -409,7 +461,8 @@ class _InferenceBase:
             raise ValueError("no object found on the table (no component of enough pixels inside the height range)")
         out = self.infer_on_scene(depth, camera, labels, num_grasps=num_grasps, num_points=num_points, num_labels=num,
                                   min_object_points=min_object_points, use_farthest_point=use_farthest_point,
-                                  selection=selection, scene_pc=scene_pc, **kw)
+                                  selection=selection, scene_pc=scene_pc, **kw, **({} if cleanup is None else
+                                                                                   dict(cleanup=cleanup)))
         out["labels"] = labels
         out["table_plane"] = plane
         return out

@@ -16,7 +16,8 @@ from disk, and clouds of more than 8192 points take gldm_farthest_points_euclid_
 (gldm_farthest_points_euclid_ragged) and one gather.  Without a label image `fit_table_plane` finds the
 table (gldm_plane_ransac, gldm_plane_moments) and `segment_tabletop` labels the objects standing on it
 (gldm_segment_tabletop).  `estimate_normals` gives a sensor cloud its surface normals (gldm_knn_radius,
-gldm_point_normals; estimate_normals_cam_from_pc, pointcloud_helpers.py:74-122).
+gldm_point_normals; estimate_normals_cam_from_pc, pointcloud_helpers.py:74-122).  `remove_outliers` drops
+the isolated points of sensor clouds before any of that sees them (gldm_neighbor_stats, gldm_filter_outliers).
 """
 import ctypes
 import typing
@@ -805,3 +806,146 @@ def estimate_normals(pc, max_radius=0.05, k=12, view_point=None):
     if pc.ndim == 2:
         return normals[0], found[0]
     return normals, found
+
+
+# ----------------------------------------------------------------------------------------------- sensor-cloud cleanup --
+# outlier removal between deprojection and farthest-point selection (gldm_neighbor_stats,
+# gldm_filter_outliers): Open3D's remove_radius_outlier / remove_statistical_outlier on ragged batches, without the round
+# trip through scipy.
+CLEANUP_MAX_K = 16              # gldm_neighbor_stats' ceiling on k
+CLEANUP_MAX_POINTS = 1 << 20    # ... on the points of one cloud
+CLEANUP_MAX_CLOUDS = 65535      # ... and on the clouds of one call
+
+
+def _check_cleanup_envelope(k, max_radius, min_neighbors=0, std_ratio=None):
+    if not 1 <= int(k) <= CLEANUP_MAX_K:
+        raise NotImplementedError(f"k = {k}: gldm_neighbor_stats keeps 1 .. {CLEANUP_MAX_K} neighbours per point")
+    r = float(max_radius)
+    if not (r >= 0.0 and float(np.float32(r)) ** 2 <= FLT_MAX):   # r2 finite in f32 (NaN fails both)
+        raise ValueError(f"max_radius must be >= 0 with a finite square in f32, not {max_radius!r}")
+    if not 0 <= int(min_neighbors) <= int(k):
+        raise ValueError(f"min_neighbors must be 0 .. k = {int(k)}, not {min_neighbors}")
+    if std_ratio is not None and float(std_ratio) != float(std_ratio):
+        raise ValueError("std_ratio must not be NaN (None or a negative value switches the statistical rule off)")
+
+
+def _ragged_layout(points, start, count):
+    """The checks in front of the ragged entries: points [n,3] / [b,n,3] dense, or [rows,3] with start / count (host
+    sequences or tensors: one read-back) -> (pts [rows,3] f32 contiguous, start, count as host lists, dense shape or None).
+    Raises before any library call."""
+    _need_cuda(points, "points")
+    if (start is None) != (count is None):
+        raise ValueError("start and count go together")
+    if start is None:
+        pcb = _as_batch(points)
+        b, n, _ = pcb.shape
+        pts, start, count, dense = pcb.reshape(b * n, 3), [i * n for i in range(b)], [n] * b, tuple(points.shape[:-1])
+    else:
+        if points.ndim != 2 or points.shape[1] != 3:
+            raise ValueError(f"with start / count, points must be [rows, 3], not {tuple(points.shape)}")
+        pts, dense = points.contiguous().float(), None
+        start = [int(s) for s in (start.tolist() if isinstance(start, torch.Tensor) else start)]
+        count = [int(c) for c in (count.tolist() if isinstance(count, torch.Tensor) else count)]
+    b, rows = len(start), pts.shape[0]
+    if len(count) != b:
+        raise ValueError(f"start holds {b} clouds, count {len(count)}")
+    if not 1 <= b <= CLEANUP_MAX_CLOUDS:
+        raise NotImplementedError(f"{b} clouds: gldm_neighbor_stats takes 1 .. {CLEANUP_MAX_CLOUDS} clouds per call")
+    if rows > 0x7fffffff:
+        raise NotImplementedError(f"{rows} rows: gldm_neighbor_stats takes at most 2^31 - 1 rows per call")
+    end = 0
+    for i, (s, c) in sorted(enumerate(zip(start, count)), key=lambda t: t[1][0]):
+        if c < 0:
+            raise ValueError(f"cloud {i}: count {c} is negative")
+        if c > CLEANUP_MAX_POINTS:
+            raise NotImplementedError(f"cloud {i} has {c} points: gldm_neighbor_stats takes at most 2^20 = "
+                                      f"{CLEANUP_MAX_POINTS} points per cloud")
+        if c and (s < 0 or s + c > rows):
+            raise ValueError(f"cloud {i}: rows {s} .. {s + c} leave points [{rows}, 3]")
+        if c and s < end:
+            raise ValueError(f"cloud {i}: rows {s} .. {s + c} overlap another cloud")
+        end = s + c if c else end
+    return pts, start, count, dense
+
+
+def _finite_rows(pts, start, count, dense):
+    """Non-finite values inside a cloud's rows raise GldmError; the gaps between the clouds may hold anything."""
+    if dense is not None:
+        return _finite_cloud(pts)
+    bad = (~torch.isfinite(pts)).any(dim=1).to(torch.int32)
+    run = torch.cat([torch.zeros(1, dtype=torch.int64, device=pts.device), torch.cumsum(bad, 0)])
+    s = torch.tensor(start, dtype=torch.int64, device=pts.device).clamp(0, pts.shape[0])
+    e = (s + torch.tensor(count, dtype=torch.int64, device=pts.device)).clamp(0, pts.shape[0])
+    if bool((run[e] - run[s]).ne(0).any()):
+        raise L.GldmError("the points hold non-finite values")
+
+
+def _neighbor_stats(pts, sc, b, n_max, k, max_radius):
+    """gldm_neighbor_stats on checked arguments; sc int32 [2, b] on the device (start, count) -> (neighbors, score) [rows]."""
+    dev, rows = pts.device, pts.shape[0]
+    ws, nbytes = L.workspace("gldm_neighbor_stats", (b, n_max), torch.float32, dev,
+                             f"b = {b}, n_max = {n_max}; b <= {CLEANUP_MAX_CLOUDS}, n_max <= 2^20")
+    neighbors = torch.zeros(rows, dtype=torch.int32, device=dev)
+    score = torch.full((rows,), float("inf"), dtype=torch.float32, device=dev)
+    if ws is not None and rows:
+        with torch.cuda.device(dev):
+            L.call("gldm_neighbor_stats", L.ptr(pts), L.ptr(sc[0]), L.ptr(sc[1]), b, n_max, rows, int(k), float(max_radius),
+                   L.ptr(ws), nbytes, L.ptr(neighbors), L.ptr(score), L.current_stream(dev))
+    return neighbors, score
+
+
+def neighbor_stats(points, k, max_radius, start=None, count=None):
+    """gldm_neighbor_stats: for every point the number of OTHER points of its cloud within max_radius, capped at k, and the
+    mean distance to the up to k nearest of them (+inf where there is none).  points [n,3] or [b,n,3]; or [rows,3] with
+    start / count (host sequences or tensors of b ints): cloud i = rows start[i] .. start[i] + count[i], rows outside every
+    cloud are never read.  -> (neighbors int32, score f32) of points' leading shape; rows outside every cloud carry 0 / +inf.
+    d2 = (dx*dx + dy*dy) + dz*dz in f32 as in knn_radius; a duplicate of a point is its neighbour at distance 0."""
+    _check_cleanup_envelope(k, max_radius)
+    pts, start, count, dense = _ragged_layout(points, start, count)
+    _finite_rows(pts, start, count, dense)
+    sc = torch.tensor([start, count], dtype=torch.int32, device=pts.device)
+    neighbors, score = _neighbor_stats(pts, sc, len(start), max(count), k, max_radius)
+    if dense is not None:
+        return neighbors.reshape(dense), score.reshape(dense)
+    return neighbors, score
+
+
+def remove_outliers(points, k=8, max_radius=0.01, min_neighbors=3, std_ratio=None, start=None, count=None):
+    """Outlier removal on the GPU (gldm_neighbor_stats + gldm_filter_outliers).  A point is kept iff it has at
+    least min_neighbors other points of its cloud within max_radius (counted up to k: Open3D's remove_radius_outlier) and,
+    with std_ratio (None or negative: off), at least one and a mean distance to its up to k nearest of them of at most
+    mu + std_ratio * sigma, mean and sample deviation of that figure over the cloud's points with at least
+    max(min_neighbors, 1) neighbours (remove_statistical_outlier, bounded by the radius).
+    points / start / count as neighbor_stats.  The kept rows keep their order.
+    -> (points, start, count, kept, stats): the packed kept rows [total, 3] (bit copies), start / count host lists of b ints
+    (ONE read-back), kept int32 [total]: the source row of every output row relative to its cloud's start; stats: dict of
+    mu, sigma (f64 [b] on the device), neighbors, score (neighbor_stats' outputs).  For one cloud [n,3]: (points [m,3], 0, m,
+    kept [m], stats)."""
+    _check_cleanup_envelope(k, max_radius, min_neighbors, std_ratio)
+    pts, start, count, dense = _ragged_layout(points, start, count)
+    total_in = sum(count)
+    if total_in > 0x7fffffff:
+        raise NotImplementedError(f"{total_in} points in all: gldm_filter_outliers packs at most 2^31 - 1 rows")
+    _finite_rows(pts, start, count, dense)
+    dev, rows, b, n_max = pts.device, pts.shape[0], len(start), max(count)
+    ratio = -1.0 if std_ratio is None else float(std_ratio)
+    sc = torch.tensor([start, count], dtype=torch.int32, device=dev)
+    neighbors, score = _neighbor_stats(pts, sc, b, n_max, k, max_radius)
+    ws, nbytes = L.workspace("gldm_filter_outliers", (b, n_max), torch.float64, dev,
+                             f"b = {b}, n_max = {n_max}; b <= {CLEANUP_MAX_CLOUDS}, n_max <= 2^20")
+    out = torch.empty((total_in, 3), dtype=torch.float32, device=dev)
+    kept = torch.empty(total_in, dtype=torch.int32, device=dev)
+    osc = torch.empty((2, b), dtype=torch.int32, device=dev)   # out_start, out_count: one buffer, one read-back
+    mom = torch.empty((b, 2), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        L.call("gldm_filter_outliers", L.ptr(pts), L.ptr(neighbors), L.ptr(score), L.ptr(sc[0]), L.ptr(sc[1]), b, n_max, rows,
+               int(k), int(min_neighbors), ratio, L.ptr(ws), nbytes, L.ptr(out), L.ptr(osc[0]), L.ptr(osc[1]), L.ptr(kept),
+               L.ptr(mom), L.current_stream(dev))
+    ostart, ocount = osc.tolist()   # the one read-back
+    total = sum(ocount)
+    stats = dict(mu=mom[:, 0], sigma=mom[:, 1], neighbors=neighbors, score=score)
+    if dense is not None:
+        stats["neighbors"], stats["score"] = neighbors.reshape(dense), score.reshape(dense)
+        if len(dense) == 1:
+            return out[:total], 0, total, kept[:total], stats
+    return out[:total], ostart, ocount, kept[:total], stats

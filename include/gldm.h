@@ -890,6 +890,55 @@ int gldm_point_normals(const float *pc /*[b,n,3]*/, const int32_t *idx /*[b,n,k]
                        const float *neighbors /*[b,n,k,3] or NULL*/, int b, int n, int k, const float *view /*host [3]*/,
                        float *normals /*[b,n,3]*/, gldm_stream_t stream);
 
+/* ------------------------------------------------ sensor-cloud cleanup (additive; csrc/cloud_filter.hip) */
+
+/* Outlier removal on ragged clouds (Open3D's remove_radius_outlier / remove_statistical_outlier; the reference has no
+ * counterpart).  Layout of both entries: the one gldm_depth_to_objects writes and gldm_farthest_points_euclid_ragged reads:
+ * points [rows,3] f32; cloud i is rows start[i] .. start[i] + min(count[i], n_max) (start / count: device int32 [b]; n_max:
+ * a host upper bound of the counts; a negative count is 0, and a cloud whose range leaves [0, rows) is empty).  The ranges
+ * do not overlap.  Rows outside every range are never read and their outputs never written; the gaps may hold anything.
+ * Inside the ranges the points are finite.
+ *
+ * gldm_neighbor_stats: for every point i of every cloud, the up to k OTHER points j of its cloud (j != i by index, so a
+ * duplicate is a neighbour at distance 0) with the smallest d2 among those with d2 <= r2, where
+ *   d2(i, j) = (dx*dx + dy*dy) + dz*dz  in f32, differences first, one rounding per operation;  r2 = max_radius * max_radius
+ * (gldm_knn_radius's arithmetic).  neighbors [rows] int32 = their number (<= k); score [rows] f32 = their mean distance,
+ *   (float)(sum_s (double)sqrtf(d2_s) / (double)neighbors),  summed in f64 in ascending d2, sqrtf and the division IEEE;
+ * +inf where neighbors = 0.  A pure function of the inputs: bitwise repeatable, independent of the launch shape and of the
+ * broad phase (gldm_knn_radius's: boxes of the 256-row chunks of every cloud, counted from the cloud's own start; a chunk is
+ * skipped only when its exact box-to-box distance exceeds the bound).  Two launches; no workgroup waits for another.
+ * Envelope, checked before any pointer or the device is touched: b >= 1, n_max >= 0, rows >= 0, max_radius >= 0 with a
+ * finite r2 (GLDM_ERR_INVALID_ARG); b <= 65535, n_max <= 2^20, 1 <= k <= 16 (GLDM_ERR_UNSUPPORTED).  n_max = 0 or rows = 0
+ * is a no-op.  workspace: gldm_neighbor_stats_workspace_bytes(b, n_max) bytes (a negative GLDM_ERR_* status outside the
+ * envelope), uninitialised, private to the stream until the work has finished. */
+long long gldm_neighbor_stats_workspace_bytes(int b, int n_max);
+int gldm_neighbor_stats(const float *points /*[rows,3]*/, const int32_t *start /*[b]*/, const int32_t *count /*[b]*/, int b,
+                        int n_max, int rows, int k, float max_radius, void *workspace, long long workspace_bytes,
+                        int32_t *neighbors /*[rows]*/, float *score /*[rows]*/, gldm_stream_t stream);
+
+/* The keep rule on gldm_neighbor_stats' outputs and the ordered compaction.  Per cloud, over the points with neighbors >=
+ * max(min_neighbors, 1):  N = their number,  mu = S1 / N with S1 = sum (double)score,  sigma = sqrt(sum ((double)score -
+ * mu)^2 / (N - 1))  (the sample deviation; 0 for N < 2; mu = 0 for N = 0), all in f64 in a fixed order: inside a 256-row
+ * chunk a fixed tree (the other points count as +0.0; a butterfly over each 64 rows with offsets 32, 16, .. 1, then
+ * (w0 + w1) + (w2 + w3)), then the chunks in ascending order, two passes (gldm_plane_moments' rule).  stats [b,2] f64 = mu,
+ * sigma.  A point is kept iff neighbors >= min_neighbors and, when the statistical rule is on (std_ratio >= 0; a negative
+ * value switches it off), neighbors >= 1 and (double)score <= mu + (double)std_ratio * sigma.
+ * The kept rows of every cloud go out in ascending row order, packed: cloud i is rows out_start[i] .. + out_count[i] of
+ * out_points (out_start = the exclusive sum of out_count; rows copied bit for bit); kept [.] int32 = the source row of every
+ * output row, relative to its cloud's start.  out_points [sum count, 3] and kept [sum count] are written up to the total
+ * only.  Six or seven launches (per-chunk sums, per-cloud moments, twice; per-chunk counts, a scan, the write pass); no
+ * atomics; no workgroup waits for another; two calls are bitwise equal.
+ * Envelope, checked before any pointer or the device is touched: gldm_neighbor_stats' on b, n_max, rows, k; 0 <=
+ * min_neighbors <= k, std_ratio not NaN (GLDM_ERR_INVALID_ARG).  With n_max = 0 or rows = 0 only out_start, out_count and
+ * stats are written.  workspace: gldm_filter_outliers_workspace_bytes(b, n_max) bytes, 8-byte aligned, uninitialised, private
+ * to the stream until the work has finished. */
+long long gldm_filter_outliers_workspace_bytes(int b, int n_max);
+int gldm_filter_outliers(const float *points /*[rows,3]*/, const int32_t *neighbors /*[rows]*/, const float *score /*[rows]*/,
+                         const int32_t *start /*[b]*/, const int32_t *count /*[b]*/, int b, int n_max, int rows, int k,
+                         int min_neighbors, float std_ratio, void *workspace, long long workspace_bytes,
+                         float *out_points /*[sum count,3]*/, int32_t *out_start /*[b]*/, int32_t *out_count /*[b]*/,
+                         int32_t *kept /*[sum count]*/, double *stats /*[b,2]*/, gldm_stream_t stream);
+
 /* ------------------------------------------------ grasp selection (additive, ABI 14; csrc/grasp_select.hip) */
 
 /* Gripper clearance and finger-sweep contacts of every pose against a whole scene cloud.  The geometry is the

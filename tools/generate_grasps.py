@@ -28,7 +28,10 @@ image, object k = label k; every object with at least N points gets its grasps i
 object_label, object_points, scene_rank), --segment_tabletop [--table_tol T] [--object_height MIN MAX] [--link_dist D]
 [--min_object_pixels N] [--ransac_hypotheses T] [--segment_seed S] (with --depth_file, instead of --labels_file: the labels
 are made on the GPU from the frame itself -- a RANSAC table plane, then the connected components above it,
-infer_on_tabletop; --out gains labels, table_plane and the --labels_file keys).  `--inference_steps` is honoured (the reference
+infer_on_tabletop; --out gains labels, table_plane and the --labels_file keys), --remove_outliers [--outlier_k K]
+[--outlier_radius R] [--outlier_min_neighbors N] [--outlier_std_ratio S] [--clean_scene] (with --depth_file: every object
+cloud loses its isolated points on the GPU before the farthest-point selection, pointcloud.remove_outliers; --out gains
+object_points_raw).  `--inference_steps` is honoured (the reference
 silently ignores it: it passes use_fast_sampler=False, tools/generate_grasps.py:69-79).
 """
 import argparse
@@ -141,6 +144,20 @@ def parse_args(argv=None):
                    help="with --depth_file: keep MIN < depth <= MAX metres (default: every finite depth > 0)")
     p.add_argument("--crop_box", type=float, nargs=6, default=None, metavar=("x0", "y0", "z0", "x1", "y1", "z1"),
                    help="with --depth_file: keep object points inside this box (camera frame, metres)")
+    p.add_argument("--remove_outliers", action="store_true",
+                   help="with --depth_file: drop the isolated points (flying pixels) of every object cloud on the GPU before "
+                        "the farthest-point selection")
+    p.add_argument("--outlier_k", type=int, default=None, metavar="K",
+                   help="with --remove_outliers: neighbours counted per point, 1 .. 16 (default 8)")
+    p.add_argument("--outlier_radius", type=float, default=None, metavar="R",
+                   help="with --remove_outliers: neighbours lie within R metres (default 0.01)")
+    p.add_argument("--outlier_min_neighbors", type=int, default=None, metavar="N",
+                   help="with --remove_outliers: keep points with at least N neighbours, 0 .. K (default 3)")
+    p.add_argument("--outlier_std_ratio", type=float, default=None, metavar="S",
+                   help="with --remove_outliers: also drop points whose mean neighbour distance exceeds the cloud's mean + S "
+                        "standard deviations (default: off)")
+    p.add_argument("--clean_scene", action="store_true",
+                   help="with --remove_outliers: filter the scene cloud the selection is checked against as well")
     p.add_argument("--out", type=str, default=None, help="write results of all samples to this .npz")
     args = p.parse_args(argv)
     check_depth_flags(args)
@@ -165,7 +182,13 @@ def check_depth_flags(args):
         for flag in SEGMENT_FLAGS:
             if getattr(args, flag) is not None and not args.segment_tabletop:
                 raise SystemExit(f"--{flag} goes with --segment_tabletop")
+        for flag in OUTLIER_FLAGS:
+            if getattr(args, flag) not in (None, False) and not args.remove_outliers:
+                raise SystemExit(f"--{flag} goes with --remove_outliers")
         return
+    for flag in ("remove_outliers",) + OUTLIER_FLAGS:
+        if getattr(args, flag) not in (None, False):
+            raise SystemExit(f"--{flag} goes with --depth_file")
     if args.segment_tabletop:
         raise SystemExit("--segment_tabletop goes with --depth_file")
     for flag in SEGMENT_FLAGS:
@@ -176,6 +199,7 @@ def check_depth_flags(args):
             raise SystemExit(f"--{flag} goes with --depth_file")
 
 
+OUTLIER_FLAGS = ("outlier_k", "outlier_radius", "outlier_min_neighbors", "outlier_std_ratio", "clean_scene")
 SEGMENT_FLAGS = ("table_tol", "object_height", "link_dist", "min_object_pixels", "ransac_hypotheses", "segment_seed")
 
 
@@ -195,6 +219,23 @@ def segmentation_options(args):
     if args.segment_seed is not None:
         opts["rng"] = np.random.default_rng(args.segment_seed)
     return opts
+
+
+def cleanup_options(args):
+    """{} without --remove_outliers, else the `cleanup` argument of the depth entry points from the --outlier_* flags (unset
+    flags keep CloudCleanup's defaults)."""
+    if not args.remove_outliers:
+        return {}
+    from graspldm_amd.grasp_select import CloudCleanup
+    opts = dict(apply_to_scene=bool(args.clean_scene))
+    for flag, field in (("outlier_k", "k"), ("outlier_radius", "max_radius"), ("outlier_min_neighbors", "min_neighbors"),
+                        ("outlier_std_ratio", "std_ratio")):
+        if getattr(args, flag) is not None:
+            opts[field] = getattr(args, flag)
+    try:
+        return dict(cleanup=CloudCleanup(**opts))
+    except ValueError as e:
+        raise SystemExit(f"--remove_outliers: {e}")
 
 
 def read_mask_file(path):
@@ -236,7 +277,8 @@ def run_depth(args, model, selection):
         common = dict(num_grasps=args.num_grasps, num_points=n_pts,
                       min_object_points=32 if args.min_object_points is None else args.min_object_points,
                       use_farthest_point=not args.random_resample, mask=mask, z_range=args.z_range,
-                      depth_scale=args.depth_scale, crop_box=box, **selection_kwargs(args, selection, 0))
+                      depth_scale=args.depth_scale, crop_box=box, **selection_kwargs(args, selection, 0),
+                      **cleanup_options(args))
         if args.segment_tabletop:
             try:
                 res = model.infer_on_tabletop(depth, cam, segmentation=segmentation_options(args), **common)
@@ -255,7 +297,8 @@ def run_depth(args, model, selection):
         return [res]
     res = model.infer_on_depth(depth, cam, mask=mask, num_grasps=args.num_grasps, num_points=n_pts,
                                use_farthest_point=not args.random_resample, z_range=args.z_range,
-                               depth_scale=args.depth_scale, crop_box=box, **selection_kwargs(args, selection, 0))
+                               depth_scale=args.depth_scale, crop_box=box, **selection_kwargs(args, selection, 0),
+                               **cleanup_options(args))
     conf = res["confidence"].flatten()
     print(f"{args.depth_file}: {tuple(depth.shape)} depth -> {n_pts} points; grasps {tuple(res['grasps'].shape)}  "
           f"confidence mean {conf.mean().item():.3f}  best {conf.max().item():.3f}")
@@ -466,7 +509,8 @@ def finish(args, results):
     if args.out:
         extra = {k: torch.cat([r[k] for r in results]).cpu().numpy()
                  for k in ("latent_mu", "latent_logvar", "success", "selected_index", "selected_count", "selected_gap",
-                           "clearance", "contacts", "aligned_contacts", "object_label", "object_points", "scene_rank")
+                           "clearance", "contacts", "aligned_contacts", "object_label", "object_points", "object_points_raw",
+                           "scene_rank")
                  if all(r.get(k) is not None for r in results)}
         if all(r.get("table_plane") is not None for r in results):   # --segment_tabletop: one frame per result
             extra["labels"] = torch.stack([r["labels"] for r in results]).cpu().numpy()
