@@ -13,27 +13,9 @@
 #include <stdint.h>
 
 #include "knn_scan.h"
+#include "ragged_compact.h"   // Range, cloud_range, chunk_count, scan_kernel: shared with cloud_downsample.hip
 
 namespace {
-
-constexpr int kMaxClouds = 65535;
-
-__host__ __device__ constexpr int chunks_of(int n) { return (n + kChunk - 1) / kChunk; }
-
-struct Range {
-  long long s;   // first row
-  int n;         // rows
-};
-
-// The rows of one cloud: count clamped to [0, n_max]; a range that leaves [0, rows) is empty (nothing outside the array is
-// ever addressed).
-__device__ __forceinline__ Range cloud_range(const int32_t *__restrict__ start, const int32_t *__restrict__ count, int cloud,
-                                             int n_max, int rows) {
-  const long long s = start[cloud];
-  int n = max(0, min(count[cloud], n_max));
-  if (s < 0 || s + n > (long long)rows) n = 0;
-  return {s, n};
-}
 
 // boxes [b, chunks_max, 6]: lo xyz, hi xyz of every 256-row chunk of every cloud (chunks past a cloud's end: not written).
 __global__ __launch_bounds__(kChunk) void ragged_box_kernel(const float *__restrict__ pts, const int32_t *__restrict__ start,
@@ -141,23 +123,6 @@ __device__ __forceinline__ double chunk_tree_sum(double v, double *red) {
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// The number of set flags in the chunk (every lane) and, in `before`, the number set in lower lanes of the workgroup.
-__device__ __forceinline__ int chunk_count(bool flag, int *red, int &before) {
-  const unsigned long long bal = __ballot(flag);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();   // red is free again
-  if (lane == 0) red[wave] = __popcll(bal);
-  __syncthreads();
-  before = __popcll(bal & ((1ull << lane) - 1ull));
-  int total = 0;
-#pragma unroll
-  for (int w = 0; w < kChunk / 64; ++w) {
-    before += w < wave ? red[w] : 0;
-    total += red[w];
-  }
-  return total;
-}
-
 // PASS 0: per chunk the number of points with neighbors >= need and the sum of their scores; PASS 1: the sum of their
 // (score - mu)^2.  f64, fixed tree.  tile_cnt / partial [b, chunks_max].
 template <int PASS>
@@ -259,46 +224,12 @@ __global__ __launch_bounds__(kChunk) void keep_kernel(const float *__restrict__ 
   }
 }
 
-// One workgroup: every cloud's tile counts -> exclusive offsets inside the cloud (in place) and out_count; then the exclusive
-// sum of out_count over the clouds -> out_start.  Lane t owns the clouds t*per .. (t+1)*per - 1.
-__global__ __launch_bounds__(256) void scan_kernel(const int32_t *__restrict__ start, const int32_t *__restrict__ count, int b,
-                                                   int n_max, int rows, int chunks_max, int32_t *__restrict__ tile_cnt,
-                                                   int32_t *__restrict__ out_start, int32_t *__restrict__ out_count) {
-  __shared__ int sums[256];
-  const int tid = threadIdx.x;
-  const int per = (b + 255) / 256;
-  const int c0 = min(b, tid * per), c1 = min(b, c0 + per);
-  int mine = 0;
-  for (int cloud = c0; cloud < c1; ++cloud) {
-    const int chunks = chunks_of(cloud_range(start, count, cloud, n_max, rows).n);
-    const long long at = (long long)cloud * chunks_max;
-    int run = 0;
-    for (int ch = 0; ch < chunks; ++ch) {
-      const int c = tile_cnt[at + ch];
-      tile_cnt[at + ch] = run;
-      run += c;
-    }
-    out_count[cloud] = run;
-    mine += run;
-  }
-  sums[tid] = mine;
-  __syncthreads();
-  int base = 0;
-  for (int t = 0; t < tid; ++t) base += sums[t];
-  for (int cloud = c0; cloud < c1; ++cloud) {
-    out_start[cloud] = base;
-    base += out_count[cloud];
-  }
-}
-
 // The envelope the two entries share; no pointer is read and the device is not touched outside it.
 int check_envelope(int b, int n_max, int rows, int k) {
   if (b < 1 || n_max < 0 || rows < 0) return GLDM_ERR_INVALID_ARG;
   if (b > kMaxClouds || n_max > kMaxN || k < 1 || k > kMaxK) return GLDM_ERR_UNSUPPORTED;
   return GLDM_OK;
 }
-
-inline long long align8(long long v) { return (v + 7) & ~7ll; }
 
 }  // namespace
 

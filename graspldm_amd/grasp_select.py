@@ -285,3 +285,31 @@ class CloudCleanup:
     def options(self):
         """The keyword arguments of pointcloud.remove_outliers."""
         return dict(k=self.k, max_radius=self.max_radius, min_neighbors=self.min_neighbors, std_ratio=self.std_ratio)
+
+
+@dataclass(frozen=True)
+class CloudDownsample:
+    """Voxel-grid downsampling of the object clouds of a depth frame or of a sensor cloud, in front of `CloudCleanup` and of
+    the point-count regularisation (pointcloud.voxel_downsample): one point per occupied voxel of
+    voxel_size metres, the centroid of the voxel's points, on a lattice anchored at the origin.  max_points (None: no
+    ceiling): while any cloud of the call keeps more points, the whole call is repeated with voxel_size * 1.25, at most 16
+    times (then ValueError); one size holds for all clouds and the results report it.  apply_to_scene: downsample the scene
+    cloud a GraspSelection is checked against as well."""
+    voxel_size: float = 0.003
+    max_points: Optional[int] = None
+    apply_to_scene: bool = False
+
+    def __post_init__(self):
+        if not (isinstance(self.voxel_size, (int, float)) and not isinstance(self.voxel_size, bool)
+                and math.isfinite(self.voxel_size) and self.voxel_size > 0):
+            raise ValueError(f"voxel_size must be finite and > 0, not {self.voxel_size!r}")
+        if self.max_points is not None and not (isinstance(self.max_points, int) and not isinstance(self.max_points, bool)
+                                                and self.max_points >= 1):
+            raise ValueError(f"max_points must be an integer >= 1 (or None), not {self.max_points!r}")
+        if not isinstance(self.apply_to_scene, bool):
+            raise ValueError(f"apply_to_scene must be a bool, not {self.apply_to_scene!r}")
+
+    @property
+    def options(self):
+        """The keyword arguments of pointcloud.voxel_downsample_capped."""
+        return dict(voxel_size=self.voxel_size, max_points=self.max_points)

@@ -284,11 +284,28 @@ class _InferenceBase:
         return self.normalize_input(pc)
 
     def infer_on_pointcloud(self, pc, num_grasps=10, return_intermediate=False, num_points=None,
-                            use_farthest_point=True, selection=None, scene_pc=None):
+                            use_farthest_point=True, selection=None, scene_pc=None, downsample=None):
         """tools/inference.py:658-666 (= generate_on_pointcloud, grasp_ldm/inference/inference_base.py:161-179).
         `num_points` (additive): first bring every cloud to the encoder's point count
         (PointCloudHelpers.regularize_pc_point_count; farthest-point selection by default).  `selection` / `scene_pc`
-        (additive): filter and select the poses (select_grasps); scene_pc is in the frame of `pc`."""
+        (additive): filter and select the poses (select_grasps); scene_pc is in the frame of `pc`.
+        `downsample` (a graspldm_amd.grasp_select.CloudDownsample; additive): the order is downsample ->
+        point-count regularisation: ONE pointcloud.voxel_downsample call over all clouds of pc before num_points is
+        applied; the results gain voxel_size (the size used), object_points and object_points_raw [B] (points after / before
+        it); with downsample.apply_to_scene a given scene_pc is downsampled too.  A cloud left empty raises ValueError."""
+        if downsample is not None:
+            pc = pc.to(self.device)
+            single = pc.ndim == 2
+            raw = list(pc.unsqueeze(0) if single else pc)
+            clouds, size = self._downsample_clouds(raw, downsample)
+            for i, c in enumerate(clouds):
+                if c.shape[0] == 0:
+                    raise ValueError(f"cloud {i} is empty")
+            if selection is not None and scene_pc is not None and downsample.apply_to_scene:
+                scene_pc = self._downsample_scene(scene_pc.to(self.device), size)
+            extra = {} if selection is None else dict(selection=selection, scene_pc=scene_pc)
+            out = self._infer_on_clouds(clouds, single, num_grasps, num_points, use_farthest_point, return_intermediate, extra)
+            return self._downsample_keys(out, size, clouds, [c.shape[0] for c in raw])
         pcn, metas = self.prepare_pointcloud(pc, num_points, use_farthest_point)
         if selection is None:
             return self.generate_grasps(pcn, metas, num_grasps=num_grasps, return_intermediate=return_intermediate)
@@ -299,7 +316,7 @@ class _InferenceBase:
 
     def infer_on_depth(self, depth, camera, mask=None, num_grasps=10, num_points=None, use_farthest_point=True,
                        z_range=None, depth_scale=None, cam_to_world=None, crop_box=None, selection=None, scene_pc=None,
-                       return_intermediate=False, cleanup=None):
+                       return_intermediate=False, cleanup=None, downsample=None):
         """From a depth frame to grasps without leaving the GPU (additive; the reference stops at
         Camera.depth_to_pointcloud_torch, grasp_ldm/utils/camera.py:176-215, and leaves the rest to the caller).
         depth [H, W] or [F, H, W] (CUDA; float32 metres or raw 16-bit units with depth_scale), camera: a
@@ -313,7 +330,13 @@ class _InferenceBase:
         `cleanup` (a graspldm_amd.grasp_select.CloudCleanup): the object clouds of all frames lose their
         outliers in one pointcloud.remove_outliers call before anything else sees them; the empty-cloud check refers to the
         filtered clouds, the results gain object_points and object_points_raw [F] (points after / before the filter), and
-        with cleanup.apply_to_scene the scene cloud taken from the frame is filtered too."""
+        with cleanup.apply_to_scene the scene cloud taken from the frame is filtered too.
+        `downsample` (a graspldm_amd.grasp_select.CloudDownsample): the order is deprojection ->
+        downsample -> cleanup (if given) -> point-count regularisation.  The object clouds of all frames go through ONE
+        pointcloud.voxel_downsample call first, so cleanup sees uniform density and fewer points; the empty-cloud check and
+        object_points refer to the counts after both steps, object_points_raw [F] to the deprojected counts, and the
+        results gain voxel_size (the size used).  With downsample.apply_to_scene the scene cloud taken from the frame is
+        downsampled (before cleanup.apply_to_scene filters it)."""
         from .pointcloud import depth_to_cloud
         depth = depth.to(self.device) if isinstance(depth, torch.Tensor) else depth
         mask = mask.to(self.device) if isinstance(mask, torch.Tensor) else mask
@@ -321,8 +344,12 @@ class _InferenceBase:
         clouds = depth_to_cloud(depth, camera, mask=mask, crop_box=crop_box, **kw)
         single = depth.ndim == 2
         clouds = [clouds] if single else clouds
-        if cleanup is not None:
+        if downsample is not None:
             raw_counts = [c.shape[0] for c in clouds]
+            clouds, voxel_size = self._downsample_clouds(clouds, downsample)
+        if cleanup is not None:
+            if downsample is None:
+                raw_counts = [c.shape[0] for c in clouds]
             clouds = self._clean_clouds(clouds, cleanup)
         for f, c in enumerate(clouds):
             if c.shape[0] == 0:
@@ -330,6 +357,9 @@ class _InferenceBase:
                                  "and the crop box)")
         if selection is not None and scene_pc is None and selection.needs_scene:
             scenes = depth_to_cloud(depth, camera, **kw)
+            if downsample is not None and downsample.apply_to_scene:
+                scenes = [self._downsample_scene(s, voxel_size) for s in ([scenes] if single else scenes)]
+                scenes = scenes[0] if single else scenes
             if cleanup is not None and cleanup.apply_to_scene:
                 scenes = self._clean_clouds([scenes] if single else scenes, cleanup)
                 scenes = scenes[0] if single else scenes
@@ -342,6 +372,8 @@ class _InferenceBase:
                                  "[F, Ns, 3], or call infer_on_depth frame by frame")
         extra = {} if selection is None else dict(selection=selection, scene_pc=scene_pc)
         out = self._infer_on_clouds(clouds, single, num_grasps, num_points, use_farthest_point, return_intermediate, extra)
+        if downsample is not None:
+            return self._downsample_keys(out, voxel_size, clouds, raw_counts)
         if cleanup is not None:
             out["object_points"] = torch.tensor([c.shape[0] for c in clouds], dtype=torch.int64, device=self.device)
             out["object_points_raw"] = torch.tensor(raw_counts, dtype=torch.int64, device=self.device)
@@ -384,9 +416,49 @@ class _InferenceBase:
         out, ostart, ocount = _InferenceBase._clean_objects(packed, starts, counts, cleanup)
         return [out[s:s + c] for s, c in zip(ostart, ocount)]
 
+    @staticmethod
+    def _downsample_objects(packed, starts, counts, downsample):
+        """The objects of one frame (rows starts[k] .. + counts[k] of packed) through ONE ragged
+        pointcloud.voxel_downsample_capped call -> (packed, starts, counts, voxel size used)."""
+        from .grasp_select import CloudDownsample
+        from .pointcloud import voxel_downsample_capped
+        if not isinstance(downsample, CloudDownsample):
+            raise TypeError("downsample must be a graspldm_amd.grasp_select.CloudDownsample")
+        (out, ostart, ocount, _, _), size = voxel_downsample_capped(packed, start=starts, count=counts, **downsample.options)
+        return out, ostart, ocount, size
+
+    @staticmethod
+    def _downsample_clouds(clouds, downsample):
+        """A list of clouds [n_i, 3] through ONE pointcloud.voxel_downsample_capped call -> (the list of the downsampled
+        clouds, voxel size used)."""
+        counts = [c.shape[0] for c in clouds]
+        starts = [sum(counts[:i]) for i in range(len(counts))]
+        packed = clouds[0] if len(clouds) == 1 else torch.cat(clouds)
+        out, ostart, ocount, size = _InferenceBase._downsample_objects(packed, starts, counts, downsample)
+        return [out[s:s + c] for s, c in zip(ostart, ocount)], size
+
+    @staticmethod
+    def _downsample_scene(scene, voxel_size):
+        """A scene cloud [Ns, 3] or [B, Ns, 3] at the voxel size the objects ended with (no ceiling on its points).  A batch
+        must keep one size per cloud to stay a batch."""
+        from .pointcloud import voxel_downsample
+        if scene.ndim == 2:
+            return voxel_downsample(scene, voxel_size)[0]
+        out, ostart, ocount, _, _ = voxel_downsample(scene, voxel_size)
+        if len(set(ocount)) != 1:
+            raise ValueError("the downsampled scene clouds differ in size and cannot form one batch: pass one scene "
+                             "[Ns, 3], or downsample.apply_to_scene=False")
+        return torch.stack([out[s:s + c] for s, c in zip(ostart, ocount)])
+
+    def _downsample_keys(self, out, voxel_size, clouds, raw_counts):
+        out["voxel_size"] = voxel_size
+        out["object_points"] = torch.tensor([c.shape[0] for c in clouds], dtype=torch.int64, device=self.device)
+        out["object_points_raw"] = torch.tensor(raw_counts, dtype=torch.int64, device=self.device)
+        return out
+
     def infer_on_scene(self, depth, camera, labels, num_grasps=10, num_points=None, num_labels=None, min_object_points=32,
                        use_farthest_point=True, mask=None, z_range=None, depth_scale=None, cam_to_world=None, crop_box=None,
-                       selection=None, scene_pc=None, cleanup=None):
+                       selection=None, scene_pc=None, cleanup=None, downsample=None):
         """One depth frame [H, W] with an instance-label image -> the grasps of every object, as ONE batch (additive,
         DESIGN.md 4.11).  labels: integer tensor of depth's shape, object k = label k (1 .. num_labels, at most 64; default
         labels.max()); the other arguments as infer_on_depth.  Objects with fewer than min_object_points points are skipped;
@@ -400,7 +472,13 @@ class _InferenceBase:
         `cleanup` (a graspldm_amd.grasp_select.CloudCleanup): ONE ragged pointcloud.remove_outliers call over
         all objects of the frame, between the deprojection and regularize_objects; min_object_points, the error above and
         object_points then refer to the filtered counts and object_points_raw [B] holds the unfiltered ones; with
-        cleanup.apply_to_scene the scene cloud taken from the frame is filtered too."""
+        cleanup.apply_to_scene the scene cloud taken from the frame is filtered too.
+        `downsample` (a graspldm_amd.grasp_select.CloudDownsample): the order is deprojection ->
+        downsample -> cleanup (if given) -> regularize_objects.  ONE ragged pointcloud.voxel_downsample call over all objects
+        of the frame comes first, so cleanup sees uniform density and fewer points; min_object_points, the error above and
+        object_points refer to the counts after both steps, object_points_raw [B] holds the deprojected ones, and the result
+        gains voxel_size (the size used).  With downsample.apply_to_scene the scene cloud taken from the frame is
+        downsampled (before cleanup.apply_to_scene filters it)."""
         from .pointcloud import _depth_to_objects_packed, depth_to_cloud, regularize_objects
         depth = depth.to(self.device) if isinstance(depth, torch.Tensor) else depth
         labels = labels.to(self.device) if isinstance(labels, torch.Tensor) else labels
@@ -411,8 +489,12 @@ class _InferenceBase:
         points, _, starts, counts = _depth_to_objects_packed(depth, camera, labels, num_labels=num_labels, mask=mask,
                                                              crop_box=crop_box, **kw)
         packed, starts, counts = points[0], starts[0], counts[0]
-        if cleanup is not None:
+        if downsample is not None:
             raw_counts = counts
+            packed, starts, counts, voxel_size = self._downsample_objects(packed, starts, counts, downsample)
+        if cleanup is not None:
+            if downsample is None:
+                raw_counts = counts
             packed, starts, counts = self._clean_objects(packed, starts, counts, cleanup)
         kept = [k for k, c in enumerate(counts) if c >= max(int(min_object_points), 1)]
         if not kept:
@@ -427,6 +509,8 @@ class _InferenceBase:
             batch = regularize_objects(packed, ks, kc, num_points, use_farthest_point)
         if selection is not None and scene_pc is None and selection.needs_scene:
             scene_pc = depth_to_cloud(depth, camera, **kw)
+            if downsample is not None and downsample.apply_to_scene:
+                scene_pc = self._downsample_scene(scene_pc, voxel_size)
             if cleanup is not None and cleanup.apply_to_scene:
                 scene_pc = self._clean_clouds([scene_pc], cleanup)[0]
             scene_pc = scene_pc.unsqueeze(0)
@@ -435,21 +519,24 @@ class _InferenceBase:
         out = self.generate_grasps(pcn, metas, num_grasps=num_grasps, **extra)
         out["object_label"] = torch.tensor([k + 1 for k in kept], dtype=torch.int64, device=self.device)
         out["object_points"] = torch.tensor(kc, dtype=torch.int64, device=self.device)
-        if cleanup is not None:
+        if cleanup is not None or downsample is not None:
             out["object_points_raw"] = torch.tensor([raw_counts[k] for k in kept], dtype=torch.int64, device=self.device)
+        if downsample is not None:
+            out["voxel_size"] = voxel_size
         out["scene_rank"] = self._scene_rank(out, selection)
         return out
 
     def infer_on_tabletop(self, depth, camera, num_grasps=10, num_points=None, segmentation=None, min_object_points=32,
                           use_farthest_point=True, mask=None, z_range=None, depth_scale=None, cam_to_world=None,
-                          crop_box=None, selection=None, scene_pc=None, cleanup=None):
+                          crop_box=None, selection=None, scene_pc=None, cleanup=None, downsample=None):
         """One depth frame [H, W] of objects standing on a table -> the grasps of every object, without a label image
         (additive): pointcloud.segment_tabletop makes the labels on the GPU (a RANSAC table plane, then the
         connected components above it), infer_on_scene does the rest with them.  segmentation: a dict of
         segment_tabletop's own options (plane, height_range, link_dist, min_pixels, max_objects, tol, hypotheses, rng,
         refit, min_cross2); the depth options go to both.  The result of infer_on_scene gains `labels` ([H, W] int32) and
         `table_plane` (pointcloud.TablePlane).  No object found: ValueError.  `cleanup`: as in infer_on_scene (the labels are made
-        from the unfiltered frame)."""
+        from the unfiltered frame).  `downsample`: as in infer_on_scene as well (deprojection -> downsample -> cleanup ->
+        regularisation; the labels are made from the full frame)."""
         from .pointcloud import segment_tabletop
         depth = depth.to(self.device) if isinstance(depth, torch.Tensor) else depth
         mask = mask.to(self.device) if isinstance(mask, torch.Tensor) else mask
@@ -462,7 +549,8 @@ class _InferenceBase:
         out = self.infer_on_scene(depth, camera, labels, num_grasps=num_grasps, num_points=num_points, num_labels=num,
                                   min_object_points=min_object_points, use_farthest_point=use_farthest_point,
                                   selection=selection, scene_pc=scene_pc, **kw, **({} if cleanup is None else
-                                                                                   dict(cleanup=cleanup)))
+                                                                                   dict(cleanup=cleanup)),
+                                  **({} if downsample is None else dict(downsample=downsample)))
         out["labels"] = labels
         out["table_plane"] = plane
         return out

@@ -17,9 +17,12 @@ from disk, and clouds of more than 8192 points take gldm_farthest_points_euclid_
 table (gldm_plane_ransac, gldm_plane_moments) and `segment_tabletop` labels the objects standing on it
 (gldm_segment_tabletop).  `estimate_normals` gives a sensor cloud its surface normals (gldm_knn_radius,
 gldm_point_normals; estimate_normals_cam_from_pc, pointcloud_helpers.py:74-122).  `remove_outliers` drops
-the isolated points of sensor clouds before any of that sees them (gldm_neighbor_stats, gldm_filter_outliers).
+the isolated points of sensor clouds before any of that sees them (gldm_neighbor_stats, gldm_filter_outliers), and
+`voxel_downsample` brings raw sensor density down to one point per voxel in front of both
+(gldm_voxel_downsample).
 """
 import ctypes
+import math
 import typing
 
 import numpy as np
@@ -829,10 +832,11 @@ def _check_cleanup_envelope(k, max_radius, min_neighbors=0, std_ratio=None):
         raise ValueError("std_ratio must not be NaN (None or a negative value switches the statistical rule off)")
 
 
-def _ragged_layout(points, start, count):
+def _ragged_layout(points, start, count, entry="gldm_neighbor_stats", max_points=CLEANUP_MAX_POINTS):
     """The checks in front of the ragged entries: points [n,3] / [b,n,3] dense, or [rows,3] with start / count (host
     sequences or tensors: one read-back) -> (pts [rows,3] f32 contiguous, start, count as host lists, dense shape or None).
-    Raises before any library call."""
+    Raises before any library call.  entry / max_points: the entry named in the messages and its ceiling on the points of
+    one cloud (a power of two)."""
     _need_cuda(points, "points")
     if (start is None) != (count is None):
         raise ValueError("start and count go together")
@@ -850,16 +854,16 @@ def _ragged_layout(points, start, count):
     if len(count) != b:
         raise ValueError(f"start holds {b} clouds, count {len(count)}")
     if not 1 <= b <= CLEANUP_MAX_CLOUDS:
-        raise NotImplementedError(f"{b} clouds: gldm_neighbor_stats takes 1 .. {CLEANUP_MAX_CLOUDS} clouds per call")
+        raise NotImplementedError(f"{b} clouds: {entry} takes 1 .. {CLEANUP_MAX_CLOUDS} clouds per call")
     if rows > 0x7fffffff:
-        raise NotImplementedError(f"{rows} rows: gldm_neighbor_stats takes at most 2^31 - 1 rows per call")
+        raise NotImplementedError(f"{rows} rows: {entry} takes at most 2^31 - 1 rows per call")
     end = 0
     for i, (s, c) in sorted(enumerate(zip(start, count)), key=lambda t: t[1][0]):
         if c < 0:
             raise ValueError(f"cloud {i}: count {c} is negative")
-        if c > CLEANUP_MAX_POINTS:
-            raise NotImplementedError(f"cloud {i} has {c} points: gldm_neighbor_stats takes at most 2^20 = "
-                                      f"{CLEANUP_MAX_POINTS} points per cloud")
+        if c > max_points:
+            raise NotImplementedError(f"cloud {i} has {c} points: {entry} takes at most 2^{max_points.bit_length() - 1} = "
+                                      f"{max_points} points per cloud")
         if c and (s < 0 or s + c > rows):
             raise ValueError(f"cloud {i}: rows {s} .. {s + c} leave points [{rows}, 3]")
         if c and s < end:
@@ -949,3 +953,103 @@ def remove_outliers(points, k=8, max_radius=0.01, min_neighbors=3, std_ratio=Non
         if len(dense) == 1:
             return out[:total], 0, total, kept[:total], stats
     return out[:total], ostart, ocount, kept[:total], stats
+
+
+# ------------------------------------------------------------------------------------------ voxel-grid downsampling --
+# one point per occupied voxel between deprojection and everything else (gldm_voxel_downsample): Open3D's
+# voxel_down_sample / PCL's VoxelGrid on ragged batches, on a lattice anchored at the origin.
+VOXEL_MAX_POINTS = 1 << 22      # gldm_voxel_downsample's ceiling on the points of one cloud
+VOXEL_MAX_ROWS = 1 << 24        # ... on the rows of one call
+VOXEL_MAX_CELL = 1 << 20        # ... and on |coordinate| / voxel_size
+VOXEL_GROW = 1.25               # voxel_downsample_capped: the factor between two attempts
+VOXEL_MAX_GROWS = 16            # ... and how often it is applied
+
+
+def _voxel_size_f32(voxel_size):
+    """voxel_size as the f32 value the entry receives; anything but a finite positive number raises ValueError."""
+    try:
+        with np.errstate(over="ignore"):
+            v = float(np.float32(voxel_size))
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(voxel_size, bool) or not (math.isfinite(v) and v > 0.0):
+        raise ValueError(f"voxel_size must be finite and > 0 in f32, not {voxel_size!r}")
+    return v
+
+
+def _voxel_rows(pts, start, count, dense, v):
+    """ONE device reduction and read-back for both conditions on the rows inside the clouds: non-finite values raise
+    GldmError, a coordinate with |p| / voxel_size >= 2^20 (in f64, as the kernel divides) raises ValueError.  The gaps
+    between the clouds may hold anything."""
+    nonfinite = (~torch.isfinite(pts)).any(dim=1)
+    far = (~(pts.double().abs() / v < float(VOXEL_MAX_CELL))).any(dim=1) & ~nonfinite
+    bad = torch.stack([nonfinite, far]).to(torch.int32)   # [2, rows]
+    if dense is not None:
+        hit = bad.any(dim=1)
+    else:
+        run = torch.cat([torch.zeros((2, 1), dtype=torch.int64, device=pts.device), torch.cumsum(bad, 1)], dim=1)
+        s = torch.tensor(start, dtype=torch.int64, device=pts.device).clamp(0, pts.shape[0])
+        e = (s + torch.tensor(count, dtype=torch.int64, device=pts.device)).clamp(0, pts.shape[0])
+        hit = (run[:, e] - run[:, s]).ne(0).any(dim=1)
+    hit_nonfinite, hit_far = hit.tolist()   # the one read-back
+    if hit_nonfinite:
+        raise L.GldmError("the points hold non-finite values")
+    if hit_far:
+        raise ValueError(f"a coordinate has |p| / voxel_size >= 2^20 = {VOXEL_MAX_CELL} (voxel_size = {v!r}): "
+                         "gldm_voxel_downsample's lattice ends there")
+
+
+def voxel_downsample(points, voxel_size, start=None, count=None, return_map=False):
+    """Voxel-grid downsampling on the GPU (gldm_voxel_downsample): one output point per occupied voxel of
+    every cloud, the centroid of the voxel's points.  The lattice is anchored at the ORIGIN (cell = floor(p / voxel_size) per
+    axis, in f64), not at the cloud's min bound as in Open3D: a voxel means the same place in every frame.  The centroid is
+    the mean of the coordinates quantised to voxel_size * 2^-16, summed exactly, so every output bit is independent of the
+    execution order (tests/cloud_downsample_ref.py restates it in numpy).  A cloud's voxels come in order of first
+    appearance.  points / start / count as neighbor_stats (at most 2^22 points per cloud, 2^24 rows, 65535 clouds per
+    call); voxel_size: finite and > 0 as f32; |p| / voxel_size < 2^20 for every coordinate.
+    -> (points, start, count, first, members): the packed centroids [total, 3], start / count host lists of b ints (the
+    second read-back; the first brings the finite / range check), first int32 [total]: the lowest source row of every
+    voxel relative to its cloud's start, members int32 [total]: its number of points.  With return_map also voxel int32
+    of points' leading shape: the output row of every source row, relative to its cloud's start in the output (-1 outside
+    every cloud): labels, pixels or normals can be carried over with it.  For one cloud [n,3]: (points [m,3], 0, m, first [m],
+    members [m][, voxel [n]])."""
+    v = _voxel_size_f32(voxel_size)
+    pts, start, count, dense = _ragged_layout(points, start, count, "gldm_voxel_downsample", VOXEL_MAX_POINTS)
+    rows, b, n_max, total_in = pts.shape[0], len(start), max(count), sum(count)
+    if rows > VOXEL_MAX_ROWS:
+        raise NotImplementedError(f"{rows} rows: gldm_voxel_downsample takes at most 2^24 = {VOXEL_MAX_ROWS} rows per call")
+    _voxel_rows(pts, start, count, dense, v)
+    dev = pts.device
+    sc = torch.tensor([start, count], dtype=torch.int32, device=dev)
+    ws, nbytes = L.workspace("gldm_voxel_downsample", (b, n_max, rows), torch.int64, dev,
+                             f"b = {b}, n_max = {n_max}, rows = {rows}; b <= {CLEANUP_MAX_CLOUDS}, n_max <= 2^22, rows <= 2^24")
+    out = torch.empty((total_in, 3), dtype=torch.float32, device=dev)
+    fm = torch.empty((2, total_in), dtype=torch.int32, device=dev)   # first, members
+    osc = torch.empty((2, b), dtype=torch.int32, device=dev)         # out_start, out_count: one buffer, one read-back
+    vox = torch.full((rows,), -1, dtype=torch.int32, device=dev) if return_map else None
+    with torch.cuda.device(dev):
+        L.call("gldm_voxel_downsample", L.ptr(pts), L.ptr(sc[0]), L.ptr(sc[1]), b, n_max, rows, v, L.ptr(ws), nbytes,
+               L.ptr(out), L.ptr(osc[0]), L.ptr(osc[1]), L.ptr(fm[0]), L.ptr(fm[1]), L.ptr(vox), L.current_stream(dev))
+    ostart, ocount = osc.tolist()   # the second read-back
+    total = sum(ocount)
+    res = (out[:total], ostart, ocount, fm[0, :total], fm[1, :total])
+    if dense is not None and len(dense) == 1:
+        res = (out[:total], 0, total, fm[0, :total], fm[1, :total])
+    if return_map:
+        res += (vox.reshape(dense) if dense is not None else vox,)
+    return res
+
+
+def voxel_downsample_capped(points, voxel_size, max_points=None, start=None, count=None, return_map=False):
+    """voxel_downsample with a ceiling on the points of every cloud: while any cloud's output count exceeds max_points
+    (None: no ceiling) the WHOLE call is repeated with voxel_size * 1.25, at most 16 times, then ValueError.  One size holds
+    for all clouds of the call.  -> (voxel_downsample's result, the voxel size used, as the f32 value the entry received)."""
+    size = float(voxel_size)
+    for _ in range(VOXEL_MAX_GROWS + 1):
+        res = voxel_downsample(points, size, start=start, count=count, return_map=return_map)
+        most = res[2] if isinstance(res[2], int) else max(res[2])
+        if max_points is None or most <= int(max_points):
+            return res, _voxel_size_f32(size)
+        size *= VOXEL_GROW
+    raise ValueError(f"a cloud still holds {most} voxels, above max_points = {max_points}, after voxel_size grew "
+                     f"{VOXEL_MAX_GROWS} times by {VOXEL_GROW} from {voxel_size!r}")

@@ -939,6 +939,40 @@ int gldm_filter_outliers(const float *points /*[rows,3]*/, const int32_t *neighb
                          float *out_points /*[sum count,3]*/, int32_t *out_start /*[b]*/, int32_t *out_count /*[b]*/,
                          int32_t *kept /*[sum count]*/, double *stats /*[b,2]*/, gldm_stream_t stream);
 
+/* ------------------------------------------------ voxel-grid downsampling (additive; csrc/cloud_downsample.hip) */
+
+/* One output row per occupied voxel of every cloud (Open3D's voxel_down_sample, PCL's VoxelGrid; the reference has no
+ * counterpart).  Layout: that of gldm_neighbor_stats / gldm_filter_outliers above, word for word (points [rows,3] f32; start /
+ * count device int32 [b]; host n_max; the ranges do not overlap; the gaps are never read; a range that leaves [0, rows) is
+ * empty; inside the ranges the points are finite).
+ * Per point and per axis, in f64:  t = (double)p / (double)voxel_size (IEEE division);  cell = floor(t);  q = rint(t * 65536.0)
+ * (round-half-even).  The lattice is anchored at the ORIGIN, not at the cloud's min bound as in Open3D: the same voxel
+ * means the same place in every frame and in every cloud.  Precondition: |t| < 2^20; beyond it cell is clamped to [-2^20,
+ * 2^20 - 1] and q to [-2^36, 2^36], so addresses and sums stay safe whatever the data holds (the Python layer raises).
+ * An output row is one occupied voxel of one cloud:  members = the number of its points;  first = the lowest source row among
+ * them, relative to the cloud's start;  centroid per axis =
+ *   (float)(((double)sum_q / (double)members) / 65536.0 * (double)voxel_size),  sum_q the exact int64 sum of q
+ * (|q| <= 2^36 and members <= 2^22 give 2^58: no overflow).  The quantum is voxel_size * 2^-16 (30 nm at a 2 mm voxel).
+ * Count, min and integer sums commute exactly, so nothing depends on execution order: two calls are bitwise equal and
+ * numpy restates every bit (tests/cloud_downsample_ref.py).
+ * The voxels of a cloud go out in ascending `first` (order of first appearance), packed as gldm_filter_outliers packs: cloud
+ * i is rows out_start[i] .. + out_count[i] of out_points (out_start = the exclusive sum of out_count); first [.] and members
+ * [.] int32 carry one entry per output row; voxel [rows] int32 (NULL allowed) = the output row of every source row,
+ * relative to its cloud's out_start.  Rows past the total are never written; the gaps of voxel are never written.
+ * A hash build (one table region of 2 * count slots per cloud, linear probing, vector atomics: compare-and-swap on the key,
+ * 64-bit adds, add, min) and the ordered compaction of gldm_filter_outliers: five launches, six with voxel; no sort; no
+ * workgroup waits for another.
+ * Envelope, checked before any pointer or the device is touched: b >= 1, n_max >= 0, rows >= 0, voxel_size finite and > 0
+ * (GLDM_ERR_INVALID_ARG); b <= 65535, n_max <= 2^22, rows <= 2^24 (GLDM_ERR_UNSUPPORTED).  With n_max = 0 or rows = 0 only
+ * out_start and out_count are written.  workspace: gldm_voxel_downsample_workspace_bytes(b, n_max, rows) bytes (a negative
+ * GLDM_ERR_* status outside the envelope), 8-byte aligned, uninitialised, private to the stream until the work has finished. */
+long long gldm_voxel_downsample_workspace_bytes(int b, int n_max, int rows);
+int gldm_voxel_downsample(const float *points /*[rows,3]*/, const int32_t *start /*[b]*/, const int32_t *count /*[b]*/, int b,
+                          int n_max, int rows, float voxel_size, void *workspace, long long workspace_bytes,
+                          float *out_points /*[sum count,3]*/, int32_t *out_start /*[b]*/, int32_t *out_count /*[b]*/,
+                          int32_t *first /*[sum count]*/, int32_t *members /*[sum count]*/, int32_t *voxel /*[rows] or NULL*/,
+                          gldm_stream_t stream);
+
 /* ------------------------------------------------ grasp selection (additive, ABI 14; csrc/grasp_select.hip) */
 
 /* Gripper clearance and finger-sweep contacts of every pose against a whole scene cloud.  The geometry is the

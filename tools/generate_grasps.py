@@ -31,6 +31,10 @@ are made on the GPU from the frame itself -- a RANSAC table plane, then the conn
 infer_on_tabletop; --out gains labels, table_plane and the --labels_file keys), --remove_outliers [--outlier_k K]
 [--outlier_radius R] [--outlier_min_neighbors N] [--outlier_std_ratio S] [--clean_scene] (with --depth_file: every object
 cloud loses its isolated points on the GPU before the farthest-point selection, pointcloud.remove_outliers; --out gains
+object_points_raw), --voxel_size V [--voxel_max_points N] [--downsample_scene] (with --depth_file, or with --pc_file
+--num_points: every cloud is downsampled on a voxel grid of V metres on the GPU first, one centroid per occupied voxel,
+pointcloud.voxel_downsample; the order is deprojection -> downsample -> --remove_outliers -> point-count regularisation;
+with N the size grows by 1.25 until no cloud keeps more than N points; --out gains voxel_size, object_points,
 object_points_raw).  `--inference_steps` is honoured (the reference
 silently ignores it: it passes use_fast_sampler=False, tools/generate_grasps.py:69-79).
 """
@@ -158,10 +162,47 @@ def parse_args(argv=None):
                         "standard deviations (default: off)")
     p.add_argument("--clean_scene", action="store_true",
                    help="with --remove_outliers: filter the scene cloud the selection is checked against as well")
+    p.add_argument("--voxel_size", type=float, default=None, metavar="V",
+                   help="with --depth_file, or --pc_file --num_points: downsample every cloud on a voxel grid of V metres on "
+                        "the GPU (one centroid per occupied voxel) before --remove_outliers and the point-count regularisation")
+    p.add_argument("--voxel_max_points", type=int, default=None, metavar="N",
+                   help="with --voxel_size: grow the voxel by 1.25 until no cloud keeps more than N points")
+    p.add_argument("--downsample_scene", action="store_true",
+                   help="with --voxel_size: downsample the scene cloud the selection is checked against as well")
     p.add_argument("--out", type=str, default=None, help="write results of all samples to this .npz")
     args = p.parse_args(argv)
     check_depth_flags(args)
+    check_downsample_flags(p, args)
     return args
+
+
+def check_downsample_flags(p, args):
+    """--voxel_size goes with --depth_file, or with --pc_file --num_points; its companions need it."""
+    if args.voxel_size is None:
+        for flag in ("voxel_max_points", "downsample_scene"):
+            if getattr(args, flag) not in (None, False):
+                p.error(f"--{flag} goes with --voxel_size")
+        return
+    if not (args.depth_file or (args.pc_file and args.num_points is not None)):
+        p.error("--voxel_size goes with --depth_file, or with --pc_file --num_points")
+    if args.refine_from:
+        p.error("--voxel_size does not go with --refine_from")
+    try:
+        downsample_options(args)
+    except SystemExit as e:
+        p.error(str(e))
+
+
+def downsample_options(args):
+    """{} without --voxel_size, else the `downsample` argument of the entry points from the --voxel_* flags."""
+    if args.voxel_size is None:
+        return {}
+    from graspldm_amd.grasp_select import CloudDownsample
+    try:
+        return dict(downsample=CloudDownsample(voxel_size=args.voxel_size, max_points=args.voxel_max_points,
+                                               apply_to_scene=bool(args.downsample_scene)))
+    except ValueError as e:
+        raise SystemExit(f"--voxel_size: {e}")
 
 
 def check_depth_flags(args):
@@ -278,7 +319,7 @@ def run_depth(args, model, selection):
                       min_object_points=32 if args.min_object_points is None else args.min_object_points,
                       use_farthest_point=not args.random_resample, mask=mask, z_range=args.z_range,
                       depth_scale=args.depth_scale, crop_box=box, **selection_kwargs(args, selection, 0),
-                      **cleanup_options(args))
+                      **cleanup_options(args), **downsample_options(args))
         if args.segment_tabletop:
             try:
                 res = model.infer_on_tabletop(depth, cam, segmentation=segmentation_options(args), **common)
@@ -298,7 +339,7 @@ def run_depth(args, model, selection):
     res = model.infer_on_depth(depth, cam, mask=mask, num_grasps=args.num_grasps, num_points=n_pts,
                                use_farthest_point=not args.random_resample, z_range=args.z_range,
                                depth_scale=args.depth_scale, crop_box=box, **selection_kwargs(args, selection, 0),
-                               **cleanup_options(args))
+                               **cleanup_options(args), **downsample_options(args))
     conf = res["confidence"].flatten()
     print(f"{args.depth_file}: {tuple(depth.shape)} depth -> {n_pts} points; grasps {tuple(res['grasps'].shape)}  "
           f"confidence mean {conf.mean().item():.3f}  best {conf.max().item():.3f}")
@@ -463,7 +504,8 @@ def main(argv=None):
             if start is None:
                 res = model.infer_on_pointcloud(pc, num_grasps=args.num_grasps, num_points=n_pts,
                                                 use_farthest_point=not args.random_resample,
-                                                **selection_kwargs(args, selection, len(results)))
+                                                **selection_kwargs(args, selection, len(results)),
+                                                **downsample_options(args))
             else:
                 pcn, metas = model.prepare_pointcloud(pc, num_points=n_pts, use_farthest_point=not args.random_resample)
                 res = run_one(args, model, pcn, metas, start, len(results), selection_kwargs(args, selection, len(results)))
@@ -512,6 +554,8 @@ def finish(args, results):
                            "clearance", "contacts", "aligned_contacts", "object_label", "object_points", "object_points_raw",
                            "scene_rank")
                  if all(r.get(k) is not None for r in results)}
+        if all(r.get("voxel_size") is not None for r in results):   # --voxel_size: the size every result ended with
+            extra["voxel_size"] = np.asarray([r["voxel_size"] for r in results], dtype=np.float32)
         if all(r.get("table_plane") is not None for r in results):   # --segment_tabletop: one frame per result
             extra["labels"] = torch.stack([r["labels"] for r in results]).cpu().numpy()
             extra["table_plane"] = np.stack([r["table_plane"].as_array() for r in results])
