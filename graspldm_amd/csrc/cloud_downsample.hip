@@ -13,17 +13,16 @@
 #include <stdint.h>
 
 #include "ragged_compact.h"
+#include "voxel_hash.h"
 
 namespace {
 
 constexpr int kMaxVoxelN = 1 << 22;      // points of one cloud
 constexpr int kMaxVoxelRows = 1 << 24;   // rows of one call: slot indices (2 per row) stay below 2^25
-constexpr unsigned long long kEmptyKey = ~0ull;
-constexpr double kCellLimit = 1048576.0;            // 2^20: |p / voxel_size| below it is the precondition
 constexpr double kQLimit = 68719476736.0;           // 2^36 = 2^20 * 2^16
 constexpr double kQScale = 65536.0;
 
-// 48 bytes, 8-byte aligned.  key: 3 x 21 bits of cell + 2^20 (bit 63 clear), all-ones = empty.
+// 48 bytes, 8-byte aligned.  key: voxel_hash.h's cell_key, all-ones = empty.
 struct Slot {
   unsigned long long key;
   unsigned long long sum[3];   // int64 sums of q, two's complement
@@ -40,15 +39,6 @@ __device__ __forceinline__ void quantise(float p, double v, long long &cell, lon
   const double t = (double)p / v;
   cell = (long long)fmin(fmax(floor(t), -kCellLimit), kCellLimit - 1.0);
   q = (long long)fmin(fmax(rint(t * kQScale), -kQLimit), kQLimit);
-}
-
-// splitmix64's finaliser
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
-  x ^= x >> 30;
-  x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27;
-  x *= 0x94d049bb133111ebull;
-  return x ^ (x >> 31);
 }
 
 // Cloud i owns the slots 2 * start[i] .. 2 * (start[i] + count[i]); a workgroup clears those of its chunk's rows.
@@ -73,8 +63,8 @@ __global__ __launch_bounds__(kChunk) void table_init_kernel(const int32_t *__res
   }
 }
 
-// One lane per point: find the slot of its voxel in the cloud's region (linear probing from a hash of the key; a slot is
-// taken when the compare-and-swap returns empty or the own key), add the point to it and remember the slot.  The region holds
+// One lane per point: find the slot of its voxel in the cloud's region (voxel_hash.h: linear probing from a hash of the key; a
+// slot is taken when the compare-and-swap returns empty or the own key), add the point to it and remember the slot.  The region holds
 // two slots per point, so an empty slot always exists and the loop ends within `len` probes; it is bounded by `len` all the
 // same and a row that found none (impossible) carries slot -1, which every later pass skips.
 __global__ __launch_bounds__(kChunk) void table_insert_kernel(const float *__restrict__ pts, const int32_t *__restrict__ start,
@@ -90,21 +80,10 @@ __global__ __launch_bounds__(kChunk) void table_insert_kernel(const float *__res
   long long cell[3], q[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) quantise(pts[row * 3 + c], voxel, cell[c], q[c]);
-  const unsigned long long key = ((unsigned long long)(cell[0] + (1 << 20)) << 42) |
-                                 ((unsigned long long)(cell[1] + (1 << 20)) << 21) |
-                                 (unsigned long long)(cell[2] + (1 << 20));
-  const unsigned len = 2u * (unsigned)rg.n;
+  const unsigned long long key = cell_key(cell[0], cell[1], cell[2]);
   const long long base = 2 * rg.s;
-  unsigned at = (unsigned)(mix64(key) % len);
-  long long slot = -1;
-  for (unsigned probe = 0; probe < len; ++probe) {
-    const unsigned long long seen = atomicCAS(&table[base + at].key, kEmptyKey, key);
-    if (seen == kEmptyKey || seen == key) {
-      slot = base + at;
-      break;
-    }
-    at = at + 1 == len ? 0 : at + 1;
-  }
+  const long long at = hash_insert(table + base, 2u * (unsigned)rg.n, key);
+  const long long slot = at < 0 ? -1 : base + at;
   slot_of[row] = (int32_t)slot;
   if (slot < 0) return;
   Slot *s = table + slot;

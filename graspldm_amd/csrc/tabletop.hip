@@ -25,6 +25,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "components.h"
 #include "depth_deproject.h"
 #include "host_util.h"
 
@@ -208,7 +209,6 @@ constexpr int kSegPer = kTh / kWaves;
 constexpr int kTilePix = kTw * kTh;
 constexpr int kMaxLabels = 64;
 constexpr int kBorderBlock = 128;            // >= kTw + kTh border pixels of a tile
-constexpr int kSelectBlock = 1024;
 static_assert(kTw == kWave && kTh % kWaves == 0, "one wave per tile row");
 static_assert(kTw + kTh <= kBorderBlock, "one thread per border pixel");
 
@@ -232,29 +232,6 @@ __device__ __forceinline__ bool foreground(const T *__restrict__ depth, const ui
 __device__ __forceinline__ bool close_enough(const SegParams &S, float x0, float y0, float z0, float x1, float y1, float z1) {
   const float dx = x1 - x0, dy = y1 - y0, dz = z1 - z0;
   return ((dx * dx + dy * dy) + dz * dz) <= S.link2;
-}
-
-// parent[x] <= x for every live x, and parents only decrease: both loops below end on their own data.
-__device__ __forceinline__ int uf_find(int *par, int x) {
-  int p;
-  while ((p = __atomic_load_n(&par[x], __ATOMIC_RELAXED)) != x) x = p;
-  return x;
-}
-
-__device__ __forceinline__ void uf_union(int *par, int a, int b) {
-  for (;;) {
-    a = uf_find(par, a);
-    b = uf_find(par, b);
-    if (a == b) return;
-    if (a < b) {
-      const int s = a;
-      a = b;
-      b = s;
-    }
-    const int old = atomicMin(&par[a], b);   // a > b: hang the higher root under the lower
-    if (old == a) return;
-    a = old;   // a had a parent by now: whatever was cut off by the min is joined again through (old, b)
-  }
 }
 
 // One tile: local union-find in LDS over the links inside the tile.  parent[p] = global index of the tile-local root, -1 for
@@ -361,11 +338,6 @@ __global__ __launch_bounds__(kBlock) void seg_flatten_kernel(int32_t *__restrict
   }
 }
 
-// Falling size, then rising root: the larger key ranks first.
-__device__ __forceinline__ unsigned long long seg_key(int size, int root) {
-  return ((unsigned long long)(unsigned)size << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)root);
-}
-
 // Roots of at least min_pixels pixels -> cand[0 .. *cand_count), in any order (the selection does not depend on it).
 __global__ __launch_bounds__(kBlock) void seg_gather_kernel(const int32_t *__restrict__ parent, const int32_t *__restrict__ size,
                                                             int hw, int min_pixels, unsigned long long *__restrict__ cand,
@@ -381,9 +353,7 @@ __global__ __launch_bounds__(kBlock) void seg_gather_kernel(const int32_t *__res
   if (is) cand[base + __popcll(bal & ((1ull << lane) - 1ull))] = seg_key(sz, pix);
 }
 
-// One workgroup.  Up to kSelectBlock candidates (the usual frame): thread i holds key i, its rank is the number of larger
-// keys.  More: round k takes the largest key below the one of round k - 1 and the rounds stop when nothing is left.  Keys are
-// distinct (distinct roots).  Entries past the number found are 0 / -1.
+// One workgroup: components.h's select_largest over the candidates.
 __global__ __launch_bounds__(kSelectBlock) void seg_select_kernel(const unsigned long long *__restrict__ cand,
                                                                   const int32_t *__restrict__ cand_count, int max_labels,
                                                                   int32_t *__restrict__ num_labels,
@@ -391,56 +361,7 @@ __global__ __launch_bounds__(kSelectBlock) void seg_select_kernel(const unsigned
                                                                   int32_t *__restrict__ label_root) {
   __shared__ unsigned long long s_key[kSelectBlock];
   __shared__ unsigned long long s_best;
-  const int tid = threadIdx.x, m = *cand_count;
-  int found = 0;
-  if (m <= kSelectBlock) {
-    const unsigned long long mine = tid < m ? cand[tid] : 0ull;
-    s_key[tid] = mine;
-    __syncthreads();
-    int rank = 0;
-    for (int j = 0; j < m; ++j) rank += s_key[j] > mine ? 1 : 0;   // LDS broadcast reads
-    if (tid < m && rank < max_labels) {
-      label_pixels[rank] = (int32_t)(mine >> 32);
-      label_root[rank] = (int32_t)(0xFFFFFFFFu - (unsigned)(mine & 0xFFFFFFFFull));
-    }
-    found = min(m, max_labels);
-  } else {
-    unsigned long long prev = ~0ull;   // no key reaches it: size <= 2^24
-    for (int k = 0; k < max_labels; ++k) {
-      unsigned long long best = 0ull;   // below every key: size >= 1
-      for (int i = tid; i < m; i += kSelectBlock) {
-        const unsigned long long c = cand[i];
-        if (c < prev && c > best) best = c;
-      }
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned long long o = __shfl_xor(best, off, kWave);
-        best = o > best ? o : best;
-      }
-      if ((tid & 63) == 0) s_key[tid >> 6] = best;
-      __syncthreads();
-      if (tid == 0) {
-        unsigned long long b = 0ull;
-        for (int wv = 0; wv < kSelectBlock / kWave; ++wv) b = s_key[wv] > b ? s_key[wv] : b;
-        s_best = b;
-      }
-      __syncthreads();
-      best = s_best;   // uniform
-      __syncthreads();
-      if (!best) break;
-      if (tid == 0) {
-        label_pixels[k] = (int32_t)(best >> 32);
-        label_root[k] = (int32_t)(0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull));
-      }
-      found = k + 1;
-      prev = best;
-    }
-  }
-  if (tid >= found && tid < max_labels) {   // max_labels <= 64 < kSelectBlock
-    label_pixels[tid] = 0;
-    label_root[tid] = -1;
-  }
-  if (tid == 0) *num_labels = found;
+  select_largest(cand, *cand_count, max_labels, num_labels, label_pixels, label_root, s_key, &s_best);
 }
 
 __global__ __launch_bounds__(kBlock) void seg_write_kernel(const int32_t *__restrict__ parent, const int32_t *__restrict__ size,

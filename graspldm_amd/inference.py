@@ -555,6 +555,89 @@ class _InferenceBase:
         out["table_plane"] = plane
         return out
 
+    def infer_on_cloud_scene(self, pc, num_grasps=10, num_points=None, segmentation=None, min_object_points=32,
+                             use_farthest_point=True, selection=None, scene_pc=None, cleanup=None, downsample=None,
+                             view_point=None):
+        """One unorganised scene cloud [N, 3] -- several cameras fused, a downsampled or filtered cloud, a file -- -> the
+        grasps of every object in it, as ONE batch (additive): infer_on_tabletop without a pixel grid.
+        The order of the steps:
+          1. `downsample` (a graspldm_amd.grasp_select.CloudDownsample): pointcloud.voxel_downsample_capped of the WHOLE
+             cloud first, because the clustering costs (points within link_dist) per point;
+          2. pointcloud.segment_cloud (segmentation: a dict of its own options -- plane, table, height_range, link_dist,
+             min_points, max_objects, tol, hypotheses, rng, refit, min_cross2; view_point goes to it too): a RANSAC table
+             plane, then the Euclidean clusters above it;
+          3. pointcloud.split_labels: the objects packed in label order;
+          4. `cleanup` (a graspldm_amd.grasp_select.CloudCleanup): ONE ragged pointcloud.remove_outliers call over them;
+          5. pointcloud.regularize_objects (num_points; None only if they all have the same size);
+          6. normalize_input;  7. generate_grasps on every object at once, exactly as infer_on_scene ends.
+        A voxel size (the one actually used) above link_dist raises ValueError: nothing would link.  When `selection` needs
+        a scene and no scene_pc is given, the scene is the input cloud as [1, Ns, 3], downsampled under
+        downsample.apply_to_scene and then filtered under cleanup.apply_to_scene.
+        Added keys: object_label, object_points, scene_rank (as infer_on_scene), object_points_raw (the counts before
+        cleanup, when it ran), labels [n] int32 and segmented_points [n, 3] (the cloud the labels refer to: the input, or its
+        downsampled copy), table_plane (a pointcloud.TablePlane, None with table=False), voxel_size (when downsampled).
+        No object, or none with min_object_points points: ValueError with the counts."""
+        from .pointcloud import _link_dist_f32, regularize_objects, segment_cloud, split_labels, voxel_downsample_capped
+        if not isinstance(pc, torch.Tensor) or pc.ndim != 2 or pc.shape[1] != 3:
+            raise ValueError("infer_on_cloud_scene takes one cloud [N, 3]")
+        pc = pc.to(self.device).contiguous().float()
+        seg = dict(segmentation or {})
+        if view_point is not None:
+            if "view_point" in seg:
+                raise ValueError("view_point was given twice: as an argument and inside segmentation")
+            seg["view_point"] = view_point
+        link = _link_dist_f32(seg.get("link_dist", 0.01))
+        cloud, voxel_size = pc, None
+        if downsample is not None:
+            from .grasp_select import CloudDownsample
+            if not isinstance(downsample, CloudDownsample):
+                raise TypeError("downsample must be a graspldm_amd.grasp_select.CloudDownsample")
+            res, voxel_size = voxel_downsample_capped(pc, **downsample.options)
+            cloud = res[0]
+            if voxel_size > link:
+                raise ValueError(f"the voxel size used, {voxel_size!r}, exceeds link_dist = {link!r}: neighbouring voxels "
+                                 "would not be linked and every point would be its own cluster")
+        labels, num, plane = segment_cloud(cloud, **seg)
+        if num < 1:
+            raise ValueError(f"no object found in the cloud: no cluster of at least {seg.get('min_points', 32)} points among "
+                             f"the {cloud.shape[0]} points (link_dist = {link!r})")
+        packed, starts, counts, _ = split_labels(cloud, labels, max_objects=seg.get("max_objects", 64))
+        starts, counts = starts[:num], counts[:num]
+        if cleanup is not None:
+            raw_counts = counts
+            packed, starts, counts = self._clean_objects(packed, starts, counts, cleanup)
+        kept = [k for k, c in enumerate(counts) if c >= max(int(min_object_points), 1)]
+        if not kept:
+            raise ValueError(f"no object has at least {min_object_points} points (labels 1 .. {len(counts)} hold {counts})")
+        ks, kc = [starts[k] for k in kept], [counts[k] for k in kept]
+        if num_points is None:
+            if len(set(kc)) != 1:
+                raise ValueError("the objects' clouds differ in size: pass num_points")
+            batch = torch.stack([packed[s:s + c] for s, c in zip(ks, kc)])
+        else:
+            batch = regularize_objects(packed, ks, kc, num_points, use_farthest_point)
+        if selection is not None and scene_pc is None and selection.needs_scene:
+            scene_pc = pc
+            if downsample is not None and downsample.apply_to_scene:
+                scene_pc = self._downsample_scene(scene_pc, voxel_size)
+            if cleanup is not None and cleanup.apply_to_scene:
+                scene_pc = self._clean_clouds([scene_pc], cleanup)[0]
+            scene_pc = scene_pc.unsqueeze(0)
+        extra = {} if selection is None else dict(selection=selection, scene_pc=scene_pc)
+        pcn, metas = self.normalize_input(batch)
+        out = self.generate_grasps(pcn, metas, num_grasps=num_grasps, **extra)
+        out["object_label"] = torch.tensor([k + 1 for k in kept], dtype=torch.int64, device=self.device)
+        out["object_points"] = torch.tensor(kc, dtype=torch.int64, device=self.device)
+        if cleanup is not None:
+            out["object_points_raw"] = torch.tensor([raw_counts[k] for k in kept], dtype=torch.int64, device=self.device)
+        if downsample is not None:
+            out["voxel_size"] = voxel_size
+        out["labels"] = labels
+        out["segmented_points"] = cloud
+        out["table_plane"] = plane
+        out["scene_rank"] = self._scene_rank(out, selection)
+        return out
+
     @staticmethod
     def _scene_rank(out, selection):
         """(object row, slot) [n, 2] of the poses of a result dict that are not NaN, by falling score; ties keep the

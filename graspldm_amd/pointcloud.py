@@ -1053,3 +1053,185 @@ def voxel_downsample_capped(points, voxel_size, max_points=None, start=None, cou
         size *= VOXEL_GROW
     raise ValueError(f"a cloud still holds {most} voxels, above max_points = {max_points}, after voxel_size grew "
                      f"{VOXEL_MAX_GROWS} times by {VOXEL_GROW} from {voxel_size!r}")
+
+
+# --------------------------------------------------------------------------------------------- Euclidean clustering --
+# the objects of a cloud that has no pixel grid (several cameras fused, a downsampled or filtered cloud, a
+# file): connected components under "closer than link_dist" (gldm_cluster_cloud: PCL's EuclideanClusterExtraction) and the
+# ordered split of the labelled cloud into its objects (gldm_split_labels), without the round trip through cKDTree.
+CLUSTER_MAX_POINTS = 1 << 22    # gldm_cluster_cloud's ceiling on the points of one cloud
+CLUSTER_MAX_ROWS = 1 << 24      # ... and on the rows of one call
+CLUSTER_MIN_LINK = 2.0 ** -60   # link_dist lies in [2^-60, 2^60]
+CLUSTER_MAX_LINK = 2.0 ** 60
+SPLIT_MAX_COUNTERS = 1 << 24    # gldm_split_labels: clouds * ceil(n_max / 256) * max_objects
+
+
+def _link_dist_f32(link_dist):
+    """link_dist as the f32 value the entry receives; anything outside [2^-60, 2^60] raises ValueError."""
+    try:
+        with np.errstate(over="ignore"):
+            v = float(np.float32(link_dist))
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(link_dist, bool) or not CLUSTER_MIN_LINK <= v <= CLUSTER_MAX_LINK:
+        raise ValueError(f"link_dist must lie in [2^-60, 2^60] as f32, not {link_dist!r}")
+    return v
+
+
+def _max_objects(max_objects):
+    k = int(max_objects)
+    if not 1 <= k <= MAX_LABELS:
+        raise ValueError(f"max_objects must be 1 .. {MAX_LABELS}, not {max_objects}")
+    return k
+
+
+def _cluster_layout(points, start, count, entry):
+    pts, start, count, dense = _ragged_layout(points, start, count, entry, CLUSTER_MAX_POINTS)
+    if pts.shape[0] > CLUSTER_MAX_ROWS:
+        raise NotImplementedError(f"{pts.shape[0]} rows: {entry} takes at most 2^24 = {CLUSTER_MAX_ROWS} rows per call")
+    return pts, start, count, dense
+
+
+def cluster_cloud(points, link_dist=0.01, min_points=32, max_objects=64, plane=None, height_range=(0.01, 0.5), start=None,
+                  count=None, return_stats=False):
+    """Euclidean clustering on the GPU (gldm_cluster_cloud): the connected components of every cloud under
+    "two rows are linked iff (dx*dx + dy*dy) + dz*dz <= link_dist^2 in f32" -- PCL's EuclideanClusterExtraction, Open3D's
+    cluster_dbscan(min_points=1) -- exact, independent of the execution order and restated bit for bit in numpy
+    (tests/cloud_cluster_ref.py).  points / start / count as voxel_downsample (at most 2^22 points per cloud, 2^24 rows,
+    65535 clouds per call); the points may hold anything: a row with a non-finite coordinate, or with |p| / link_dist
+    beyond 2^20, is inactive (label 0, linked to nothing).  plane: a TablePlane or 4 numbers; then only the rows whose
+    height over it lies in (height_range[0], height_range[1]] are active (segment_tabletop's rule).  Components of at least
+    min_points rows are labelled 1 .. K (K <= max_objects <= 64) by falling size, ties to the lower first row.
+    The cost per row is the number of rows in the 27 cells of size link_dist around it; a cloud with all its points within
+    link_dist of each other costs n^2: downsample first (voxel_downsample at a voxel below link_dist).
+    -> (labels int32 of points' leading shape on the device -- rows outside every cloud carry 0 --, num_labels); with
+    return_stats also (label_points, label_root): the sizes and the lowest rows (relative to the cloud's start) of the
+    labels.  For one cloud [n,3] num_labels is an int and the stats are lists of max_objects ints; otherwise lists per
+    cloud.  ONE read-back (the small tables)."""
+    link = _link_dist_f32(link_dist)
+    k = _max_objects(max_objects)
+    if int(min_points) < 1:
+        raise ValueError(f"min_points must be at least 1, not {min_points}")
+    pl = None
+    if plane is not None:
+        pl = plane.as_array() if isinstance(plane, TablePlane) else _host_floats(plane, 4, "plane")
+        h0, h1 = float(height_range[0]), float(height_range[1])
+        if not np.isfinite(pl).all() or not h0 < h1:
+            raise ValueError(f"the plane must be finite and height_range rising, not {pl.tolist()}, {height_range!r}")
+    else:
+        h0, h1 = 0.0, 0.0
+    pts, start, count, dense = _cluster_layout(points, start, count, "gldm_cluster_cloud")
+    dev, rows, b, n_max = pts.device, pts.shape[0], len(start), max(count)
+    sc = torch.tensor([start, count], dtype=torch.int32, device=dev)
+    ws, nbytes = L.workspace("gldm_cluster_cloud", (b, n_max, rows), torch.int64, dev,
+                             f"b = {b}, n_max = {n_max}, rows = {rows}; b <= {CLEANUP_MAX_CLOUDS}, n_max <= 2^22, rows <= 2^24")
+    labels = torch.zeros(rows, dtype=torch.int32, device=dev)
+    stats = torch.empty(b * (1 + 2 * k), dtype=torch.int32, device=dev)   # num_labels, label_points, label_root
+    with torch.cuda.device(dev):
+        L.call("gldm_cluster_cloud", L.ptr(pts), L.ptr(sc[0]), L.ptr(sc[1]), b, n_max, rows, link,
+               None if pl is None else _host_ptr(pl), h0, h1, int(min_points), k, L.ptr(ws), nbytes, L.ptr(labels),
+               L.ptr(stats[:b]), L.ptr(stats[b:b + b * k]), L.ptr(stats[b + b * k:]), L.current_stream(dev))
+    host = stats.tolist()   # the one read-back
+    num = host[:b]
+    sizes = [host[b + i * k:b + (i + 1) * k] for i in range(b)]
+    roots = [host[b + b * k + i * k:b + b * k + (i + 1) * k] for i in range(b)]
+    if dense is not None:
+        labels = labels.reshape(dense)
+        if len(dense) == 1:
+            num, sizes, roots = num[0], sizes[0], roots[0]
+    if return_stats:
+        return labels, num, sizes, roots
+    return labels, num
+
+
+def split_labels(points, labels, max_objects=64, start=None, count=None):
+    """The rows of a labelled cloud packed object by object (gldm_split_labels): the rows with label 1 ..
+    max_objects go out cloud-major, then by ascending label, then by ascending row; every other label is dropped.
+    points / start / count as cluster_cloud; labels: an integer tensor of points' leading shape.
+    -> (packed [total, 3] -- bit copies --, obj_start, obj_count, src_row): obj_start / obj_count are host lists of
+    clouds * max_objects ints in (cloud, label) order (ONE read-back), obj_start absolute in packed and running on over
+    empty objects; src_row int32 [total] is every output row's source row relative to its cloud.  (packed, obj_start,
+    obj_count) with the empty objects left out is what regularize_objects, remove_outliers and voxel_downsample take."""
+    k = _max_objects(max_objects)
+    pts, start, count, dense = _cluster_layout(points, start, count, "gldm_split_labels")
+    dev, rows, b, n_max = pts.device, pts.shape[0], len(start), max(count)
+    if not isinstance(labels, torch.Tensor) or labels.dtype.is_floating_point or labels.numel() != rows:
+        raise ValueError(f"labels must be an integer tensor of {rows} entries, one per row of points")
+    if b * ((n_max + 255) // 256) * k > SPLIT_MAX_COUNTERS:
+        raise NotImplementedError(f"{b} clouds of up to {n_max} points at {k} objects: gldm_split_labels keeps clouds * "
+                                  f"ceil(n_max / 256) * max_objects <= 2^24 = {SPLIT_MAX_COUNTERS}")
+    lab = labels.to(device=dev, dtype=torch.int32).reshape(rows).contiguous()
+    sc = torch.tensor([start, count], dtype=torch.int32, device=dev)
+    ws, nbytes = L.workspace("gldm_split_labels", (b, n_max, rows, k), torch.int64, dev,
+                             f"b = {b}, n_max = {n_max}, rows = {rows}, max_objects = {k}")
+    out = torch.empty((rows, 3), dtype=torch.float32, device=dev)
+    src = torch.empty(rows, dtype=torch.int32, device=dev)
+    tab = torch.empty(2 * b * k + 1, dtype=torch.int32, device=dev)   # obj_start, obj_count, out_total: one read-back
+    with torch.cuda.device(dev):
+        L.call("gldm_split_labels", L.ptr(pts), L.ptr(lab), L.ptr(sc[0]), L.ptr(sc[1]), b, n_max, rows, k, L.ptr(ws), nbytes,
+               L.ptr(out), L.ptr(src), L.ptr(tab[:b * k]), L.ptr(tab[b * k:2 * b * k]), L.ptr(tab[2 * b * k:]),
+               L.current_stream(dev))
+    host = tab.tolist()   # the one read-back
+    total = host[-1]
+    return out[:total], host[:b * k], host[b * k:2 * b * k], src[:total]
+
+
+def fit_plane(points, tol=0.005, hypotheses=512, rng=None, refit=True, min_cross2=1e-8, view_point=None):
+    """The dominant plane of a cloud [n, 3] by RANSAC on the GPU -> TablePlane: everything fit_table_plane does after its
+    deprojection, on a given cloud.  The triples are rng.integers(0, n, (hypotheses, 3)) drawn on the host (rng=None:
+    np.random.default_rng(0)); ONE gldm_plane_ransac call scores them and ONE read-back brings the counts; the best is the
+    highest count, ties to the lowest index.  With refit, one gldm_plane_moments call over its inliers and the smallest
+    eigenvector of their f64 covariance replace it.  view_point (3 numbers, default the origin) gets positive height: it plays
+    the camera centre's part.  Fewer than 3 points, or every hypothesis degenerate: ValueError."""
+    _need_cuda(points, "points")
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError(f"fit_plane takes one cloud [n, 3], not {tuple(points.shape)}")
+    t = int(hypotheses)
+    if not 1 <= t <= RANSAC_MAX_HYPOTHESES:
+        raise ValueError(f"hypotheses must be 1 .. {RANSAC_MAX_HYPOTHESES}, not {t}")
+    view = np.zeros(3, dtype=np.float64) if view_point is None else _host_floats(view_point, 3, "view_point").astype(np.float64)
+    if not np.isfinite(view).all():
+        raise ValueError("view_point must be finite")
+    n = points.shape[0]
+    if n < 3:
+        raise ValueError(f"the cloud holds {n} points; a plane needs 3")
+    rng = np.random.default_rng(0) if rng is None else rng
+    triples = np.asarray(rng.integers(0, n, (t, 3)), dtype=np.int32)
+    planes, counts = plane_ransac(points, torch.from_numpy(triples), tol, min_cross2)
+    host = counts.cpu().numpy()   # the one read-back of the T counts
+    best = int(np.argmax(host))   # the first of the highest
+    if host[best] < 0:
+        raise ValueError(f"all {t} hypotheses are degenerate (repeated or collinear points); no plane")
+    plane = planes[best].cpu().numpy()
+    normal, offset = plane[:3], plane[3]
+    if refit:
+        normal, offset = plane_from_moments(plane_moments(points, plane, tol).cpu().numpy())
+    normal, offset = orient_plane(normal, offset, view)
+    return TablePlane(normal, offset, inliers=int(host[best]), hypothesis=best)
+
+
+def segment_cloud(points, plane=None, table=True, height_range=(0.01, 0.5), link_dist=0.01, min_points=32, max_objects=64,
+                  tol=0.005, hypotheses=512, rng=None, refit=True, min_cross2=1e-8, view_point=None):
+    """One unorganised cloud [n, 3] -> the labels of the objects in it, segment_tabletop without a pixel
+    grid.  table=True: the rows whose height over the table plane lies in (height_range[0], height_range[1]] are clustered
+    (cluster_cloud); plane: a TablePlane or 4 numbers, None fits one with fit_plane (tol, hypotheses, rng, refit, min_cross2,
+    view_point).  table=False: plain clustering of every row, and the plane returned is None (a plane given with it is an
+    error).  -> (labels [n] int32 on the device, num_labels, plane)."""
+    _need_cuda(points, "points")
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError(f"segment_cloud takes one cloud [n, 3], not {tuple(points.shape)}")
+    if not table:
+        if plane is not None:
+            raise ValueError("table=False clusters every row: it takes no plane")
+        labels, num = cluster_cloud(points, link_dist=link_dist, min_points=min_points, max_objects=max_objects)
+        return labels, num, None
+    _link_dist_f32(link_dist), _max_objects(max_objects)   # before the fit's launches
+    if plane is None:
+        plane = fit_plane(points, tol=tol, hypotheses=hypotheses, rng=rng, refit=refit, min_cross2=min_cross2,
+                          view_point=view_point)
+    elif not isinstance(plane, TablePlane):
+        pl = _host_floats(plane, 4, "plane")
+        plane = TablePlane(pl[:3], pl[3])
+    labels, num = cluster_cloud(points, link_dist=link_dist, min_points=min_points, max_objects=max_objects, plane=plane,
+                                height_range=height_range)
+    return labels, num, plane

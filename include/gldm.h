@@ -973,6 +973,76 @@ int gldm_voxel_downsample(const float *points /*[rows,3]*/, const int32_t *start
                           int32_t *first /*[sum count]*/, int32_t *members /*[sum count]*/, int32_t *voxel /*[rows] or NULL*/,
                           gldm_stream_t stream);
 
+/* ------------------------------------------------ Euclidean clustering (additive; csrc/cloud_cluster.hip) */
+
+/* Connected components of an unorganised cloud under "closer than link_dist" (PCL's EuclideanClusterExtraction, Open3D's
+ * cluster_dbscan with min_points = 1; the reference has no counterpart), for every cloud of a ragged batch.  Layout: that of
+ * gldm_voxel_downsample above (points [rows,3] f32; start / count device int32 [b]; host n_max; the ranges do not overlap;
+ * the gaps are never read; a range that leaves [0, rows) is empty), except that the points may hold anything.
+ * Cell size.  cs = (double)link_dist * (1 + 2^-10).
+ * Active row.  A row is active when all of these hold:
+ *   - its three coordinates are finite;
+ *   - per axis, floor((double)p / cs) lies strictly inside (-2^20, 2^20 - 1);
+ *   - if plane is given, hgt = ((a*x + b*y) + c*z) + d satisfies hgt > h_min && hgt <= h_max (gldm_segment_tabletop's formula
+ *     and rule, in f32).
+ * Link.  Two active rows i, j of the same cloud are linked iff ((dx*dx + dy*dy) + dz*dz) <= link2, dx = xi - xj in f32,
+ * link2 = link_dist * link_dist computed once in f32 on the host.
+ * Components.  The transitive closure of links.  The root of a component is its lowest row, relative to the cloud's start.
+ * Ranking.  Per cloud, components of at least min_points >= 1 rows are ranked by falling size, ties to the lower root.  The
+ * first max_labels (1..64) become labels 1..K.
+ * Outputs.  labels[row] is the label of the row's component, or 0; every row of every valid cloud range is written, rows
+ * outside all ranges are left alone.  num_labels[i] = K.  label_points [b, max_labels] holds the sizes and label_root
+ * [b, max_labels] the roots; past K they hold 0 and -1.
+ * Every output is a pure function of the inputs: the components are a property of the link graph, the root is a minimum,
+ * the sizes are counts; two calls are bitwise equal and numpy restates every value (tests/cloud_cluster_ref.py).
+ * Why the grid may not lose a link.  The reference is the all-pairs test.  The rows are binned by cell = floor((double)p / cs)
+ * and a row is tested against the rows of the 27 cells around its own.  The f32 test can admit a pair whose true per-axis
+ * distance D exceeds link_dist L by a few ulp: |dx| = |fl(xi - xj)| >= |D| (1 - 2^-24), each of the product and the two sums of
+ * non-negative terms loses at most another factor (1 - 2^-24), and link2 <= L^2 (1 + 2^-24), so an admitted pair has
+ * D^2 <= L^2 (1 + 2^-24) / (1 - 2^-24)^5 and |D| < L (1 + 2^-21).  With the 2^-10 margin on cs:
+ *   - every admitted pair has |D| < cs * (1 - 2^-11)   [(1 + 2^-10)(1 - 2^-11) = 1 + 2^-11 - 2^-21 > 1 + 2^-21];
+ *   - the f64 quotients carry at most 2^-33 absolute error inside the lattice (|p / cs| < 2^20, one rounding of 2^-53 relative);
+ *   - so the two quotients differ by less than 1 - 2^-11 + 2^-32 < 1 and their floors differ by at most 1.
+ * link_dist must lie in [2^-60, 2^60]: then link2 is a normal f32, and a dx whose square underflows is far below cs.
+ * Cost: about (rows of a 27-cell neighbourhood) distance tests per row.  A cloud with all its rows in one cell is
+ * inherently quadratic: downsample first (gldm_voxel_downsample at a voxel below link_dist).
+ * Eleven launches on one stream (csrc/cloud_cluster.hip names them); vector atomics only (compare-and-swap, add, min); no
+ * host round trip; no workgroup waits for another; every loop is bounded by the data it walks.
+ * Envelope, checked before any pointer or the device is touched: b >= 1, n_max >= 0, rows >= 0, min_points >= 1, max_labels
+ * >= 1, link_dist in [2^-60, 2^60] (NaN fails), with a plane: no NaN in it and h_min < h_max (GLDM_ERR_INVALID_ARG); b <=
+ * 65535, n_max <= 2^22, rows <= 2^24, max_labels <= 64 (GLDM_ERR_UNSUPPORTED).  With n_max = 0 or rows = 0 only num_labels,
+ * label_points and label_root are written.  workspace: gldm_cluster_cloud_workspace_bytes(b, n_max, rows) bytes (a negative
+ * GLDM_ERR_* status outside the envelope; 84 per row, 4 per chunk, 12 per cloud), 16-BYTE aligned, uninitialised, private to
+ * the stream until the work has finished. */
+long long gldm_cluster_cloud_workspace_bytes(int b, int n_max, int rows);
+int gldm_cluster_cloud(const float *points /*[rows,3]*/, const int32_t *start /*[b]*/, const int32_t *count /*[b]*/, int b,
+                       int n_max, int rows, float link_dist, const float *plane /*host [4] or NULL*/, float h_min, float h_max,
+                       int min_points, int max_labels, void *workspace, long long workspace_bytes, int32_t *labels /*[rows]*/,
+                       int32_t *num_labels /*[b]*/, int32_t *label_points /*[b,max_labels]*/,
+                       int32_t *label_root /*[b,max_labels]*/, gldm_stream_t stream);
+
+/* The ordered split of labelled clouds into their objects.  Layout as above; labels [rows] int32 is read inside the cloud
+ * ranges only.  The rows with label 1..max_labels are packed cloud-major, then by ascending label, then by ascending row,
+ * densely from row 0 of out_points (bit copies); rows with any other label (0, negative, above max_labels) are dropped.
+ * out_row [.] is the source row relative to its cloud; obj_count [b, max_labels] the rows of (cloud, label); obj_start
+ * [b, max_labels] their first row, absolute in out_points: the exclusive sum of obj_count in (cloud, label) order, so a
+ * count of 0 keeps the running start; out_total [1] the rows written.  out_points / out_row past the total are never
+ * written.  (out_points, obj_start, obj_count) is a ragged batch of b * max_labels clouds in the layout above.
+ * Four launches: per-chunk per-label counts, a scan over the chunks of every (cloud, label), a scan over the (cloud, label)
+ * table, and a write pass that ranks by ballot and popcount among equal labels.  No atomics: bitwise a pure function of the
+ * inputs.
+ * Envelope, checked before any pointer or the device is touched: b >= 1, n_max >= 0, rows >= 0, max_labels >= 1
+ * (GLDM_ERR_INVALID_ARG); b <= 65535, n_max <= 2^22, rows <= 2^24, max_labels <= 64 and, because the counters are dense,
+ * b * ceil(n_max / 256) * max_labels <= 2^24 (GLDM_ERR_UNSUPPORTED): one cloud of 2^22 rows or 256 clouds of 8192 at 64 labels
+ * use 2^20 and 2^19 of them.  With n_max = 0 or rows = 0 only obj_start, obj_count and out_total are written.  workspace:
+ * gldm_split_labels_workspace_bytes(b, n_max, rows, max_labels) bytes (4 per counter), 8-byte aligned, uninitialised. */
+long long gldm_split_labels_workspace_bytes(int b, int n_max, int rows, int max_labels);
+int gldm_split_labels(const float *points /*[rows,3]*/, const int32_t *labels /*[rows]*/, const int32_t *start /*[b]*/,
+                      const int32_t *count /*[b]*/, int b, int n_max, int rows, int max_labels, void *workspace,
+                      long long workspace_bytes, float *out_points /*[rows,3]*/, int32_t *out_row /*[rows]*/,
+                      int32_t *obj_start /*[b,max_labels]*/, int32_t *obj_count /*[b,max_labels]*/, int32_t *out_total /*[1]*/,
+                      gldm_stream_t stream);
+
 /* ------------------------------------------------ grasp selection (additive, ABI 14; csrc/grasp_select.hip) */
 
 /* Gripper clearance and finger-sweep contacts of every pose against a whole scene cloud.  The geometry is the

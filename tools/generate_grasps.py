@@ -35,7 +35,12 @@ object_points_raw), --voxel_size V [--voxel_max_points N] [--downsample_scene] (
 --num_points: every cloud is downsampled on a voxel grid of V metres on the GPU first, one centroid per occupied voxel,
 pointcloud.voxel_downsample; the order is deprojection -> downsample -> --remove_outliers -> point-count regularisation;
 with N the size grows by 1.25 until no cloud keeps more than N points; --out gains voxel_size, object_points,
-object_points_raw).  `--inference_steps` is honoured (the reference
+object_points_raw), --segment_cloud [--min_cluster_points N] [--no_table_plane] (with exactly one --pc_file and
+--num_points: the file is a whole scene without a pixel grid -- several cameras fused, a downsampled cloud --; the table plane
+is fitted and the points above it are split into objects by Euclidean clustering on the GPU, infer_on_cloud_scene; --table_tol,
+--object_height, --link_dist, --ransac_hypotheses, --segment_seed, --min_object_points, --voxel_size and --remove_outliers
+with their families keep their meaning; --no_table_plane clusters every point; --out gains labels, segmented_points,
+table_plane and the --labels_file keys).  `--inference_steps` is honoured (the reference
 silently ignores it: it passes use_fast_sampler=False, tools/generate_grasps.py:69-79).
 """
 import argparse
@@ -142,6 +147,14 @@ def parse_args(argv=None):
                    help="with --segment_tabletop: plane hypotheses to score, 1 .. 4096 (default 512)")
     p.add_argument("--segment_seed", type=int, default=None, metavar="S",
                    help="with --segment_tabletop: seed of the hypothesis draws (default 0)")
+    p.add_argument("--segment_cloud", action="store_true",
+                   help="with one --pc_file and --num_points: the file is a whole scene; find the table plane and split the "
+                        "points above it into objects by Euclidean clustering on the GPU, grasps for every object (excludes "
+                        "--depth_file)")
+    p.add_argument("--min_cluster_points", type=int, default=None, metavar="N",
+                   help="with --segment_cloud: drop clusters of fewer than N points (default 32)")
+    p.add_argument("--no_table_plane", action="store_true",
+                   help="with --segment_cloud: no plane fit and no height window, every point is clustered")
     p.add_argument("--depth_scale", type=float, default=None, metavar="S",
                    help="with --depth_file of raw 16-bit units: metres per unit (e.g. 0.001)")
     p.add_argument("--z_range", type=float, nargs=2, default=None, metavar=("MIN", "MAX"),
@@ -171,6 +184,7 @@ def parse_args(argv=None):
                    help="with --voxel_size: downsample the scene cloud the selection is checked against as well")
     p.add_argument("--out", type=str, default=None, help="write results of all samples to this .npz")
     args = p.parse_args(argv)
+    check_cloud_scene_flags(p, args)
     check_depth_flags(args)
     check_downsample_flags(p, args)
     return args
@@ -205,6 +219,34 @@ def downsample_options(args):
         raise SystemExit(f"--voxel_size: {e}")
 
 
+CLOUD_SCENE_FLAGS = ("min_cluster_points", "no_table_plane")
+# the --segment_tabletop flags that --segment_cloud shares (--min_object_pixels counts pixels: it stays with the frame)
+CLOUD_SEGMENT_FLAGS = ("table_tol", "object_height", "link_dist", "ransac_hypotheses", "segment_seed")
+
+
+def check_cloud_scene_flags(p, args):
+    """--segment_cloud takes exactly one --pc_file with --num_points and excludes --depth_file; its companions need it."""
+    if not args.segment_cloud:
+        for flag in CLOUD_SCENE_FLAGS:
+            if getattr(args, flag) not in (None, False):
+                p.error(f"--{flag} goes with --segment_cloud")
+        return
+    if args.depth_file:
+        p.error("--segment_cloud runs on a --pc_file cloud: it excludes --depth_file (see --segment_tabletop)")
+    if not args.pc_file or len(args.pc_file) != 1 or args.num_points is None:
+        p.error("--segment_cloud takes exactly one --pc_file, and --num_points")
+    if args.synthetic or args.refine_from:
+        p.error("--segment_cloud does not go with --synthetic / --refine_from")
+    if args.scene_file and len(args.scene_file) != 1:
+        p.error("--scene_file: one file for the one --segment_cloud scene")
+    if args.min_cluster_points is not None and args.min_cluster_points < 1:
+        p.error("--min_cluster_points must be at least 1")
+    if args.no_table_plane:
+        for flag in ("table_tol", "object_height", "ransac_hypotheses", "segment_seed"):
+            if getattr(args, flag) is not None:
+                p.error(f"--{flag} fits or uses the table plane: it does not go with --no_table_plane")
+
+
 def check_depth_flags(args):
     """--depth_file excludes --pc_file / --synthetic and needs --camera_json; its companions need it."""
     if args.depth_file:
@@ -228,15 +270,18 @@ def check_depth_flags(args):
                 raise SystemExit(f"--{flag} goes with --remove_outliers")
         return
     for flag in ("remove_outliers",) + OUTLIER_FLAGS:
-        if getattr(args, flag) not in (None, False):
+        if getattr(args, flag) not in (None, False) and not args.segment_cloud:
             raise SystemExit(f"--{flag} goes with --depth_file")
+    for flag in OUTLIER_FLAGS:
+        if getattr(args, flag) not in (None, False) and not args.remove_outliers:
+            raise SystemExit(f"--{flag} goes with --remove_outliers")
     if args.segment_tabletop:
         raise SystemExit("--segment_tabletop goes with --depth_file")
     for flag in SEGMENT_FLAGS:
-        if getattr(args, flag) is not None:
+        if getattr(args, flag) is not None and not (args.segment_cloud and flag in CLOUD_SEGMENT_FLAGS):
             raise SystemExit(f"--{flag} goes with --segment_tabletop")
     for flag in ("camera_json", "mask_file", "labels_file", "min_object_points", "depth_scale", "z_range", "crop_box"):
-        if getattr(args, flag) is not None:
+        if getattr(args, flag) is not None and not (args.segment_cloud and flag == "min_object_points"):
             raise SystemExit(f"--{flag} goes with --depth_file")
 
 
@@ -259,6 +304,16 @@ def segmentation_options(args):
         opts["hypotheses"] = args.ransac_hypotheses
     if args.segment_seed is not None:
         opts["rng"] = np.random.default_rng(args.segment_seed)
+    return opts
+
+
+def cloud_segmentation_options(args):
+    """segment_cloud's options from the --segment_cloud flags (unset flags keep its defaults)."""
+    opts = {k: v for k, v in segmentation_options(args).items() if k != "min_pixels"}
+    if args.min_cluster_points is not None:
+        opts["min_points"] = args.min_cluster_points
+    if args.no_table_plane:
+        opts["table"] = False
     return opts
 
 
@@ -343,6 +398,30 @@ def run_depth(args, model, selection):
     conf = res["confidence"].flatten()
     print(f"{args.depth_file}: {tuple(depth.shape)} depth -> {n_pts} points; grasps {tuple(res['grasps'].shape)}  "
           f"confidence mean {conf.mean().item():.3f}  best {conf.max().item():.3f}")
+    return [res]
+
+
+def run_cloud_scene(args, model, selection):
+    """--segment_cloud: the one --pc_file scene through infer_on_cloud_scene."""
+    from graspldm_amd.pointcloud import read_cloud_file
+    path = args.pc_file[0]
+    pc = torch.from_numpy(read_cloud_file(path))
+    try:
+        res = model.infer_on_cloud_scene(pc, num_grasps=args.num_grasps, num_points=args.num_points,
+                                         segmentation=cloud_segmentation_options(args),
+                                         min_object_points=32 if args.min_object_points is None else args.min_object_points,
+                                         use_farthest_point=not args.random_resample, **selection_kwargs(args, selection, 0),
+                                         **cleanup_options(args), **downsample_options(args))
+    except ValueError as e:
+        raise SystemExit(f"{path}: {e}")
+    tp = res["table_plane"]
+    if tp is not None:
+        print(f"{path}: table plane n = {tp.normal.tolist()}, d = {tp.offset:.6f} ({tp.inliers} inliers)")
+    conf = res["confidence"].flatten()
+    conf = conf[~torch.isnan(conf)]
+    print(f"{path}: {pc.shape[0]} points ({res['segmented_points'].shape[0]} clustered), objects "
+          f"{res['object_label'].tolist()} with {res['object_points'].tolist()} points -> {args.num_points} each; grasps "
+          f"{tuple(res['grasps'].shape)}  confidence mean {conf.mean().item():.3f}  best {conf.max().item():.3f}")
     return [res]
 
 
@@ -496,6 +575,8 @@ def main(argv=None):
     results = []
     if args.depth_file:
         return finish(args, run_depth(args, model, selection))
+    if args.segment_cloud:
+        return finish(args, run_cloud_scene(args, model, selection))
     if args.pc_file:
         from graspldm_amd.pointcloud import read_cloud_file
         n_pts = args.num_points or encoder_points(model.model)
@@ -556,7 +637,12 @@ def finish(args, results):
                  if all(r.get(k) is not None for r in results)}
         if all(r.get("voxel_size") is not None for r in results):   # --voxel_size: the size every result ended with
             extra["voxel_size"] = np.asarray([r["voxel_size"] for r in results], dtype=np.float32)
-        if all(r.get("table_plane") is not None for r in results):   # --segment_tabletop: one frame per result
+        if all(r.get("segmented_points") is not None for r in results):   # --segment_cloud: one scene per result
+            extra["labels"] = torch.stack([r["labels"] for r in results]).cpu().numpy()
+            extra["segmented_points"] = torch.stack([r["segmented_points"] for r in results]).cpu().numpy()
+            if all(r.get("table_plane") is not None for r in results):
+                extra["table_plane"] = np.stack([r["table_plane"].as_array() for r in results])
+        elif all(r.get("table_plane") is not None for r in results):   # --segment_tabletop: one frame per result
             extra["labels"] = torch.stack([r["labels"] for r in results]).cpu().numpy()
             extra["table_plane"] = np.stack([r["table_plane"].as_array() for r in results])
         np.savez_compressed(args.out, grasps=torch.cat([r["grasps"] for r in results]).cpu().numpy(),
