@@ -74,8 +74,46 @@ class Camera:
         pc, pix = depth_to_cloud(depth, self, return_pixels=True)
         return pc, rgb.reshape(height * width, -1)[pix.long()]
 
+    def render_depth(self, meshes, world_to_cam, instances=None, return_labels=False, return_faces=False):
+        """Depth frames of meshes seen by this camera (graspldm_amd.pointcloud.render_depth: one HIP entry,
+        gldm_render_depth), in the conventions of depth_to_pointcloud_torch: what the reference asks pyrender for."""
+        from .pointcloud import render_depth
+        return render_depth(meshes, self, world_to_cam, instances=instances, return_labels=return_labels,
+                            return_faces=return_faces)
+
     def write_to_dir(self, out_dir):
         json_fp = os.path.join(out_dir, f"camera_{self.name}.json")
         with open(json_fp, "w") as f:
             json.dump(self.data, f)
         return json_fp
+
+
+def look_at(eye, target, up=(0.0, 0.0, 1.0)):
+    """World-to-camera 4 x 4 (f64) of a camera at `eye` looking at `target`, in the frame of the deprojection: +z forward,
+    +x right, +y down.  `up` only has to be no multiple of the viewing direction; where it is, another axis takes its place."""
+    eye, target = np.asarray(eye, dtype=np.float64).reshape(3), np.asarray(target, dtype=np.float64).reshape(3)
+    z = target - eye
+    if not np.linalg.norm(z) > 0:
+        raise ValueError("look_at: eye and target coincide")
+    z = z / np.linalg.norm(z)
+    up = np.asarray(up, dtype=np.float64).reshape(3)
+    x = np.cross(z, up)
+    if np.linalg.norm(x) < 1e-9 * max(np.linalg.norm(up), 1e-300):
+        x = np.cross(z, np.eye(3)[np.argmin(np.abs(z))])
+    x = x / np.linalg.norm(x)
+    y = np.cross(z, x)
+    m = np.eye(4)
+    m[:3, :3] = np.stack([x, y, z])
+    m[:3, 3] = -m[:3, :3] @ eye
+    return m
+
+
+def views_on_sphere(n, radius, target=(0.0, 0.0, 0.0), rng=None):
+    """n world-to-camera poses [n, 4, 4] (look_at) from eyes drawn uniformly on the sphere of `radius` around `target`, as
+    the partial-cloud renders of the reference are taken (acronym_partial_pointclouds.py:521-581).  rng: a
+    np.random.Generator / RandomState (with .normal); default np.random."""
+    rng = np.random if rng is None else rng
+    d = np.asarray(rng.normal(size=(int(n), 3)), dtype=np.float64)
+    d = d / np.linalg.norm(d, axis=1, keepdims=True)
+    target = np.asarray(target, dtype=np.float64).reshape(3)
+    return np.stack([look_at(target + float(radius) * v, target) for v in d]) if n else np.zeros((0, 4, 4))

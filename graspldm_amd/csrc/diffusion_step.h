@@ -3,9 +3,9 @@
 // DDIM / DDPM / DPM-Solver++ updates (no contraction: one rounding per written operation).  Device code only, __forceinline__;
 // include it inside the translation unit's anonymous namespace, behind <hip/hip_runtime.h> and gldm.h (all it needs).
 
-// Philox4x32-10 (Salmon et al., SC'11: the counter-based generator of curand / torch's device RNG) and Box-Muller: four
-// unit normals per (key, counter).  z[0..3] of counter (latent, position block, step) are positions 4 block + 0..3.
-__device__ __forceinline__ void philox_normal4(unsigned long long seed, unsigned c0, unsigned c1, unsigned c2, unsigned c3, float (&z)[4]) {
+// Philox4x32-10 (Salmon et al., SC'11: the counter-based generator of curand / torch's device RNG): the four words of
+// (key = seed, counter).  Also the uniforms of mesh_sample.hip.
+__device__ __forceinline__ void philox4x32_10(unsigned long long seed, unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned (&u)[4]) {
   unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
 #pragma unroll
   for (int r = 0; r < 10; ++r) {
@@ -14,7 +14,14 @@ __device__ __forceinline__ void philox_normal4(unsigned long long seed, unsigned
     c1 = (unsigned)p1; c3 = (unsigned)p0; c0 = n0; c2 = n2;
     k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
   }
-  const unsigned u[4] = {c0, c1, c2, c3};
+  u[0] = c0; u[1] = c1; u[2] = c2; u[3] = c3;
+}
+
+// Box-Muller on those words: four unit normals per (key, counter).  z[0..3] of counter (latent, position block, step) are
+// positions 4 block + 0..3.
+__device__ __forceinline__ void philox_normal4(unsigned long long seed, unsigned c0, unsigned c1, unsigned c2, unsigned c3, float (&z)[4]) {
+  unsigned u[4];
+  philox4x32_10(seed, c0, c1, c2, c3, u);
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     const float a = ((float)u[2 * h] + 1.0f) * 2.3283064365386963e-10f;   // (0, 1]

@@ -14,6 +14,7 @@ import os
 import warnings
 from enum import Enum
 
+import numpy as np
 import torch
 
 from .builder import build_model_from_cfg
@@ -395,6 +396,79 @@ class _InferenceBase:
                                  for c in clouds])
         pcn, metas = self.normalize_input(batch)
         return self.generate_grasps(pcn, metas, num_grasps=num_grasps, return_intermediate=return_intermediate, **extra)
+
+    def _encoder_points(self):
+        """n_points of the model's cloud encoder (its out_layer[1] is a Linear over the point axis: N is fixed)."""
+        vae = getattr(self.model, "vae_model", self.model)
+        try:
+            enc = vae.encoder.pc_encoder if hasattr(vae, "encoder") else vae.pc_encoder
+            return int(enc.out_layer[1].in_features)
+        except (AttributeError, IndexError, TypeError):
+            raise ValueError("cannot infer the encoder's point count: pass num_points") from None
+
+    def infer_on_mesh(self, mesh, num_grasps=10, num_points=None, view=None, camera=None, seed=None, selection=None,
+                      scene_points=None, view_radius=None, use_farthest_point=True, return_intermediate=False):
+        """From an object model to grasps without leaving the GPU (additive): the two inputs the reference's
+        experiments read from ACRONYM meshes -- `mesh.sample(n)` for the full-cloud model (acronym_pointclouds.py:173-176,
+        402) and rendered depth frames for the partial-cloud model (acronym_partial_pointclouds.py:521-581).
+        mesh: a graspldm_amd.mesh.Mesh (load_mesh reads OBJ / STL / npz).  num_points: default the encoder's point count.
+        view=None: pointcloud.sample_mesh_surface draws num_points surface points (seed: the in-kernel generator's; None
+        draws one from torch's CPU generator) and the rest is exactly infer_on_pointcloud on them.  When `selection` asks for
+        a scene (collision_free, min_contacts, min_aligned_contacts) the scene is a denser sample of the same surface:
+        scene_points of them (default 8 num_points), drawn with seed + 1.
+        view = a world-to-camera pose [4, 4] or [F, 4, 4] (camera.look_at), or an int F for camera.views_on_sphere(F,
+        view_radius, centre of the mesh's bounding box, np.random.default_rng(seed)); view_radius defaults to 4 times the
+        bounding sphere's radius.  `camera` (a graspldm_amd.camera.Camera) is then required: pointcloud.render_depth renders
+        the frames and the rest is exactly infer_on_depth on them, one result per view, poses in each view's camera frame.
+        The results gain mesh_face -- the mesh face under every input point: [1, num_points] int32 without a view; with
+        views a list of F tensors, one entry per deprojected point in pixel order -- and cam_pose (the world-to-camera
+        poses [F, 4, 4] float64 on the host; None without a view)."""
+        from .camera import views_on_sphere
+        from .mesh import Mesh
+        from .pointcloud import depth_to_cloud, render_depth, sample_mesh_surface
+        if not isinstance(mesh, Mesh):
+            raise TypeError("infer_on_mesh takes one graspldm_amd.mesh.Mesh (mesh.load_mesh reads OBJ, STL and npz files)")
+        if mesh.faces.shape[0] == 0:
+            raise ValueError("the mesh has no faces")
+        n = self._encoder_points() if num_points is None else int(num_points)
+        extra = {} if selection is None else dict(selection=selection)
+        if view is None:
+            if camera is not None or view_radius is not None:
+                raise ValueError("camera and view_radius go with a view")
+            seed = int(torch.randint(0, 2 ** 62, ())) if seed is None else int(seed)
+            pts, face = sample_mesh_surface(mesh, n, seed=seed, return_faces=True, device=self.device)
+            if bool((face < 0).any()):
+                raise ValueError("the mesh has no surface area")
+            if selection is not None and selection.needs_scene:
+                m = 8 * n if scene_points is None else int(scene_points)
+                extra["scene_pc"] = sample_mesh_surface(mesh, m, seed=(seed + 1) % 2 ** 64, device=self.device)[0]
+            out = self.infer_on_pointcloud(pts[0], num_grasps=num_grasps, return_intermediate=return_intermediate, **extra)
+            out["mesh_face"], out["cam_pose"] = face, None
+            return out
+        if camera is None:
+            raise ValueError("a view needs a camera (graspldm_amd.camera.Camera: intrinsics and image size)")
+        lo, hi = mesh.bounds
+        centre = (lo.astype(np.float64) + hi.astype(np.float64)) / 2
+        if isinstance(view, (int, np.integer)) and not isinstance(view, bool):
+            if view < 1:
+                raise ValueError(f"view = {view}: at least one view")
+            radius = 4 * float(np.linalg.norm(mesh.vertices.astype(np.float64) - centre, axis=1).max())
+            radius = radius if view_radius is None else float(view_radius)
+            poses = views_on_sphere(int(view), radius, centre, np.random.default_rng(seed))
+            single = False
+        else:
+            if view_radius is not None:
+                raise ValueError("view_radius goes with a number of views")
+            poses = np.asarray(view.detach().cpu() if isinstance(view, torch.Tensor) else view, dtype=np.float64)
+            single = poses.ndim == 2
+            poses = poses.reshape(-1, 4, 4)
+        depth, face = render_depth(mesh, camera, poses, return_faces=True, device=self.device)
+        out = self.infer_on_depth(depth[0] if single else depth, camera, num_grasps=num_grasps, num_points=n,
+                                  use_farthest_point=use_farthest_point, return_intermediate=return_intermediate, **extra)
+        _, pix = depth_to_cloud(depth, camera, return_pixels=True)
+        out["mesh_face"] = [face[f].reshape(-1)[p.long()] for f, p in enumerate(pix)]
+        out["cam_pose"] = torch.from_numpy(poses.copy())
+        return out
 
     @staticmethod
     def _clean_objects(packed, starts, counts, cleanup):

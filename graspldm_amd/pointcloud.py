@@ -19,7 +19,9 @@ table (gldm_plane_ransac, gldm_plane_moments) and `segment_tabletop` labels the 
 gldm_point_normals; estimate_normals_cam_from_pc, pointcloud_helpers.py:74-122).  `remove_outliers` drops
 the isolated points of sensor clouds before any of that sees them (gldm_neighbor_stats, gldm_filter_outliers), and
 `voxel_downsample` brings raw sensor density down to one point per voxel in front of both
-(gldm_voxel_downsample).
+(gldm_voxel_downsample).  From an object model instead of a sensor: `sample_mesh_surface` draws the full cloud
+the reference takes from trimesh (gldm_mesh_sample_surface) and `render_depth` the depth frames it takes from pyrender
+(gldm_render_depth), with ground-truth labels and face indices.
 """
 import ctypes
 import math
@@ -1235,3 +1237,181 @@ def segment_cloud(points, plane=None, table=True, height_range=(0.01, 0.5), link
     labels, num = cluster_cloud(points, link_dist=link_dist, min_points=min_points, max_objects=max_objects, plane=plane,
                                 height_range=height_range)
     return labels, num, plane
+
+
+# ------------------------------------------------------------------------------------------------ meshes
+
+MESH_MAX_SAMPLES = 1 << 24       # gldm_mesh_sample_surface: n
+MESH_MAX_SAMPLE_ROWS = 1 << 28   # b * n
+RENDER_MAX_PIXELS = 1 << 24      # gldm_render_depth: h * w
+RENDER_MAX_FRAMES = 65535
+RENDER_MAX_INSTANCES = 65535
+RENDER_MAX_TRIANGLES = 1 << 24
+
+
+def _mesh_device(device, *tensors):
+    for t in tensors:
+        if t is not None:
+            return t.device
+    return torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+
+
+def sample_mesh_surface(meshes, n, rand=None, seed=None, return_faces=False, return_normals=False, device=None):
+    """n points on the surface of every mesh, faces drawn by area: trimesh's `mesh.sample(n)` (acronym_pointclouds.py:
+    173-176, 402) as one HIP entry (gldm_mesh_sample_surface; the exact rule is in include/gldm.h).
+      meshes   a graspldm_amd.mesh.MeshBatch, a Mesh or a sequence of meshes (B of them)
+      rand     CUDA f32 [B, n, 3] uniforms in [0, 1), multiples of 2^-24 (torch.rand gives such); or
+      seed     int: the uniforms are drawn in the kernel (Philox4x32-10 keyed on (seed, mesh, sample)); with neither, a seed
+               is drawn from torch's CPU generator, so torch.manual_seed makes a run repeatable
+    -> points [B, n, 3]; with return_faces also face [B, n] int32 (the row of the batch's packed face array, -1 for a mesh
+    without area, whose points are zero); with return_normals also the unit face normals [B, n, 3]."""
+    from .mesh import MeshBatch
+    mb = MeshBatch.of(meshes)
+    b, n = len(mb), int(n)
+    if n < 0:
+        raise ValueError(f"n must not be negative, not {n}")
+    if n > MESH_MAX_SAMPLES or b * n > MESH_MAX_SAMPLE_ROWS:
+        raise NotImplementedError(f"{b} meshes x {n} samples: gldm_mesh_sample_surface takes at most 2^24 samples per mesh "
+                                  f"and 2^28 per call")
+    if rand is not None and seed is not None:
+        raise ValueError("give the uniforms (rand) or a seed for the in-kernel generator, not both")
+    if rand is not None:
+        _need_cuda(rand, "rand")
+        if tuple(rand.shape) != (b, n, 3) or rand.dtype != torch.float32:
+            raise ValueError(f"rand must be f32 [{b}, {n}, 3], not {rand.dtype} {tuple(rand.shape)}")
+        rand = rand.contiguous()
+    elif seed is None:
+        seed = int(torch.randint(0, 2 ** 62, ()))
+    seed = 0 if seed is None else int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"seed must fit 64 unsigned bits, not {seed}")
+    dev = _mesh_device(device, rand)
+    verts, faces, rg = mb.on(dev)
+    sizes = (b, mb.f_max, verts.shape[0], faces.shape[0], n)
+    points = torch.empty((b, n, 3), dtype=torch.float32, device=dev)
+    face = torch.empty((b, n), dtype=torch.int32, device=dev) if return_faces else None
+    normals = torch.empty((b, n, 3), dtype=torch.float32, device=dev) if return_normals else None
+    if n:
+        ws, nbytes = L.workspace("gldm_mesh_sample_surface", sizes, torch.int64, dev, f"{b} meshes, {n} samples")
+        with torch.cuda.device(dev):
+            L.call("gldm_mesh_sample_surface", L.ptr(verts), L.ptr(faces), L.ptr(rg[0]), L.ptr(rg[1]), L.ptr(rg[2]),
+                   L.ptr(rg[3]), *sizes, L.ptr(rand), seed, L.ptr(ws), nbytes, L.ptr(points), L.ptr(face), L.ptr(normals),
+                   L.current_stream(dev))
+    out = (points,) + ((face,) if return_faces else ()) + ((normals,) if return_normals else ())
+    return out[0] if len(out) == 1 else out
+
+
+def _poses(m, name):
+    a = np.asarray(m.detach().cpu() if isinstance(m, torch.Tensor) else m, dtype=np.float64)
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3 or a.shape[1:] not in ((4, 4), (3, 4)):
+        raise ValueError(f"{name} must be 4 x 4 (or 3 x 4) or a stack of such, not {a.shape}")
+    if not np.isfinite(a).all():
+        raise ValueError(f"{name} must be finite")
+    full = np.tile(np.eye(4), (a.shape[0], 1, 1))
+    full[:, :a.shape[1]] = a
+    return full
+
+
+def render_plan(mb, camera, world_to_cam, instances):
+    """The host half of render_depth, without a HIP call: the instance table and the frame ranges of gldm_render_depth as
+    numpy arrays, every limit checked.  -> dict(mesh, xf [I, 12] f32, label, tri [I], n_tris, frame_start, frame_count,
+    h, w, optics (fx, fy, cx, cy, z_near, z_far))."""
+    b = len(mb)
+    poses = _poses(world_to_cam, "world_to_cam")
+    if instances is None:   # one frame per (mesh, pose) pair, mesh-major
+        frames = [[(i, np.eye(4), 1)] for i in range(b) for _ in range(poses.shape[0])]
+        poses = np.tile(poses, (b, 1, 1))
+    else:
+        frames = [list(f) for f in instances]
+        if poses.shape[0] == 1:
+            poses = np.tile(poses, (len(frames), 1, 1))
+        if poses.shape[0] != len(frames):
+            raise ValueError(f"{len(frames)} frames of instances but {poses.shape[0]} camera poses")
+    h, w = int(camera.height), int(camera.width)
+    fx, fy, cx, cy = camera.intrinsics
+    z_near, z_far = float(np.float32(camera.z_near)), float(np.float32(camera.z_far))
+    if h < 1 or w < 1 or not frames:
+        raise ValueError(f"render_depth needs at least one frame of at least one pixel, not {len(frames)} of {h} x {w}")
+    if h * w > RENDER_MAX_PIXELS:
+        raise NotImplementedError(f"frames of {h} x {w}: gldm_render_depth takes at most 2^24 pixels per frame")
+    if len(frames) > RENDER_MAX_FRAMES:
+        raise NotImplementedError(f"{len(frames)} frames: gldm_render_depth takes at most {RENDER_MAX_FRAMES} per call")
+    if not (np.isfinite([fx, fy, cx, cy]).all() and np.float32(fx) != 0 and np.float32(fy) != 0):
+        raise ValueError(f"the camera needs finite intrinsics and fx, fy != 0, not {(fx, fy, cx, cy)}")
+    if not 0 < z_near < z_far < float("inf"):
+        raise ValueError(f"the camera needs 0 < z_near < z_far, not {camera.z_near}, {camera.z_far}")
+    mesh, xf, label, fstart, fcount = [], [], [], [], []
+    for pose, frame in zip(poses, frames):
+        fstart.append(len(mesh))
+        fcount.append(len(frame))
+        for inst in frame:
+            inst = tuple(inst)
+            if len(inst) not in (2, 3):
+                raise ValueError("an instance is (mesh id, obj_to_world) or (mesh id, obj_to_world, label)")
+            m, obj_to_world = inst[:2]
+            lab = inst[2] if len(inst) == 3 else len(mesh) - fstart[-1] + 1
+            if not 0 <= int(m) < b:
+                raise ValueError(f"instance of mesh {m}: the batch holds {b} meshes")
+            if int(lab) < 1 or int(lab) > 2 ** 31 - 1:
+                raise ValueError(f"an instance label must be an int32 >= 1, not {lab}")
+            mesh.append(int(m))
+            label.append(int(lab))
+            xf.append((pose @ _poses(obj_to_world, "obj_to_world")[0])[:3].astype(np.float32).reshape(12))
+    if len(mesh) > RENDER_MAX_INSTANCES:
+        raise NotImplementedError(f"{len(mesh)} instances: gldm_render_depth takes at most {RENDER_MAX_INSTANCES} per call")
+    tris = mb.face_count.astype(np.int64)[np.asarray(mesh, dtype=np.int64)] if mesh else np.zeros(0, np.int64)
+    n_tris = int(tris.sum())
+    if n_tris > RENDER_MAX_TRIANGLES:
+        raise NotImplementedError(f"{n_tris} triangles: gldm_render_depth takes at most 2^24 per call")
+    i32 = lambda v: np.asarray(v, dtype=np.int32).reshape(-1)
+    return dict(mesh=i32(mesh), xf=np.asarray(xf, dtype=np.float32).reshape(-1, 12), label=i32(label),
+                tri=i32(np.cumsum(tris) - tris), n_tris=n_tris, frame_start=i32(fstart), frame_count=i32(fcount), h=h, w=w,
+                optics=tuple(float(np.float32(v)) for v in (fx, fy, cx, cy, z_near, z_far)))
+
+
+def render_depth(meshes, camera, world_to_cam, instances=None, return_labels=False, return_faces=False, device=None):
+    """Depth frames of meshes seen by a pinhole camera, one HIP entry (gldm_render_depth; the exact rule is in
+    include/gldm.h): what the reference takes from pyrender (acronym_partial_pointclouds.py:521-581).  The frames follow the
+    deprojection's conventions -- +z forward, +x right, +y down, pixel (u, v) sampled at its integer coordinates -- so
+    depth_to_cloud(render_depth(...)) lies on the surface.  (An OpenGL renderer samples pixel centres, half a pixel further.)
+      meshes        a MeshBatch, a Mesh or a sequence of meshes
+      camera        graspldm_amd.camera.Camera: intrinsics, image size, z_near / z_far
+      world_to_cam  4 x 4, or [P, 4, 4] (camera.look_at / views_on_sphere); host or device, read on the host
+      instances     None: every mesh at its own coordinates, one frame per (mesh, pose) pair, mesh-major, label 1.
+                    Otherwise one list per frame of (mesh id, obj_to_world 4 x 4, label >= 1) (without a label: 1, 2, .. in
+                    the frame's order); world_to_cam then holds one pose, or one per frame.  obj_to_cam = world_to_cam
+                    obj_to_world is composed in f64 and rounded once.
+    A triangle with a vertex in front of z_near is dropped whole (no clipping), with a warning.
+    -> depth [R, h, w] f32, 0 where empty; with return_labels also the labels [R, h, w] int32 (0 = background); with
+    return_faces also the rows of the batch's packed face array [R, h, w] int32 (-1 where empty)."""
+    from .mesh import MeshBatch
+    mb = MeshBatch.of(meshes)
+    plan = render_plan(mb, camera, world_to_cam, instances)
+    dev = _mesh_device(device)
+    verts, faces, rg = mb.on(dev)
+    r, h, w, n_inst, n_tris = plan["frame_start"].size, plan["h"], plan["w"], plan["mesh"].size, plan["n_tris"]
+    table = torch.from_numpy(np.concatenate([plan["mesh"], plan["label"], plan["tri"], plan["frame_start"],
+                                             plan["frame_count"]])).to(dev)
+    i_mesh, i_label, i_tri, f_start, f_count = torch.split(table, [n_inst] * 3 + [r] * 2)
+    xf = torch.from_numpy(plan["xf"]).to(dev)
+    sizes = (len(mb), verts.shape[0], faces.shape[0], n_inst, n_tris, r, h, w)
+    ws, nbytes = L.workspace("gldm_render_depth", sizes, torch.int64, dev, f"{r} frames of {h} x {w}, {n_tris} triangles")
+    ws = None if ws is None else ws[(-ws.data_ptr() // 8) % 2:]   # 16-byte aligned (torch's allocations are, anyway)
+    depth = torch.empty((r, h, w), dtype=torch.float32, device=dev)
+    label = torch.empty((r, h, w), dtype=torch.int32, device=dev) if return_labels else None
+    face = torch.empty((r, h, w), dtype=torch.int32, device=dev) if return_faces else None
+    dropped = torch.empty(r, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.call("gldm_render_depth", L.ptr(verts), L.ptr(faces), L.ptr(rg[0]), L.ptr(rg[1]), L.ptr(rg[2]), L.ptr(rg[3]),
+               sizes[0], sizes[1], sizes[2], L.ptr(i_mesh), L.ptr(xf), L.ptr(i_label), L.ptr(i_tri), n_inst, n_tris,
+               L.ptr(f_start), L.ptr(f_count), r, h, w, *plan["optics"], L.ptr(ws), nbytes, L.ptr(depth), L.ptr(label),
+               L.ptr(face), L.ptr(dropped), L.current_stream(dev))
+    n_dropped = int(dropped.sum())   # the one read-back
+    if n_dropped:
+        import warnings
+        warnings.warn(f"render_depth: {n_dropped} triangles reach in front of z_near = {camera.z_near} and were dropped whole "
+                      f"(there is no clipping): move the camera back or lower z_near", RuntimeWarning, stacklevel=2)
+    out = (depth,) + ((label,) if return_labels else ()) + ((face,) if return_faces else ())
+    return out[0] if len(out) == 1 else out

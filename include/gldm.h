@@ -1043,6 +1043,94 @@ int gldm_split_labels(const float *points /*[rows,3]*/, const int32_t *labels /*
                       int32_t *obj_start /*[b,max_labels]*/, int32_t *obj_count /*[b,max_labels]*/, int32_t *out_total /*[1]*/,
                       gldm_stream_t stream);
 
+/* ------------------------------------------------ meshes (additive; csrc/mesh_sample.hip, csrc/mesh_render.hip) */
+
+/* A ragged batch of b triangle meshes.  vertices [n_verts,3] f32 and faces [n_faces,3] int32 are packed; mesh i owns the
+ * vertex rows vert_start[i] .. + vert_count[i] and the face rows face_start[i] .. + face_count[i] (device int32 [b]); the
+ * indices of a face are local to its mesh.  A face count is clamped to [0, 2^22] (and to f_max where an entry takes one);
+ * a range that leaves its array is empty; a face with an index outside [0, vert_count) is DEGENERATE: its vertices are never
+ * read, it has no area and draws nothing.  Nothing outside the arrays is ever addressed, whatever they hold.
+ *
+ * gldm_mesh_sample_surface: n points on every mesh, each on a face drawn with probability proportional to its area (the
+ * rule of trimesh.sample.sample_surface; ref: grasp_ldm/dataset/acronym/acronym_pointclouds.py:173-176), made exact.
+ * Face weight.  In f64 from the f32 vertices: e1 = v1 - v0, e2 = v2 - v0 per component; c = (e1y e2z - e1z e2y,
+ *   e1z e2x - e1x e2z, e1x e2y - e1y e2x); n2 = (cx cx + cy cy) + cz cz; A = 0.5 * sqrt(n2).  A degenerate face, and one
+ *   whose A is not a positive finite number, has A = 0.  Amax = the largest A of the mesh = m 2^e with m in [0.5, 1)
+ *   (frexp).  q = (uint64) rint(ldexp(A, 40 - e)): the largest face weighs 2^39 .. 2^40, at most 2^22 faces sum below 2^62;
+ *   every q is 0 when Amax is 0.  cum[f] = q[0] + .. + q[f] in the mesh's face order, total = cum[last]: integer sums.
+ * Uniforms.  (u0, u1, u2) of sample i of mesh j, multiples of 2^-24 in [0, 1):
+ *   - rand != NULL: rand[(j n + i) 3 + 0..2] (device f32), each first brought into [0, 1 - 2^-24] with
+ *     fminf(fmaxf(u, 0), 1 - 2^-24) (a NaN becomes 0); k0 = (uint32)(u0 * 2^24), truncated;
+ *   - rand == NULL: the words (x0, x1, x2, x3) of Philox4x32-10 with key = seed (low, high) and counter = (i, j, 0, 0)
+ *     (the generator of gldm_denoise_rng; oracle/philox.py); k0 = x0 >> 8, u1 = (float)(x1 >> 8) * 2^-24, u2 likewise.
+ * Face.  t = (k0 * total) >> 24 (an 88-bit product); the sample lies on the first face of the mesh with cum > t.
+ * Point.  In f32, one rounding per written operation: if (u1 + u2 > 1) { u1 = 1 - u1; u2 = 1 - u2; } then per component
+ *   p = v0 + ((v1 - v0) * u1 + (v2 - v0) * u2).
+ * Outputs.  points [b,n,3]; face [b,n] (optional): the row of the packed face array; normals [b,n,3] (optional): (float)(c
+ * / sqrt(n2)) per component, the f64 cross product above.  A mesh whose total is 0 (no faces, all degenerate) gets zero
+ * points, zero normals and face -1.  Every element is written; two calls are bitwise equal; numpy restates every bit
+ * (tests/mesh_ref.py).
+ * Four launches on one stream (clear, areas with a vector atomicMax on the bits of non-negative doubles, weights + scan with
+ * one workgroup per mesh, samples); no host round trip.
+ * Envelope, checked before any pointer or the device is touched: b >= 1, f_max, n_verts, n_faces, n >= 0
+ * (GLDM_ERR_INVALID_ARG); b <= 65535, f_max <= 2^22, n_verts <= 2^24, n_faces <= 2^24, n <= 2^24, b n <= 2^28
+ * (GLDM_ERR_UNSUPPORTED).  f_max: at least the largest face_count (host).  n = 0 writes nothing.  workspace:
+ * gldm_mesh_sample_surface_workspace_bytes(...) bytes (a negative GLDM_ERR_* status outside the envelope; 16 per face, 16 per
+ * mesh), 8-byte aligned, uninitialised, private to the stream until the work has finished. */
+long long gldm_mesh_sample_surface_workspace_bytes(int b, int f_max, int n_verts, int n_faces, int n);
+int gldm_mesh_sample_surface(const float *vertices /*[n_verts,3]*/, const int32_t *faces /*[n_faces,3]*/,
+                             const int32_t *vert_start /*[b]*/, const int32_t *vert_count /*[b]*/,
+                             const int32_t *face_start /*[b]*/, const int32_t *face_count /*[b]*/, int b, int f_max, int n_verts,
+                             int n_faces, int n, const float *rand /*[b,n,3] or NULL*/, unsigned long long seed, void *workspace,
+                             long long workspace_bytes, float *points /*[b,n,3]*/, int32_t *face /*[b,n] or NULL*/,
+                             float *normals /*[b,n,3] or NULL*/, gldm_stream_t stream);
+
+/* gldm_render_depth: `frames` frames of h x w pixels of the meshes above seen by a pinhole camera at the origin looking down
+ * +z with +x right and +y down -- the frame of gldm_depth_to_cloud, so that deprojecting a rendered frame lands on the
+ * surface (ref: the pyrender depth frames of grasp_ldm/dataset/acronym/acronym_partial_pointclouds.py:521-581).
+ * Instances.  Row k of the instance table (device arrays of n_inst rows) draws mesh inst_mesh[k] under the rigid transform
+ * inst_xf[k] (obj_to_cam, 3 x 4 row major, f32) with label inst_label[k]; inst_tri[k] is its first RECORD: the caller's
+ * exclusive sum of the face counts in table order, n_tris their total.  Record r belongs to the last instance with inst_tri <=
+ * r and is face r - inst_tri of its mesh; a record whose instance has no such face, or a mesh id outside [0, b), draws
+ * nothing.  Frame f draws the records from inst_tri[frame_start[f]] up to the first record of instance frame_start[f] +
+ * frame_count[f] (n_tris behind the last); a frame whose instance range leaves the table is empty.
+ * Vertex.  X = ((m00 x + m01 y) + m02 z) + m03, Y and Z likewise (gldm_depth_to_cloud's expression); px = (X * fx) / Z + cx,
+ * py = (Y * fy) / Z + cy; f32, one rounding each.
+ * Dropped triangles.  A triangle with a vertex for which Z >= z_near does not hold (NaN included), or with a projected
+ * coordinate that is not finite, is dropped whole -- there is no clipping -- and counted in dropped[f].  Degenerate faces
+ * (above) are skipped without being counted.
+ * Coverage.  Pixel (u, v) is sampled at its integer coordinates (gldm_depth_to_cloud's convention; an OpenGL renderer samples
+ * at u + 0.5, v + 0.5: shift cx, cy by 0.5 to compare).  For an edge a -> b, E_ab = (bx - ax)(v - ay) - (by - ay)(u - ax) in
+ * f64 from the f32 projections, when (ax, ay) <= (bx, by) lexicographically; otherwise E_ab = -E_ba, E_ba evaluated that
+ * way: the two triangles on a shared edge see bitwise opposite values, which leaves no cracks and draws no pixel of an
+ * interior edge less than once.  w0 = E_bc, w1 = E_ca, w2 = E_ab, S = (w0 + w1) + w2.  The pixel is inside when min(px) <=
+ * u <= max(px) and min(py) <= v <= max(py) (f32 comparisons; implied by the rest in exact arithmetic, stated so that the
+ * broad phase is exact), all three w are >= 0 or all three are <= 0, and S != 0.  There is no back-face culling.
+ * Depth.  z = (float)(1 / (((w0 / za + w1 / zb) + w2 / zc) / S)) in f64, za .. zc the vertices' Z; kept iff z_near <= z <=
+ * z_far.
+ * Resolve.  The pixel takes the minimum of (bits(z) << 32) | r over the kept records r of its frame: the nearest surface,
+ * coincident surfaces to the lower record.
+ * Outputs.  depth [frames,h,w] f32, 0 where empty; label (optional) int32, the instance's label, 0 where empty; face
+ * (optional) int32, the row of the packed face array, -1 where empty; dropped [frames] int32.  Every element is written;
+ * bitwise a pure function of the inputs (tests/mesh_ref.py restates every bit).
+ * Two launches: one record and one pixel box per (instance, face); then one workgroup per 16 x 16 pixel tile, which walks its
+ * frame's boxes 256 at a time, stages the records whose box meets the tile in LDS and keeps every pixel's minimum in
+ * registers.  No atomics on device memory, no initialising pass, no workgroup waits for another.
+ * Envelope, checked before any pointer or the device is touched: b, frames, h, w >= 1, n_verts, n_faces, n_inst, n_tris >= 0,
+ * fx, fy finite and != 0, cx, cy finite, 0 < z_near < z_far < inf (GLDM_ERR_INVALID_ARG); b <= 65535, n_verts, n_faces <=
+ * 2^24, n_inst <= 65535, n_tris <= 2^24, frames <= 65535, h w <= 2^24 (GLDM_ERR_UNSUPPORTED).  workspace:
+ * gldm_render_depth_workspace_bytes(...) bytes (64 per record), 16-BYTE aligned, uninitialised. */
+long long gldm_render_depth_workspace_bytes(int b, int n_verts, int n_faces, int n_inst, int n_tris, int frames, int h, int w);
+int gldm_render_depth(const float *vertices /*[n_verts,3]*/, const int32_t *faces /*[n_faces,3]*/,
+                      const int32_t *vert_start /*[b]*/, const int32_t *vert_count /*[b]*/, const int32_t *face_start /*[b]*/,
+                      const int32_t *face_count /*[b]*/, int b, int n_verts, int n_faces, const int32_t *inst_mesh /*[n_inst]*/,
+                      const float *inst_xf /*[n_inst,12]*/, const int32_t *inst_label /*[n_inst]*/,
+                      const int32_t *inst_tri /*[n_inst]*/, int n_inst, int n_tris, const int32_t *frame_start /*[frames]*/,
+                      const int32_t *frame_count /*[frames]*/, int frames, int h, int w, float fx, float fy, float cx, float cy,
+                      float z_near, float z_far, void *workspace, long long workspace_bytes, float *depth /*[frames,h,w]*/,
+                      int32_t *label /*[frames,h,w] or NULL*/, int32_t *face /*[frames,h,w] or NULL*/,
+                      int32_t *dropped /*[frames]*/, gldm_stream_t stream);
+
 /* ------------------------------------------------ grasp selection (additive, ABI 14; csrc/grasp_select.hip) */
 
 /* Gripper clearance and finger-sweep contacts of every pose against a whole scene cloud.  The geometry is the

@@ -40,7 +40,11 @@ object_points_raw), --segment_cloud [--min_cluster_points N] [--no_table_plane] 
 is fitted and the points above it are split into objects by Euclidean clustering on the GPU, infer_on_cloud_scene; --table_tol,
 --object_height, --link_dist, --ransac_hypotheses, --segment_seed, --min_object_points, --voxel_size and --remove_outliers
 with their families keep their meaning; --no_table_plane clusters every point; --out gains labels, segmented_points,
-table_plane and the --labels_file keys).  `--inference_steps` is honoured (the reference
+table_plane and the --labels_file keys), --mesh_file FILE [--mesh_scale S] [--mesh_views N | --mesh_view EX EY EZ]
+[--view_radius R] [--camera_json FILE] [--mesh_seed S] (generate on an object model read from .obj / .stl / .npz,
+infer_on_mesh: its surface sampled on the GPU into the encoder's point count, or -- with a view, which needs --camera_json --
+depth frames of it rendered on the GPU and deprojected, one result per view; excludes --pc_file and --depth_file; --out gains
+mesh_face without a view and cam_pose with one).  `--inference_steps` is honoured (the reference
 silently ignores it: it passes use_fast_sampler=False, tools/generate_grasps.py:69-79).
 """
 import argparse
@@ -182,12 +186,56 @@ def parse_args(argv=None):
                    help="with --voxel_size: grow the voxel by 1.25 until no cloud keeps more than N points")
     p.add_argument("--downsample_scene", action="store_true",
                    help="with --voxel_size: downsample the scene cloud the selection is checked against as well")
+    p.add_argument("--mesh_file", type=str, default=None, metavar="FILE",
+                   help="generate on an object model (.obj, .stl, .npz with vertices and faces): its surface is sampled on the "
+                        "GPU into the encoder's point count (--num_points), or with --mesh_views / --mesh_view depth frames "
+                        "of it are rendered on the GPU and deprojected, as --depth_file")
+    p.add_argument("--mesh_scale", type=float, default=None, metavar="S", help="with --mesh_file: multiply the vertices by S")
+    p.add_argument("--mesh_views", type=int, default=None, metavar="N",
+                   help="with --mesh_file and --camera_json: render N views from random eyes on a sphere around the object")
+    p.add_argument("--mesh_view", type=float, nargs=3, default=None, metavar=("EX", "EY", "EZ"),
+                   help="with --mesh_file and --camera_json: render one view from this eye, looking at the object's centre")
+    p.add_argument("--view_radius", type=float, default=None, metavar="R",
+                   help="with --mesh_views: the sphere's radius in metres (default: 4 times the object's bounding radius)")
+    p.add_argument("--mesh_seed", type=int, default=None, metavar="S",
+                   help="with --mesh_file: seed of the surface samples / of the random views (default: drawn from --seed)")
     p.add_argument("--out", type=str, default=None, help="write results of all samples to this .npz")
     args = p.parse_args(argv)
+    check_mesh_flags(p, args)
     check_cloud_scene_flags(p, args)
     check_depth_flags(args)
     check_downsample_flags(p, args)
     return args
+
+
+MESH_FLAGS = ("mesh_scale", "mesh_views", "mesh_view", "view_radius", "mesh_seed")
+
+
+def check_mesh_flags(p, args):
+    """--mesh_file excludes --pc_file / --depth_file / --synthetic clouds; a view needs --camera_json; its companions need it."""
+    if not args.mesh_file:
+        for flag in MESH_FLAGS:
+            if getattr(args, flag) is not None:
+                p.error(f"--{flag} goes with --mesh_file")
+        return
+    if args.pc_file or args.depth_file:
+        p.error("--mesh_file, --pc_file and --depth_file exclude each other")
+    if args.mesh_views is not None and args.mesh_view is not None:
+        p.error("--mesh_views and --mesh_view exclude each other")
+    view = args.mesh_views is not None or args.mesh_view is not None
+    if view and not args.camera_json:
+        p.error("--mesh_views / --mesh_view need --camera_json")
+    if not view and args.camera_json:
+        p.error("--camera_json goes with --mesh_views / --mesh_view (or with --depth_file)")
+    if args.view_radius is not None and args.mesh_views is None:
+        p.error("--view_radius goes with --mesh_views")
+    if args.mesh_views is not None and args.mesh_views < 1:
+        p.error("--mesh_views must be at least 1")
+    if args.mesh_scale is not None and not args.mesh_scale > 0:
+        p.error("--mesh_scale must be positive")
+    if args.refine_from or args.segment_cloud or args.voxel_size is not None:
+        p.error("--mesh_file generates on the sampled or rendered cloud as it is: it excludes --refine_from, "
+                "--segment_cloud and --voxel_size")
 
 
 def check_downsample_flags(p, args):
@@ -281,7 +329,8 @@ def check_depth_flags(args):
         if getattr(args, flag) is not None and not (args.segment_cloud and flag in CLOUD_SEGMENT_FLAGS):
             raise SystemExit(f"--{flag} goes with --segment_tabletop")
     for flag in ("camera_json", "mask_file", "labels_file", "min_object_points", "depth_scale", "z_range", "crop_box"):
-        if getattr(args, flag) is not None and not (args.segment_cloud and flag == "min_object_points"):
+        if getattr(args, flag) is not None and not (args.segment_cloud and flag == "min_object_points") \
+                and not (args.mesh_file and flag == "camera_json"):
             raise SystemExit(f"--{flag} goes with --depth_file")
 
 
@@ -398,6 +447,35 @@ def run_depth(args, model, selection):
     conf = res["confidence"].flatten()
     print(f"{args.depth_file}: {tuple(depth.shape)} depth -> {n_pts} points; grasps {tuple(res['grasps'].shape)}  "
           f"confidence mean {conf.mean().item():.3f}  best {conf.max().item():.3f}")
+    return [res]
+
+
+def run_mesh(args, model, selection):
+    """--mesh_file: the object model through infer_on_mesh -- its sampled surface, or rendered views of it."""
+    from graspldm_amd.camera import Camera, look_at
+    from graspldm_amd.mesh import load_mesh
+    try:
+        mesh = load_mesh(args.mesh_file, scale=1.0 if args.mesh_scale is None else args.mesh_scale)
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"{args.mesh_file}: {e}")
+    n_pts = args.num_points or encoder_points(model.model)
+    seed = int(np.random.randint(0, 1 << 31)) if args.mesh_seed is None else args.mesh_seed
+    sel = {} if selection is None else dict(selection=selection)
+    view, cam = None, None
+    if args.camera_json:
+        cam = Camera(args.camera_json)
+        lo, hi = mesh.bounds
+        view = args.mesh_views if args.mesh_view is None else look_at(args.mesh_view, (lo.astype(float) + hi.astype(float)) / 2)
+    try:
+        res = model.infer_on_mesh(mesh, num_grasps=args.num_grasps, num_points=n_pts, view=view, camera=cam, seed=seed,
+                                  view_radius=args.view_radius, use_farthest_point=not args.random_resample, **sel)
+    except ValueError as e:
+        raise SystemExit(f"{args.mesh_file}: {e}")
+    conf = res["confidence"].flatten()
+    conf = conf[~torch.isnan(conf)]
+    what = f"{n_pts} surface points" if view is None else f"{res['grasps'].shape[0]} rendered view(s) -> {n_pts} points each"
+    print(f"{args.mesh_file}: {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} faces -> {what}; grasps "
+          f"{tuple(res['grasps'].shape)}  confidence mean {conf.mean().item():.3f}  best {conf.max().item():.3f}")
     return [res]
 
 
@@ -575,6 +653,8 @@ def main(argv=None):
     results = []
     if args.depth_file:
         return finish(args, run_depth(args, model, selection))
+    if args.mesh_file:
+        return finish(args, run_mesh(args, model, selection))
     if args.segment_cloud:
         return finish(args, run_cloud_scene(args, model, selection))
     if args.pc_file:
@@ -633,8 +713,10 @@ def finish(args, results):
         extra = {k: torch.cat([r[k] for r in results]).cpu().numpy()
                  for k in ("latent_mu", "latent_logvar", "success", "selected_index", "selected_count", "selected_gap",
                            "clearance", "contacts", "aligned_contacts", "object_label", "object_points", "object_points_raw",
-                           "scene_rank")
+                           "scene_rank", "cam_pose")
                  if all(r.get(k) is not None for r in results)}
+        if all(isinstance(r.get("mesh_face"), torch.Tensor) for r in results):   # --mesh_file without a view
+            extra["mesh_face"] = torch.cat([r["mesh_face"] for r in results]).cpu().numpy()
         if all(r.get("voxel_size") is not None for r in results):   # --voxel_size: the size every result ended with
             extra["voxel_size"] = np.asarray([r["voxel_size"] for r in results], dtype=np.float32)
         if all(r.get("segmented_points") is not None for r in results):   # --segment_cloud: one scene per result
