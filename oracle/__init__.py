@@ -8,7 +8,16 @@ Contents
 --------
 point_ops.c / cpu_backend.py  scalar C restatement of the reference's nine
                               forward CUDA kernels behind the 12 ``_backend``
-                              names (self-pinned: the reference has no CPU path)
+                              names, pinned to the reference's own kernels
+                              (tests/test_ref_kernels_gpu.py and the recorded
+                              tests/golden/ref_point_ops.npz)
+ref_build.py, ref_shim/       compile the reference's six point-op .cu files,
+                              unmodified, as HIP for gfx950 into the
+                              git-ignored oracle/_ref/ (two libraries: default
+                              contraction and -ffp-contract=off)
+ref_backend.py, ref_cases.py  ctypes front end of those libraries on CUDA
+                              tensors; the cases they are compared on
+record_ref_point_ops.py       GPU-only: writes tests/golden/ref_point_ops.npz
 schedulers.py                 DDIM / DDPM step restated from the public
                               algorithm (diffusers is absent here: PARITY
                               UNPINNED at that third-party boundary)

@@ -10,9 +10,11 @@
  * float-atomic voxel scatter the canonical order "ascending point index".
  *
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may
- * load this library.  Parity status: SELF-PINNED (the reference ships no CPU
- * path, tests or golden vectors for these kernels); cross-checked against an
- * independent torch formulation in tests/test_oracle_point_ops.py.
+ * load this library.  Parity status: pinned to the reference's own kernels,
+ * compiled unmodified for gfx950 (oracle/ref_build.py) and run on an MI355X:
+ * bit-equal on every case of tests/test_ref_kernels_gpu.py, and replayed from
+ * tests/golden/ref_point_ops.npz in tests/test_oracle_point_ops.py, which also
+ * cross-checks an independent torch formulation.
  *
  * All paths cited are relative to
  *   /root/reference/grasp_ldm/models/modules/ext/pvcnn/modules/functional/src/

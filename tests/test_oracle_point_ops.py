@@ -119,3 +119,33 @@ def test_trilinear_devoxelize_reproduces_a_linear_field():
     o2, inds, wgts = B.trilinear_devoxelize_forward(r, True, coords, grid.contiguous())
     assert torch.equal(o2, out) and torch.allclose(wgts.sum(1), torch.ones(1, n), atol=1e-6)
     assert int(inds.max()) < r ** 3 and int(inds.min()) >= 0
+
+
+def test_oracle_reproduces_the_recorded_reference_kernels():
+    """tests/golden/ref_point_ops.npz holds what the reference's OWN kernels computed on the MI355X (its .cu files
+    compiled unmodified for gfx950, -ffp-contract=off; written by oracle/record_ref_point_ops.py) on inputs that
+    ref_cases.make_inputs() regenerates here from shapes, seeds and cloud kinds.  The C oracle must reproduce every
+    recorded output bit for bit: a rule mis-stated in oracle/point_ops.c (the FPS slot order, the first-hit fill, the
+    strict `<` against r^2, the double running bests of 3-NN) fails here without a GPU."""
+    import json
+    import os
+
+    import numpy as np
+
+    from oracle import ref_cases
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_point_ops.npz")
+    with np.load(path) as z:
+        manifest = json.loads(str(z["manifest"]))
+        ops = {c["op"] for c in manifest}
+        assert ops == set(ref_cases.OPS) and len(manifest) >= 50
+        for c in manifest:
+            got = ref_cases.run(B, c["op"], c["params"], ref_cases.make_inputs(c["op"], c["params"]))
+            assert c["outputs"], c["name"]
+            for k in c["outputs"]:
+                exp = z[f"{c['name']}/{k}"]
+                g = got[k].numpy()
+                assert g.shape == exp.shape, (c["name"], k)
+                if g.dtype == np.int32:
+                    assert np.array_equal(g, exp.astype(np.int32)), (c["name"], k)
+                else:
+                    assert exp.dtype == np.float32 and np.array_equal(g.view(np.int32), exp.view(np.int32)), (c["name"], k)
